@@ -19,8 +19,15 @@ log-softmax, decode, D2H, string building all on the clock), split over the N ra
 the product's path on a multi-GPU node outside torchrun.  `--share_device` puts every rank on device 0 (the tests' way to run
 the N > 1 code on a one-GPU box; the figures mean nothing then).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--T 4000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--T 4000] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run generates the inputs, warms up, times the K steps and prints the headline (`value`, `ms_per_step`,
+`mbases_per_s`, `config`).  Everything else this script measures or checks runs only with `--full`: the CPU baseline,
+the per-kernel timers and both rooflines, the parity check against the oracle's digests, the weak-scaling and
+end-to-end legs, the two-stream rate and the secondary configurations (`--no_strong`, `--no_secondary`, `--no_weak`,
+`--cpu_sample` and `--inprocess_devices` select among them).  `--dump-outputs DIR` writes what the last timed step
+returned (rank 0's pairs) as .npy files; the inputs are seeded, so two builds can be compared output for output.
 
 `--gpus N` (N > 1) outside a torchrun environment starts the N ranks itself (a fresh torch.distributed.run child,
 created before this process has touched torch or HIP) and relays rank 0's line; the reported n_gpus is always the
@@ -122,6 +129,50 @@ def _digest(seq1, seq2, cons):
     return hashlib.md5(("%s|%s|%s" % (seq1, seq2, cons)).encode()).hexdigest()[:10]
 
 
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much
+DUMP_SAMPLE = 1000      # at most this many pairs have their strings and envelope written
+
+
+def dump_outputs(path, o1, s1o, so, d_seq1d, d_l1, d_l2, d_id, d_env, d_seq, d_len, d_st):
+    """--dump-outputs: what po_pair_decode_batch returned, masked as batch.pair_decode_batch hands it to its callers.
+    Every pair: status, length1, length2, consensus_length (0 unless decoded) and sequence_identity (NaN after a length
+    skip), float64.  A seeded sample of pairs (`sample_pairs`, ascending; chosen from the input shapes alone, as many as
+    fit in DUMP_BYTES): seq1, seq2 and consensus as float32 character codes and envelope as float32 (rows, 2), each
+    concatenated over the sampled pairs in that order."""
+    import torch
+    from poreover_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    st = d_st.cpu().numpy()
+    n = len(st)
+    ok = st == 0
+    called = ok | (st == _lib.SKIP_LENGTH) | (st == _lib.SKIP_IDENTITY)
+    l1 = np.where(called, d_l1.cpu().numpy(), 0)
+    l2 = np.where(called, d_l2.cpu().numpy(), 0)
+    lens = np.where(ok, d_len.cpu().numpy(), 0)
+    ident = np.where(called & (st != _lib.SKIP_LENGTH), d_id.cpu().numpy(), np.nan)
+    # bytes a sampled pair can take at most: both basecalls and the consensus at their capacity, two bounds per row
+    rows1 = np.diff(o1)
+    cost = 4 * ((s1o[2::2] - s1o[0:-1:2]) + np.diff(so) + 2 * rows1)
+    budget = DUMP_BYTES - 6 * 8 * n - (1 << 20)   # (the per-pair arrays, sample_pairs and the .npy headers first)
+    order = np.random.default_rng(20240).permutation(n)[:DUMP_SAMPLE]
+    take = np.sort(order[:int(np.searchsorted(np.cumsum(cost[order]), budget, side="right"))])
+
+    def gather(d, spans):
+        spans = [(int(a), int(b)) for a, b in spans if b > a]
+        return torch.cat([d[a:b] for a, b in spans]).cpu().numpy().astype(np.float32) if spans else np.zeros(0, np.float32)
+    arrays = {
+        "status": st.astype(np.float64), "length1": l1.astype(np.float64), "length2": l2.astype(np.float64),
+        "consensus_length": lens.astype(np.float64), "sequence_identity": ident.astype(np.float64),
+        "sample_pairs": take.astype(np.float64),
+        "seq1": gather(d_seq1d, [(s1o[2 * i], s1o[2 * i] + l1[i]) for i in take]),
+        "seq2": gather(d_seq1d, [(s1o[2 * i + 1], s1o[2 * i + 1] + l2[i]) for i in take]),
+        "consensus": gather(d_seq, [(so[i], so[i] + lens[i]) for i in take]),
+        "envelope": gather(d_env, [(2 * o1[i], 2 * o1[i + 1]) for i in take if ok[i]]).reshape(-1, 2),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -141,6 +192,10 @@ def main():
                     "single-pair latency, end-to-end) measured after the timed region at N = 1")
     ap.add_argument("--share_device", action="store_true", help="every rank on device 0 (testing the N > 1 path on a one-GPU box)")
     ap.add_argument("--no_weak", action="store_true", help="N > 1: skip the weak-scaling leg (every rank its own P pairs)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beside the headline (CPU "
+                    "baseline, per-kernel timers and rooflines, digest parity, weak / end-to-end / two-stream / secondary legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the outputs of the last timed step (rank 0) "
+                    "as DIR/<name>.npy")
     args = ap.parse_args()
 
     if "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -169,15 +224,15 @@ def main():
     job_pairs = gen(list(range(slo, shi)))
     y1, o1, Cc = pack_rows([p[0] for p in job_pairs])
     y2, o2, _ = pack_rows([p[1] for p in job_pairs])
-    strong_pairs = job_pairs if (world > 1 and not args.no_strong) else None   # (N = 1: the end-to-end leg slices y1 / y2)
+    strong_pairs = job_pairs if (args.full and world > 1 and not args.no_strong) else None   # (N = 1: the end-to-end leg slices y1 / y2)
     del job_pairs
     # weak scaling (N > 1 only): every rank its OWN P pairs, the seeds of rounds 1 - 5 (rank 0: the job's)
     weak_in = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         wp_ = gen(list(podist.shard_seeds(P, rank)))
         weak_in = (pack_rows([p[0] for p in wp_]), pack_rows([p[1] for p in wp_]))
         del wp_
-    secondary = rank == 0 and world == 1 and not args.no_secondary
+    secondary = args.full and rank == 0 and world == 1 and not args.no_secondary
     ff_reads = None
     if secondary:   # BASELINE config 5: 1 000 flip-flop reads (T x 8)
         from poreover_amd.synth import synth_read
@@ -198,7 +253,7 @@ def main():
         else:
             ff_pairs = [synth_pair(700000 + i, T=T, flipflop=True) for i in range(nfp)]
     cpu_base = None
-    if rank == 0 and args.gpus == 1 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and args.gpus == 1 and world == 1 and args.cpu_sample > 0:
         cpu_base = cpu_baseline(T, args.cpu_sample)
 
     import torch
@@ -268,22 +323,26 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    lib.po_profile_enable(1)
-    lib.po_profile_reset()
+    if args.full:   # per-kernel HIP events around the launches: the rooflines' kernel times
+        lib.po_profile_enable(1)
+        lib.po_profile_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     barrier()
     elapsed = time.perf_counter() - t0
-    lib.po_profile_enable(0)
-    # update_prob evaluations (reference schedule, executed) of ONE more step, outside the timed region: with the counter
-    # attached the kernels count per step (ballots, a wave reduction per scan) — diagnostics the product path does not run
-    d_upd = torch.zeros(2, dtype=torch.int64, device=dev)
-    lib.po_profile_update_counter(d_upd.data_ptr())
-    step()
-    barrier()
-    lib.po_profile_update_counter(None)
-    n_upd, n_upd_exec = (int(x) * args.steps for x in d_upd.cpu().tolist())   # (every step decodes the same pairs)
+    if args.dump_outputs and rank == 0:   # (before anything below launches into the same output buffers)
+        dump_outputs(args.dump_outputs, o1, s1o, so, d_seq1d, d_l1, d_l2, d_id, d_env, d_seq, d_len, d_st)
+    if args.full:
+        lib.po_profile_enable(0)
+        # update_prob evaluations (reference schedule, executed) of ONE more step, outside the timed region: with the counter
+        # attached the kernels count per step (ballots, a wave reduction per scan) — diagnostics the product path does not run
+        d_upd = torch.zeros(2, dtype=torch.int64, device=dev)
+        lib.po_profile_update_counter(d_upd.data_ptr())
+        step()
+        barrier()
+        lib.po_profile_update_counter(None)
+        n_upd, n_upd_exec = (int(x) * args.steps for x in d_upd.cpu().tolist())   # (every step decodes the same pairs)
 
     # ---- N > 1: the WEAK figure beside the headline — every rank its own P pairs resident, the same W + K steps and clock
     weak = None
@@ -335,9 +394,9 @@ def main():
         lib.po_profile_get(k, C.byref(ms), C.byref(cnt))
         return ms.value, cnt.value
     # (read now: the secondary configurations below use the same per-kernel timers)
-    prof = {k: _kernel_ms(k) for k in (_lib.K_BEAM2D, _lib.K_VITERBI, _lib.K_ALIGN, _lib.K_BEAM2D_MAIN)}
+    prof = {k: _kernel_ms(k) for k in (_lib.K_BEAM2D, _lib.K_VITERBI, _lib.K_ALIGN, _lib.K_BEAM2D_MAIN)} if args.full else None
     lae_peak = C.c_double(0.0)
-    if rank == 0:   # outside the timed region: the device's peak rate of the engine's logaddexp
+    if args.full and rank == 0:   # outside the timed region: the device's peak rate of the engine's logaddexp
         _lib.check(lib.po_lae_peak(20000, C.byref(lae_peak), stream), "po_lae_peak")
 
     st = d_st.cpu().numpy()
@@ -351,7 +410,7 @@ def main():
     # ---- parity of what was just timed: the first pairs of rank 0 against the committed digests of the oracle's
     # results for the same seeds (tests/golden/batch_digest.json) — strings, not only statuses
     parity = None
-    if rank == 0 and T == 4000 and args.beam_width == 5:
+    if args.full and rank == 0 and T == 4000 and args.beam_width == 5:
         try:
             with open(os.path.join(REPO, "tests", "golden", "batch_digest.json")) as f:
                 dig = json.load(f)["records"]
@@ -385,7 +444,7 @@ def main():
     #  (gpurun_out/r04_g38: packing 31 instead of 20 ms, H2D 11 instead of 14 GB/s); what is measured is the pipeline, not the
     #  state the other legs leave the host in.)
     strong = None
-    if not args.no_strong:
+    if args.full and not args.no_strong:
         from poreover_amd import batch as pobatch
         torch.cuda.empty_cache()
         if os.environ.get("PO_BENCH_SETTLE"):   # experiment: let the driver finish with the memory just freed
@@ -670,47 +729,6 @@ def main():
         return prof[k]
 
     if rank == 0:
-        # algorithmic bytes per launch of the dominant kernel (pair beam search), SURVEY.md §8(d):
-        # 8*C*(U+V) log-probs + 8*U envelope + L output characters, summed over the launch's pairs
-        alg_bytes = 8.0 * Cc * (tr1 + tr2) + 8.0 * tr1 + bases
-        b2_ms, b2_n = kernel_ms(_lib.K_BEAM2D)
-        vt_ms, vt_n = kernel_ms(_lib.K_VITERBI)
-        al_ms, al_n = kernel_ms(_lib.K_ALIGN)
-        b2_avg = b2_ms / max(b2_n, 1)               # the stage: pre-pass + walk + store memset + kernel + deferred pass
-        bk_ms, bk_n = kernel_ms(_lib.K_BEAM2D_MAIN)  # the dominant kernel alone (HIP events around its launch)
-        bk_avg = bk_ms / max(bk_n, 1)
-        achieved = alg_bytes / (bk_avg * 1e-3) / 1e9 if bk_avg > 0 else 0.0
-        n1d = int(d_l1.sum().item() + d_l2.sum().item())
-        vt_bytes = 8.0 * Cc * (tr1 + tr2) + 5.0 * n1d  # log-probs in; per base one character + one int32 frame index out
-        vt_avg = vt_ms / max(vt_n, 1)
-        # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so this figure is
-        # NOT measured in this run — it comes from the newest committed rocprofv3 counter passes (profiles/
-        # rNN_pmc_hbm*.json: FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate --pmc passes, same T / W), scaled
-        # from that run's pairs per launch to this launch's
-        traffic, traffic_src = None, None
-        try:
-            import glob
-            pdir = os.path.join(REPO, "profiles")
-            cands = []
-            for pj in glob.glob(os.path.join(pdir, "r*_pmc_hbm*.json")):
-                with open(pj) as f:
-                    pm = json.load(f)
-                kks = [v for k, v in pm.get("kernels", {}).items() if k.startswith(MAIN_KERNEL)]
-                if not kks or not (T == 4000 and args.beam_width == 5):
-                    continue
-                per_launch = float(pm.get("pairs_per_launch", 1250))
-                rnd = os.path.basename(pj).split("_")[0]
-                # newest round first, then the pass whose pairs per launch is closest to this run's (traffic per pair
-                # grows with the launch size: 34 x the algorithmic bytes at 1 250 pairs per launch, 43 x at 10 000)
-                cands.append((rnd, -abs(per_launch - Pl), pj, kks[0], per_launch))
-            if cands:
-                rnd, _, pj, kk, per_launch = sorted(cands, key=lambda c: (c[0], c[1]), reverse=True)[0]
-                per_pair = (2.0 * kk["FETCH_SIZE_KB_per_launch"] + kk["WRITE_SIZE_KB_per_launch"]) * 1024.0 / per_launch
-                traffic = per_pair * Pl
-                traffic_src = ("NOT measured in this run: %s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at %d "
-                               "pairs per launch; FETCH_SIZE x 2 on gfx950), scaled by pairs" % (os.path.relpath(pj, REPO), int(per_launch)))
-        except Exception:
-            pass
         out = {
             "metric": "decoded Mbases/s + read-pairs/s, 10k synthetic pairs T~4000, 1/2/4/8 MI355X",
             "value": round(tot_pairs / tmax, 3),
@@ -725,40 +743,84 @@ def main():
                                    "HBM" % (P, "" if world == 1 else " split over %d GPUs (%d per GPU)" % (world, Pl), T, args.beam_width),
                        "pairs_per_job": P, "pairs_per_gpu": Pl, "T": T, "beam_width": args.beam_width, "method": "row_col",
                        "decoded_pairs_rank0": decoded, "parallelism": "shard%d (no collective)" % args.gpus},
-            "roofline": {"bound": "hbm", "kernel": MAIN_KERNEL + (", true>" if LEGACY else ""), "achieved": round(achieved, 3),
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6),
-                         "traffic": traffic, "traffic_source": traffic_src, "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": round(bk_avg, 3),
-                         "launches": bk_n, "stage_ms": round(b2_avg, 3),
-                         "note": "f64 log-space beam search: bound by the f64 instruction stream of logaddexp and "
-                                 "per-step bookkeeping latency, not by HBM (SURVEY.md §8(d), DESIGN.md §3.3); the "
-                                 "streaming Viterbi kernel is the HBM-bound one, see viterbi_roofline"},
-            "viterbi_roofline": {"bound": "hbm", "kernel": "viterbi_ctc_kernel (2 launches per step)",
-                                 "achieved": round(vt_bytes / (vt_avg * 1e-3) / 1e9, 3) if vt_avg > 0 else 0.0,
-                                 "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                 "frac": round(vt_bytes / (vt_avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 6) if vt_avg > 0 else 0.0,
-                                 "avg_ms_per_step": round(vt_avg, 3)},
-            "stage_ms_per_step": {"viterbi_x2": round(vt_avg, 3), "align_envelope": round(al_ms / max(al_n, 1), 3),
-                                  "pair_beam": round(b2_avg, 3)},
         }
-        # the pair beam search priced against what actually bounds it: one logaddexp per update_prob (ctc)
-        lae_rate = n_upd / (bk_ms * 1e-3) if bk_ms > 0 else 0.0   # (kernel time, like `roofline`)
-        exe_rate = n_upd_exec / (bk_ms * 1e-3) if bk_ms > 0 else 0.0
-        out["compute_roofline"] = {"bound": "f64 logaddexp stream (VALU)", "unit": "logaddexp/s",
-                                   "achieved": round(exe_rate, 1), "peak": round(lae_peak.value, 1),
-                                   "frac": round(exe_rate / lae_peak.value, 5) if lae_peak.value > 0 else None,
-                                   "executed_per_step": n_upd_exec // max(args.steps, 1),
-                                   "reference_schedule_per_step": n_upd // max(args.steps, 1),
-                                   "reference_schedule_frac": round(lae_rate / lae_peak.value, 5) if lae_peak.value > 0 else None,
-                                   "note": "achieved / frac = update_prob evaluations the pair beam kernel EXECUTES / its "
-                                           "time, against the po_lae_peak micro-benchmark on this device (all lanes busy, 4 "
-                                           "independent chains per lane, same table-driven logaddexp); "
-                                           "reference_schedule_* counts what the reference's schedule evaluates for this "
-                                           "input (every element over its full windows in every step) — the kernel skips "
-                                           "the ones whose result is provably already stored (bit-identical output).  "
-                                           "beam2d_reg_kernel (round 4) executes about HALF of what round 3's "
-                                           "beam2d_kernel did on the same pairs (3.6e9 against 7.3e9 per 10 000 pairs: "
-                                           "continuing elements compute new times only), so `frac` fell while the kernel "
-                                           "got faster; reference_schedule_frac compares like with like across rounds"}
+        if args.full:
+            # algorithmic bytes per launch of the dominant kernel (pair beam search), SURVEY.md §8(d):
+            # 8*C*(U+V) log-probs + 8*U envelope + L output characters, summed over the launch's pairs
+            alg_bytes = 8.0 * Cc * (tr1 + tr2) + 8.0 * tr1 + bases
+            b2_ms, b2_n = kernel_ms(_lib.K_BEAM2D)
+            vt_ms, vt_n = kernel_ms(_lib.K_VITERBI)
+            al_ms, al_n = kernel_ms(_lib.K_ALIGN)
+            b2_avg = b2_ms / max(b2_n, 1)               # the stage: pre-pass + walk + store memset + kernel + deferred pass
+            bk_ms, bk_n = kernel_ms(_lib.K_BEAM2D_MAIN)  # the dominant kernel alone (HIP events around its launch)
+            bk_avg = bk_ms / max(bk_n, 1)
+            achieved = alg_bytes / (bk_avg * 1e-3) / 1e9 if bk_avg > 0 else 0.0
+            n1d = int(d_l1.sum().item() + d_l2.sum().item())
+            vt_bytes = 8.0 * Cc * (tr1 + tr2) + 5.0 * n1d  # log-probs in; per base one character + one int32 frame index out
+            vt_avg = vt_ms / max(vt_n, 1)
+            # HBM traffic of the dominant kernel: PMC counters cannot be read from inside this process, so this figure is
+            # NOT measured in this run — it comes from the newest committed rocprofv3 counter passes (profiles/
+            # rNN_pmc_hbm*.json: FETCH_SIZE x2 gfx950 correction + WRITE_SIZE, separate --pmc passes, same T / W), scaled
+            # from that run's pairs per launch to this launch's
+            traffic, traffic_src = None, None
+            try:
+                import glob
+                pdir = os.path.join(REPO, "profiles")
+                cands = []
+                for pj in glob.glob(os.path.join(pdir, "r*_pmc_hbm*.json")):
+                    with open(pj) as f:
+                        pm = json.load(f)
+                    kks = [v for k, v in pm.get("kernels", {}).items() if k.startswith(MAIN_KERNEL)]
+                    if not kks or not (T == 4000 and args.beam_width == 5):
+                        continue
+                    per_launch = float(pm.get("pairs_per_launch", 1250))
+                    rnd = os.path.basename(pj).split("_")[0]
+                    # newest round first, then the pass whose pairs per launch is closest to this run's (traffic per pair
+                    # grows with the launch size: 34 x the algorithmic bytes at 1 250 pairs per launch, 43 x at 10 000)
+                    cands.append((rnd, -abs(per_launch - Pl), pj, kks[0], per_launch))
+                if cands:
+                    rnd, _, pj, kk, per_launch = sorted(cands, key=lambda c: (c[0], c[1]), reverse=True)[0]
+                    per_pair = (2.0 * kk["FETCH_SIZE_KB_per_launch"] + kk["WRITE_SIZE_KB_per_launch"]) * 1024.0 / per_launch
+                    traffic = per_pair * Pl
+                    traffic_src = ("NOT measured in this run: %s (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes at %d "
+                                   "pairs per launch; FETCH_SIZE x 2 on gfx950), scaled by pairs" % (os.path.relpath(pj, REPO), int(per_launch)))
+            except Exception:
+                pass
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": MAIN_KERNEL + (", true>" if LEGACY else ""), "achieved": round(achieved, 3),
+                             "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 6),
+                             "traffic": traffic, "traffic_source": traffic_src, "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": round(bk_avg, 3),
+                             "launches": bk_n, "stage_ms": round(b2_avg, 3),
+                             "note": "f64 log-space beam search: bound by the f64 instruction stream of logaddexp and "
+                                     "per-step bookkeeping latency, not by HBM (SURVEY.md §8(d), DESIGN.md §3.3); the "
+                                     "streaming Viterbi kernel is the HBM-bound one, see viterbi_roofline"},
+                "viterbi_roofline": {"bound": "hbm", "kernel": "viterbi_ctc_kernel (2 launches per step)",
+                                     "achieved": round(vt_bytes / (vt_avg * 1e-3) / 1e9, 3) if vt_avg > 0 else 0.0,
+                                     "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                     "frac": round(vt_bytes / (vt_avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 6) if vt_avg > 0 else 0.0,
+                                     "avg_ms_per_step": round(vt_avg, 3)},
+                "stage_ms_per_step": {"viterbi_x2": round(vt_avg, 3), "align_envelope": round(al_ms / max(al_n, 1), 3),
+                                      "pair_beam": round(b2_avg, 3)},
+            })
+            # the pair beam search priced against what actually bounds it: one logaddexp per update_prob (ctc)
+            lae_rate = n_upd / (bk_ms * 1e-3) if bk_ms > 0 else 0.0   # (kernel time, like `roofline`)
+            exe_rate = n_upd_exec / (bk_ms * 1e-3) if bk_ms > 0 else 0.0
+            out["compute_roofline"] = {"bound": "f64 logaddexp stream (VALU)", "unit": "logaddexp/s",
+                                       "achieved": round(exe_rate, 1), "peak": round(lae_peak.value, 1),
+                                       "frac": round(exe_rate / lae_peak.value, 5) if lae_peak.value > 0 else None,
+                                       "executed_per_step": n_upd_exec // max(args.steps, 1),
+                                       "reference_schedule_per_step": n_upd // max(args.steps, 1),
+                                       "reference_schedule_frac": round(lae_rate / lae_peak.value, 5) if lae_peak.value > 0 else None,
+                                       "note": "achieved / frac = update_prob evaluations the pair beam kernel EXECUTES / its "
+                                               "time, against the po_lae_peak micro-benchmark on this device (all lanes busy, 4 "
+                                               "independent chains per lane, same table-driven logaddexp); "
+                                               "reference_schedule_* counts what the reference's schedule evaluates for this "
+                                               "input (every element over its full windows in every step) — the kernel skips "
+                                               "the ones whose result is provably already stored (bit-identical output).  "
+                                               "beam2d_reg_kernel (round 4) executes about HALF of what round 3's "
+                                               "beam2d_kernel did on the same pairs (3.6e9 against 7.3e9 per 10 000 pairs: "
+                                               "continuing elements compute new times only), so `frac` fell while the kernel "
+                                               "got faster; reference_schedule_frac compares like with like across rounds"}
         if weak is not None:
             out["weak_scaling"] = weak
         if parity is not None:

@@ -8,7 +8,7 @@ for rep in $(seq 1 $reps); do
 for v in closed_form serial; do
   if [ "$v" = closed_form ]; then export PO_CHAIN_CLOSED=1; else unset PO_CHAIN_CLOSED; fi
   echo -n "$v: "
-  timeout 400 python bench.py --steps 4 --warmup 1 --no_secondary --no_strong --cpu_sample 0 2>gpurun_out/ab_chain_err.log | tail -1 | python3 -c "
+  timeout 400 python bench.py --full --steps 4 --warmup 1 --no_secondary --no_strong --cpu_sample 0 | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], 'kernel', d['roofline']['avg_launch_ms'], 'stage', d['roofline']['stage_ms'], 'parity', d['parity_check'])"
 done; done > gpurun_out/ab_chain_$label.log 2>&1
 cat gpurun_out/ab_chain_$label.log

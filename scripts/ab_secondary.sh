@@ -8,7 +8,7 @@ for rep in 1 2; do
 for v in "$@"; do
   if [ "$v" = main ]; then unset POREOVER_HIP_LIB; else export POREOVER_HIP_LIB=$PWD/scripts/variants/libporeover_hip_$v.so; fi
   echo "$v:"
-  timeout 600 python bench.py --steps 2 --warmup 1 --no_strong --cpu_sample 0 2>&1 | tail -1 | python3 -c "
+  timeout 600 python bench.py --full --steps 2 --warmup 1 --no_strong --cpu_sample 0 2>&1 | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read())
 print('   headline', d['value'], 'kernel', d['roofline']['avg_launch_ms'])
 for k,v in d['secondary'].items():

@@ -154,7 +154,7 @@ def test_bench_inprocess_devices_leg():
     nd = _lib.load().po_device_count()
     devs = ",".join(str(i % max(nd, 1)) for i in range(2))
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--pairs", "256", "--steps", "1", "--warmup", "1", "--cpu_sample", "0",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--pairs", "256", "--steps", "1", "--warmup", "1", "--cpu_sample", "0",
                           "--no_secondary", "--inprocess_devices", devs], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
@@ -170,7 +170,7 @@ def test_bench_two_ranks_one_job():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share_device", "--pairs", "192", "--steps", "1",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--share_device", "--pairs", "192", "--steps", "1",
                           "--warmup", "1", "--cpu_sample", "0", "--no_secondary"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.strip().splitlines() if l.startswith("{")][-1])
