@@ -410,6 +410,41 @@ int po_multi_stats(po_multi* m, int i, int* pairs, double* pack_ms, double* wait
 int po_wave_plan(const int64_t* rows1, const int64_t* rows2, int n, int wave_pairs, int64_t wave_rows, int ndev, int* first,
                  int* count, int cap);
 
+/* ---- basecalling network forward pass (`call`) ------------------------------------------------
+ * Replaces the reference's TensorFlow forward pass of call_helper (network.py:253-282): the Keras models of build_model
+ * (network.py:15-55) on windows of scaled FAST5 signal, then tf.nn.softmax.  f32 weights, f32 arithmetic.
+ *   - signal:  n windows of T f32 samples each, window-major (n * T values); each window starts from a zero state
+ *   - layers_h: HOST array of n_layers po_call_layer, in the order the model applies them; layer k's cin is layer
+ *              k-1's cout (1 for the first); the last layer is PO_CALL_DENSE with cout 5
+ *   - weights: every layer's f32 tensors back to back, in Keras' layouts, layer by layer:
+ *              PO_CALL_CONV   kernel (kernel, cin, cout), bias (cout)          Conv1D, padding "same", stride 1, ReLU
+ *              PO_CALL_BIGRU  forward then backward GRU(128), each: kernel (cin, 384), recurrent kernel (128, 384),
+ *                             bias (2, 384) (input bias, recurrent bias; reset_after); gates z, r, h; cout = 256,
+ *                             [forward, backward] with the backward output in forward time order (Bidirectional)
+ *              PO_CALL_GRU    one forward GRU(128), tensors as above; cout = 128
+ *              PO_CALL_GRU_BACK  GRU(128, go_backwards = True): walks the window from its end and writes its outputs in
+ *                             that reversed order (the next layer consumes them so); cout = 128
+ *              PO_CALL_DENSE  kernel (cin, 5), bias (5)
+ *   - probs:   n * T * 5 softmax probabilities; logits (or NULL): the Dense outputs before the softmax
+ *   - stage_ms_h (or NULL): HOST float[4] to which device milliseconds are ADDED per stage — 0 Conv1D, 1 GRU input
+ *              projection, 2 GRU recurrence, 3 Dense + softmax — measured with events (the call then synchronises)
+ * po_call_workspace_bytes returns 0 for an unusable model.  po_call_batch_h takes host arrays, runs the windows in
+ * passes of bounded device memory (a window's output does not depend on the pass it runs in) and is synchronous. */
+#define PO_CALL_CONV 0
+#define PO_CALL_BIGRU 1
+#define PO_CALL_GRU 2
+#define PO_CALL_GRU_BACK 3
+#define PO_CALL_DENSE 4
+typedef struct po_call_layer {
+    int kind, cin, cout, kernel; /* kernel: Conv1D kernel size (0 otherwise) */
+} po_call_layer;
+size_t po_call_workspace_bytes(int n, int T, const po_call_layer* layers_h, int n_layers);
+int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers_h, int n_layers, const float* weights,
+                  int64_t n_weights, float* probs, float* logits, void* ws, size_t ws_bytes, void* stream,
+                  float* stage_ms_h);
+int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* layers_h, int n_layers,
+                    const float* weights_h, int64_t n_weights, float* probs_h, float* logits_h, float* stage_ms_h);
+
 /* ---- timing aid for bench.py: HIP events on the stream the kernels run on ----------------- */
 void* po_event_create(void);
 int po_event_record(void* ev, void* stream);

@@ -1,6 +1,8 @@
-"""`python -m poreover_amd decode|pair-decode ...` — the decode / pair-decode sub-commands of the
-reference CLI (reference __main__.py:52-91) with the same flags and defaults, on the GPU engine.
-(`train`, `call` and `benchmark` are outside this engine's scope: SURVEY.md §2.)"""
+"""`python -m poreover_amd call|decode|pair-decode ...` — the call / decode / pair-decode sub-commands of the
+reference CLI (reference __main__.py:39-91) with the same flags and defaults, on the GPU engine.  `call` runs the
+basecalling network in HIP and needs `--weights` (no weights ship with this package: a TF checkpoint prefix or
+directory, or an .npz from `python -m poreover_amd.network.convert`).
+(`train` and `benchmark` are outside this engine's scope: SURVEY.md §2.)"""
 import argparse
 import logging
 import sys
@@ -13,6 +15,20 @@ def build_parser():
                                      description='PoreOver decoding on MI355X: consensus basecalling for nanopore sequencing')
     subparsers = parser.add_subparsers(dest="command")
     subparsers.required = True
+
+    p = subparsers.add_parser('call', help='Run basecalling forward pass on set of FAST5 reads',
+                              formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('in', help='Single FAST5 file or directory of FAST5 files')
+    p.add_argument('--weights', default=None, help='Trained weights to load into model: a TF checkpoint prefix, a directory (loads latest from its checkpoint file) or an .npz (required: no weights ship with this package)')
+    p.add_argument('--model', help='Model config JSON file (default: conv1_bigru3)', default=None)
+    p.add_argument('--scaling', default='standard', choices=['standard', 'current', 'median', 'rescale'], help='Type of preprocessing (should be same as training)')
+    p.add_argument('--use_id', default=False, action='store_true', help='Save logits by read ID instead of FAST5 filename')
+    p.add_argument('--dir', default='.', help='Directory to write logits to')
+    p.add_argument('--window', type=int, default=1000, help='Call read using chunks of this size')
+    p.add_argument('--format', choices=['csv', 'npy'], default='npy', help='Save softmax probabilities to CSV file or logits to binarized NumPy format')
+    p.add_argument('--no_stack', default=False, action='store_true', help='Basecall [1xSIGNAL_LENGTH] tensor instead of splitting it into windows (slower)')
+    p.add_argument('-v', '--version', action='version', version=__version__)
+    p.set_defaults(func="call")
 
     p = subparsers.add_parser('decode', help='Decode basecaller probabilities to a FASTA file')
     p.add_argument('in', nargs='+', help='Probabilities to decode (.npy from PoreOver/Bonito, .csv, or HDF5/FAST5 from Flappie/Guppy)')
@@ -56,6 +72,13 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     logging.basicConfig(format='%(message)s', level=logging.DEBUG if getattr(args, 'logging', 'info') == 'debug' else logging.INFO)
+    if args.func == "call":
+        from .network import call as _call
+        if args.window < 1:
+            raise SystemExit("call: --window must be positive")
+        _call(args)
+        print(args, file=sys.stderr)
+        return
     from .decoding import decode as _decode, pair_decode as _pair
     if args.func == "decode":
         _decode.decode(args)

@@ -41,6 +41,13 @@ class PairOptions(C.Structure):
                 ("full_alignment", C.c_int), ("diagonal_envelope", C.c_int), ("diagonal_width", C.c_int)]
 
 
+class CallLayer(C.Structure):
+    _fields_ = [("kind", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("kernel", C.c_int)]
+
+
+CALL_KINDS = {"conv": 0, "bigru": 1, "gru": 2, "gru_back": 3, "dense": 4}
+CALL_STAGES = ("conv", "gru_proj", "gru_recur", "dense_softmax")
+
 _vp, _i64p, _i32p, _dp, _cp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
 # every symbol include/poreover_hip.h declares: (restype, argtypes)
 PROTOTYPES = {
@@ -140,6 +147,11 @@ PROTOTYPES = {
                                  C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "po_pipeline_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                     C.POINTER(C.c_int)]),
+    "po_call_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int]),
+    "po_call_batch": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64, _vp, _vp, _vp,
+                                C.c_size_t, _vp, C.POINTER(C.c_float)]),
+    "po_call_batch_h": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64, _vp, _vp,
+                                  C.POINTER(C.c_float)]),
     "po_event_create": (C.c_void_p, []),
     "po_event_record": (C.c_int, [C.c_void_p, C.c_void_p]),
     "po_event_elapsed_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),

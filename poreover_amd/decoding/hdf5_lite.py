@@ -12,13 +12,16 @@ not a dependency of this engine; this module implements the part of the HDF5 fil
   * datasets: dataspace (versions 1, 2), fixed-point / floating-point datatypes, data layout message
     version 3 (compact, contiguous, chunked through a version-1 chunk B-tree) and versions 1 / 2
   * filters: deflate (zlib) and byte shuffle
+  * attribute messages (versions 1 - 3, compact storage) on groups and datasets, as `.attrs`: fixed-point,
+    floating-point, fixed-length and variable-length (global heap) string values, scalar or 1-D — what
+    FAST5 readers need (the reference's network.py:199-217 reads `read_id`, `duration`, `digitisation`, ...)
 Anything else raises Hdf5Error with the name of the unsupported feature."""
 import struct
 import zlib
 
 import numpy as np
 
-__all__ = ["Hdf5Error", "File"]
+__all__ = ["Hdf5Error", "File", "Attributes"]
 
 _SIG = b"\x89HDF\r\n\x1a\n"
 _UNDEF = 0xFFFFFFFFFFFFFFFF
@@ -103,6 +106,10 @@ class Dataset:
         self.dtype = self._datatype(dt[0][2])
         self._layout = lay[0][2]
         self._filters = self._pipeline(obj.find(0x000B)[0][2]) if obj.find(0x000B) else []
+
+    @property
+    def attrs(self):
+        return Attributes(self.f, self.obj, self.name)
 
     @staticmethod
     def _dataspace(d):
@@ -253,10 +260,112 @@ class Dataset:
         return a.astype(dtype) if dtype is not None else a
 
 
+def _pad8(n):
+    return (n + 7) // 8 * 8
+
+
+class Attributes:
+    """An object's attribute messages (0x000C), read-only and dict-like, with h5py's value conventions: a scalar
+    attribute is a NumPy scalar (fixed-length strings: bytes), a 1-D one an array; variable-length strings are str.
+    Attributes kept in dense storage (an attribute-info message with a fractal heap) raise Hdf5Error."""
+
+    def __init__(self, f, obj, name):
+        self.f, self.name = f, name
+        self._raw = {}
+        for _t, _fl, d in obj.find(0x000C):
+            nm, dt, ds, data = self._split(d)
+            self._raw[nm] = (dt, ds, data)
+        if not self._raw:
+            for _t, _fl, d in obj.find(0x0015):     # attribute info: dense storage unless its heap address is undefined
+                pos = 2 + (2 if d[1] & 1 else 0)
+                fh, = struct.unpack_from("<Q", d, pos)
+                if fh != _UNDEF:
+                    raise Hdf5Error("dense attribute storage (fractal heap) in %s" % name)
+
+    @staticmethod
+    def _split(d):
+        ver = d[0]
+        nsz, tsz, ssz = struct.unpack_from("<HHH", d, 2)
+        if ver == 1:
+            pos = 8
+            nm = bytes(d[pos:pos + nsz]); pos += _pad8(nsz)
+            dt = bytes(d[pos:pos + tsz]); pos += _pad8(tsz)
+            ds = bytes(d[pos:pos + ssz]); pos += _pad8(ssz)
+        elif ver in (2, 3):
+            pos = 8 if ver == 2 else 9
+            nm = bytes(d[pos:pos + nsz]); pos += nsz
+            dt = bytes(d[pos:pos + tsz]); pos += tsz
+            ds = bytes(d[pos:pos + ssz]); pos += ssz
+        else:
+            raise Hdf5Error("attribute message version %d" % ver)
+        return nm.rstrip(b"\0").decode(), dt, ds, bytes(d[pos:])
+
+    def keys(self):
+        return list(self._raw)
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self):
+        return len(self._raw)
+
+    def __contains__(self, k):
+        return k in self._raw
+
+    def items(self):
+        return [(k, self[k]) for k in self._raw]
+
+    def get(self, k, default=None):
+        return self[k] if k in self._raw else default
+
+    def __getitem__(self, k):
+        if k not in self._raw:
+            raise KeyError("%s has no attribute %r" % (self.name, k))
+        dt, ds, data = self._raw[k]
+        if ds[0] == 2 and ds[3] == 2:       # null dataspace
+            return None
+        shape = Dataset._dataspace(ds)
+        if len(shape) > 1:
+            raise Hdf5Error("attribute %r of rank %d" % (k, len(shape)))
+        n = int(np.prod(shape)) if shape else 1
+        cls = dt[0] & 0x0F
+        if cls == 9:                        # variable-length
+            if (dt[1] & 0x0F) != 1:
+                raise Hdf5Error("variable-length sequence attribute %r" % k)
+            vals = [self._vlen_string(data, 16 * i) for i in range(n)]
+            return vals[0] if not shape else np.array(vals, dtype=object)
+        dtype = Dataset._datatype(dt)
+        a = np.frombuffer(data, dtype=dtype, count=n)     # (fixed-length strings: bytes, NULs stripped, as h5py)
+        return a[0] if not shape else a.reshape(shape).copy()
+
+    def _vlen_string(self, data, pos):
+        ln, addr, idx = struct.unpack_from("<IQI", data, pos)
+        if ln == 0 or addr == 0 or addr == _UNDEF:
+            return ""
+        b = self.f.buf
+        col = addr + self.f.base
+        if b[col:col + 4] != b"GCOL":
+            raise Hdf5Error("global heap signature")
+        csize, = struct.unpack_from("<Q", b, col + 8)
+        p, end = col + 16, col + csize
+        while p + 16 <= end:
+            oidx, _ref, osize = struct.unpack_from("<HH4xQ", b, p)
+            if oidx == 0:
+                break
+            if oidx == idx:
+                return bytes(b[p + 16:p + 16 + min(ln, osize)]).decode("utf-8")
+            p += 16 + _pad8(osize)
+        raise Hdf5Error("global heap object %d not found" % idx)
+
+
 class Group:
     def __init__(self, f, obj, name):
         self.f, self.obj, self.name = f, obj, name
         self._links = None
+
+    @property
+    def attrs(self):
+        return Attributes(self.f, self.obj, self.name)
 
     def _load(self):
         if self._links is not None:

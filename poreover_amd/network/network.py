@@ -1,0 +1,152 @@
+"""`call`: the basecalling network's forward pass on FAST5 reads (the reference's network.py:181-282), on the GPU.
+
+Host side, as the reference: parse_fast5 reads and scales the raw signal, batch_input cuts it into windows (zero-padded
+to whole windows; each window starts from a zero state, and the last window's padding is part of its input), and
+call_helper writes the softmax probabilities trimmed to len(signal) frames.  The network itself runs in HIP
+(poreover_amd/csrc/po_call.hip through po_call_batch_h): f32 weights and arithmetic, as the reference's TensorFlow
+graph.  Windows of many reads share device passes; that changes no output bit."""
+import ctypes as C
+import glob
+import logging
+import os
+from pathlib import Path
+
+import numpy as np
+
+from .. import _lib
+from ..decoding import hdf5_lite
+from . import checkpoint as ckpt
+
+__all__ = ["parse_fast5", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model"]
+
+SCALINGS = ("standard", "current", "median", "rescale", "raw")
+
+
+def parse_fast5(f, scaling="standard"):
+    """(read_id, scaled signal) of a single-read FAST5 file — network.py:199-239 line for line"""
+    hdf = hdf5_lite.File(f, "r")
+    read_string = list(hdf["/Raw/Reads"].keys())[0]
+    read = hdf["/Raw/Reads/" + read_string]
+    read_id = read.attrs["read_id"]
+    read_duration = read.attrs["duration"]
+    raw_signal = np.array(hdf["/Raw/Reads/" + read_string + "/Signal"])
+    if len(raw_signal) != read_duration:
+        raise ValueError("%s: %d signal samples, duration attribute %d" % (f, len(raw_signal), read_duration))
+    ch = hdf["UniqueGlobalKey"]["channel_id"].attrs
+    alpha = ch["digitisation"] / ch["range"]
+    offset = ch["offset"]
+    # very rough heuristic for abasic region (the reference's)
+    raw_signal = raw_signal[np.logical_and(raw_signal > 200, raw_signal < 800)]
+    if scaling == "standard":
+        signal = (raw_signal - np.mean(raw_signal)) / np.std(raw_signal)
+    elif scaling == "current":
+        signal = (raw_signal + offset) / alpha
+    elif scaling == "median":
+        signal = raw_signal / np.median(raw_signal)
+    elif scaling == "rescale":
+        signal = (raw_signal - np.mean(raw_signal)) / (np.max(raw_signal) - np.min(raw_signal))
+    elif scaling == "raw":
+        signal = raw_signal
+    else:
+        raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
+    return read_id, signal
+
+
+def batch_input(signal, window_size):
+    """(windows, frames): the signal zero-padded to whole windows, shape (n, window_size) float32, and len(signal) — the
+    number of output frames to keep (the reference pads to whole batches of 128 windows, network.py:241-251; the extra
+    all-zero windows it computes are discarded there, so they are not made here)"""
+    n = max(1, -(-len(signal) // window_size))
+    padded = np.zeros(n * window_size, dtype=np.float32)
+    padded[:len(signal)] = signal
+    return padded.reshape(n, window_size), len(signal)
+
+
+def _layers_array(net):
+    arr = (_lib.CallLayer * len(net.layers))()
+    for i, l in enumerate(net.layers):
+        arr[i].kind, arr[i].cin, arr[i].cout, arr[i].kernel = _lib.CALL_KINDS[l.kind], l.cin, l.cout, l.kernel
+    return arr
+
+
+def forward(net, windows, logits=False, stage_ms=None):
+    """softmax probabilities (n, T, 5) float32 of `windows` (n, T) through `net` on the device; with logits=True also the
+    Dense outputs; stage_ms (a dict) gets the device milliseconds per stage added (_lib.CALL_STAGES)"""
+    lib = _lib.load()
+    x = np.ascontiguousarray(windows, dtype=np.float32)
+    n, T = x.shape
+    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+    probs = np.empty((n, T, ckpt.NUM_LABELS), dtype=np.float32)
+    lg = np.empty_like(probs) if logits else None
+    ms = (C.c_float * 4)() if stage_ms is not None else None
+    rc = lib.po_call_batch_h(x.ctypes.data, n, T, _layers_array(net), len(net.layers), w.ctypes.data, w.size,
+                             probs.ctypes.data, lg.ctypes.data if logits else None, ms)
+    _lib.check(rc, "po_call_batch_h")
+    if stage_ms is not None:
+        for k, name in enumerate(_lib.CALL_STAGES):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+    return (probs, lg) if logits else probs
+
+
+def basecall_signals(net, signals, window=1000, no_stack=False, logits=False):
+    """[(len(s), 5) float32 probabilities] for each scaled signal: all reads' windows in shared device passes (windows
+    of one length go together; --no_stack: each read is one window of its own length, reads of equal length together)"""
+    groups = {}
+    for i, s in enumerate(signals):
+        T = max(1, len(s)) if no_stack else window
+        groups.setdefault(T, []).append(i)
+    out = [None] * len(signals)
+    for T, idx in groups.items():
+        parts = [batch_input(signals[i], T) for i in idx]
+        res = forward(net, np.concatenate([p[0] for p in parts]), logits=logits)
+        pr, lg = res if logits else (res, None)
+        k = 0
+        for i, (wins, frames) in zip(idx, parts):
+            nw = len(wins)
+            p = pr[k:k + nw].reshape(-1, ckpt.NUM_LABELS)[:frames]
+            out[i] = (p, lg[k:k + nw].reshape(-1, ckpt.NUM_LABELS)[:frames]) if logits else p
+            k += nw
+    return out
+
+
+def load_model(args):
+    """the Network of --weights (required: no weights ship with this package) and --model (None: conv1_bigru3)"""
+    weights = getattr(args, "weights", None)
+    if weights is None:
+        raise SystemExit("call: --weights is required (a TF checkpoint prefix, a directory with a `checkpoint` file, "
+                         "or an .npz written by `python -m poreover_amd.network.convert`); no weights ship with this package")
+    return ckpt.load_network(weights, getattr(args, "model", None))
+
+
+def _write(args, fast5_file, read_id, probs):
+    if getattr(args, "use_id", False):
+        rid = read_id.decode("utf-8") if isinstance(read_id, (bytes, np.bytes_)) else str(read_id)
+        out_prefix = os.path.join(args.dir, rid)
+    else:
+        out_prefix = os.path.join(args.dir, Path(fast5_file).stem)
+    if args.format == "csv":
+        np.savetxt(out_prefix + ".csv", probs, delimiter=",", header=",".join(["A", "C", "G", "T", ""]), comments="")
+        return out_prefix + ".csv"
+    np.save(out_prefix, probs)
+    return out_prefix + ".npy"
+
+
+def call_helper(args, model, files=None):
+    """basecall getattr(args, 'in') (or `files`) with `model` and write one output per read; returns the paths"""
+    files = [getattr(args, "in")] if files is None else files
+    parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
+    probs = basecall_signals(model, [s for _, s in parsed], window=args.window, no_stack=getattr(args, "no_stack", False))
+    return [_write(args, f, rid, p) for f, (rid, _), p in zip(files, parsed, probs)]
+
+
+def call(args):
+    """`poreover call IN`: IN is a FAST5 file or a directory of *.fast5 (network.py:181-197)"""
+    model = load_model(args)
+    src = getattr(args, "in")
+    files = sorted(glob.glob(os.path.join(src, "*.fast5"))) if os.path.isdir(src) else [src]
+    if not files:
+        raise SystemExit("call: no *.fast5 files in %s" % src)
+    os.makedirs(args.dir, exist_ok=True)
+    out = call_helper(args, model, files)
+    logging.info("call: %d read(s) -> %s", len(out), args.dir)
+    return out
