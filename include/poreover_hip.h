@@ -445,6 +445,37 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
 int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* layers_h, int n_layers,
                     const float* weights_h, int64_t n_weights, float* probs_h, float* logits_h, float* stage_ms_h);
 
+/* ---- CTC training of the basecalling network (`train`) -------------------------------------------
+ * Replaces the reference's TensorFlow training step (train_ctc_model, network.py:78-131): the forward pass above,
+ * tf.compat.v1.nn.ctc_loss (blank = class 4, softmax inside the loss) averaged over the batch, its gradient and Keras
+ * Adam.  A trainer holds the model (layers_h as for po_call_batch), its f32 parameters, their gradient and Adam's m, v
+ * on the current device, all in po_call_batch's flat weight layout, and workspace for max_batch windows of T samples.
+ *   - po_train_create returns NULL on an unusable model or a failed allocation (po_last_error says which)
+ *   - po_train_set_params loads n = the model's weight count parameters and resets Adam (m = v = 0, step 0);
+ *     po_train_get_params copies them back
+ *   - po_train_step runs one step on n (1 .. max_batch) windows: signal_h n * T f32 samples, labels_h the windows'
+ *     labels back to back (0..3 = A C G T), label_len_h[n] their lengths.  merge_repeated 0: the reference's default
+ *     lattice (ctc_merge_repeated = False: repeated labels are separate emissions, no blank needed between them); 1:
+ *     standard CTC.  A label must fit the window: L <= T (merge off), L + the number of adjacent equal labels <= T (on);
+ *     labels outside 0..3 and labels that do not fit are PO_E_ARG naming the window.  Writes loss_h[n] (-log P(label |
+ *     window) per window), grad_h (or NULL: the gradient of the batch-mean loss, flat layout).  update = 1 then applies
+ *     Adam: m += (g - m)(1 - beta1); v += (g^2 - v)(1 - beta2); p -= lr sqrt(1 - beta2^t) / (1 - beta1^t) m / (sqrt(v) + eps)
+ *     with t the trainer's step count after the increment; update = 0 leaves the parameters and Adam as they are.
+ *   - stage_ms_h (or NULL): HOST float[5] set to device milliseconds per stage, by events: 0 forward, 1 CTC loss and
+ *     gradient, 2 GRU backward recurrences, 3 weight and input gradients (GEMMs, bias sums, Dense / Conv1D backward), 4 Adam
+ *   - po_train_last copies the last step's logits (the Dense outputs, as po_call_batch's) and/or the gradient of the
+ *     batch-mean loss with respect to them (n * T * 5 f32 each, NULL skips) of its first n windows
+ * A step is synchronous, and its gradient is the same bits on every run (no float atomics). */
+typedef struct po_trainer po_trainer;
+po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max_batch, int T);
+void po_train_destroy(po_trainer* tr);
+int po_train_set_params(po_trainer* tr, const float* w_h, int64_t n);
+int po_train_get_params(po_trainer* tr, float* w_h, int64_t n);
+int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                  int merge_repeated, float lr, float beta1, float beta2, float eps, int update, float* loss_h,
+                  float* grad_h, float* stage_ms_h);
+int po_train_last(po_trainer* tr, int n, float* logits_h, float* dlogits_h);
+
 /* ---- timing aid for bench.py: HIP events on the stream the kernels run on ----------------- */
 void* po_event_create(void);
 int po_event_record(void* ev, void* stream);

@@ -1,8 +1,9 @@
-"""`python -m poreover_amd call|decode|pair-decode ...` — the call / decode / pair-decode sub-commands of the
-reference CLI (reference __main__.py:39-91) with the same flags and defaults, on the GPU engine.  `call` runs the
-basecalling network in HIP and needs `--weights` (no weights ship with this package: a TF checkpoint prefix or
-directory, or an .npz from `python -m poreover_amd.network.convert`).
-(`train` and `benchmark` are outside this engine's scope: SURVEY.md §2.)"""
+"""`python -m poreover_amd train|call|decode|pair-decode ...` — the train / call / decode / pair-decode sub-commands of
+the reference CLI (reference __main__.py:19-91) with the same flags and defaults, on the GPU engine.  `train` runs CTC
+training of the basecalling network in HIP and writes .npz checkpoints; `call` runs the network's forward pass and needs
+`--weights` (no weights ship with this package: a TF checkpoint prefix or directory, a `train` output directory, or an
+.npz from `python -m poreover_amd.network.convert`).
+(`benchmark`, which needs a genome mapper, is outside this engine's scope.)"""
 import argparse
 import logging
 import sys
@@ -15,6 +16,25 @@ def build_parser():
                                      description='PoreOver decoding on MI355X: consensus basecalling for nanopore sequencing')
     subparsers = parser.add_subparsers(dest="command")
     subparsers.required = True
+
+    p = subparsers.add_parser('train', help='Train a neural network base calling model', formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('--data', help='Location of training data in compressed npz format', required=True)
+    p.add_argument('--name', default='run', help='Name of run')
+    p.add_argument('--epochs', type=int, default=1, help='Number of epochs to train on')
+    p.add_argument('--save_every', type=int, default=1000, help='Frequency with which to save checkpoint files')
+    p.add_argument('--holdout', default=0.05, type=float, help='Fraction of training data to hold out for calculating test error')
+    p.add_argument('--loss_every', type=int, default=100, help='Frequency with which to output minibatch loss')
+    p.add_argument('--ctc_merge_repeated', action='store_true', default=False, help='boolean option for tf.compat.v1.nn.ctc_loss')
+    p.add_argument('--model', default='conv1_bigru3', choices=['bigru3', 'conv1_bigru3', 'conv2_bigru3', 'conv1_gru5'], help='Neural network architecture')
+    p.add_argument('--restart', default=False, help='Trained model to load (if directory, loads latest from checkpoint file)')
+    p.add_argument('--batch_size', default=64, type=int, help='Minibatch size for training')
+    p.add_argument('--learning_rate', type=float, default=0.001, help='Learning rate for Adam optimizer')
+    p.add_argument('--seed', type=int, default=None, help='Explicitly set random seed')
+    p.add_argument('--num_neurons', type=int, default=128, help='Number of neurons in RNN layers')
+    p.add_argument('--kernel_size', type=int, default=9, help='Kernel size in Conv1D layer')
+    p.add_argument('--filters', type=int, default=256, help='Number of filters in Conv1D layer')
+    p.add_argument('-v', '--version', action='version', version=__version__)
+    p.set_defaults(func="train")
 
     p = subparsers.add_parser('call', help='Run basecalling forward pass on set of FAST5 reads',
                               formatter_class=argparse.ArgumentDefaultsHelpFormatter)
@@ -72,6 +92,13 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     logging.basicConfig(format='%(message)s', level=logging.DEBUG if getattr(args, 'logging', 'info') == 'debug' else logging.INFO)
+    if args.func == "train":
+        from .network import train as _train
+        try:
+            _train.train(args)
+        except _train.TrainError as e:
+            raise SystemExit(str(e))
+        return
     if args.func == "call":
         from .network import call as _call
         if args.window < 1:

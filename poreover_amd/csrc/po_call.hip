@@ -21,190 +21,14 @@
 // output is the same bits whichever batch, tile or chunk it runs in.
 #include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
-#include "po_device.h"
+#include "po_call_kernels.h"
 
 extern "C" void po_set_error(const char* msg);
 
 namespace {
-
-constexpr int H = 128;          // GRU units
-constexpr int G = 3 * H;        // gate columns per direction
-constexpr int NOUT = 5;         // Dense outputs (A, C, G, T, blank)
-constexpr int RT = 16;          // windows per recurrence workgroup (the MFMA's M)
-constexpr int RWAVES = H / 16;  // 8 waves, 16 units each
-constexpr int HS = H + 1;       // LDS row stride of h (one pad word: the 16 rows of an MFMA operand hit distinct banks)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// out[m][f] = relu(bias[f] + sum_{j, c} x[w][t + j - padl][c] * W[j][c][f]), m = w * T + t, rows outside [0, T) read 0
-__global__ __launch_bounds__(256) void conv_relu_kernel(const float* __restrict__ x, int cin, const float* __restrict__ Wt,
-                                                        const float* __restrict__ bias, int K, int F, float* __restrict__ out,
-                                                        int64_t M, int T) {
-    const int64_t m = blockIdx.x;
-    const int t = (int)(m % T);
-    const int64_t w0 = m - t;
-    const int padl = (K - 1) / 2;
-    for (int f = threadIdx.x; f < F; f += blockDim.x) {
-        float acc = 0.f;
-        for (int j = 0; j < K; ++j) {
-            const int ts = t + j - padl;
-            if (ts < 0 || ts >= T) continue;
-            const float* xr = x + (w0 + ts) * cin;
-            const float* wr = Wt + (int64_t)j * cin * F + f;
-            for (int c = 0; c < cin; ++c) acc = fmaf(xr[c], wr[(int64_t)c * F], acc);
-        }
-        out[m * F + f] = fmaxf(acc + bias[f], 0.f);
-    }
-}
-
-// P[d][m][c] = sum_k x[m][k] * W[d][k][c] + b_in[d][c] for m < M, c < 384, d < ndir.  One wave per 16 rows x 64 columns
-// (four 16 x 16 accumulators), four waves per workgroup along the rows; K is walked 4 at a time, zero-filled past cin.
-__global__ __launch_bounds__(256) void gru_proj_kernel(const float* __restrict__ x, int cin, const float* __restrict__ W,
-                                                       const float* __restrict__ bin, int64_t wstride, int64_t bstride,
-                                                       float* __restrict__ P, int64_t M) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
-    if (m0 >= M) return;
-    const int d = blockIdx.y / (G / 64);
-    const int c0 = (blockIdx.y % (G / 64)) * 64;
-    const float* Wd = W + d * wstride;
-    const int i = lane & 15, kq = lane >> 4;
-    const int64_t arow = m0 + i;
-    const bool arow_ok = arow < M;
-    f32x4 acc[4];
-    for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < cin; k0 += 4) {
-        const int k = k0 + kq;
-        const bool kok = k < cin;
-        const float a = (arow_ok && kok) ? x[arow * cin + k] : 0.f;
-        const float* wr = Wd + (int64_t)k * G + c0 + i;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = mfma4(a, kok ? wr[q * 16] : 0.f, acc[q]);
-    }
-    float* Pd = P + (int64_t)d * M * G;
-    const float* bd = bin + d * bstride;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int col = c0 + q * 16 + i;
-        const float b = bd[col];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int64_t row = m0 + kq * 4 + r;
-            if (row < M) Pd[row * G + col] = acc[q][r] + b;
-        }
-    }
-}
-
-struct RecurDir {
-    const float* P;     // [n * T][384] input projections of this direction
-    const float* U;     // [128][384] recurrent kernel
-    const float* brec;  // [384] recurrent bias
-    int backward;       // walk t = T-1 .. 0
-    int rev_out;        // write step s at position s (go_backwards without Bidirectional) instead of at t
-    int col;            // first output channel
-};
-struct RecurArgs {
-    RecurDir dir[2];
-    float* out;         // [n * T][out_stride]
-    int out_stride, n, T;
-};
-
-__device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
-
-__global__ __launch_bounds__(RWAVES * 64) void gru_recur_kernel(RecurArgs a) {
-    __shared__ float hs[2][RT][HS];
-    const RecurDir D = a.dir[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, kq = lane >> 4;
-    const int unit = wave * 16 + i;
-    const int w0 = blockIdx.x * RT;
-    const int T = a.T;
-    // this lane's B operands for every k-step and gate: U[4 kk + kq][g * 128 + unit]
-    float u[3][H / 4];
-#pragma unroll
-    for (int kk = 0; kk < H / 4; ++kk)
-#pragma unroll
-        for (int g = 0; g < 3; ++g) u[g][kk] = D.U[(4 * kk + kq) * G + g * H + unit];
-    float br[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) br[g] = D.brec[g * H + unit];
-    for (int e = threadIdx.x; e < 2 * RT * HS; e += blockDim.x) (&hs[0][0][0])[e] = 0.f;
-    float h[4] = {0.f, 0.f, 0.f, 0.f};     // (window w0 + kq * 4 + r, unit): the lane's own slice of the state
-    bool live[4];
-    const float* prow[4];
-    float* orow[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int w = w0 + kq * 4 + r;
-        live[r] = w < a.n;
-        prow[r] = D.P + (int64_t)(live[r] ? w : 0) * T * G + unit;
-        orow[r] = a.out + (int64_t)(live[r] ? w : 0) * T * a.out_stride + D.col + unit;
-    }
-    __syncthreads();
-    for (int s = 0; s < T; ++s) {
-        const int t = D.backward ? T - 1 - s : s;
-        const int to = D.rev_out ? s : t;
-        const int cur = s & 1;
-        float px[4][3];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int g = 0; g < 3; ++g) px[r][g] = live[r] ? prow[r][(int64_t)t * G + g * H] : 0.f;
-        f32x4 acc[3];
-#pragma unroll
-        for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float* hrow = &hs[cur][i][0];
-#pragma unroll
-        for (int kk = 0; kk < H / 4; ++kk) {
-            const float hv = hrow[4 * kk + kq];
-#pragma unroll
-            for (int g = 0; g < 3; ++g) acc[g] = mfma4(hv, u[g][kk], acc[g]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float z = sigmoidf_(px[r][0] + (acc[0][r] + br[0]));
-            const float rg = sigmoidf_(px[r][1] + (acc[1][r] + br[1]));
-            const float hh = tanhf(px[r][2] + rg * (acc[2][r] + br[2]));
-            const float hn = z * h[r] + (1.f - z) * hh;
-            if (live[r]) {
-                h[r] = hn;
-                hs[cur ^ 1][kq * 4 + r][unit] = hn;
-                orow[r][(int64_t)to * a.out_stride] = hn;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// probs[m][c] = softmax(x[m]·Wd + bd)[c]; logits too when asked
-__global__ __launch_bounds__(256) void dense_softmax_kernel(const float* __restrict__ x, int cin, const float* __restrict__ Wd,
-                                                            const float* __restrict__ bd, float* __restrict__ probs,
-                                                            float* __restrict__ logits, int64_t M) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    float acc[NOUT];
-    for (int c = 0; c < NOUT; ++c) acc[c] = 0.f;
-    const float* xr = x + m * cin;
-    for (int k = 0; k < cin; ++k) {
-        const float v = xr[k];
-#pragma unroll
-        for (int c = 0; c < NOUT; ++c) acc[c] = fmaf(v, Wd[k * NOUT + c], acc[c]);
-    }
-    float mx = -__builtin_inff();
-    for (int c = 0; c < NOUT; ++c) { acc[c] += bd[c]; mx = fmaxf(mx, acc[c]); }
-    float e[NOUT], sum = 0.f;
-    for (int c = 0; c < NOUT; ++c) { e[c] = expf(acc[c] - mx); sum += e[c]; }
-    for (int c = 0; c < NOUT; ++c) {
-        probs[m * NOUT + c] = e[c] / sum;
-        if (logits) logits[m * NOUT + c] = acc[c];
-    }
-}
 
 thread_local std::string g_call_err;
 int call_fail(int code, const std::string& msg) {
@@ -222,34 +46,7 @@ int call_hip(hipError_t e, const char* what) {
     } while (0)
 
 // the model checked against the weights' length; returns the widest activation (channels) or a PO_E_* code
-int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
-    if (!L || nl < 1) return call_fail(PO_E_ARG, "po_call: empty model");
-    int64_t wmax = 1, nw = 0;
-    int cin = 1;
-    for (int k = 0; k < nl; ++k) {
-        const po_call_layer& l = L[k];
-        if (l.cin != cin) return call_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " takes " + std::to_string(l.cin) +
-                                                         " channels, its input has " + std::to_string(cin));
-        if (l.kind == PO_CALL_CONV) {
-            if (l.cout < 1 || l.kernel < 1 || l.kernel > 64) return call_fail(PO_E_ARG, "po_call: conv filters / kernel size");
-            nw += (int64_t)l.kernel * l.cin * l.cout + l.cout;
-        } else if (l.kind == PO_CALL_BIGRU || l.kind == PO_CALL_GRU || l.kind == PO_CALL_GRU_BACK) {
-            const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
-            if (l.cout != nd * H) return call_fail(PO_E_UNSUPPORTED, "po_call: GRU layers have 128 units per direction");
-            nw += nd * ((int64_t)l.cin * G + (int64_t)H * G + 2 * G);
-        } else if (l.kind == PO_CALL_DENSE) {
-            if (k != nl - 1 || l.cout != NOUT) return call_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
-            nw += (int64_t)l.cin * NOUT + NOUT;
-        } else {
-            return call_fail(PO_E_ARG, "po_call: layer kind " + std::to_string(l.kind));
-        }
-        cin = l.cout;
-        wmax = std::max<int64_t>(wmax, l.cout);
-    }
-    if (L[nl - 1].kind != PO_CALL_DENSE) return call_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
-    *nweights = nw;
-    return wmax;
-}
+int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) { return check_model_for(L, nl, nweights, call_fail); }
 
 inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 

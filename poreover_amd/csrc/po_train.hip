@@ -1,0 +1,834 @@
+// CTC training of the basecalling network (`poreover train`) on the device, in f32 like `call` (the CTC lattice in f64).
+//
+// Replaces, from network/network.py of the reference: train_ctc_model's step (network.py:78-131): the Keras model's
+// forward pass, tf.compat.v1.nn.ctc_loss averaged over the batch, its gradient through GradientTape and Keras Adam.
+// The forward pass is `call`'s (po_call_kernels.h), with the recurrence also saving what backpropagation needs.  One
+// step, for a batch of n windows of T samples:
+//
+//   forward            conv_relu_kernel, gru_proj_kernel, gru_recur_body<SAVE = true>, dense_softmax_kernel; every
+//                      layer's output is kept
+//   ctc_lsm_kernel     log-softmax of the logits, f64, one lane per frame
+//   ctc_alpha_beta_kernel  one workgroup per window: the α and β recursions over the 2L+1 states, f64 in log space;
+//                      merge_repeated = 0 is the decoder's `ctc` lattice (label states do not self-loop, a blank may always
+//                      be skipped), 1 is standard CTC; writes -log Z
+//   ctc_grad_kernel    one lane per frame: dlogits = (softmax - posterior occupancy) / n, summed over states in order
+//   dense backward     dW = Xᵀ·dlogits (wgrad), db = column sums, dX = dlogits·Wᵀ (dense_dx_kernel)
+//   gru_back_recur_kernel  BPTT, one persistent launch per GRU layer covering both directions, the mirror of the forward
+//                      recurrence: 16 windows x one direction per workgroup, 8 waves x 16 units; each lane keeps its unit's
+//                      row of U (384 f32 = 96 VGPRs) as the B operand of dh_prev = dh⊙z + dR·Uᵀ (96 MFMA per step); dR
+//                      passes through LDS, double buffered (one barrier per step)
+//   wgrad_kernel + combine_kernel  every weight gradient as Aᵀ·B over the M = n·T rows on v_mfma_f32_16x16x4_f32: dW = Xᵀ·dA,
+//                      dU = H_prevᵀ·dR, Conv1D dW per tap from row-shifted inputs; split over M in a fixed partition, the
+//                      partial sums combined in a fixed order by a second launch (colsum_kernel: the bias gradients so)
+//   dx_kernel          dX = Σ_d dA_d·W_dᵀ of a GRU layer (directions in a fixed order); conv_dx_kernel for a deeper Conv1D
+//   adam_kernel        Keras Adam on the flat parameter vector
+// No float atomics and no hand-off between workgroups within a launch: a step's gradient is the same bits every run.
+//
+// BPTT of one direction, walk step s (input time t, output position to), dh = dout[to] + the carried dh:
+//   dz = dh·(h_prev − h~);  dah = dh·(1 − z)·(1 − h~²);  dr = dah·u_h;  daz = dz·z(1 − z);  dar = dr·r(1 − r)
+//   dA = (daz, dar, dah) → input projection and b_in;  dR = (daz, dar, dah·r) → U and b_rec;  dh_prev = dh·z + dR·Uᵀ
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "po_call_kernels.h"
+
+extern "C" void po_set_error(const char* msg);
+
+namespace {
+
+constexpr int GS = G + 1;        // LDS row stride of dR (one pad word: the 16 rows of an MFMA operand hit distinct banks)
+constexpr int WG_ROWS = 1024;    // rows per split of the M-reductions (at most MAX_SPLIT splits)
+constexpr int MAX_SPLIT = 64;
+constexpr int NSTAGE = 5;        // forward, CTC, backward recurrence, weight and input GEMMs, Adam
+
+__device__ __forceinline__ double lse2(double a, double b) {
+    const double m = fmax(a, b);
+    if (m == -INFINITY) return -INFINITY;
+    return m + log1p(exp(-fabs(a - b)));
+}
+
+// lsm[m][c] = log softmax(logits[m])[c] in f64
+__global__ __launch_bounds__(256) void ctc_lsm_kernel(const float* __restrict__ logits, double* __restrict__ lsm, int64_t M) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    double x[NOUT], mx = -INFINITY, sum = 0.0;
+    for (int c = 0; c < NOUT; ++c) { x[c] = logits[m * NOUT + c]; mx = fmax(mx, x[c]); }
+    for (int c = 0; c < NOUT; ++c) sum += exp(x[c] - mx);
+    const double lz = mx + log(sum);
+    for (int c = 0; c < NOUT; ++c) lsm[m * NOUT + c] = x[c] - lz;
+}
+
+// state s of a window with labels lab[0..L): blank (4) for even s, lab[(s - 1) / 2] for odd s
+__device__ __forceinline__ int state_label(const int32_t* lab, int s) { return (s & 1) ? lab[s >> 1] : NOUT - 1; }
+// may the path reach label state s (odd) from label state s - 2, skipping the blank between?
+__device__ __forceinline__ bool skip_ok(const int32_t* lab, int s, int merge) {
+    return s >= 3 && (!merge || lab[s >> 1] != lab[(s >> 1) - 1]);
+}
+
+// One workgroup per window.  A[t][s] = log P(frames 0..t, state s at t), B[t][s] = log P(frames t+1..T-1 | state s at
+// t) (exclusive of frame t), rows of S = 2L+1 states at stride Smax; logz[w] = log P(label | window)
+__global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const double* __restrict__ lsm, const int32_t* __restrict__ labels,
+                                                             const int64_t* __restrict__ loff, int T, int Smax, int merge,
+                                                             double* __restrict__ A, double* __restrict__ B,
+                                                             double* __restrict__ logz) {
+    const int w = blockIdx.x;
+    const int32_t* lab = labels + loff[w];
+    const int L = (int)(loff[w + 1] - loff[w]);
+    const int S = 2 * L + 1;
+    const double* lp = lsm + (int64_t)w * T * NOUT;
+    double* Aw = A + (int64_t)w * T * Smax;
+    double* Bw = B + (int64_t)w * T * Smax;
+    for (int s = threadIdx.x; s < S; s += blockDim.x)
+        Aw[s] = s == 0 ? lp[NOUT - 1] : (s == 1 ? lp[lab[0]] : -INFINITY);
+    __syncthreads();
+    for (int t = 1; t < T; ++t) {
+        const double* prev = Aw + (int64_t)(t - 1) * Smax;
+        double* row = Aw + (int64_t)t * Smax;
+        for (int s = threadIdx.x; s < S; s += blockDim.x) {
+            const bool lbl = s & 1;
+            double v = (!lbl || merge) ? prev[s] : -INFINITY;
+            if (s >= 1) v = lse2(v, prev[s - 1]);
+            if (lbl && skip_ok(lab, s, merge)) v = lse2(v, prev[s - 2]);
+            row[s] = v + lp[(int64_t)t * NOUT + state_label(lab, s)];
+        }
+        __syncthreads();
+    }
+    for (int s = threadIdx.x; s < S; s += blockDim.x)
+        Bw[(int64_t)(T - 1) * Smax + s] = (s == S - 1 || s == S - 2) ? 0.0 : -INFINITY;
+    __syncthreads();
+    for (int t = T - 2; t >= 0; --t) {
+        const double* nx = Bw + (int64_t)(t + 1) * Smax;
+        const double* lpn = lp + (int64_t)(t + 1) * NOUT;
+        double* row = Bw + (int64_t)t * Smax;
+        for (int s = threadIdx.x; s < S; s += blockDim.x) {
+            const bool lbl = s & 1;
+            double v = (!lbl || merge) ? nx[s] + lpn[state_label(lab, s)] : -INFINITY;
+            if (s + 1 < S) v = lse2(v, nx[s + 1] + lpn[state_label(lab, s + 1)]);
+            if (lbl && s + 2 < S && skip_ok(lab, s + 2, merge)) v = lse2(v, nx[s + 2] + lpn[state_label(lab, s + 2)]);
+            row[s] = v;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double* last = Aw + (int64_t)(T - 1) * Smax;
+        logz[w] = S >= 2 ? lse2(last[S - 1], last[S - 2]) : last[0];
+    }
+}
+
+// dlogits[m][c] = (softmax[m][c] - sum_{s: label(s) = c} exp(A + B - log Z)) * inv_n; loss[w] = -log Z
+__global__ __launch_bounds__(256) void ctc_grad_kernel(const double* __restrict__ lsm, const int32_t* __restrict__ labels,
+                                                       const int64_t* __restrict__ loff, int n, int T, int Smax,
+                                                       const double* __restrict__ A, const double* __restrict__ B,
+                                                       const double* __restrict__ logz, float inv_n,
+                                                       float* __restrict__ dlogits, float* __restrict__ loss) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= (int64_t)n * T) return;
+    const int w = (int)(m / T), t = (int)(m % T);
+    const int32_t* lab = labels + loff[w];
+    const int S = 2 * (int)(loff[w + 1] - loff[w]) + 1;
+    const double lz = logz[w];
+    const double* a = A + ((int64_t)w * T + t) * Smax;
+    const double* b = B + ((int64_t)w * T + t) * Smax;
+    double occ[NOUT] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int s = 0; s < S; ++s) occ[state_label(lab, s)] += exp(a[s] + b[s] - lz);
+    for (int c = 0; c < NOUT; ++c) dlogits[m * NOUT + c] = (float)(exp(lsm[m * NOUT + c]) - occ[c]) * inv_n;
+    if (t == 0) loss[w] = (float)(-lz);
+}
+
+// dX[m][c] = sum_k dY[m][k] * Wd[c][k]  (Dense: k < 5)
+__global__ __launch_bounds__(256) void dense_dx_kernel(const float* __restrict__ dY, const float* __restrict__ Wd, int cin,
+                                                       float* __restrict__ dX, int64_t M) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= M * cin) return;
+    const int64_t m = e / cin;
+    const int c = (int)(e % cin);
+    float acc = 0.f;
+    for (int k = 0; k < NOUT; ++k) acc = fmaf(dY[m * NOUT + k], Wd[c * NOUT + k], acc);
+    dX[e] = acc;
+}
+
+// dY[e] = 0 where the ReLU output is 0 (the Conv1D's pre-activation gradient, in place)
+__global__ __launch_bounds__(256) void relu_mask_kernel(float* __restrict__ dY, const float* __restrict__ out, int64_t n) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < n && !(out[e] > 0.f)) dY[e] = 0.f;
+}
+
+// part[z][p0 + k][c] = sum over rows m of split z of A[m + shift][k] * Bm[m][c], k < K, c < N; the A row counts as zero
+// where its time index m % T + shift falls outside [0, T) (Conv1D taps).  One wave per 16 (k) x 64 (c) tile, four waves
+// per workgroup along k; the split's rows are walked 4 at a time (v_mfma_f32_16x16x4_f32, zero-filled past its end).
+__global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ Bm,
+                                                    int64_t ldb, int K, int N, int64_t M, int T, int shift, int64_t rows,
+                                                    float* __restrict__ part, int ldp, int p0, int64_t pstride) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k0 = (blockIdx.x * 4 + wave) * 16;
+    if (k0 >= K) return;
+    const int c0 = blockIdx.y * 64;
+    const int i = lane & 15, kq = lane >> 4;
+    const int64_t mbeg = (int64_t)blockIdx.z * rows, mend = mbeg + rows < M ? mbeg + rows : M;
+    const bool kok = k0 + i < K;
+    f32x4 acc[4];
+    for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int64_t m0 = mbeg; m0 < mend; m0 += 4) {
+        const int64_t m = m0 + kq;
+        const bool mok = m < mend;
+        bool aok = mok && kok;
+        if (shift != 0 && aok) {
+            const int ts = (int)(m % T) + shift;
+            aok = ts >= 0 && ts < T;
+        }
+        const float a = aok ? A[(m + shift) * lda + k0 + i] : 0.f;
+        const float* br = Bm + (mok ? m : 0) * ldb + c0 + i;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool cok = mok && c0 + q * 16 + i < N;
+            acc[q] = mfma4(a, cok ? br[q * 16] : 0.f, acc[q]);
+        }
+    }
+    float* pz = part + (int64_t)blockIdx.z * pstride;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = c0 + q * 16 + i;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = k0 + kq * 4 + r;
+            if (k < K && c < N) pz[(int64_t)(p0 + k) * ldp + c] = acc[q][r];
+        }
+    }
+}
+
+// part[z][c] = sum over rows m of split z of X[m][c], in row order
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ X, int64_t ldx, int N, int64_t M,
+                                                     int64_t rows, float* __restrict__ part, int64_t pstride) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const int64_t mbeg = (int64_t)blockIdx.y * rows, mend = mbeg + rows < M ? mbeg + rows : M;
+    float acc = 0.f;
+    for (int64_t m = mbeg; m < mend; ++m) acc += X[m * ldx + c];
+    part[(int64_t)blockIdx.y * pstride + c] = acc;
+}
+
+// out[e] = sum_{z < nz} part[z][e], in z order
+__global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ part, int nz, int64_t pstride, int64_t n,
+                                                      float* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    float acc = part[e];
+    for (int z = 1; z < nz; ++z) acc += part[(int64_t)z * pstride + e];
+    out[e] = acc;
+}
+
+// dX[m][c] = sum_{d < nd} sum_k dA_d[m][k] * W_d[c][k], k < 384: the GRU layer's input gradient.  One wave per 16 rows x
+// 64 columns, four waves per workgroup along the rows (gru_proj_kernel's tiling).
+__global__ __launch_bounds__(256) void dx_kernel(const float* __restrict__ dA, int64_t dastride, const float* __restrict__ W,
+                                                 int64_t wstride, int nd, int cin, float* __restrict__ dX, int64_t M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
+    if (m0 >= M) return;
+    const int c0 = blockIdx.y * 64;
+    const int i = lane & 15, kq = lane >> 4;
+    const int64_t arow = m0 + i;
+    const bool arow_ok = arow < M;
+    f32x4 acc[4];
+    for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int d = 0; d < nd; ++d) {
+        const float* Ad = dA + d * dastride + (arow_ok ? arow : 0) * G;
+        const float* Wd = W + d * wstride;
+        for (int k0 = 0; k0 < G; k0 += 4) {
+            const int k = k0 + kq;
+            const float a = arow_ok ? Ad[k] : 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = c0 + q * 16 + i;
+                acc[q] = mfma4(a, c < cin ? Wd[(int64_t)c * G + k] : 0.f, acc[q]);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int c = c0 + q * 16 + i;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t row = m0 + kq * 4 + r;
+            if (row < M && c < cin) dX[row * cin + c] = acc[q][r];
+        }
+    }
+}
+
+// dX[m][c] = sum_j sum_f dpre[w][t - j + padl][f] * Wt[j][c][f] (rows outside [0, T) read 0): a deeper Conv1D's input
+// gradient, one lane per element
+__global__ __launch_bounds__(256) void conv_dx_kernel(const float* __restrict__ dpre, const float* __restrict__ Wt, int K,
+                                                      int cin, int F, float* __restrict__ dX, int64_t M, int T) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= M * cin) return;
+    const int64_t m = e / cin;
+    const int c = (int)(e % cin);
+    const int t = (int)(m % T);
+    const int64_t w0 = m - t;
+    const int padl = (K - 1) / 2;
+    float acc = 0.f;
+    for (int j = 0; j < K; ++j) {
+        const int ts = t - j + padl;
+        if (ts < 0 || ts >= T) continue;
+        const float* dr = dpre + (w0 + ts) * F;
+        const float* wr = Wt + ((int64_t)j * cin + c) * F;
+        for (int f = 0; f < F; ++f) acc = fmaf(dr[f], wr[f], acc);
+    }
+    dX[e] = acc;
+}
+
+struct BackDir {
+    const float* save;  // [n * T][SV] the forward recurrence's saved values, walk order
+    const float* U;     // [128][384] recurrent kernel
+    float* dA;          // [n * T][384] input-projection gradient (daz, dar, dah) at input time t
+    float* dR;          // [n * T][384] recurrent gradient (daz, dar, dah·r), walk order
+    int backward, rev_out, col;
+};
+struct BackArgs {
+    BackDir dir[2];
+    const float* dout;  // [n * T][dout_stride] gradient of the layer's output
+    int dout_stride, n, T;
+};
+
+// LDS-only barrier: the stores of dA / dR to global memory need not complete before the next step
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__global__ __launch_bounds__(RWAVES * 64) void gru_back_recur_kernel(BackArgs a) {
+    __shared__ float ds[2][RT][GS];
+    const BackDir D = a.dir[blockIdx.y];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, kq = lane >> 4;
+    const int unit = wave * 16 + i;
+    const int w0 = blockIdx.x * RT;
+    const int T = a.T;
+    // this lane's B operands: Uᵀ[4 kk + kq][unit] = U[unit][4 kk + kq]
+    float u[G / 4];
+#pragma unroll
+    for (int kk = 0; kk < G / 4; ++kk) u[kk] = D.U[(int64_t)unit * G + 4 * kk + kq];
+    for (int e = threadIdx.x; e < 2 * RT * GS; e += blockDim.x) (&ds[0][0][0])[e] = 0.f;   // rows of absent windows stay 0
+    bool live[4];
+    int64_t wrow[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int w = w0 + kq * 4 + r;
+        live[r] = w < a.n;
+        wrow[r] = (int64_t)(live[r] ? w : 0) * T;
+    }
+    float carry[4] = {0.f, 0.f, 0.f, 0.f};
+    float sv[4][5], go[4];
+    auto fetch = [&](int s) {
+        const int to = D.rev_out ? s : (D.backward ? T - 1 - s : s);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float* p = D.save + (wrow[r] + s) * SV + unit;
+#pragma unroll
+            for (int g = 0; g < 5; ++g) sv[r][g] = live[r] ? p[g * H] : 0.f;
+            go[r] = live[r] ? a.dout[(wrow[r] + to) * a.dout_stride + D.col + unit] : 0.f;
+        }
+    };
+    __syncthreads();
+    fetch(T - 1);
+    for (int s = T - 1; s >= 0; --s) {
+        const int t = D.backward ? T - 1 - s : s;
+        const int cur = s & 1;
+        float dhz[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float z = sv[r][0], rg = sv[r][1], hh = sv[r][2], uh = sv[r][3], hp = sv[r][4];
+            const float dh = go[r] + carry[r];
+            const float dz = dh * (hp - hh);
+            const float dah = dh * (1.f - z) * (1.f - hh * hh);
+            const float dr = dah * uh;
+            const float daz = dz * z * (1.f - z);
+            const float dar = dr * rg * (1.f - rg);
+            const float drh = dah * rg;
+            dhz[r] = dh * z;
+            if (live[r]) {
+                float* pa = D.dA + (wrow[r] + t) * G + unit;
+                float* pr = D.dR + (wrow[r] + s) * G + unit;
+                pa[0] = daz; pa[H] = dar; pa[2 * H] = dah;
+                pr[0] = daz; pr[H] = dar; pr[2 * H] = drh;
+                float* l = &ds[cur][kq * 4 + r][unit];
+                l[0] = daz; l[H] = dar; l[2 * H] = drh;
+            }
+        }
+        lds_barrier();
+        if (s > 0) fetch(s - 1);   // in flight during the MFMAs
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        const float* drow = &ds[cur][i][0];
+#pragma unroll
+        for (int kk = 0; kk < G / 4; ++kk) acc = mfma4(drow[4 * kk + kq], u[kk], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) carry[r] = dhz[r] + acc[r];
+    }
+}
+
+// Keras Adam (ResourceApplyAdam): m += (g - m)(1 - b1); v += (g² - v)(1 - b2); p -= lr_t · m / (sqrt(v) + eps)
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n, float lr_t, float b1, float b2, float eps) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n) return;
+    const float ge = g[e];
+    const float me = m[e] + (ge - m[e]) * (1.f - b1);
+    const float ve = v[e] + (ge * ge - v[e]) * (1.f - b2);
+    m[e] = me;
+    v[e] = ve;
+    p[e] = p[e] - lr_t * me / (sqrtf(ve) + eps);
+}
+
+thread_local std::string g_train_err;
+int train_fail(int code, const std::string& msg) {
+    g_train_err = msg;
+    po_set_error(msg.c_str());
+    return code;
+}
+int train_hip(hipError_t e, const char* what) {
+    return train_fail(PO_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+#define TRCHK(x)                                        \
+    do {                                                \
+        hipError_t e_ = (x);                            \
+        if (e_ != hipSuccess) return train_hip(e_, #x); \
+    } while (0)
+
+int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) { return check_model_for(L, nl, nweights, train_fail); }
+
+__global__ __launch_bounds__(RWAVES * 64) void gru_recur_save_kernel(RecurArgs a, float* save0, float* save1) {
+    __shared__ float hs[2][RT][HS];
+    gru_recur_body<true>(a, blockIdx.y ? save1 : save0, hs);
+}
+
+inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
+
+}  // namespace
+
+struct po_trainer {
+    std::vector<po_call_layer> layers;
+    std::vector<int64_t> woff;          // each layer's first weight
+    int max_batch = 0, T = 0;
+    int64_t nw = 0, wmax = 0;
+    int64_t step = 0;                   // Adam's t
+    float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
+    float* sig = nullptr;
+    std::vector<float*> act;            // each layer's output [max_batch * T][cout]
+    std::vector<float*> save;           // per GRU direction [max_batch * T][SV], 2 per layer (the second unused for 1-dir)
+    float *P = nullptr, *probs = nullptr, *dlog = nullptr, *loss = nullptr;
+    float *dact[2] = {nullptr, nullptr}, *dA = nullptr, *dR = nullptr, *part = nullptr;
+    double *lsm = nullptr, *logz = nullptr, *alpha = nullptr, *beta = nullptr;
+    size_t ab_cap = 0, lab_cap = 0;
+    int32_t* lab = nullptr;
+    int64_t* loff = nullptr;
+    int64_t part_cap = 0;
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+void trainer_free(po_trainer* tr) {
+    auto f = [](void* q) { if (q) (void)hipFree(q); };
+    for (void* q : {(void*)tr->p, (void*)tr->g, (void*)tr->m, (void*)tr->v, (void*)tr->sig, (void*)tr->P, (void*)tr->probs,
+                    (void*)tr->dlog, (void*)tr->loss, (void*)tr->dact[0], (void*)tr->dact[1], (void*)tr->dA, (void*)tr->dR,
+                    (void*)tr->part, (void*)tr->lsm, (void*)tr->logz, (void*)tr->alpha, (void*)tr->beta, (void*)tr->lab,
+                    (void*)tr->loff})
+        f(q);
+    for (float* q : tr->act) f(q);
+    for (float* q : tr->save) f(q);
+    if (tr->stream) (void)hipStreamDestroy(tr->stream);
+    delete tr;
+}
+
+int64_t split_rows(int64_t M) {
+    const int64_t nz = std::min<int64_t>(MAX_SPLIT, std::max<int64_t>(1, (M + WG_ROWS - 1) / WG_ROWS));
+    return ((M + nz - 1) / nz + 3) / 4 * 4;
+}
+
+// grad[0 .. K·N) = sum over the M rows of A[m + shift]ᵀ·B[m] (one call per Conv1D tap: rows p0 .. p0 + K of a K_tot x N
+// result); the partial sums of the splits, then their fixed-order combine
+int wgrad(po_trainer* tr, const float* A, int64_t lda, const float* B, int64_t ldb, int K, int N, int64_t M, int shift,
+          int p0, int Ktot, float* out, bool combine) {
+    const int64_t rows = split_rows(M);
+    const int nz = (int)((M + rows - 1) / rows);
+    const int64_t pstride = (int64_t)Ktot * N;
+    if ((int64_t)nz * pstride > tr->part_cap) return train_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
+    hipLaunchKernelGGL(wgrad_kernel, dim3(blocks(K, 64), blocks(N, 64), nz), dim3(256), 0, tr->stream, A, lda, B, ldb, K, N,
+                       M, tr->T, shift, rows, tr->part, N, p0, pstride);
+    if (combine)
+        hipLaunchKernelGGL(combine_kernel, dim3(blocks(pstride, 256)), dim3(256), 0, tr->stream, tr->part, nz, pstride,
+                           pstride, out);
+    return PO_OK;
+}
+
+int colsum(po_trainer* tr, const float* X, int64_t ldx, int N, int64_t M, float* out) {
+    const int64_t rows = split_rows(M);
+    const int nz = (int)((M + rows - 1) / rows);
+    if ((int64_t)nz * N > tr->part_cap) return train_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
+    hipLaunchKernelGGL(colsum_kernel, dim3(blocks(N, 256), nz), dim3(256), 0, tr->stream, X, ldx, N, M, rows, tr->part,
+                       (int64_t)N);
+    hipLaunchKernelGGL(combine_kernel, dim3(blocks(N, 256)), dim3(256), 0, tr->stream, tr->part, nz, (int64_t)N, (int64_t)N,
+                       out);
+    return PO_OK;
+}
+
+struct Timer {
+    po_trainer* tr;
+    float* ms;
+    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev;
+    int open = -1;
+    int begin(int kind) {
+        if (!ms) return PO_OK;
+        if (open >= 0) { int rc = end(); if (rc) return rc; }
+        hipEvent_t a, b;
+        TRCHK(hipEventCreate(&a));
+        TRCHK(hipEventCreate(&b));
+        ev.push_back({kind, {a, b}});
+        TRCHK(hipEventRecord(a, tr->stream));
+        open = kind;
+        return PO_OK;
+    }
+    int end() {
+        if (!ms || open < 0) return PO_OK;
+        TRCHK(hipEventRecord(ev.back().second.second, tr->stream));
+        open = -1;
+        return PO_OK;
+    }
+    void finish(bool ok) {
+        for (auto& e : ev) {
+            float t = 0.f;
+            if (ok && hipEventElapsedTime(&t, e.second.first, e.second.second) == hipSuccess) ms[e.first] += t;
+            (void)hipEventDestroy(e.second.first);
+            (void)hipEventDestroy(e.second.second);
+        }
+    }
+};
+
+int64_t per_dir_weights(const po_call_layer& l) { return (int64_t)l.cin * G + (int64_t)H * G + 2 * G; }
+
+// the forward pass of n windows (tr->sig) into every layer's output and the logits; the GRU recurrences save for BPTT
+int train_forward(po_trainer* tr, int n, Timer& tm) {
+    const int T = tr->T;
+    const int64_t M = (int64_t)n * T;
+    const float* x = tr->sig;
+    int rc;
+    if ((rc = tm.begin(0)) != PO_OK) return rc;
+    for (size_t k = 0; k < tr->layers.size(); ++k) {
+        const po_call_layer& l = tr->layers[k];
+        const float* w = tr->p + tr->woff[k];
+        float* out = tr->act[k];
+        if (l.kind == PO_CALL_CONV) {
+            hipLaunchKernelGGL(conv_relu_kernel, dim3((unsigned)M), dim3(256), 0, tr->stream, x, l.cin, w,
+                               w + (int64_t)l.kernel * l.cin * l.cout, l.kernel, l.cout, out, M, T);
+        } else if (l.kind == PO_CALL_DENSE) {
+            hipLaunchKernelGGL(dense_softmax_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, x, l.cin, w,
+                               w + (int64_t)l.cin * NOUT, tr->probs, out, M);
+        } else {
+            const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
+            const int64_t per_dir = per_dir_weights(l);
+            hipLaunchKernelGGL(gru_proj_kernel, dim3(blocks(M, 64), (unsigned)(nd * (G / 64))), dim3(256), 0, tr->stream,
+                               x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, tr->P, M);
+            RecurArgs ra;
+            std::memset(&ra, 0, sizeof(ra));
+            for (int d = 0; d < nd; ++d) {
+                const float* wd = w + d * per_dir;
+                ra.dir[d].P = tr->P + (int64_t)d * M * G;
+                ra.dir[d].U = wd + (int64_t)l.cin * G;
+                ra.dir[d].brec = wd + (int64_t)l.cin * G + (int64_t)H * G + G;
+                ra.dir[d].backward = (d == 1 || l.kind == PO_CALL_GRU_BACK) ? 1 : 0;
+                ra.dir[d].rev_out = l.kind == PO_CALL_GRU_BACK ? 1 : 0;
+                ra.dir[d].col = d * H;
+            }
+            ra.out = out;
+            ra.out_stride = l.cout;
+            ra.n = n;
+            ra.T = T;
+            hipLaunchKernelGGL(gru_recur_save_kernel, dim3(blocks(n, RT), (unsigned)nd), dim3(RWAVES * 64), 0, tr->stream,
+                               ra, tr->save[2 * k], tr->save[2 * k + 1]);
+        }
+        x = out;
+    }
+    return tm.end();
+}
+
+int train_backward(po_trainer* tr, int n, Timer& tm) {
+    const int T = tr->T;
+    const int64_t M = (int64_t)n * T;
+    const int nl = (int)tr->layers.size();
+    int rc, cur = 0;
+    float* dY = tr->dlog;        // gradient of the current layer's output
+    for (int k = nl - 1; k >= 0; --k) {
+        const po_call_layer& l = tr->layers[k];
+        const float* w = tr->p + tr->woff[k];
+        float* gw = tr->g + tr->woff[k];
+        const float* X = k > 0 ? tr->act[k - 1] : tr->sig;
+        float* dX = tr->dact[cur];
+        if (l.kind == PO_CALL_DENSE) {
+            if ((rc = tm.begin(3)) != PO_OK) return rc;
+            if ((rc = wgrad(tr, X, l.cin, dY, NOUT, l.cin, NOUT, M, 0, 0, l.cin, gw, true)) != PO_OK) return rc;
+            if ((rc = colsum(tr, dY, NOUT, NOUT, M, gw + (int64_t)l.cin * NOUT)) != PO_OK) return rc;
+            if (k > 0)
+                hipLaunchKernelGGL(dense_dx_kernel, dim3(blocks(M * l.cin, 256)), dim3(256), 0, tr->stream, dY, w, l.cin,
+                                   dX, M);
+        } else if (l.kind == PO_CALL_CONV) {
+            if ((rc = tm.begin(3)) != PO_OK) return rc;
+            const int K = l.kernel, F = l.cout, padl = (K - 1) / 2;
+            hipLaunchKernelGGL(relu_mask_kernel, dim3(blocks(M * F, 256)), dim3(256), 0, tr->stream, dY, tr->act[k], M * F);
+            for (int j = 0; j < K; ++j)
+                if ((rc = wgrad(tr, X, l.cin, dY, F, l.cin, F, M, j - padl, j * l.cin, K * l.cin, gw, j == K - 1)) != PO_OK)
+                    return rc;
+            if ((rc = colsum(tr, dY, F, F, M, gw + (int64_t)K * l.cin * F)) != PO_OK) return rc;
+            if (k > 0)
+                hipLaunchKernelGGL(conv_dx_kernel, dim3(blocks(M * l.cin, 256)), dim3(256), 0, tr->stream, dY, w, K, l.cin,
+                                   F, dX, M, T);
+        } else {
+            const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
+            const int64_t per_dir = per_dir_weights(l);
+            BackArgs ba;
+            std::memset(&ba, 0, sizeof(ba));
+            for (int d = 0; d < nd; ++d) {
+                ba.dir[d].save = tr->save[2 * k + d];
+                ba.dir[d].U = w + d * per_dir + (int64_t)l.cin * G;
+                ba.dir[d].dA = tr->dA + (int64_t)d * M * G;
+                ba.dir[d].dR = tr->dR + (int64_t)d * M * G;
+                ba.dir[d].backward = (d == 1 || l.kind == PO_CALL_GRU_BACK) ? 1 : 0;
+                ba.dir[d].rev_out = l.kind == PO_CALL_GRU_BACK ? 1 : 0;
+                ba.dir[d].col = d * H;
+            }
+            ba.dout = dY;
+            ba.dout_stride = l.cout;
+            ba.n = n;
+            ba.T = T;
+            if ((rc = tm.begin(2)) != PO_OK) return rc;
+            hipLaunchKernelGGL(gru_back_recur_kernel, dim3(blocks(n, RT), (unsigned)nd), dim3(RWAVES * 64), 0, tr->stream, ba);
+            if ((rc = tm.begin(3)) != PO_OK) return rc;
+            for (int d = 0; d < nd; ++d) {
+                float* gd = gw + d * per_dir;
+                const float* dAd = tr->dA + (int64_t)d * M * G;
+                const float* dRd = tr->dR + (int64_t)d * M * G;
+                if ((rc = wgrad(tr, X, l.cin, dAd, G, l.cin, G, M, 0, 0, l.cin, gd, true)) != PO_OK) return rc;
+                if ((rc = wgrad(tr, tr->save[2 * k + d] + SV_HP, SV, dRd, G, H, G, M, 0, 0, H, gd + (int64_t)l.cin * G,
+                                true)) != PO_OK)
+                    return rc;
+                float* gb = gd + (int64_t)l.cin * G + (int64_t)H * G;
+                if ((rc = colsum(tr, dAd, G, G, M, gb)) != PO_OK) return rc;
+                if ((rc = colsum(tr, dRd, G, G, M, gb + G)) != PO_OK) return rc;
+            }
+            if (k > 0)
+                hipLaunchKernelGGL(dx_kernel, dim3(blocks(M, 64), blocks(l.cin, 64)), dim3(256), 0, tr->stream, tr->dA, M * G,
+                                   w, per_dir, nd, l.cin, dX, M);
+        }
+        dY = dX;
+        cur ^= 1;
+    }
+    return tm.end();
+}
+
+}  // namespace
+
+extern "C" {
+
+po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max_batch, int T) {
+    g_train_err.clear();
+    po_set_error("");
+    int64_t nw;
+    const int64_t wmax = check_model(layers_h, n_layers, &nw);
+    if (wmax < 0) return nullptr;
+    if (max_batch < 1 || T < 1) {
+        train_fail(PO_E_ARG, "po_train_create: max_batch and T must be positive");
+        return nullptr;
+    }
+    po_trainer* tr = new po_trainer;
+    tr->layers.assign(layers_h, layers_h + n_layers);
+    tr->max_batch = max_batch;
+    tr->T = T;
+    tr->nw = nw;
+    tr->wmax = wmax;
+    const int64_t M = (int64_t)max_batch * T;
+    int64_t off = 0, maxkn = NOUT;
+    bool ok = true;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](void** q, size_t bytes) {
+        if (ok && (e = hipMalloc(q, std::max<size_t>(bytes, 4))) != hipSuccess) ok = false;
+    };
+    for (int k = 0; k < n_layers; ++k) {
+        const po_call_layer& l = layers_h[k];
+        tr->woff.push_back(off);
+        float *a = nullptr, *s0 = nullptr, *s1 = nullptr;
+        alloc((void**)&a, (size_t)M * l.cout * 4);
+        tr->act.push_back(a);
+        if (l.kind == PO_CALL_CONV) {
+            off += (int64_t)l.kernel * l.cin * l.cout + l.cout;
+            maxkn = std::max<int64_t>(maxkn, (int64_t)l.kernel * l.cin * l.cout);
+        } else if (l.kind == PO_CALL_DENSE) {
+            off += (int64_t)l.cin * NOUT + NOUT;
+            maxkn = std::max<int64_t>(maxkn, (int64_t)l.cin * NOUT);
+        } else {
+            const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
+            off += nd * per_dir_weights(l);
+            maxkn = std::max<int64_t>(maxkn, (int64_t)std::max(l.cin, H) * G);
+            alloc((void**)&s0, (size_t)M * SV * 4);
+            if (nd == 2) alloc((void**)&s1, (size_t)M * SV * 4);
+        }
+        tr->save.push_back(s0);
+        tr->save.push_back(s1);
+    }
+    tr->part_cap = MAX_SPLIT * maxkn;
+    alloc((void**)&tr->p, nw * 4);
+    alloc((void**)&tr->g, nw * 4);
+    alloc((void**)&tr->m, nw * 4);
+    alloc((void**)&tr->v, nw * 4);
+    alloc((void**)&tr->sig, (size_t)M * 4);
+    alloc((void**)&tr->P, (size_t)2 * M * G * 4);
+    alloc((void**)&tr->probs, (size_t)M * NOUT * 4);
+    alloc((void**)&tr->dlog, (size_t)M * NOUT * 4);
+    alloc((void**)&tr->loss, (size_t)max_batch * 4);
+    alloc((void**)&tr->dact[0], (size_t)M * wmax * 4);
+    alloc((void**)&tr->dact[1], (size_t)M * wmax * 4);
+    alloc((void**)&tr->dA, (size_t)2 * M * G * 4);
+    alloc((void**)&tr->dR, (size_t)2 * M * G * 4);
+    alloc((void**)&tr->part, (size_t)tr->part_cap * 4);
+    alloc((void**)&tr->lsm, (size_t)M * NOUT * 8);
+    alloc((void**)&tr->logz, (size_t)max_batch * 8);
+    alloc((void**)&tr->loff, (size_t)(max_batch + 1) * 8);
+    if (ok && (e = hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking)) != hipSuccess) ok = false;
+    if (ok && (e = hipMemset(tr->p, 0, nw * 4)) != hipSuccess) ok = false;
+    if (ok && (e = hipMemset(tr->m, 0, nw * 4)) != hipSuccess) ok = false;
+    if (ok && (e = hipMemset(tr->v, 0, nw * 4)) != hipSuccess) ok = false;
+    if (!ok) {
+        train_hip(e, "po_train_create: device allocation");
+        trainer_free(tr);
+        return nullptr;
+    }
+    return tr;
+}
+
+void po_train_destroy(po_trainer* tr) {
+    if (tr) trainer_free(tr);
+}
+
+int po_train_set_params(po_trainer* tr, const float* w_h, int64_t n) {
+    po_set_error("");
+    if (!tr || !w_h) return train_fail(PO_E_ARG, "po_train_set_params: null argument");
+    if (n != tr->nw) return train_fail(PO_E_ARG, "po_train_set_params: the model has " + std::to_string(tr->nw) +
+                                                     " weights, " + std::to_string(n) + " given");
+    TRCHK(hipMemcpy(tr->p, w_h, n * 4, hipMemcpyHostToDevice));
+    TRCHK(hipMemset(tr->m, 0, n * 4));
+    TRCHK(hipMemset(tr->v, 0, n * 4));
+    tr->step = 0;
+    return PO_OK;
+}
+
+int po_train_get_params(po_trainer* tr, float* w_h, int64_t n) {
+    po_set_error("");
+    if (!tr || !w_h) return train_fail(PO_E_ARG, "po_train_get_params: null argument");
+    if (n != tr->nw) return train_fail(PO_E_ARG, "po_train_get_params: the model has " + std::to_string(tr->nw) +
+                                                     " weights, " + std::to_string(n) + " asked for");
+    TRCHK(hipStreamSynchronize(tr->stream));
+    TRCHK(hipMemcpy(w_h, tr->p, n * 4, hipMemcpyDeviceToHost));
+    return PO_OK;
+}
+
+int po_train_last(po_trainer* tr, int n, float* logits_h, float* dlogits_h) {
+    po_set_error("");
+    if (!tr || n < 1 || n > tr->max_batch) return train_fail(PO_E_ARG, "po_train_last: null trainer or bad window count");
+    const size_t b = (size_t)n * tr->T * NOUT * 4;
+    TRCHK(hipStreamSynchronize(tr->stream));
+    if (logits_h) TRCHK(hipMemcpy(logits_h, tr->act.back(), b, hipMemcpyDeviceToHost));
+    if (dlogits_h) TRCHK(hipMemcpy(dlogits_h, tr->dlog, b, hipMemcpyDeviceToHost));
+    return PO_OK;
+}
+
+int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                  int merge_repeated, float lr, float beta1, float beta2, float eps, int update, float* loss_h,
+                  float* grad_h, float* stage_ms_h) {
+    g_train_err.clear();
+    po_set_error("");
+    if (!tr || !signal_h || !label_len_h || !loss_h) return train_fail(PO_E_ARG, "po_train_step: null argument");
+    if (n < 1 || n > tr->max_batch)
+        return train_fail(PO_E_ARG, "po_train_step: " + std::to_string(n) + " windows, the trainer holds 1 to " +
+                                        std::to_string(tr->max_batch));
+    const int T = tr->T;
+    std::vector<int64_t> loff(n + 1, 0);
+    int64_t maxL = 0;
+    for (int w = 0; w < n; ++w) {
+        const int L = label_len_h[w];
+        if (L < 0) return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has a negative label length");
+        int rep = 0;
+        for (int j = 0; j < L; ++j) {
+            const int32_t c = labels_h[loff[w] + j];
+            if (c < 0 || c > 3)
+                return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has label " + std::to_string(c) +
+                                                " at position " + std::to_string(j) + " (labels are 0..3 = A C G T)");
+            if (j > 0 && c == labels_h[loff[w] + j - 1]) ++rep;
+        }
+        const int need = L + (merge_repeated ? rep : 0);
+        if (need > T)
+            return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + "'s " + std::to_string(L) +
+                                            " labels need " + std::to_string(need) + " frames, the window has " +
+                                            std::to_string(T));
+        loff[w + 1] = loff[w] + L;
+        maxL = std::max<int64_t>(maxL, L);
+    }
+    if (loff[n] > 0 && !labels_h) return train_fail(PO_E_ARG, "po_train_step: null labels");
+    const int64_t M = (int64_t)n * T;
+    const int Smax = (int)(2 * maxL + 1);
+    // α / β and the labels: sized by this batch's longest label, grown when a batch needs more
+    const size_t ab = (size_t)M * Smax * 8;
+    if (ab > tr->ab_cap) {
+        if (tr->alpha) (void)hipFree(tr->alpha);
+        if (tr->beta) (void)hipFree(tr->beta);
+        tr->alpha = tr->beta = nullptr;
+        tr->ab_cap = 0;
+        TRCHK(hipMalloc(&tr->alpha, ab));
+        TRCHK(hipMalloc(&tr->beta, ab));
+        tr->ab_cap = ab;
+    }
+    const size_t lb = (size_t)std::max<int64_t>(1, loff[n]) * 4;
+    if (lb > tr->lab_cap) {
+        if (tr->lab) (void)hipFree(tr->lab);
+        tr->lab = nullptr;
+        tr->lab_cap = 0;
+        TRCHK(hipMalloc(&tr->lab, lb));
+        tr->lab_cap = lb;
+    }
+    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + NSTAGE, 0.f);
+    TRCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
+    if (loff[n] > 0) TRCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
+    TRCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
+    Timer tm{tr, stage_ms_h};
+    int rc = train_forward(tr, n, tm);
+    if (rc == PO_OK) rc = tm.begin(1);
+    if (rc == PO_OK) {
+        const float* logits = tr->act.back();
+        hipLaunchKernelGGL(ctc_lsm_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, logits, tr->lsm, M);
+        hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)n), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, T,
+                           Smax, merge_repeated ? 1 : 0, tr->alpha, tr->beta, tr->logz);
+        hipLaunchKernelGGL(ctc_grad_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, n, T,
+                           Smax, tr->alpha, tr->beta, tr->logz, 1.f / (float)n, tr->dlog, tr->loss);
+        rc = tm.end();
+    }
+    if (rc == PO_OK) rc = train_backward(tr, n, tm);
+    if (rc == PO_OK && update) {
+        rc = tm.begin(4);
+        tr->step += 1;
+        const double t = (double)tr->step;
+        const float lr_t = (float)(lr * std::sqrt(1.0 - std::pow((double)beta2, t)) / (1.0 - std::pow((double)beta1, t)));
+        hipLaunchKernelGGL(adam_kernel, dim3(blocks(tr->nw, 256)), dim3(256), 0, tr->stream, tr->p, tr->g, tr->m, tr->v,
+                           tr->nw, lr_t, beta1, beta2, eps);
+        if (rc == PO_OK) rc = tm.end();
+    }
+    if (rc == PO_OK) {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = train_hip(e, "po_train_step: launch");
+    }
+    if (rc == PO_OK) {
+        hipError_t e = hipMemcpyAsync(loss_h, tr->loss, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess && grad_h) e = hipMemcpyAsync(grad_h, tr->g, (size_t)tr->nw * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
+        if (e != hipSuccess) rc = train_hip(e, "po_train_step: results");
+    }
+    tm.finish(rc == PO_OK);
+    return rc;
+}
+
+}  // extern "C"

@@ -22,7 +22,8 @@ import struct
 import numpy as np
 
 __all__ = ["NetworkError", "Layer", "Network", "read_index", "read_checkpoint", "read_weights", "resolve_checkpoint",
-           "parse_model_json", "default_model_config", "load_network", "synthetic_weights", "ARCHITECTURES", "crc32c"]
+           "parse_model_json", "default_model_config", "load_network", "synthetic_weights", "ARCHITECTURES", "architecture",
+           "write_weights", "crc32c"]
 
 UNITS = 128          # the only GRU width the device kernel is built for (build_model's num_neurons default)
 NUM_LABELS = 5       # A, C, G, T, blank
@@ -222,11 +223,28 @@ def read_checkpoint(prefix, names=None, verify=True):
 
 
 def read_weights(path):
-    """tensors from a checkpoint (prefix / directory) or an .npz of the same names"""
-    if str(path).endswith(".npz"):
+    """tensors from a checkpoint (prefix / directory) or an .npz of the same names; a resolved prefix without a `.index`
+    whose `<prefix>.npz` exists (what `train` writes) is read from that"""
+    path = str(path)
+    if not path.endswith(".npz"):
+        prefix = resolve_checkpoint(path)
+        if not os.path.exists(prefix + ".index") and os.path.exists(prefix + ".npz"):
+            path = prefix + ".npz"
+    if path.endswith(".npz"):
         with np.load(path) as z:
             return {k: z[k] for k in z.files}
     return read_checkpoint(path)
+
+
+def write_weights(path, net):
+    """an .npz of `net`'s tensors under the checkpoint's tensor names (what read_weights / load_network read back)"""
+    v = "/.ATTRIBUTES/VARIABLE_VALUE"
+    out = {}
+    for l in net.layers:
+        for name, t in zip(l.names, l.tensors):
+            out[name + v] = np.asarray(t, dtype=np.float32)
+    np.savez(path, **out)
+    return path if str(path).endswith(".npz") else str(path) + ".npz"
 
 
 # ---- architecture ---------------------------------------------------------------------------------------------------
@@ -257,6 +275,20 @@ class Network:
 
     def n_params(self):
         return int(sum(t.size for l in self.layers for t in l.tensors))
+
+    def with_flat(self, flat):
+        """a Network of the same layers whose tensors are taken, in order, from a flat vector (flat_weights' layout)"""
+        flat = np.asarray(flat, dtype=np.float32)
+        if flat.size != self.n_params():
+            raise NetworkError("%d weights given, the model has %d" % (flat.size, self.n_params()))
+        layers, k = [], 0
+        for l in self.layers:
+            ts = []
+            for t in l.tensors:
+                ts.append(flat[k:k + t.size].reshape(t.shape).copy())
+                k += t.size
+            layers.append(Layer(l.kind, l.cin, l.cout, l.kernel, ts, list(l.names)))
+        return Network(layers)
 
 
 def _conv(k=9, filters=256, first=False, input_size=1000):
@@ -300,6 +332,20 @@ ARCHITECTURES = {
     "conv1_gru5": lambda: _sequential([_conv(first=True), _gru(), _gru(go_backwards=True), _gru(), _gru(go_backwards=True),
                                        _gru(), _dense()]),
 }
+
+
+def architecture(name, kernel_size=9, filters=256):
+    """the Keras config of build_model(args).<name>() with its --kernel_size and --filters (network.py:14-55)"""
+    if name not in ARCHITECTURES:
+        _refuse("architecture %s" % name)
+    conv = lambda first=False: _conv(k=kernel_size, filters=filters, first=first)
+    return {
+        "bigru3": lambda: _sequential([_bigru(first=True), _bigru(), _bigru(), _dense()]),
+        "conv1_bigru3": lambda: _sequential([conv(True), _bigru(), _bigru(), _bigru(), _dense()]),
+        "conv2_bigru3": lambda: _sequential([conv(True), conv(), _bigru(), _bigru(), _bigru(), _dense()]),
+        "conv1_gru5": lambda: _sequential([conv(True), _gru(), _gru(go_backwards=True), _gru(), _gru(go_backwards=True),
+                                           _gru(), _dense()]),
+    }[name]()
 
 
 def default_model_config():
@@ -425,7 +471,7 @@ def load_network(weights, model=None):
                     raise NetworkError("%s GRU tensors have shapes %s %s %s, the model needs %s %s %s" % (
                         q, k.shape, u.shape, b.shape, (cin, 3 * UNITS), (UNITS, 3 * UNITS), (2, 3 * UNITS)))
                 ts += [k, u, b]
-                names += [q + "kernel", q + "recurrent_kernel", q + "bias"]
+                names += [q + "cell/kernel", q + "cell/recurrent_kernel", q + "cell/bias"]
             cout = UNITS * len(dirs)
             layers.append(Layer(kind, cin, cout, 0, ts, names))
             cin = cout

@@ -1,0 +1,296 @@
+"""`train`: CTC training of the basecalling network (the reference's network.py:66-179), on the GPU.
+
+The step (forward pass, tf.compat.v1.nn.ctc_loss averaged over the batch, its gradient, Keras Adam) runs in HIP
+(poreover_amd/csrc/po_train.hip through a po_trainer handle); this module does what the reference's host loop does:
+loads the .npz, draws the holdout and the batches, runs the schedule, prints the same stderr lines, writes train.log,
+model.json and the checkpoints.  Where the reference differs from its own flags, this honours them:
+--learning_rate and --ctc_merge_repeated take effect, T is the data's window length, the holdout is fixed for the run,
+checkpoints are .npz files of the checkpoint's tensor names next to a TF-style `checkpoint` file."""
+import ctypes as C
+import datetime
+import json
+import os
+import sys
+
+import numpy as np
+
+from .. import _lib
+from . import checkpoint as ckpt
+
+__all__ = ["TrainError", "Trainer", "load_data", "check_labels", "plan_batches", "init_weights", "validation_error",
+           "train"]
+
+ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7)     # Keras Adam()'s defaults
+
+
+class TrainError(ValueError):
+    pass
+
+
+def load_data(path):
+    """(signal (N, T) float32, labels int32, row_lengths int32) of a training .npz (to_npz.py's layout), checked"""
+    try:
+        z = np.load(path)
+    except (OSError, ValueError) as e:
+        raise TrainError("train: cannot read --data %s: %s" % (path, e))
+    with z:
+        missing = [k for k in ("signal", "labels", "row_lengths") if k not in z.files]
+        if missing:
+            raise TrainError("train: %s has no %s array (a training .npz holds signal, labels and row_lengths)" %
+                             (path, ", ".join(missing)))
+        sig, lab, rl = z["signal"], z["labels"], z["row_lengths"]
+    if sig.ndim != 2 or sig.shape[0] < 1 or sig.shape[1] < 1:
+        raise TrainError("train: signal has shape %s, not (windows, samples)" % (sig.shape,))
+    if rl.ndim != 1 or len(rl) != sig.shape[0]:
+        raise TrainError("train: row_lengths has %d entries for %d signal windows" % (rl.size, sig.shape[0]))
+    if np.any(rl < 0):
+        raise TrainError("train: row_lengths holds a negative length (window %d)" % int(np.argmax(rl < 0)))
+    if int(rl.sum()) != lab.size:
+        raise TrainError("train: row_lengths sums to %d, labels holds %d values" % (int(rl.sum()), lab.size))
+    lab = np.asarray(lab).ravel()
+    if lab.size and (not np.all(np.isfinite(lab)) or np.any(lab != np.round(lab))):
+        raise TrainError("train: labels must be integers 0..3 (A C G T)")
+    lab = lab.astype(np.int64)
+    if not np.all(np.isfinite(sig)):
+        raise TrainError("train: signal holds NaN or infinite samples")
+    return np.ascontiguousarray(sig, dtype=np.float32), lab.astype(np.int32), np.asarray(rl, dtype=np.int32)
+
+
+def check_labels(labels, row_lengths, T, merge_repeated):
+    """refuse labels outside 0..3 and windows whose label cannot fit in T frames, naming the window"""
+    bad = np.flatnonzero((labels < 0) | (labels > 3))
+    off = np.concatenate([[0], np.cumsum(row_lengths)])
+    if bad.size:
+        w = int(np.searchsorted(off, bad[0], side="right") - 1)
+        raise TrainError("train: window %d has label %d (labels are 0..3 = A C G T)" % (w, int(labels[bad[0]])))
+    for w in range(len(row_lengths)):
+        l = labels[off[w]:off[w + 1]]
+        need = len(l) + (int(np.sum(l[1:] == l[:-1])) if merge_repeated else 0)
+        if need > T:
+            raise TrainError("train: window %d has %d labels, which need %d frames; windows have %d samples%s" % (
+                w, len(l), need, T, " (--ctc_merge_repeated needs a blank between equal labels)" if merge_repeated else ""))
+
+
+def plan_batches(n_windows, batch_size, holdout, epochs, seed):
+    """(holdout batches, [training batches of every epoch]): one seeded permutation; its first validation_size batches are
+    held out for the whole run (validation_size = int(int(N / batch_size) * holdout), as the reference), the rest is
+    reshuffled every epoch and cut into whole batches (the remainder is dropped)"""
+    rng = np.random.default_rng(seed)
+    perm = rng.permutation(n_windows)
+    nval = int(int(n_windows / batch_size) * holdout)
+    held = perm[:nval * batch_size].reshape(nval, batch_size)
+    rest = perm[nval * batch_size:]
+    nb = len(rest) // batch_size
+    batches = []
+    for _ in range(epochs):
+        order = rest[rng.permutation(len(rest))]
+        batches.extend(order[:nb * batch_size].reshape(nb, batch_size))
+    return held, batches
+
+
+def _glorot(rng, shape, fan_in, fan_out):
+    lim = np.sqrt(6.0 / (fan_in + fan_out))
+    return rng.uniform(-lim, lim, shape)
+
+
+def _orthogonal(rng, rows, cols):
+    """Keras Orthogonal(gain=1) of a (rows, cols) matrix: QR of a normal matrix, signs fixed by diag(R)"""
+    a = rng.standard_normal((max(rows, cols), min(rows, cols)))
+    q, r = np.linalg.qr(a)
+    q = q * np.sign(np.diag(r))
+    return q.T if rows < cols else q
+
+
+def init_weights(model_config, seed=None):
+    """{name: array} of Keras' initial weights for an architecture, drawn with numpy from `seed`: glorot_uniform for
+    every kernel (Conv1D fan_in = K·cin, fan_out = K·F), orthogonal for each recurrent kernel (128, 384), zero biases"""
+    spec = ckpt.parse_model_json(model_config)
+    rng = np.random.default_rng(seed)
+    v = "/.ATTRIBUTES/VARIABLE_VALUE"
+    out, cin = {}, 1
+    H = ckpt.UNITS
+    for i, (kind, s) in enumerate(spec):
+        p = "layer_with_weights-%d/" % i
+        if kind == "conv":
+            K, F = s["kernel"], s["filters"]
+            out[p + "kernel" + v] = _glorot(rng, (K, cin, F), K * cin, K * F)
+            out[p + "bias" + v] = np.zeros(F)
+            cin = F
+        elif kind == "dense":
+            out[p + "kernel" + v] = _glorot(rng, (cin, ckpt.NUM_LABELS), cin, ckpt.NUM_LABELS)
+            out[p + "bias" + v] = np.zeros(ckpt.NUM_LABELS)
+        else:
+            dirs = ["forward_layer/", "backward_layer/"] if kind == "bigru" else [""]
+            for d in dirs:
+                q = p + d + "cell/"
+                out[q + "kernel" + v] = _glorot(rng, (cin, 3 * H), cin, 3 * H)
+                out[q + "recurrent_kernel" + v] = _orthogonal(rng, H, 3 * H)
+                out[q + "bias" + v] = np.zeros((2, 3 * H))
+            cin = H * len(dirs)
+    return {k: a.astype(np.float32) for k, a in out.items()}
+
+
+class Trainer:
+    """a po_trainer: the model's parameters, gradient and Adam state on the device, for batches of up to max_batch
+    windows of T samples"""
+
+    def __init__(self, net, max_batch, T):
+        from .network import _layers_array
+        self.lib = _lib.load()
+        self.net, self.T, self.max_batch = net, int(T), int(max_batch)
+        self._layers = _layers_array(net)
+        self.h = self.lib.po_train_create(self._layers, len(net.layers), self.max_batch, self.T)
+        if not self.h:
+            detail = self.lib.po_last_error()
+            raise _lib.EngineError(_lib.E_ARG, "po_train_create", detail.decode() if detail else "")
+        self.n_params = net.n_params()
+        self.set_params(net.flat_weights())
+
+    def close(self):
+        if self.h:
+            self.lib.po_train_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, flat):
+        """load the parameters (flat layout) and reset Adam"""
+        w = np.ascontiguousarray(flat, dtype=np.float32)
+        _lib.check(self.lib.po_train_set_params(self.h, w.ctypes.data, w.size), "po_train_set_params")
+
+    def get_params(self):
+        w = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self.lib.po_train_get_params(self.h, w.ctypes.data, w.size), "po_train_get_params")
+        return w
+
+    def network(self):
+        """the current parameters as a Network"""
+        return self.net.with_flat(self.get_params())
+
+    def step(self, windows, labels, merge_repeated=False, lr=1e-3, update=True, grad=False, stage_ms=None, **adam):
+        """one step on windows (n, T) with labels (a list of n int sequences): per-window losses (n,) float32, and the
+        gradient of the batch-mean loss (flat layout) with grad=True; update=False leaves parameters and Adam alone"""
+        a = dict(ADAM, **adam)
+        x = np.ascontiguousarray(windows, dtype=np.float32)
+        n = x.shape[0]
+        lens = np.asarray([len(l) for l in labels], dtype=np.int32)
+        lab = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).ravel() for l in labels])
+                                   if lens.sum() else np.zeros(1, dtype=np.int32), dtype=np.int32)
+        loss = np.empty(n, dtype=np.float32)
+        g = np.empty(self.n_params, dtype=np.float32) if grad else None
+        ms = (C.c_float * len(_lib.TRAIN_STAGES))() if stage_ms is not None else None
+        rc = self.lib.po_train_step(self.h, x.ctypes.data, n, lab.ctypes.data, lens.ctypes.data, 1 if merge_repeated else 0,
+                                    float(lr), float(a["beta1"]), float(a["beta2"]), float(a["eps"]), 1 if update else 0,
+                                    loss.ctypes.data, g.ctypes.data if grad else None, ms)
+        _lib.check(rc, "po_train_step")
+        if stage_ms is not None:
+            for k, name in enumerate(_lib.TRAIN_STAGES):
+                stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+        return (loss, g) if grad else loss
+
+
+    def last(self, n):
+        """(logits, dlogits), each (n, T, 5) float32, of the last step's first n windows"""
+        lg = np.empty((n, self.T, ckpt.NUM_LABELS), dtype=np.float32)
+        dl = np.empty_like(lg)
+        _lib.check(self.lib.po_train_last(self.h, n, lg.ctypes.data, dl.ctypes.data), "po_train_last")
+        return lg, dl
+
+
+def _split_labels(labels, row_lengths):
+    off = np.concatenate([[0], np.cumsum(row_lengths)])
+    return [labels[off[i]:off[i + 1]] for i in range(len(row_lengths))]
+
+
+def _edit(a, b):
+    from ..accuracy import alignment_summary
+    return alignment_summary("".join("ACGT"[i] for i in a), "".join("ACGT"[i] for i in b))["edit_distance"]
+
+
+def validation_error(net, batches, signal, labels):
+    """the reference's validation_error: per held-out batch the mean over its windows of edit_distance(argmax of the
+    softmax without class 4, truth) / len(truth) (repeats are not merged), then the mean over batches; windows with no
+    labels are left out (TensorFlow would divide by zero)"""
+    from .network import forward
+    per_batch = []
+    for b in batches:
+        probs = forward(net, signal[b])
+        best = np.argmax(probs, axis=2)
+        d = [_edit(p[p < 4], labels[w]) / len(labels[w]) for p, w in zip(best, b) if len(labels[w])]
+        if d:
+            per_batch.append(np.mean(d))
+    return float(np.mean(per_batch)) if per_batch else float("nan")
+
+
+def _write_state(out_dir, names):
+    with open(os.path.join(out_dir, "checkpoint"), "w") as fh:
+        fh.write('model_checkpoint_path: "%s"\n' % names[-1])
+        for n in names:
+            fh.write('all_model_checkpoint_paths: "%s"\n' % n)
+
+
+def train(args):
+    """`poreover train --data DATA.npz ...` (network.py:133-179); returns the output directory"""
+    if args.num_neurons != ckpt.UNITS:
+        raise TrainError("train: --num_neurons %d is not supported (the device kernels are built for %d GRU units)" %
+                         (args.num_neurons, ckpt.UNITS))
+    for flag in ("batch_size", "epochs", "save_every", "loss_every", "kernel_size", "filters"):
+        if getattr(args, flag) < 1:
+            raise TrainError("train: --%s must be positive" % flag)
+    if not 0.0 <= args.holdout < 1.0:
+        raise TrainError("train: --holdout must be in [0, 1)")
+    signal, labels, row_lengths = load_data(args.data)
+    N, T = signal.shape
+    check_labels(labels, row_lengths, T, args.ctc_merge_repeated)
+    config = ckpt.architecture(args.model, kernel_size=args.kernel_size, filters=args.filters)
+    held, batches = plan_batches(N, args.batch_size, args.holdout, args.epochs, args.seed)
+    if not batches:
+        raise TrainError("train: %d windows leave no whole training batch of %d" % (N, args.batch_size))
+    if args.restart:
+        net = ckpt.load_network(args.restart, config)
+    else:
+        net = ckpt.load_network(init_weights(config, args.seed), config)
+
+    print("PoreOver train", file=sys.stderr)
+    out_dir = "{}_{}_{}".format(args.model, args.name, datetime.datetime.now().strftime("%Y-%m-%d_%H-%M"))
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "train.log"), "w") as log:
+        print("Command-line arguments:", file=log)
+        for k, v in args.__dict__.items():
+            if k != "func":
+                print(k, "=", v, file=log)
+        print("Setting aside {}% of data for validation: {} batches".format(args.holdout * 100, len(held)), file=log)
+    with open(os.path.join(out_dir, "model.json"), "w") as fh:
+        fh.write(json.dumps(config))
+
+    lab_list = _split_labels(labels, row_lengths)
+    saved = []
+    with Trainer(net, args.batch_size, T) as tr:
+        for t, b in enumerate(batches):
+            loss = tr.step(signal[b], [lab_list[i] for i in b], merge_repeated=args.ctc_merge_repeated,
+                           lr=args.learning_rate)
+            mean = np.mean(loss, dtype=np.float32)
+            if t % args.save_every == 0:
+                name = "checkpoint-%d" % len(saved)
+                ckpt.write_weights(os.path.join(out_dir, name + ".npz"), tr.network())
+                saved.append(name)
+                _write_state(out_dir, saved)
+            if t % args.loss_every == 0:
+                print("Iteration:{}\tLoss:{}".format(t, mean), file=sys.stderr)
+            if t % args.save_every == 0 and len(held) > 0:
+                d = validation_error(tr.network(), held, signal, lab_list)
+                print("Iteration:{}\tEdit distance (test):{}".format(t, d), file=sys.stderr)
+        ckpt.write_weights(os.path.join(out_dir, "final.npz"), tr.network())
+    saved.append("final")
+    _write_state(out_dir, saved)
+    return out_dir

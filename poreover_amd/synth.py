@@ -6,7 +6,7 @@ float64 — the form the reference's decoders receive (decode.py:34-51).
 """
 import numpy as np
 
-__all__ = ["synth_pair", "synth_read", "synth_truth", "synth_pair_noise", "log_softmax"]
+__all__ = ["synth_pair", "synth_read", "synth_truth", "synth_pair_noise", "log_softmax", "synth_training"]
 
 
 def log_softmax(logits):
@@ -87,3 +87,29 @@ def synth_pair_noise(index, T=4000, base_seed=0, peak=5.0, sigma=1.6):
     y1 = _render(rng, ref, T, False, peak, sigma)
     y2 = _render(rng, ref, T2, False, peak, sigma)
     return y1, y2, "".join("ACGT"[b] for b in ref)
+
+
+def synth_training(n, T=1000, seed=0, dwell=(4, 12), noise=0.3):
+    """A learnable training set for `train`, as the reference's to_npz.py lays it out: (signal (n, T) float32, labels (every
+    window's bases 0..3 concatenated, int32), row_lengths (n,) int32).  Each window is a random base sequence rendered as
+    a squiggle: a fixed current level per base (seeded), held for a random dwell of `dwell` samples, plus Gaussian noise,
+    then standardised per window."""
+    rng = np.random.default_rng(seed)
+    levels = np.array([-1.2, -0.4, 0.4, 1.2])
+    sig = np.empty((n, T), dtype=np.float32)
+    labels, lens = [], []
+    for w in range(n):
+        x, seq = [], []
+        while len(x) < T:
+            b = int(rng.integers(4))
+            d = int(rng.integers(dwell[0], dwell[1] + 1))
+            if len(x) + d > T:
+                break
+            seq.append(b)
+            x.extend([levels[b]] * d)
+        x = np.asarray(x + [0.0] * (T - len(x)))
+        x = x + noise * rng.standard_normal(T)
+        sig[w] = ((x - x.mean()) / x.std()).astype(np.float32)
+        labels.extend(seq)
+        lens.append(len(seq))
+    return sig, np.asarray(labels, dtype=np.int32), np.asarray(lens, dtype=np.int32)
