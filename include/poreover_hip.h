@@ -476,6 +476,60 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
                   float* grad_h, float* stage_ms_h);
 int po_train_last(po_trainer* tr, int n, float* logits_h, float* dlogits_h);
 
+/* ---- read-to-genome mapping for `benchmark` (replaces mappy.Aligner as benchmark.py:16-20 uses it) ----
+ * minimap2's map-ont seeds (k = 15, w = 10, its hash64) and scores reduced to a fixed integer specification: one
+ * primary hit per read, a local affine alignment in a 512-column band around the best chain.  Sequences are upper-case
+ * ASCII; any byte but A C G T is "not a base" (no k-mer covers it; it scores -1 against anything).  All calls are
+ * synchronous and use the current device.
+ *   - po_map_sketch_h: the minimizers of n sequences (seq_h back to back, off_h int64[n+1] from 0): hash_h (30-bit
+ *     hashes), pos_h (k-mer start in its sequence), strand_h (0: the forward k-mer is the smaller code) in position
+ *     order, sequence i's at moff_h[i] .. moff_h[i+1]; the three outputs hold off_h[n] entries at most
+ *   - po_map_index_create: the contigs (ctg_h back to back, ctg_off_h int64[n_ctg+1], each < 2^31 bases) and their
+ *     index: n_entries minimizers sorted by (hash, contig offset + pos), the hashes that occur more than max_occ times
+ *     already left out, with pos_h[i] the position in its contig and ctg_strand_h[i] = contig << 1 | strand.  Returns
+ *     NULL on failure (po_last_error says why).  The index keeps its batch workspace (grow-only) until destroyed.
+ *   - po_map_batch_h: maps n reads (seq_h, off_h as above; each < 2^31 bases) in batches of at most budget_bytes of
+ *     workspace (0: min(8 GB, device memory / 16)), longest first; a read larger than the budget goes alone.  hits_h[n]
+ *     gets one po_map_hit per read; the alignment columns of read i (0 M, 1 X = mismatch or a non-ACGT pair, 2 I,
+ *     3 D; forward along the contig and Q, the read reverse-complemented on the - strand) are ops_h[op_off ..
+ *     op_off + n_ops).  *ops_len gets the number of op bytes; if it exceeds ops_cap the call returns PO_E_CAP (hits_h
+ *     is still written).  dbg (or NULL): the sorted anchors, the best chains and the band starts of every read, laid out
+ *     by the n_anchors / n_chain that a previous call with the same reads left in hits_h (and the reads' own offsets
+ *     for band_lo).  stats_h (or NULL): double[6] = device ms of sketch, anchors + sort, chain, align + trace-back; the
+ *     band cells computed; the number of batches.
+ *   - po_map_workspace_bytes: the workspace one batch of n_reads reads of `bases` bases in all needs, anchors aside
+ *     (they are sized once counted: 28 B each) */
+typedef struct po_map_index po_map_index;
+typedef struct po_map_hit {
+    int32_t mapped;        /* 1: the fields below describe the primary hit; 0: unmapped */
+    int32_t ctg;           /* contig index */
+    int32_t strand;        /* +1 / -1 */
+    int32_t score;         /* the best local alignment score (0 when no alignment ran) */
+    int64_t r_st, r_en;    /* half-open contig interval */
+    int32_t q_st, q_en;    /* half-open interval on the read as given */
+    int32_t mlen, blen, nm; /* matches; alignment columns; mismatches + inserted + deleted bases */
+    int32_t n_anchors;     /* the read's anchors */
+    int32_t n_chain;       /* anchors in its best chain */
+    int32_t chain_score;   /* that chain's score */
+    int64_t op_off;        /* into ops_h */
+    int32_t n_ops, pad;
+} po_map_hit;
+typedef struct po_map_debug {
+    uint64_t* anchor_key;  /* HOST: (2 * contig + rev) << 32 | x per anchor, each read's in sort order */
+    uint32_t* anchor_y;    /* HOST: y per anchor */
+    int32_t* chain;        /* HOST: the best chain as indices into the read's sorted anchors, in y order */
+    int32_t* band_lo;      /* HOST: the first band column (unclipped) of every row of Q, at the read's offset */
+} po_map_debug;
+int po_map_sketch_h(const char* seq_h, const int64_t* off_h, int n, uint32_t* hash_h, int32_t* pos_h, uint8_t* strand_h,
+                    int64_t* moff_h);
+po_map_index* po_map_index_create(const char* ctg_h, const int64_t* ctg_off_h, int n_ctg, const uint32_t* hash_h,
+                                  const uint32_t* pos_h, const uint32_t* ctg_strand_h, int64_t n_entries);
+void po_map_index_destroy(po_map_index* ix);
+int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t* off_h, int n, int64_t budget_bytes,
+                   po_map_hit* hits_h, uint8_t* ops_h, int64_t ops_cap, int64_t* ops_len, po_map_debug* dbg,
+                   double* stats_h);
+size_t po_map_workspace_bytes(int64_t bases, int n_reads);
+
 /* ---- timing aid for bench.py: HIP events on the stream the kernels run on ----------------- */
 void* po_event_create(void);
 int po_event_record(void* ev, void* stream);

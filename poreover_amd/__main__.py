@@ -1,9 +1,9 @@
-"""`python -m poreover_amd train|call|decode|pair-decode ...` — the train / call / decode / pair-decode sub-commands of
-the reference CLI (reference __main__.py:19-91) with the same flags and defaults, on the GPU engine.  `train` runs CTC
+"""`python -m poreover_amd train|call|decode|pair-decode|benchmark ...` — the five sub-commands of the reference CLI
+(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine.  `train` runs CTC
 training of the basecalling network in HIP and writes .npz checkpoints; `call` runs the network's forward pass and needs
 `--weights` (no weights ship with this package: a TF checkpoint prefix or directory, a `train` output directory, or an
-.npz from `python -m poreover_amd.network.convert`).
-(`benchmark`, which needs a genome mapper, is outside this engine's scope.)"""
+.npz from `python -m poreover_amd.network.convert`).  `benchmark` maps decoded reads to a reference genome with the
+engine's own mapper (minimap2's map-ont seeds and scores, simplified) and reports their identities."""
 import argparse
 import logging
 import sys
@@ -86,6 +86,14 @@ def build_parser():
     p.add_argument('--beam_search_method', choices=['row', 'row_col', 'grid'], default="row_col", help=argparse.SUPPRESS)
     p.add_argument('--window', type=int, default=200, help=argparse.SUPPRESS)
     p.set_defaults(func="pair-decode")
+
+    p = subparsers.add_parser('benchmark', help='Assess accuracy of basecalled FASTA/FASTQ files')
+    p.add_argument('--fasta', help='FASTA file', default=None)
+    p.add_argument('--fasta_pair', help='Prefix with 1D/2D (*.1d.fasta and *.2d.fasta)', default=None)
+    p.add_argument('--fastq', help='FASTQ file', default=None)
+    p.add_argument('--reference', help='Reference genome', required=True)
+    p.add_argument('--full', action="store_true", help="Collect more statistics on types of errors")
+    p.set_defaults(func="benchmark")
     return parser
 
 
@@ -104,6 +112,11 @@ def main(argv=None):
         if args.window < 1:
             raise SystemExit("call: --window must be positive")
         _call(args)
+        print(args, file=sys.stderr)
+        return
+    if args.func == "benchmark":
+        from . import benchmark as _benchmark
+        _benchmark.benchmark(args)
         print(args, file=sys.stderr)
         return
     from .decoding import decode as _decode, pair_decode as _pair

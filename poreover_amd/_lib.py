@@ -160,6 +160,12 @@ PROTOTYPES = {
     "po_train_step": (C.c_int, [C.c_void_p, _vp, C.c_int, _i32p, _i32p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int, _vp, _vp, C.POINTER(C.c_float)]),
     "po_train_last": (C.c_int, [C.c_void_p, C.c_int, _vp, _vp]),
+    "po_map_sketch_h": (C.c_int, [_cp, _i64p, C.c_int, _vp, _vp, _vp, _i64p]),
+    "po_map_index_create": (C.c_void_p, [_cp, _i64p, C.c_int, _vp, _vp, _vp, C.c_int64]),
+    "po_map_index_destroy": (None, [C.c_void_p]),
+    "po_map_batch_h": (C.c_int, [C.c_void_p, _cp, _i64p, C.c_int, C.c_int64, C.c_void_p, _vp, C.c_int64,
+                                 C.POINTER(C.c_int64), C.c_void_p, _dp]),
+    "po_map_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "po_event_create": (C.c_void_p, []),
     "po_event_record": (C.c_int, [C.c_void_p, C.c_void_p]),
     "po_event_elapsed_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),

@@ -6,7 +6,8 @@ float64 — the form the reference's decoders receive (decode.py:34-51).
 """
 import numpy as np
 
-__all__ = ["synth_pair", "synth_read", "synth_truth", "synth_pair_noise", "log_softmax", "synth_training"]
+__all__ = ["synth_pair", "synth_read", "synth_truth", "synth_pair_noise", "log_softmax", "synth_training", "synth_genome",
+           "synth_mapping_reads"]
 
 
 def log_softmax(logits):
@@ -113,3 +114,78 @@ def synth_training(n, T=1000, seed=0, dwell=(4, 12), noise=0.3):
         labels.extend(seq)
         lens.append(len(seq))
     return sig, np.asarray(labels, dtype=np.int32), np.asarray(lens, dtype=np.int32)
+
+
+_ASCII = np.frombuffer(b"ACGTN", dtype=np.uint8)
+
+
+def _to_str(codes):
+    return _ASCII[np.asarray(codes, dtype=np.int64)].tobytes().decode()
+
+
+def synth_genome(seed=0, contig_lengths=(600000, 400000), n_runs=3, run_len=(50, 400), repeat_len=3000):
+    """A seeded genome for `benchmark`'s mapper: (names, sequences, repeat) with uniform random contigs, `n_runs` runs of N
+    per contig and one planted repeat — the first repeat_len bases at the middle of contig 0 copied to the middle of the
+    last contig.  repeat = ((contig, start), (contig, start), length)."""
+    rng = np.random.default_rng(seed)
+    seqs = [rng.integers(4, size=L).astype(np.int8) for L in contig_lengths]
+    for s in seqs:
+        for _ in range(n_runs):
+            L = int(rng.integers(run_len[0], run_len[1] + 1))
+            if len(s) > 2 * L:
+                a = int(rng.integers(0, len(s) - L))
+                s[a:a + L] = 4
+    rep = None
+    if repeat_len and len(seqs[0]) > 2 * repeat_len and len(seqs[-1]) > 4 * repeat_len:
+        a, b = len(seqs[0]) // 2, len(seqs[-1]) // 4
+        seqs[-1][b:b + repeat_len] = seqs[0][a:a + repeat_len]
+        rep = ((0, a), (len(seqs) - 1, b), repeat_len)
+    names = ["ctg%d" % i for i in range(len(seqs))]
+    return names, [_to_str(s) for s in seqs], rep
+
+
+def _mutate_codes(rng, frag, err):
+    """substitutions, insertions and deletions at a total rate `err` (40 / 30 / 30 %); N stays N"""
+    L = len(frag)
+    r = rng.random((L, 3))
+    keep = r[:, 0] >= 0.3 * err
+    sub = (r[:, 1] < 0.4 * err) & (frag < 4)
+    base = frag.copy()
+    base[sub] = (base[sub] + 1 + rng.integers(3, size=int(sub.sum()))) % 4
+    ins = r[:, 2] < 0.3 * err
+    pair = np.stack([base, rng.integers(4, size=L).astype(frag.dtype)], axis=1).ravel()
+    return pair[np.stack([keep, ins], axis=1).ravel()]
+
+
+def synth_mapping_reads(seqs, n, seed=0, mean_len=10000, sigma=0.5, err=(0.03, 0.12), random_frac=0.02, min_len=30,
+                        max_len=None, lengths=None):
+    """Reads of a synth_genome with known truth: a list of dicts (name, seq, ctg, strand, start, end, err, random).  The
+    lengths are log-normal with mean ~mean_len (or given), each read is cut from a random contig and strand and mutated at
+    a rate drawn from `err`; a fraction random_frac of reads are random sequence that should not map."""
+    rng = np.random.default_rng(seed)
+    codes = [np.frombuffer(s.encode(), dtype=np.uint8) for s in seqs]
+    codes = [np.select([c == 65, c == 67, c == 71, c == 84], [0, 1, 2, 3], 4).astype(np.int8) for c in codes]
+    if lengths is None:
+        mu = np.log(mean_len) - sigma * sigma / 2
+        lengths = np.exp(rng.normal(mu, sigma, n)).astype(np.int64)
+    lengths = np.maximum(np.asarray(lengths, dtype=np.int64), min_len)
+    if max_len:
+        lengths = np.minimum(lengths, max_len)
+    out = []
+    for i, L in enumerate(lengths):
+        L = int(L)
+        e = float(rng.uniform(err[0], err[1]))
+        if rng.random() < random_frac:
+            out.append({"name": "read%d" % i, "seq": _to_str(rng.integers(4, size=L)), "ctg": -1, "strand": 0, "start": 0,
+                        "end": 0, "err": 1.0, "random": True})
+            continue
+        c = int(rng.integers(len(codes)))
+        L = min(L, len(codes[c]))
+        a = int(rng.integers(0, len(codes[c]) - L + 1))
+        q = _mutate_codes(rng, codes[c][a:a + L], e)
+        strand = 1 if rng.random() < 0.5 else -1
+        if strand < 0:
+            q = np.where(q < 4, 3 - q, 4)[::-1]
+        out.append({"name": "read%d" % i, "seq": _to_str(q), "ctg": c, "strand": strand, "start": a, "end": a + L,
+                    "err": e, "random": False})
+    return out
