@@ -530,6 +530,30 @@ int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t* off_h, in
                    double* stats_h);
 size_t po_map_workspace_bytes(int64_t bases, int n_reads);
 
+/* ---- make_labeled_data: guided, banded CTC forced alignment (po_label.hip) ----
+ * The frame of every base of a known sequence, over a whole read.  Plain `ctc` model (a non-blank frame emits one
+ * base, blank = column A = C - 1); state k = number of label bases emitted.  Per read i: y float64 [T_i][C] (rows
+ * y_off[i] .. y_off[i+1]), label characters [L_i] at label_off[i], guide int32 [T_i] at y_off[i] or guide == NULL
+ * (c[t] = floor((t + 1) * L / T)); one band_size B per batch (<= 0: no band).  Row t admits
+ * max(0, c[t] - B) <= k <= min(L, c[t] + B), every other cell is -inf;  S(-1, 0) = 0,
+ * S(t, k) = max(S(t-1, k) + y[t][blank], S(t-1, k-1) + y[t][code(label[k-1])]), the emitting move only when
+ * strictly greater.  score[i] = S(T-1, L); map int32[total_labels] at label_off[i]: map[k] = the frame at which
+ * the best path moves k -> k + 1.  Float64 throughout, the additions of a path in frame order: a numpy restatement
+ * gives the same bits.
+ * status[i] (no batch abort): 0; PO_E_ENVELOPE when S(T-1, L) is -inf (the band admits no path from (-1, 0) to
+ * (T-1, L), or L > T); PO_E_ARG for a label character outside the alphabet, or a guide that decreases or leaves
+ * [0, L].  A read with a non-zero status gets score -inf and map -1.  L == 0 is valid (score = the sum of blanks).
+ * Trace-back storage is one bit per admitted cell: po_label_align_workspace_bytes is at most
+ * total_rows * (2 * ceil((2B + 1) / 64) * 8 + 16) + 32 * total_labels + 64 * n + 2^20 for B >= 1.
+ * B <= 63 runs on the register kernels (one wave per read); wider bands and band_size <= 0 on the general kernel. */
+size_t po_label_align_workspace_bytes(int n, int64_t total_rows, int64_t max_rows, int64_t total_labels, int band_size);
+int po_label_align_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int band_size,
+                         const char* labels, const int64_t* label_off, const int32_t* guide, int32_t* map,
+                         double* score, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int po_label_align_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, const char* alphabet,
+                           int band_size, const char* labels_h, const int64_t* label_off_h, const int32_t* guide_h,
+                           int32_t* map_h, double* score_h, int32_t* status_h);
+
 /* ---- timing aid for bench.py: HIP events on the stream the kernels run on ----------------- */
 void* po_event_create(void);
 int po_event_record(void* ev, void* stream);

@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib as L
 
 __all__ = ["viterbi_batch", "beam_search_batch", "beam_search_2d_batch", "pair_decode_batch", "pair_decode_batch_sharded", "pair_decode_stream", "decode_1d_batch", "pack_rows",
-           "forward_batch", "viterbi_acceptor_batch", "prefix_search_batch", "pair_prefix_search_batch", "forward_vec_batch", "align_batch", "envelope_batch", "ingest_batch", "pair_gamma_batch"]
+           "forward_batch", "viterbi_acceptor_batch", "label_align_batch", "prefix_search_batch", "pair_prefix_search_batch", "forward_vec_batch", "align_batch", "envelope_batch", "ingest_batch", "pair_gamma_batch"]
 
 
 def pack_rows(arrays, C_expected=None):
@@ -531,6 +531,34 @@ def viterbi_acceptor_batch(arrays, labels, band_size=1000, alphabet="ACGT", flav
         if st[i] != 0:
             raise L.EngineError(int(st[i]), "viterbi acceptor of item %d" % i)
     return [path[off[i]:off[i + 1]].astype(np.int64) for i in range(n)]
+
+
+def label_align_batch(arrays, labels, guides=None, band_size=32, alphabet="ACGT"):
+    """Guided, banded CTC forced alignment (po_label_align_batch_h): for each (T, C) float64 table and its
+    known sequence, the frame at which every base is emitted on the best path of the plain ctc model.  guides: per read
+    an int array (T,) with the state the band is centred on at every frame (non-decreasing, 0..L), or None for the
+    straight diagonal; band_size <= 0: no band.  Returns (maps, scores, status): maps[i] int64 (L_i,), scores float64
+    (n,), status int32 (n,): 0, E_ENVELOPE (the band admits no path, or L > T), E_ARG (a label character outside the
+    alphabet, a bad guide).  A read with a non-zero status has score -inf and map -1; no read fails the batch."""
+    lib = L.load()
+    y, off, Cc = pack_rows(arrays, len(alphabet) + 1)
+    n = len(arrays)
+    if len(labels) != n or (guides is not None and len(guides) != n):
+        raise ValueError("label_align_batch: one label (and one guide) per table")
+    lb, lo = _pack_labels(labels)
+    g = None
+    if guides is not None:
+        for i, gi in enumerate(guides):
+            if len(gi) != off[i + 1] - off[i]:
+                raise ValueError("label_align_batch: guide %d has %d entries for %d frames" % (i, len(gi), off[i + 1] - off[i]))
+        g = np.ascontiguousarray(np.concatenate([np.asarray(gi, dtype=np.int64) for gi in guides] + [np.zeros(1, np.int64)])
+                                 .clip(-2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+    mp = np.zeros(max(int(lo[-1]), 1), dtype=np.int32)
+    sc = np.zeros(max(n, 1), dtype=np.float64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    L.check(lib.po_label_align_batch_h(_ptr(y), _ptr(off), n, Cc, alphabet.encode(), int(band_size), _ptr(lb), _ptr(lo),
+                                       _ptr(g), _ptr(mp), _ptr(sc), _ptr(st)), "po_label_align_batch_h")
+    return [mp[lo[i]:lo[i + 1]].astype(np.int64) for i in range(n)], sc[:n].copy(), st[:n].copy()
 
 
 def prefix_search_batch(y, offsets, alphabet="ACGT"):

@@ -7,7 +7,7 @@ float64 — the form the reference's decoders receive (decode.py:34-51).
 import numpy as np
 
 __all__ = ["synth_pair", "synth_read", "synth_truth", "synth_pair_noise", "log_softmax", "synth_training", "synth_genome",
-           "synth_mapping_reads"]
+           "synth_mapping_reads", "synth_render"]
 
 
 def log_softmax(logits):
@@ -53,6 +53,25 @@ def _render(rng, seq, T, flipflop, peak=6.0, sigma=1.0):
     logits = rng.normal(0, sigma, (T, C)).astype(np.float32)
     logits[np.arange(T), lab] += peak
     return log_softmax(logits)
+
+
+def synth_render(seq, T, seed=0, peak=6.0, sigma=1.0):
+    """(y, frames): `seq` (codes 0..3, or a string over ACGT) rendered as _render does for the plain ctc layout — one
+    peaked frame per base, blank elsewhere — together with the planted frame of every base (_render draws them and
+    throws them away).  len(seq) <= T.  A generator of its own: the streams of the functions below are untouched."""
+    if isinstance(seq, str):
+        seq = np.frombuffer(seq.encode(), dtype=np.uint8)
+        seq = np.select([seq == 65, seq == 67, seq == 71, seq == 84], [0, 1, 2, 3], -1)
+    seq = np.asarray(seq, dtype=np.int64)
+    if len(seq) > T or (len(seq) and (seq.min() < 0 or seq.max() > 3)):
+        raise ValueError("synth_render: at most T bases, all of them A/C/G/T")
+    rng = np.random.default_rng(seed)
+    pos = np.sort(rng.choice(T, size=len(seq), replace=False))
+    lab = np.full(T, 4, dtype=np.int64)
+    lab[pos] = seq
+    logits = rng.normal(0, sigma, (T, 5)).astype(np.float32)
+    logits[np.arange(T), lab] += peak
+    return log_softmax(logits), pos.astype(np.int64)
 
 
 def synth_pair(index, T=4000, base_seed=0, flipflop=False):
