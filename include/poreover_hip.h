@@ -530,6 +530,26 @@ int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t* off_h, in
                    double* stats_h);
 size_t po_map_workspace_bytes(int64_t bases, int n_reads);
 
+/* ---- pairwise mapping for `find-pairs`: every candidate against its OWN target ----
+ *   - po_map_pairs_h: n_tgt target sequences (tgt_h back to back, tgt_off_h int64[n_tgt+1] from 0, each < 2^31 bases),
+ *     n_qry query sequences (qry_h, qry_off_h likewise; the two sets may be the same arrays) and n_cand candidates,
+ *     cand_h int32[n_cand][2] = (query index, target index).  hits_h[c] and its alignment columns are exactly what
+ *     po_map_batch_h gives for that query against an index whose only contig is that target: the target's own
+ *     minimizers in (hash, pos) order, max_occ from the target's own occurrence counts, anchors, chain, band, alignment
+ *     and thresholds unchanged; ctg is the target's index (of every record, mapped or not).  Everything per target and
+ *     per candidate runs on the device: the targets a batch names are sketched once each, their minimizers sorted
+ *     inside per-target segments, and each query minimizer is looked up in its candidate's segment alone; candidates that
+ *     share a target share its segment, and a sequence no candidate names is never touched.  Candidates go in batches
+ *     of at most budget_bytes of workspace (0: min(8 GB, device memory / 16)), longest query first; one larger than the
+ *     budget goes alone.  An empty, short or all-N sequence, the same read as query and target, n_cand = 0 are results
+ *     (mostly mapped = 0), not errors; an index out of range is PO_E_ARG before any launch.  ops_h / ops_cap / ops_len
+ *     and PO_E_CAP as in po_map_batch_h.  stats_h (or NULL): double[8] = device ms of sketch (targets and queries),
+ *     anchors + sort, chain, align + trace-back; the band cells computed; the number of batches; device ms of the
+ *     per-target index (segmented sort + max_occ); the number of target segments built. */
+int po_map_pairs_h(const char* tgt_h, const int64_t* tgt_off_h, int n_tgt, const char* qry_h, const int64_t* qry_off_h,
+                   int n_qry, const int32_t* cand_h, int n_cand, int64_t budget_bytes, po_map_hit* hits_h, uint8_t* ops_h,
+                   int64_t ops_cap, int64_t* ops_len, double* stats_h);
+
 /* ---- make_labeled_data: guided, banded CTC forced alignment (po_label.hip) ----
  * The frame of every base of a known sequence, over a whole read.  Plain `ctc` model (a non-blank frame emits one
  * base, blank = column A = C - 1); state k = number of label bases emitted.  Per read i: y float64 [T_i][C] (rows

@@ -1,5 +1,6 @@
 """`python -m poreover_amd train|call|decode|pair-decode|benchmark ...` — the five sub-commands of the reference CLI
-(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine.  `train` runs CTC
+(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine — and `find-pairs`, which the
+reference lacks: the list of read pairs `pair-decode` starts from.  `train` runs CTC
 training of the basecalling network in HIP and writes .npz checkpoints; `call` runs the network's forward pass and needs
 `--weights` (no weights ship with this package: a TF checkpoint prefix or directory, a `train` output directory, or an
 .npz from `python -m poreover_amd.network.convert`).  `benchmark` maps decoded reads to a reference genome with the
@@ -94,6 +95,21 @@ def build_parser():
     p.add_argument('--reference', help='Reference genome', required=True)
     p.add_argument('--full', action="store_true", help="Collect more statistics on types of errors")
     p.set_defaults(func="benchmark")
+
+    p = subparsers.add_parser('find-pairs', help='Find 1D2 read pairs: reads that follow each other in a channel and map to each other on opposite strands',
+                              formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('IN', nargs='*', help='Single-read FAST5 files or directories of them: the reads and their metadata')
+    p.add_argument('--summary', default=None, help='The reads and their channel / start_time / duration from a tab-separated summary table (then no IN)')
+    p.add_argument('--candidates', default=None, help='Two names per line: verify these pairs instead of deriving candidates (then neither IN nor --summary)')
+    p.add_argument('--fasta', default=None, help='1D basecalls, one record per read')
+    p.add_argument('--dir', default=None, help='Directory of basecaller probabilities as pair-decode finds them; called here by Viterbi')
+    p.add_argument('--basecaller', choices=['poreover', 'flappie', 'guppy', 'bonito'], help='Basecaller used to generate probabilities')
+    p.add_argument('--max_gap', type=float, default=1.0, help='Seconds between the end of one read and the start of the next in a channel')
+    p.add_argument('--min_identity', type=float, default=0.6, help='Smallest mlen / blen of an accepted pair')
+    p.add_argument('--min_cover', type=float, default=0.5, help='Smallest share of the shorter read the alignment spans')
+    p.add_argument('--out', default='out', help='Prefix for PREFIX.pairs.txt and PREFIX.pairs.csv')
+    p.add_argument('-v', '--version', action='version', version=__version__)
+    p.set_defaults(func="find-pairs")
     return parser
 
 
@@ -112,6 +128,11 @@ def main(argv=None):
         if args.window < 1:
             raise SystemExit("call: --window must be positive")
         _call(args)
+        print(args, file=sys.stderr)
+        return
+    if args.func == "find-pairs":
+        from . import pairs as _pairs
+        _pairs.find_pairs_cli(args)
         print(args, file=sys.stderr)
         return
     if args.func == "benchmark":

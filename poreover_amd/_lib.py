@@ -166,6 +166,8 @@ PROTOTYPES = {
     "po_map_batch_h": (C.c_int, [C.c_void_p, _cp, _i64p, C.c_int, C.c_int64, C.c_void_p, _vp, C.c_int64,
                                  C.POINTER(C.c_int64), C.c_void_p, _dp]),
     "po_map_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "po_map_pairs_h": (C.c_int, [_cp, _i64p, C.c_int, _cp, _i64p, C.c_int, _i32p, C.c_int, C.c_int64, C.c_void_p, _vp,
+                                 C.c_int64, C.POINTER(C.c_int64), _dp]),
     "po_label_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int]),
     "po_label_align_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, _i32p, _dp, _i32p,
                                        _vp, C.c_size_t, _vp]),

@@ -579,6 +579,158 @@ __global__ __launch_bounds__(64) void map_trace_kernel(TraceArgs g) {
     g.hits[r] = h;
 }
 
+// ---------------------------------------------------------------------------------------------------- pairs (§14)
+
+// One index segment per target read, built here: the key of a target minimizer is hash << 32 | pos << 1 | strand
+// (pos < 2^31 is unique inside a target, so ascending keys are the (hash, pos) order of a one-contig index).
+constexpr int SEG_LDS = 4096;
+
+// one workgroup per target: bitonic sort of its keys, in LDS up to SEG_LDS and in a global scratch slice beyond
+__global__ __launch_bounds__(TPB) void pairs_segsort_kernel(const uint32_t* mh, const int32_t* mpos, const uint8_t* mst,
+                                                            const int64_t* tmoff, uint64_t* key, uint64_t* scratch,
+                                                            const int64_t* soff) {
+    __shared__ uint64_t sh[SEG_LDS];
+    const int t = blockIdx.x;
+    const int64_t b = tmoff[t];
+    const int64_t n = tmoff[t + 1] - b;
+    if (n <= 0) return;
+    int64_t np2 = 1;
+    while (np2 < n) np2 <<= 1;
+    uint64_t* buf = np2 <= SEG_LDS ? sh : scratch + soff[t];
+    for (int64_t i = threadIdx.x; i < np2; i += TPB)
+        buf[i] = i < n ? ((uint64_t)mh[b + i] << 32 | (uint64_t)(uint32_t)mpos[b + i] << 1 | (uint64_t)(mst[b + i] & 1u))
+                       : ~0ull;
+    __syncthreads();
+    for (int64_t k = 2; k <= np2; k <<= 1) {
+        for (int64_t j = k >> 1; j > 0; j >>= 1) {
+            for (int64_t i = threadIdx.x; i < np2; i += TPB) {
+                const int64_t ixj = i ^ j;
+                if (ixj > i) {
+                    const uint64_t a = buf[i], c = buf[ixj];
+                    const bool asc = (i & k) == 0;
+                    if (asc ? c < a : a < c) { buf[i] = c; buf[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int64_t i = threadIdx.x; i < n; i += TPB) key[b + i] = buf[i];
+}
+
+// first index in key[0..n) whose hash is >= h
+__device__ __forceinline__ int64_t seg_bound(const uint64_t* key, int64_t n, uint64_t h) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((key[mid] >> 32) < h) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ int64_t block_max(int64_t v, int64_t* sh) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int o = TPB / 2; o > 0; o >>= 1) {
+        if (t < o && sh[t + o] > sh[t]) sh[t] = sh[t + o];
+        __syncthreads();
+    }
+    const int64_t m = sh[0];
+    __syncthreads();
+    return m;
+}
+
+// one workgroup per target: the occurrence count of every distinct hash (runc, at the first entry of its run, 0
+// elsewhere) and §12's max_occ over them: the count at rank min(n - 1, int((1 - 2e-4) n)) of the n ascending counts,
+// found as the smallest v with at least rank + 1 counts <= v (integer counting: no order to depend on)
+__global__ __launch_bounds__(TPB) void pairs_maxocc_kernel(const uint64_t* key, const int64_t* tmoff, uint32_t* runc,
+                                                           int32_t* max_occ) {
+    __shared__ int64_t sh[TPB];
+    const int t = blockIdx.x;
+    const int64_t b = tmoff[t];
+    const int64_t n = tmoff[t + 1] - b;
+    const uint64_t* kp = key + b;
+    int64_t nd = 0, mx = 0;
+    for (int64_t i = threadIdx.x; i < n; i += TPB) {
+        const uint64_t h = kp[i] >> 32;
+        uint32_t c = 0;
+        if (i == 0 || (kp[i - 1] >> 32) != h) {
+            c = (uint32_t)seg_bound(kp + i, n - i, h + 1);
+            ++nd;
+            mx = mx > c ? mx : (int64_t)c;
+        }
+        runc[b + i] = c;
+    }
+    int64_t tot;
+    block_excl_scan(nd, sh, &tot);
+    nd = tot;
+    mx = block_max(mx, sh);
+    int64_t q = 0;
+    if (nd > 0) {
+        int64_t rank = (int64_t)((1.0 - 2e-4) * (double)nd);
+        if (rank > nd - 1) rank = nd - 1;
+        if (rank == nd - 1) {
+            q = mx;
+        } else {
+            // (every thread reads back only the run counts it wrote itself: the same strided walk)
+            int64_t lo = 1, hi = mx;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                int64_t le = 0;
+                for (int64_t i = threadIdx.x; i < n; i += TPB) {
+                    const uint32_t c = runc[b + i];
+                    le += (c != 0 && c <= mid) ? 1 : 0;
+                }
+                block_excl_scan(le, sh, &tot);
+                if (tot >= rank + 1) hi = mid; else lo = mid + 1;
+            }
+            q = lo;
+        }
+    }
+    if (threadIdx.x == 0) max_occ[t] = (int32_t)(q < 10 ? 10 : q > 1000000 ? 1000000 : q);
+}
+
+// the lookup of one query minimizer, confined to the segment of its candidate's target
+__global__ __launch_bounds__(TPB) void pairs_anchor_count_kernel(const uint32_t* mh, const int32_t* mseq, int64_t M,
+                                                                 const int32_t* cand_tgt, const uint64_t* key,
+                                                                 const int64_t* tmoff, const int32_t* max_occ,
+                                                                 uint32_t* cnt, int64_t* lbo) {
+    const int64_t m = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (m >= M) return;
+    const int t = cand_tgt[mseq[m]];
+    const int64_t b = tmoff[t], n = tmoff[t + 1] - b;
+    const uint64_t h = mh[m];
+    const int64_t lo = seg_bound(key + b, n, h);
+    const int64_t hi = lo + seg_bound(key + b + lo, n - lo, h + 1);
+    const int64_t c = hi - lo;
+    cnt[m] = c > max_occ[t] ? 0u : (uint32_t)c;
+    lbo[m] = b + lo;
+}
+
+__global__ __launch_bounds__(TPB) void pairs_anchor_write_kernel(const int64_t* off, int64_t M, const int32_t* mpos,
+                                                                 const uint8_t* mst, const int32_t* mseq,
+                                                                 const uint32_t* cnt, const int64_t* lbo,
+                                                                 const int64_t* aoff, const int32_t* cand_tgt,
+                                                                 const uint64_t* key, Anc* A) {
+    const int64_t m = (int64_t)blockIdx.x * TPB + threadIdx.x;
+    if (m >= M) return;
+    const int s = mseq[m];
+    const int64_t len = off[s + 1] - off[s], i = mpos[m];
+    const uint32_t sq = mst[m];
+    const uint64_t grp = (uint64_t)(uint32_t)cand_tgt[s] * 2u;
+    const int64_t b = aoff[m], e0 = lbo[m];
+    for (uint32_t e = 0; e < cnt[m]; ++e) {
+        const uint64_t k = key[e0 + e];
+        const uint32_t rev = sq != (uint32_t)(k & 1u) ? 1u : 0u;
+        const uint64_t x = ((k >> 1) & 0x7fffffffull) + MK - 1;
+        Anc a;
+        a.key = ((grp + rev) << 32) | x;
+        a.y = (uint32_t)(rev ? len - 1 - i : i + MK - 1);
+        a.pad = 0;
+        A[b + e] = a;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------- host
 
 thread_local std::string g_map_err;
@@ -761,6 +913,18 @@ void po_map_index_destroy(po_map_index* ix) {
 
 namespace {
 
+// what a batch of candidates adds to a batch of reads (device pointers, but qry): the target slot of every read of the
+// batch, the targets' sorted keys with their segment offsets and max_occ, and the targets themselves as the contigs
+struct PairCtx {
+    const int32_t* qry;  // HOST: the sequence each read of the batch is
+    const int32_t* cand_tgt;
+    const uint64_t* key;
+    const int64_t* tmoff;
+    const int32_t* max_occ;
+    const char* ctg;
+    const int64_t* ctg_off;
+};
+
 float elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, a, b) != hipSuccess) ms = 0.f;
@@ -769,15 +933,17 @@ float elapsed(hipEvent_t a, hipEvent_t b) {
 
 // one batch: reads ids (indices into the caller's arrays); hits into hits_h, op bytes appended to ops_all; debug arrays
 // at the caller's offsets
+// pc (pairs, §14): read ids[i] is sequence pc->qry[ids[i]] of seq_h and is looked up in the segment of its own target alone
 int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const std::vector<int>& ids, po_map_hit* hits_h,
               std::vector<uint8_t>& ops_all, const int64_t* aoff_h, const int64_t* choff_h, po_map_debug* dbg,
-              double* stats) {
+              double* stats, const PairCtx* pc = nullptr) {
     const int nb = (int)ids.size();
+    auto src = [&](int i) { return pc ? pc->qry[ids[i]] : ids[i]; };
     std::vector<int64_t> off(nb + 1, 0);
-    for (int i = 0; i < nb; ++i) off[i + 1] = off[i] + (off_h[ids[i] + 1] - off_h[ids[i]]);
+    for (int i = 0; i < nb; ++i) off[i + 1] = off[i] + (off_h[src(i) + 1] - off_h[src(i)]);
     const int64_t P = off[nb];
     std::vector<char> hseq(P + 1, 0);
-    for (int i = 0; i < nb; ++i) memcpy(hseq.data() + off[i], seq_h + off_h[ids[i]], off[i + 1] - off[i]);
+    for (int i = 0; i < nb; ++i) memcpy(hseq.data() + off[i], seq_h + off_h[src(i)], off[i + 1] - off[i]);
     Sketch& s = ix->sk;
     MPCHK(s.seq.need(P + 1)); MPCHK(s.off.need((nb + 1) * 8));
     MPCHK(hipMemcpy(s.seq.p, hseq.data(), P + 1, hipMemcpyHostToDevice));
@@ -792,7 +958,11 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
     const int64_t M = mo[nb];
     MPCHK(ix->cnt.need(M * 4 + 4)); MPCHK(ix->lbo.need(M * 8 + 8)); MPCHK(ix->aoff.need((M + 1) * 8));
     MPCHK(ix->raoff.need((nb + 1) * 8));
-    if (M)
+    if (M && pc)
+        pairs_anchor_count_kernel<<<blocks(M, TPB), TPB>>>(s.mh.as<uint32_t>(), s.mseq.as<int32_t>(), M, pc->cand_tgt,
+                                                           pc->key, pc->tmoff, pc->max_occ, ix->cnt.as<uint32_t>(),
+                                                           ix->lbo.as<int64_t>());
+    else if (M)
         map_anchor_count_kernel<<<blocks(M, TPB), TPB>>>(s.mh.as<uint32_t>(), M, ix->ih.as<uint32_t>(), ix->n_entries,
                                                          ix->cnt.as<uint32_t>(), ix->lbo.as<int64_t>());
     MPCHK(s.tmp.need((blocks(M, TILE) + 1) * 8));
@@ -813,7 +983,11 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
     MPCHK(ix->A.need((NA + 1) * (int64_t)sizeof(Anc))); MPCHK(ix->scratch.need((soff[nb] + 1) * (int64_t)sizeof(Anc)));
     MPCHK(ix->soff.need((nb + 1) * 8));
     MPCHK(hipMemcpy(ix->soff.p, soff.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
-    if (M)
+    if (M && pc)
+        pairs_anchor_write_kernel<<<blocks(M, TPB), TPB>>>(s.off.as<int64_t>(), M, s.mpos.as<int32_t>(), s.mst.as<uint8_t>(),
+                                                           s.mseq.as<int32_t>(), ix->cnt.as<uint32_t>(), ix->lbo.as<int64_t>(),
+                                                           ix->aoff.as<int64_t>(), pc->cand_tgt, pc->key, ix->A.as<Anc>());
+    else if (M)
         map_anchor_write_kernel<<<blocks(M, TPB), TPB>>>(s.off.as<int64_t>(), M, s.mpos.as<int32_t>(), s.mst.as<uint8_t>(),
                                                          s.mseq.as<int32_t>(), ix->cnt.as<uint32_t>(), ix->lbo.as<int64_t>(),
                                                          ix->aoff.as<int64_t>(), ix->ipos.as<uint32_t>(),
@@ -862,12 +1036,14 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
     if (nl) MPCHK(hipMemcpy(ix->list.p, list.data(), nl * 4, hipMemcpyHostToDevice));
     MPCHK(hipEventRecord(ix->ev[4], 0));
     if (nl) {
+        const char* ctg = pc ? pc->ctg : ix->ctg.as<char>();
+        const int64_t* ctg_off = pc ? pc->ctg_off : ix->ctg_off.as<int64_t>();
         AlignArgs a{ix->list.as<int32_t>(), s.seq.as<char>(), s.off.as<int64_t>(), ix->A.as<Anc>(), ix->raoff.as<int64_t>(),
-                    ix->chain.as<int32_t>(), ix->co.as<ChainOut>(), ix->ctg.as<char>(), ix->ctg_off.as<int64_t>(),
+                    ix->chain.as<int32_t>(), ix->co.as<ChainOut>(), ctg, ctg_off,
                     ix->band_lo.as<int32_t>(), ix->tb.as<uint32_t>(), ix->best.as<BestOut>()};
         map_align_kernel<<<nl, 64>>>(a);
         TraceArgs t{ix->list.as<int32_t>(), nl, s.seq.as<char>(), s.off.as<int64_t>(), ix->co.as<ChainOut>(),
-                    ix->ctg.as<char>(), ix->ctg_off.as<int64_t>(), ix->band_lo.as<int32_t>(), ix->tb.as<uint32_t>(),
+                    ctg, ctg_off, ix->band_lo.as<int32_t>(), ix->tb.as<uint32_t>(),
                     ix->best.as<BestOut>(), ix->opoff.as<int64_t>(), ix->ops.as<uint8_t>(), ix->hits.as<po_map_hit>()};
         map_trace_kernel<<<blocks(nl, 64), 64>>>(t);
         MPCHK(hipGetLastError());
@@ -964,6 +1140,169 @@ extern "C" int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t
     if (ops_len) *ops_len = (int64_t)ops_all.size();
     if ((int64_t)ops_all.size() > ops_cap || (!ops_h && !ops_all.empty()))
         return map_fail(PO_E_CAP, "po_map_batch_h: ops_cap " + std::to_string(ops_cap) + " < " +
+                                      std::to_string(ops_all.size()) + " alignment columns");
+    if (!ops_all.empty()) memcpy(ops_h, ops_all.data(), ops_all.size());
+    return PO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- pairs: host
+
+namespace {
+
+// device bytes per target base of a batch: sequence, hashes, strands, flags, scan, minimizers, and per minimizer (at most
+// one per base) the key, its sort scratch (two slots: the next power of two) and the run count
+constexpr int64_t TGT_BYTES_PER_BASE = 1 + 4 + 1 + 4 + 8 + (4 + 4 + 1) + 8 + 16 + 4;
+
+struct PairWork {
+    Sketch ts;
+    DBuf key, scratch, soff, runc, max_occ, cand_tgt;
+    hipEvent_t ev[3] = {};
+    void release() {
+        ts.release();
+        for (DBuf* b : {&key, &scratch, &soff, &runc, &max_occ, &cand_tgt}) b->release();
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// one batch of candidates: sketch the distinct targets they name, sort each target's minimizers inside its own segment,
+// take its max_occ, then the read pipeline with the lookup confined to each candidate's segment
+int run_pairs_batch(po_map_index* ix, PairWork& w, const char* tgt_h, const int64_t* tgt_off_h, const char* qry_h,
+                    const int64_t* qry_off_h, const int32_t* cand_h, const std::vector<int>& ids,
+                    std::vector<int32_t>& slot_of, po_map_hit* hits_h, std::vector<uint8_t>& ops_all, double* stats) {
+    const int nb = (int)ids.size();
+    std::vector<int32_t> tgts, cand_tgt(nb);
+    for (int i = 0; i < nb; ++i) {
+        const int32_t t = cand_h[2 * (int64_t)ids[i] + 1];
+        if (slot_of[t] < 0) {
+            slot_of[t] = (int32_t)tgts.size();
+            tgts.push_back(t);
+        }
+        cand_tgt[i] = slot_of[t];
+    }
+    for (int32_t t : tgts) slot_of[t] = -1;
+    const int nt = (int)tgts.size();
+    std::vector<int64_t> toff(nt + 1, 0);
+    for (int i = 0; i < nt; ++i) toff[i + 1] = toff[i] + (tgt_off_h[tgts[i] + 1] - tgt_off_h[tgts[i]]);
+    const int64_t PT = toff[nt];
+    std::vector<char> tseq(PT + 1, 0);
+    for (int i = 0; i < nt; ++i) memcpy(tseq.data() + toff[i], tgt_h + tgt_off_h[tgts[i]], toff[i + 1] - toff[i]);
+    Sketch& ts = w.ts;
+    MPCHK(ts.seq.need(PT + 1)); MPCHK(ts.off.need((nt + 1) * 8)); MPCHK(w.cand_tgt.need(nb * 4 + 4));
+    MPCHK(hipMemcpy(ts.seq.p, tseq.data(), PT + 1, hipMemcpyHostToDevice));
+    MPCHK(hipMemcpy(ts.off.p, toff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    MPCHK(hipMemcpy(w.cand_tgt.p, cand_tgt.data(), nb * 4, hipMemcpyHostToDevice));
+    MPCHK(hipEventRecord(w.ev[0], 0));
+    int rc = run_sketch(ts, nt, PT, false);
+    if (rc) return rc;
+    MPCHK(hipEventRecord(w.ev[1], 0));
+    std::vector<int64_t> tmoff(nt + 1);
+    MPCHK(hipMemcpy(tmoff.data(), ts.moff.p, (nt + 1) * 8, hipMemcpyDeviceToHost));
+    const int64_t MT = tmoff[nt];
+    std::vector<int64_t> soff(nt + 1, 0);
+    for (int i = 0; i < nt; ++i) {
+        int64_t n = tmoff[i + 1] - tmoff[i], np2 = 1;
+        while (np2 < n) np2 <<= 1;
+        soff[i + 1] = soff[i] + (np2 > SEG_LDS ? np2 : 0);
+    }
+    MPCHK(w.key.need(MT * 8 + 8)); MPCHK(w.runc.need(MT * 4 + 4)); MPCHK(w.max_occ.need(nt * 4 + 4));
+    MPCHK(w.scratch.need(soff[nt] * 8 + 8)); MPCHK(w.soff.need((nt + 1) * 8));
+    MPCHK(hipMemcpy(w.soff.p, soff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    pairs_segsort_kernel<<<nt, TPB>>>(ts.mh.as<uint32_t>(), ts.mpos.as<int32_t>(), ts.mst.as<uint8_t>(),
+                                      ts.moff.as<int64_t>(), w.key.as<uint64_t>(), w.scratch.as<uint64_t>(),
+                                      w.soff.as<int64_t>());
+    pairs_maxocc_kernel<<<nt, TPB>>>(w.key.as<uint64_t>(), ts.moff.as<int64_t>(), w.runc.as<uint32_t>(),
+                                     w.max_occ.as<int32_t>());
+    MPCHK(hipGetLastError());
+    MPCHK(hipEventRecord(w.ev[2], 0));
+    // the batch's reads are its candidates' queries, numbered 0 .. nb - 1
+    std::vector<int> local(nb);
+    std::vector<int32_t> qry(nb);
+    for (int i = 0; i < nb; ++i) { qry[i] = cand_h[2 * (int64_t)ids[i]]; local[i] = i; }
+    const PairCtx pc{qry.data(), w.cand_tgt.as<int32_t>(), w.key.as<uint64_t>(), ts.moff.as<int64_t>(),
+                     w.max_occ.as<int32_t>(), ts.seq.as<char>(), ts.off.as<int64_t>()};
+    std::vector<po_map_hit> hb(nb);
+    rc = run_batch(ix, qry_h, qry_off_h, local, hb.data(), ops_all, nullptr, nullptr, nullptr, stats, &pc);
+    if (rc) return rc;
+    for (int i = 0; i < nb; ++i) {
+        hb[i].ctg = cand_h[2 * (int64_t)ids[i] + 1];
+        hits_h[ids[i]] = hb[i];
+    }
+    if (stats) {
+        stats[0] += elapsed(w.ev[0], w.ev[1]);
+        stats[6] += elapsed(w.ev[1], w.ev[2]);
+        stats[7] += nt;
+    }
+    return PO_OK;
+}
+
+}  // namespace
+
+extern "C" int po_map_pairs_h(const char* tgt_h, const int64_t* tgt_off_h, int n_tgt, const char* qry_h,
+                              const int64_t* qry_off_h, int n_qry, const int32_t* cand_h, int n_cand, int64_t budget,
+                              po_map_hit* hits_h, uint8_t* ops_h, int64_t ops_cap, int64_t* ops_len, double* stats_h) {
+    g_map_err.clear();
+    po_set_error("");
+    if (n_tgt < 0 || n_qry < 0 || n_cand < 0 || ops_cap < 0 || (n_tgt > 0 && !tgt_off_h) || (n_qry > 0 && !qry_off_h) ||
+        (n_cand > 0 && (!cand_h || !hits_h)))
+        return map_fail(PO_E_ARG, "po_map_pairs_h: bad arguments");
+    if (stats_h)
+        for (int i = 0; i < 8; ++i) stats_h[i] = 0;
+    if (ops_len) *ops_len = 0;
+    for (int s = 0; s < 2; ++s) {
+        const int64_t* off = s ? qry_off_h : tgt_off_h;
+        const int n = s ? n_qry : n_tgt;
+        if (n > 0 && off[0] != 0) return map_fail(PO_E_ARG, "po_map_pairs_h: offsets must start at 0");
+        for (int i = 0; i < n; ++i)
+            if (off[i + 1] < off[i] || off[i + 1] - off[i] >= ((int64_t)1 << 31))
+                return map_fail(PO_E_ARG, "po_map_pairs_h: offsets must not decrease and sequences must be < 2^31 bases");
+    }
+    for (int64_t c = 0; c < n_cand; ++c)
+        if (cand_h[2 * c] < 0 || cand_h[2 * c] >= n_qry || cand_h[2 * c + 1] < 0 || cand_h[2 * c + 1] >= n_tgt)
+            return map_fail(PO_E_ARG, "po_map_pairs_h: candidate " + std::to_string(c) + " names a sequence out of range");
+    if (n_cand == 0) return PO_OK;
+    if (budget <= 0) budget = (int64_t)std::min<size_t>((size_t)8 << 30, po_dev_info().mem / 16);
+    auto qlen = [&](int c) { return qry_off_h[cand_h[2 * (int64_t)c] + 1] - qry_off_h[cand_h[2 * (int64_t)c]]; };
+    auto tlen = [&](int c) { return tgt_off_h[cand_h[2 * (int64_t)c + 1] + 1] - tgt_off_h[cand_h[2 * (int64_t)c + 1]]; };
+    std::vector<int> order(n_cand);
+    std::iota(order.begin(), order.end(), 0);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return qlen(a) > qlen(b); });
+    po_map_index* ix = new po_map_index;  // the batch workspace only: no contigs, no entries
+    PairWork w;
+    std::vector<uint8_t> ops_all;
+    std::vector<int32_t> slot_of(n_tgt, -1);
+    std::vector<char> in_batch(n_tgt, 0);
+    auto body = [&]() -> int {
+        for (auto& e : ix->ev) MPCHK(hipEventCreate(&e));
+        for (auto& e : w.ev) MPCHK(hipEventCreate(&e));
+        for (size_t i = 0; i < order.size();) {
+            std::vector<int> ids;
+            int64_t bytes = 0;
+            while (i < order.size()) {
+                const int c = order[i];
+                const int32_t t = cand_h[2 * (int64_t)c + 1];
+                int64_t b = qlen(c) * BYTES_PER_BASE + BYTES_PER_READ;
+                if (!in_batch[t]) b += tlen(c) * TGT_BYTES_PER_BASE + BYTES_PER_READ;
+                if (!ids.empty() && bytes + b > budget) break;
+                in_batch[t] = 1;
+                ids.push_back(c);
+                bytes += b;
+                ++i;
+            }
+            for (int c : ids) in_batch[cand_h[2 * (int64_t)c + 1]] = 0;
+            const int rc = run_pairs_batch(ix, w, tgt_h, tgt_off_h, qry_h, qry_off_h, cand_h, ids, slot_of, hits_h, ops_all,
+                                           stats_h);
+            if (rc) return rc;
+        }
+        return PO_OK;
+    };
+    const int rc = body();
+    w.release();
+    po_map_index_destroy(ix);
+    if (rc) return rc;
+    if (ops_len) *ops_len = (int64_t)ops_all.size();
+    if ((int64_t)ops_all.size() > ops_cap || (!ops_h && !ops_all.empty()))
+        return map_fail(PO_E_CAP, "po_map_pairs_h: ops_cap " + std::to_string(ops_cap) + " < " +
                                       std::to_string(ops_all.size()) + " alignment columns");
     if (!ops_all.empty()) memcpy(ops_h, ops_all.data(), ops_all.size());
     return PO_OK;

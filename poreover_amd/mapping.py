@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["Aligner", "Hit", "read_records", "read_fasta", "sketch_device", "hit_from_ops", "reverse_complement_q",
-           "K", "W"]
+           "map_pairs", "map_pairs_raw", "K", "W"]
 
 K, W = 15, 10
 OP_M, OP_X, OP_I, OP_D = 0, 1, 2, 3
@@ -168,6 +168,57 @@ def sketch_device(seqs):
     _lib.check(lib.po_map_sketch_h(buf.ctypes.data, off.ctypes.data, len(seqs), h.ctypes.data, p.ctypes.data,
                                    st.ctypes.data, moff.ctypes.data), "po_map_sketch_h")
     return [(h[moff[i]:moff[i + 1]], p[moff[i]:moff[i + 1]], st[moff[i]:moff[i + 1]]) for i in range(len(seqs))]
+
+
+def map_pairs_raw(targets, queries, candidates, budget=0, ops_cap=None, stats=None):
+    """one po_map_pairs_h call: candidates are (query index, target index); -> (records, op bytes), one
+    record per candidate; stats: a float64[8] array to fill or None"""
+    lib = _lib.load()
+    tbuf, toff = _pack(targets)
+    qbuf, qoff = (tbuf, toff) if queries is targets else _pack(queries)
+    cand = np.ascontiguousarray(np.asarray(candidates, dtype=np.int64).reshape(-1, 2))
+    n = len(cand)
+    if n and (cand.min() < -2 ** 31 or cand.max() >= 2 ** 31):
+        raise _lib.EngineError(_lib.E_ARG, "po_map_pairs_h", "a candidate names a sequence out of range")
+    cand = np.ascontiguousarray(cand.astype(np.int32))
+    recs = (MapHit * max(n, 1))()
+    qlen = (qoff[1:] - qoff[:-1])
+    in_range = n and cand[:, 0].min() >= 0 and cand[:, 0].max() < len(queries)
+    cap = int(2 * qlen[cand[:, 0]].sum() + 1024 * n + 1024) if (ops_cap is None and in_range) else int(ops_cap or 0)
+    need = C.c_int64(0)
+    st = stats.ctypes.data if stats is not None else None
+    while True:
+        ops = np.empty(max(cap, 1), np.uint8)
+        rc = lib.po_map_pairs_h(tbuf.ctypes.data, toff.ctypes.data, len(targets), qbuf.ctypes.data, qoff.ctypes.data,
+                                len(queries), cand.ctypes.data, n, int(budget), C.addressof(recs), ops.ctypes.data, cap,
+                                C.byref(need), st)
+        if rc == _lib.E_CAP and ops_cap is None and need.value > cap:
+            cap = need.value
+            continue
+        _lib.check(rc, "po_map_pairs_h")
+        break
+    return recs, ops[:need.value]
+
+
+def map_pairs(targets, queries, candidates, budget=0, stats=None, names=None):
+    """the primary Hit (or None) of every candidate (query index, target index): the query mapped against an index that
+    holds its target alone, all candidates in one device call.  ctg is the target's name (names) or its index."""
+    targets = [s.upper() for s in targets]
+    queries = targets if queries is targets else [s.upper() for s in queries]
+    candidates = [(int(q), int(t)) for q, t in candidates]
+    recs, ops = map_pairs_raw(targets, queries, candidates, budget, stats=stats)
+    out = []
+    for i, (q, t) in enumerate(candidates):
+        r = recs[i]
+        if not r.mapped:
+            out.append(None)
+            continue
+        s = queries[q]
+        Q = reverse_complement_q(s) if r.strand < 0 else s
+        qs = len(s) - r.q_en if r.strand < 0 else r.q_st
+        out.append(hit_from_ops(ops[r.op_off:r.op_off + r.n_ops], names[t] if names is not None else t, len(targets[t]),
+                                targets[t], Q, len(s), r.r_st, qs, r.strand))
+    return out
 
 
 class Aligner:
