@@ -574,6 +574,39 @@ int po_label_align_batch_h(const double* y_h, const int64_t* y_off_h, int n, int
                            int band_size, const char* labels_h, const int64_t* label_off_h, const int32_t* guide_h,
                            int32_t* map_h, double* score_h, int32_t* status_h);
 
+/* ---- decode --fastq: per-base log-odds of a called sequence (po_qual.hip) ----
+ * A guided, banded forward-backward lattice over a whole read.  F(x) = log P(x | y) under the model's tree recurrence
+ * (what po_forward_batch computes); for a read with table y [T][C] and called sequence s [L]:
+ *   odds[k][b] = F(s with s[k] replaced by alphabet[b]) - F(s), b < len(alphabet) (0 for s[k] itself, -inf for b >=
+ *                len(alphabet));   odds[k][4] = F(s with s[k] deleted) - F(s).      Insertions are not among the alternatives.
+ * model: PO_MODEL_CTC (a non-blank frame emits one base; state k = bases emitted) or PO_MODEL_MERGE (a run of equal
+ * frames is one base, equal neighbours need a blank between them, and — as in the tree — the first base's run starts
+ * at frame 0; every label position has a blank and a label state, which the band admits together).
+ * PO_MODEL_FLIPFLOP returns PO_E_UNSUPPORTED.  C = len(alphabet) + 1, blank = column C - 1.
+ * Per read i: y float64 rows y_off[i] .. y_off[i+1], label characters [L_i] at label_off[i], guide int32 [T_i] at
+ * y_off[i] or guide == NULL (c[t] = floor((t + 1) * L / T)); one band_size B per batch (<= 0: no band); L_i < 2^26.  Rows are
+ * counted u = 0 .. T, "after frame u - 1": row 0 admits position 0, row u >= 1 admits
+ * max(0, c[u-1] - B) <= k <= min(L, c[u-1] + B); every other cell is -inf in the forward and in the backward lattice
+ * alike, so every F above is the sum over the paths that stay inside the band in the coordinates of s (a substitution
+ * at k is in state k before its first frame and k + 1 from then on; a deletion of k moves from k to k + 2 with the
+ * frame that emits s[k+1], or ends the read in state L - 1 for k = L - 1).
+ * odds float64 [total_labels][5] at label_off[i] * 5; logp[i] = F(s) in the band (the backward lattice's corner).
+ * status[i] (no batch abort): 0; PO_E_ENVELOPE when F(s) is -inf in the band (or L > T); PO_E_ARG for a label
+ * character outside the alphabet, or a guide that decreases or leaves [0, L].  A read with a non-zero status gets
+ * odds 0 and logp -inf.  L == 0 is valid: no rows of odds, logp = the sum of the blanks.
+ * Float64 and log-space (logaddexp) throughout, no atomics, one workgroup per read: two runs give the same bits and a
+ * read's bits do not depend on the rest of the batch.  The backward lattice's rows are kept in the workspace:
+ * po_qual_workspace_bytes is at most (total_rows + n) * (2B + 2) * 8 (* 2 for PO_MODEL_MERGE) +
+ * 112 * (total_labels + n) + 32 * n + 2^10 for B >= 1, and (max_rows + 1) * (total_labels + n) * 8 (* 2) + the same
+ * tail without a band; 0 for a model other than the two. */
+size_t po_qual_workspace_bytes(int n, int64_t total_rows, int64_t max_rows, int64_t total_labels, int band_size, int model);
+int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
+                  const int64_t* label_off, const int32_t* guide, int band_size, double* odds, double* logp,
+                  int32_t* status, void* ws, size_t ws_bytes, void* stream);
+int po_qual_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, const char* alphabet, int model,
+                    const char* labels_h, const int64_t* label_off_h, const int32_t* guide_h, int band_size,
+                    double* odds_h, double* logp_h, int32_t* status_h);
+
 /* ---- timing aid for bench.py: HIP events on the stream the kernels run on ----------------- */
 void* po_event_create(void);
 int po_event_record(void* ev, void* stream);

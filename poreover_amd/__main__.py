@@ -10,6 +10,7 @@ import logging
 import sys
 
 from . import __version__
+from .quality import DEFAULT_BAND
 
 
 def build_parser():
@@ -59,6 +60,8 @@ def build_parser():
     p.add_argument('--window', type=int, default=400, help='Use chunks of this size for prefix search')
     p.add_argument('--beam_width', type=int, default=25, help='Width for beam search')
     p.add_argument('--threads', type=int, default=1, help='Upper bound on the GPUs one call is spread over when > 1 (the reference: worker processes); batching replaces processes on each device')
+    p.add_argument('--fastq', action='store_true', default=False, help='Also write {out}.fastq with a Phred quality per base (poreover and bonito inputs)')
+    p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="decode")
 
@@ -86,6 +89,8 @@ def build_parser():
     p.add_argument('--skip_threshold', type=int, default=10, help='Number of consecutive matches to use for --skip_matches')
     p.add_argument('--beam_search_method', choices=['row', 'row_col', 'grid'], default="row_col", help=argparse.SUPPRESS)
     p.add_argument('--window', type=int, default=200, help=argparse.SUPPRESS)
+    p.add_argument('--fastq', action='store_true', default=False, help='Also write FASTQ with a Phred quality per base: {out}.1d.fastq and {out}.2d.fastq for a list of pairs, {out}.fastq for one pair (poreover and bonito inputs)')
+    p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.set_defaults(func="pair-decode")
 
     p = subparsers.add_parser('benchmark', help='Assess accuracy of basecalled FASTA/FASTQ files')

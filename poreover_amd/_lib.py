@@ -173,6 +173,11 @@ PROTOTYPES = {
                                        _vp, C.c_size_t, _vp]),
     "po_label_align_batch_h": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, _i32p, _dp,
                                          _i32p]),
+    "po_qual_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int]),
+    "po_qual_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, C.c_int, _dp, _dp, _i32p,
+                                _vp, C.c_size_t, _vp]),
+    "po_qual_batch_h": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, C.c_int, _dp, _dp,
+                                  _i32p]),
     "po_event_create": (C.c_void_p, []),
     "po_event_record": (C.c_int, [C.c_void_p, C.c_void_p]),
     "po_event_elapsed_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),

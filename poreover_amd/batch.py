@@ -13,7 +13,7 @@ import numpy as np
 from . import _lib as L
 
 __all__ = ["viterbi_batch", "beam_search_batch", "beam_search_2d_batch", "pair_decode_batch", "pair_decode_batch_sharded", "pair_decode_stream", "decode_1d_batch", "pack_rows",
-           "forward_batch", "viterbi_acceptor_batch", "label_align_batch", "prefix_search_batch", "pair_prefix_search_batch", "forward_vec_batch", "align_batch", "envelope_batch", "ingest_batch", "pair_gamma_batch"]
+           "forward_batch", "viterbi_acceptor_batch", "label_align_batch", "qual_batch", "prefix_search_batch", "pair_prefix_search_batch", "forward_vec_batch", "align_batch", "envelope_batch", "ingest_batch", "pair_gamma_batch"]
 
 
 def pack_rows(arrays, C_expected=None):
@@ -559,6 +559,66 @@ def label_align_batch(arrays, labels, guides=None, band_size=32, alphabet="ACGT"
     L.check(lib.po_label_align_batch_h(_ptr(y), _ptr(off), n, Cc, alphabet.encode(), int(band_size), _ptr(lb), _ptr(lo),
                                        _ptr(g), _ptr(mp), _ptr(sc), _ptr(st)), "po_label_align_batch_h")
     return [mp[lo[i]:lo[i + 1]].astype(np.int64) for i in range(n)], sc[:n].copy(), st[:n].copy()
+
+
+QUAL_DEFAULT_BAND = 16        # label positions either side of the guide (how it was chosen)
+_QUAL_CHUNK_BYTES = 8 << 30   # stored lattice rows of one po_qual_batch_h call: enough reads to fill the device (a read's bits do not depend on its batch)
+
+
+def qual_batch(arrays, labels, guides=None, band_size=None, alphabet="ACGT", model="ctc"):
+    """Per-base log-odds of called sequences (po_qual_batch_h): for each (T, C) float64 table and its called
+    sequence s, odds[k][b] = log P(s with s[k] replaced by alphabet[b] | y) - log P(s | y) (0 for s[k] itself) and
+    odds[k][4] = the same for s with s[k] deleted, under `model` ("ctc" or "ctc_merge_repeats"; "ctc_flipflop" raises
+    EngineError(E_UNSUPPORTED)), all of them inside the band of band_size label positions around guides[i] (per read an
+    int array (T,), non-decreasing, 0..L; None: the straight diagonal; band_size None: QUAL_DEFAULT_BAND, <= 0: no band).  Insertions are not
+    among the alternatives.  Returns (odds, logp, status): odds[i] float64 (L_i, 5), logp float64 (n,) = log P(s | y) in
+    the band, status int32 (n,): 0, E_ENVELOPE (the band admits no path, or L > T), E_ARG (a label character outside
+    the alphabet, a bad guide).  A read with a non-zero status has odds 0 and logp -inf; no read fails the batch."""
+    lib = L.load()
+    n = len(arrays)
+    if len(labels) != n or (guides is not None and len(guides) != n):
+        raise ValueError("qual_batch: one label (and one guide) per table")
+    if model not in L.MODELS:
+        raise ValueError("qual_batch: unknown model %r" % (model,))
+    if model == "ctc_flipflop":
+        raise L.EngineError(L.E_UNSUPPORTED, "qual_batch", "the flip-flop model has no quality lattice")
+    if guides is not None:
+        for i, gi in enumerate(guides):
+            if len(gi) != len(arrays[i]):
+                raise ValueError("qual_batch: guide %d has %d entries for %d frames" % (i, len(gi), len(arrays[i])))
+    nb = 2 if model == "ctc_merge_repeats" else 1
+    band = QUAL_DEFAULT_BAND if band_size is None else int(band_size)
+
+    def cost(i):
+        Li = len(labels[i])
+        w = Li + 1 if (band < 1 or 2 * band + 2 >= Li + 1) else 2 * band + 2
+        return (len(arrays[i]) + 1) * w * nb * 8
+
+    odds, logp, status = [None] * n, np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.int32)
+    lo = 0
+    while lo < n:
+        hi, tot = lo, 0
+        while hi < n and (hi == lo or tot + cost(hi) <= _QUAL_CHUNK_BYTES):
+            tot += cost(hi)
+            hi += 1
+        y, off, Cc = pack_rows(arrays[lo:hi], len(alphabet) + 1)
+        m = hi - lo
+        lb, lof = _pack_labels(labels[lo:hi])
+        g = None
+        if guides is not None:
+            g = np.ascontiguousarray(np.concatenate([np.asarray(gi, dtype=np.int64) for gi in guides[lo:hi]] + [np.zeros(1, np.int64)])
+                                     .clip(-2 ** 31, 2 ** 31 - 1), dtype=np.int32)
+        od = np.zeros((max(int(lof[-1]), 1), 5), dtype=np.float64)
+        lp = np.zeros(m, dtype=np.float64)
+        st = np.zeros(m, dtype=np.int32)
+        L.check(lib.po_qual_batch_h(_ptr(y), _ptr(off), m, Cc, alphabet.encode(), L.MODELS[model], _ptr(lb), _ptr(lof), _ptr(g),
+                                    band, _ptr(od), _ptr(lp), _ptr(st)), "po_qual_batch_h")
+        for j in range(m):
+            odds[lo + j] = od[lof[j]:lof[j + 1]].copy()
+        logp[lo:hi] = lp
+        status[lo:hi] = st
+        lo = hi
+    return odds, logp, status
 
 
 def prefix_search_batch(y, offsets, alphabet="ACGT"):

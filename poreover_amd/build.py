@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libporeover_hip.so")
-SOURCES = ["po_capi.hip", "po_viterbi.hip", "po_beam1d.hip", "po_beam2d.hip", "po_beam2d_reg.hip", "po_pair.hip", "po_lattice.hip", "po_prefix.hip", "po_ingest.hip", "po_gamma.hip", "po_stream.hip", "po_call.hip", "po_train.hip", "po_map.hip", "po_label.hip"]
+SOURCES = ["po_capi.hip", "po_viterbi.hip", "po_beam1d.hip", "po_beam2d.hip", "po_beam2d_reg.hip", "po_pair.hip", "po_lattice.hip", "po_prefix.hip", "po_ingest.hip", "po_gamma.hip", "po_stream.hip", "po_call.hip", "po_train.hip", "po_map.hip", "po_label.hip", "po_qual.hip"]
 HEADERS = ["po_device.h", os.path.join("..", "..", "include", "poreover_hip.h")]
 # Per-object compiler options (measured, round 6: profiles/r06_ab_compiler_flags.txt).  -amdgpu-use-amdgpu-trackers (the AMDGPU register-pressure
 # trackers in the machine scheduler) is worth 1 % on the 32-slot pair kernel, costs 1.5 % on the 64-slot pair kernel and 5 % on beam2d_kernel's

@@ -171,9 +171,43 @@ def decode_models(models, args):
     return out
 
 
+def model_qualities(models, seqs, args):
+    """--fastq: the quality string of seqs[i] (the final decoded string, whatever --algorithm made it) on read i: one
+    guided lattice call per model kind (quality.call_qualities)"""
+    from .. import quality
+    band = getattr(args, 'qual_band', None)
+    band = quality.DEFAULT_BAND if band is None else band
+    out = [None] * len(models)
+    by_kind = {}
+    for i, m in enumerate(models):
+        by_kind.setdefault(m.kind, []).append(i)
+    for kind, idx in by_kind.items():
+        quals = quality.qualities([models[i] for i in idx], [seqs[i] for i in idx], kind, band)
+        for i, q in zip(idx, quals):
+            out[i] = quality.qual_string(q)
+    return out
+
+
+def _refuse_fastq_flipflop(models, args):
+    from .. import quality
+    quality.refuse_flipflop(args.basecaller)
+    for m in models:
+        if m.kind == 'flipflop':
+            quality.refuse_flipflop('flipflop')
+
+
 def decode_files_local(in_files, args):
-    """Sequences of a list of trace files, decoded on THIS process's device (one batched engine call per kind)."""
-    return decode_models([model_from_trace(p, args.basecaller) for p in in_files], args)
+    """Sequences of a list of trace files, decoded on THIS process's device (one batched engine call per kind); with
+    --fastq, (sequence, quality string) per file."""
+    fastq = bool(getattr(args, 'fastq', False))
+    if fastq:
+        _refuse_fastq_flipflop([], args)
+    models = [model_from_trace(p, args.basecaller) for p in in_files]
+    if not fastq:
+        return decode_models(models, args)
+    _refuse_fastq_flipflop(models, args)   # a .csv says what it holds only once it is read
+    seqs = decode_models(models, args)
+    return list(zip(seqs, model_qualities(models, seqs, args)))
 
 
 def decode_files(in_files, args, devices=None, decode_fn=None):
@@ -214,6 +248,10 @@ def decode(args):
     logger = logging.getLogger("poreover_amd")
     in_path = getattr(args, 'in')
     in_files = in_path
+    fastq = bool(getattr(args, 'fastq', False))
+    if fastq:
+        from .. import quality
+        quality.refuse_flipflop(args.basecaller)
     if len(in_path) == 1 and os.path.isdir(in_path[0]):
         file_ext = {'guppy': '.fast5', 'flappie': '.hdf5', 'bonito': '.npy', 'poreover': '.npy'}[args.basecaller]
         in_files = sorted(glob.glob("{}/*{}".format(in_path[0], file_ext)))
@@ -222,9 +260,21 @@ def decode(args):
         seqs = decode_files(in_files, args)
         if seqs is None:   # a rank other than 0 of a torchrun launch: rank 0 writes the file
             return
+        if fastq:
+            seqs, quals = [s for s, _ in seqs], [q for _, q in seqs]
         with open(args.out + '.fasta', 'w') as out_f:
             for p, s in zip(in_files, seqs):
                 print(fasta_format(Path(p).stem, s), file=out_f)
+        if fastq:
+            with open(args.out + '.fastq', 'w') as out_q:
+                for p, s, q in zip(in_files, seqs, quals):
+                    out_q.write(quality.fastq_format(Path(p).stem, s, q))
+    elif fastq:
+        seq, qual = decode_files_local(in_files[:1], args)[0]
+        with open(args.out + '.fasta', 'w') as out_fasta:
+            print(fasta_format(Path(in_files[0]).stem, seq), file=out_fasta)
+        with open(args.out + '.fastq', 'w') as out_q:
+            out_q.write(quality.fastq_format(Path(in_files[0]).stem, seq, qual))
     else:
         seqs = decode_helper(in_files[0], args)
         with open(args.out + '.fasta', 'w') as out_fasta:

@@ -256,12 +256,82 @@ def _write_debug_pickle(pair, rec, args):
                      'sequence_to_signal2': [int(x) for x in maps[1]], 'alignment': alignment}, pfile)
 
 
+def _fasta_records(text):
+    """(name, sequence) of every record of a FASTA text as fasta_format wrote it"""
+    recs = []
+    for line in text.split('\n'):
+        if line.startswith('>'):
+            recs.append([line[1:], []])
+        elif recs:
+            recs[-1][1].append(line)
+    return [(name, ''.join(parts)) for name, parts in recs]
+
+
+def _attach_fastq(loaded, out, args):
+    """--fastq: qualities of the final strings of every decoded pair, whatever route made them.  seq1 is scored on read
+    1's table and seq2 on read 2's (as the pair decoder saw it: after --reverse_complement); the consensus is scored on
+    both and the two tables are summed (quality.combine).  All lattices of a kind go to the engine in one call.  The
+    FASTQ texts travel in the record's summary under 'fastq': (1D text or None, 2D text)."""
+    from .. import quality
+    band = getattr(args, 'qual_band', None)
+    band = quality.DEFAULT_BAND if band is None else band
+    by_kind = {}
+    for i, rec in enumerate(out):
+        if rec is not None and len(rec) in (2, 3):
+            by_kind.setdefault(loaded[i][2].kind, []).append(i)
+    for kind, idx in by_kind.items():
+        tables, seqs, slots = [], [], []
+        for i in idx:
+            rec = out[i]
+            y1, y2 = loaded[i][2].log_prob, loaded[i][3].log_prob
+            cons = _fasta_records(rec[-2])[0]
+            if len(rec) == 3:
+                (n1, s1), (n2, s2) = _fasta_records(rec[0])
+                tables += [y1, y2]; seqs += [s1, s2]; slots += [(i, 'seq1', n1), (i, 'seq2', n2)]
+            tables += [y1, y2]; seqs += [cons[1], cons[1]]; slots += [(i, 'cons1', cons[0]), (i, 'cons2', cons[0])]
+        odds, status, _ = quality.call_qualities(tables, seqs, kind, band)
+        got = {}
+        for (i, what, name), o, s, st in zip(slots, odds, seqs, status):
+            got.setdefault(i, {})[what] = (name, s, o, st)
+        unscored = ["%s of pair %d (%s)" % (what, i, _lib._CODE_NAMES.get(int(st), int(st)))
+                    for (i, what, _), st in zip(slots, status) if st != 0]
+        if unscored:
+            quality.warn_unscored(unscored)
+        for i in idx:
+            g = got[i]
+
+            def q_of(o, s, ok):
+                return quality.phred(o, s) if ok else [0] * len(s)
+            text_1d = None
+            if 'seq1' in g:
+                text_1d = ''.join(quality.fastq_format(name, s, q_of(o, s, st == 0)) for name, s, o, st in (g['seq1'], g['seq2']))
+            (name, s, o1, st1), (_, _, o2, st2) = g['cons1'], g['cons2']
+            if st1 == 0 and st2 == 0:
+                qc = quality.phred(quality.combine(o1, o2), s)
+            else:   # one read cannot score the consensus: the other's evidence alone
+                qc = q_of(o1, s, True) if st1 == 0 else q_of(o2, s, st2 == 0)
+            out[i][-1]['fastq'] = (text_1d, quality.fastq_format(name, s, qc))
+    return out
+
+
 def decode_pairs_local(in_paths, args, devices=None):
     """pair_decode_helper for a list of pairs in THIS process — on its device, or on every device of `devices` through
     the multi-device pipeline: returns a list of the reference's return tuples (1-, 2- or 3-tuples,
-    pair_decode.py:375,398,526-529)."""
+    pair_decode.py:375,398,526-529).  With --fastq the summary of a decoded pair carries its FASTQ texts (_attach_fastq)."""
     _check_supported(args)
+    if getattr(args, 'fastq', False):
+        from .. import quality
+        quality.refuse_flipflop(args.basecaller)
     loaded = [_load_pair(p, args) for p in in_paths]
+    if getattr(args, 'fastq', False):
+        for _, _, m1, _ in loaded:
+            if m1.kind == 'flipflop':
+                quality.refuse_flipflop('flipflop')
+        return _attach_fastq(loaded, _decode_pairs_local(in_paths, loaded, args, devices), args)
+    return _decode_pairs_local(in_paths, loaded, args, devices)
+
+
+def _decode_pairs_local(in_paths, loaded, args, devices=None):
     out = [None] * len(loaded)
     if getattr(args, 'method', 'envelope') == 'split':
         return _decode_pairs_split(in_paths, loaded, args, out)
@@ -354,6 +424,10 @@ def pair_decode(args):
     {out}.log; two positionals = one pair -> {out}.fasta."""
     logger = logging.getLogger("poreover_amd")
     in_path = getattr(args, 'in')
+    fastq = bool(getattr(args, 'fastq', False))
+    if fastq:
+        from .. import quality
+        quality.refuse_flipflop(args.basecaller)
     if len(in_path) == 1:
         with open(in_path[0], 'r') as read_pairs:
             pairs = [line.split() for line in read_pairs if line.split()]
@@ -361,6 +435,13 @@ def pair_decode(args):
         results = decode_pairs(pairs, args)
         if results is None:   # a rank other than 0 of a torchrun launch: rank 0 writes the files
             return
+        if fastq:
+            texts = [x[-1].pop('fastq', None) if len(x) in (2, 3) else None for x in results]
+            with open(args.out + '.1d.fastq', 'w') as q1, open(args.out + '.2d.fastq', 'w') as q2:
+                for t in texts:
+                    if t is not None:
+                        q1.write(t[0] or '')
+                        q2.write(t[1])
         keys = ["read1", "read2", "length1", "length2", "sequence_identity", "skipped"]
         with open(args.out + '.1d.fasta', 'w') as out_1d_f, open(args.out + '.2d.fasta', 'w') as out_2d_f, \
                 open(args.out + '.log', 'w', 1) as log_f:
@@ -386,6 +467,10 @@ def pair_decode(args):
         else:
             print(res[0], file=sys.stderr)
             return
+        text = summary.pop('fastq', None) if fastq else None
         print(summary, file=sys.stderr)
+        if text is not None:
+            with open(args.out + '.fastq', 'w') as out_fastq:
+                out_fastq.write(text[1])
         with open(args.out + '.fasta', 'w') as out_fasta:
             print(seq_2d, file=out_fasta)

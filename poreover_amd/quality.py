@@ -1,0 +1,151 @@
+"""Per-base qualities of decoded sequences (`decode --fastq`, `pair-decode --fastq`).
+
+The engine gives, for a read's table y and a called sequence s, the log-odds table of the call (batch.qual_batch):
+odds[k][b] = log P(s with s[k] replaced by base b | y) - log P(s | y) and odds[k][4] for s[k] deleted.  Insertions
+next to k are not among the alternatives.  The error probability of base k is the alternatives' share,
+
+    e_k = (sum_{b != s[k]} exp(odds[k][b]) + exp(odds[k][4])) / (the same sum + 1),
+
+Q_k = clip(floor(-10 log10(e_k) + 0.5), 0, 60) and the FASTQ character is chr(33 + Q_k).  Two reads of one molecule are
+independent evidence: a pair consensus gets one table per read and their element-wise sum (combine)."""
+import numpy as np
+
+from . import _lib
+from . import batch as _batch
+
+__all__ = ["DEFAULT_BAND", "MODEL_OF_KIND", "phred", "combine", "fastq_format", "qual_string", "call_qualities", "refuse_flipflop"]
+
+DEFAULT_BAND = _batch.QUAL_DEFAULT_BAND   # the one default of the knob (batch.qual_batch, --qual_band)
+MODEL_OF_KIND = {"poreover": "ctc", "bonito": "ctc_merge_repeats"}
+Q_MAX = 60
+
+
+def phred(odds, seq, alphabet="ACGT"):
+    """uint8 (L,): Q_k of every base of seq from its log-odds table (L, 5), in log space"""
+    odds = np.asarray(odds, dtype=np.float64).reshape(-1, 5)
+    L = len(seq)
+    if odds.shape[0] != L:
+        raise ValueError("phred: %d rows of odds for %d bases" % (odds.shape[0], L))
+    if L == 0:
+        return np.zeros(0, dtype=np.uint8)
+    raw = np.frombuffer(seq.encode("ascii"), dtype=np.uint8)
+    own = np.full(L, -1, dtype=np.int64)
+    for b, ch in enumerate(alphabet):
+        own[raw == ord(ch)] = b
+    if np.any(own < 0):
+        raise ValueError("phred: a base outside the alphabet")
+    alt = odds.copy()
+    alt[np.arange(L), own] = -np.inf
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        m = alt.max(axis=1)
+        ms = np.where(np.isfinite(m), m, 0.0)
+        la = np.log(np.sum(np.exp(alt - ms[:, None]), axis=1)) + ms     # log of the alternatives' odds
+        la = np.where(m == np.inf, np.inf, la)
+        log_e = np.where(la == np.inf, 0.0, la - np.logaddexp(la, 0.0))
+        q = -10.0 * log_e / np.log(10.0)
+        return np.clip(np.floor(q + 0.5), 0, Q_MAX).astype(np.uint8)
+
+
+def combine(odds1, odds2):
+    """the table of two independent reads of one sequence: the element-wise sum"""
+    a, b = np.asarray(odds1, dtype=np.float64), np.asarray(odds2, dtype=np.float64)
+    if a.shape != b.shape:
+        raise ValueError("combine: tables of %s and %s" % (a.shape, b.shape))
+    return a + b
+
+
+def qual_string(q):
+    return (np.asarray(q, dtype=np.uint8) + 33).tobytes().decode("ascii")
+
+
+def fastq_format(name, seq, qual):
+    """one four-line record, the sequence on one line; qual: Phred values (L,) or the quality string itself"""
+    if not isinstance(qual, str):
+        qual = qual_string(qual)
+    if len(qual) != len(seq):
+        raise ValueError("fastq_format: %d qualities for %d bases" % (len(qual), len(seq)))
+    return "@" + name + "\n" + seq + "\n+\n" + qual + "\n"
+
+
+def refuse_flipflop(basecaller, flag="--fastq"):
+    """flip-flop inputs have no quality lattice: refused before any device work"""
+    if basecaller in ("guppy", "flappie", "flipflop"):
+        raise _lib.EngineError(_lib.E_UNSUPPORTED, flag,
+                               "%s is not available for flip-flop (%s) inputs: qualities exist for the ctc and "
+                               "ctc_merge_repeats models only" % (flag, basecaller))
+
+
+def warn_unscored(what):
+    """one log line for the sequences that could not be scored and are written with Q 0 (or with one read's evidence)"""
+    import logging
+    logging.getLogger("poreover_amd").warning("--fastq: %d sequence(s) not scored, written with Q 0 or one read's evidence: %s%s",
+                                              len(what), ", ".join(what[:8]), " ..." if len(what) > 8 else "")
+
+
+def call_guides(tables, seqs, kind):
+    """Band guides for scoring seqs[i] on tables[i]: the Viterbi call's frame map says how many called bases every frame
+    has behind it; when seqs[i] is not that call (beam, prefix, consensus) the two are aligned and the count is taken
+    in seqs[i]'s bases, as make_labeled_data does for a truth.  A read without a Viterbi call gets the diagonal."""
+    from .network.make_labeled_data import consumed_from_columns, guide_from_alignment   # the same two rules
+    n = len(tables)
+    called, maps, vst = _batch.viterbi_batch(tables, kind, return_map=True) if n else ([], [], [])
+    consumed = [None] * n
+    todo = []
+    for i in range(n):
+        if vst[i] != 0 or not len(called[i]) or not len(seqs[i]):
+            continue
+        if called[i] == seqs[i]:
+            consumed[i] = np.arange(1, len(called[i]) + 1, dtype=np.int64)
+        else:
+            todo.append(i)
+    if todo:
+        slack = max(abs(len(called[i]) - len(seqs[i])) for i in todo)
+        cols = _batch.align_batch([(called[i], seqs[i]) for i in todo], band_width=500 + slack)
+        for i, (a1, a2) in zip(todo, cols):
+            # (the banded aligner can repeat a base of its second row at a band edge: the count stays within seqs[i])
+            consumed[i] = np.minimum(consumed_from_columns(a1, a2)[0], len(seqs[i]))
+    guides = []
+    for i in range(n):
+        T, L = len(tables[i]), len(seqs[i])
+        if consumed[i] is None or len(consumed[i]) != len(maps[i]):
+            guides.append((np.arange(1, T + 1, dtype=np.int64) * L) // max(T, 1))
+        else:
+            guides.append(guide_from_alignment(maps[i], consumed[i], T))
+    return guides
+
+
+def call_qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND, return_guides=False, timings=None):
+    """Log-odds tables of seqs[i] on read i (a transducer object or a (T, 5) float64 table), kind "poreover" or "bonito".
+    A read whose banded lattice is lost (E_ENVELOPE) is tried once more without a band.  Returns (odds, status, retried):
+    odds[i] float64 (L_i, 5); status int32 (n,) after the retry; retried: the indices that needed it.  timings (a dict)
+    gets the wall seconds of the two stages added: guides, lattice."""
+    import time
+    if kind not in MODEL_OF_KIND:
+        raise _lib.EngineError(_lib.E_UNSUPPORTED, "call_qualities", "no quality lattice for %r inputs" % (kind,))
+    tables = [np.ascontiguousarray(m.log_prob if hasattr(m, "log_prob") else m, dtype=np.float64) for m in models_or_arrays]
+    if len(seqs) != len(tables):
+        raise ValueError("call_qualities: one sequence per read")
+    model = MODEL_OF_KIND[kind]
+    t0 = time.perf_counter()
+    guides = call_guides(tables, seqs, kind)
+    t1 = time.perf_counter()
+    odds, _, status = _batch.qual_batch(tables, seqs, guides, band_size=band, model=model) if tables else ([], None, np.zeros(0, np.int32))
+    retried = [i for i in range(len(tables)) if status[i] == _lib.E_ENVELOPE] if band > 0 else []
+    if retried:
+        o2, _, s2 = _batch.qual_batch([tables[i] for i in retried], [seqs[i] for i in retried], None, band_size=0, model=model)
+        for j, i in enumerate(retried):
+            odds[i], status[i] = o2[j], s2[j]
+    if timings is not None:
+        timings["guides"] = timings.get("guides", 0.0) + t1 - t0
+        timings["lattice"] = timings.get("lattice", 0.0) + time.perf_counter() - t1
+    out = (odds, status, retried)
+    return out + (guides,) if return_guides else out
+
+
+def qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND):
+    """Phred arrays of seqs[i] on read i; a read that cannot be scored at all (status != 0) gets Q 0 throughout"""
+    odds, status, _ = call_qualities(models_or_arrays, seqs, kind, band)
+    bad = [i for i, st in enumerate(status) if st != 0]
+    if bad:
+        warn_unscored(["read %d (%s)" % (i, _lib._CODE_NAMES.get(int(status[i]), int(status[i]))) for i in bad])
+    return [phred(o, s) if st == 0 else np.zeros(len(s), dtype=np.uint8) for o, s, st in zip(odds, seqs, status)]
