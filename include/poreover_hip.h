@@ -108,6 +108,13 @@ int po_set_pair_route(int route, int defer_odd);
 #define PO_CHAIN_CLOSED_GUARD3 2
 int po_set_chain_mode(int mode);
 int po_get_chain_mode(void);
+/* The register-state pair kernel has one instantiation compiled for the default shape — the ctc model, beam_width 5, four
+ * bases (A = 4, C = 5) — with the three numbers as compile-time constants: the same arithmetic in the same
+ * order, fewer vector instructions per pair.  on != 0 (default): launches of that shape take it; on == 0: they run the
+ * run-time kernel every other shape runs — for the tests, which compare the two, and for A/B timing from one library.
+ * The environment variable PO_REG_FIXED_SHAPE=0 gives the initial value "off".  Process-wide; results are identical. */
+int po_set_reg_fixed_shape(int on);
+int po_get_reg_fixed_shape(void);
 /* The register-state pair kernel keeps its value stores and tree arenas in a slice POOL the library owns: one per device, tree
  * model and lane layout (beam_width <= 6 / 7..12), as many slices as the device holds pair waves (<ctc, W <= 6>: 4 096 x 1.28 MB
  * = 5.3 GB), made by the first workspace-size query that selects the route and kept for the life of the process.

@@ -61,6 +61,8 @@ PROTOTYPES = {
     "po_set_pair_route": (C.c_int, [C.c_int, C.c_int]),
     "po_set_chain_mode": (C.c_int, [C.c_int]),
     "po_get_chain_mode": (C.c_int, []),
+    "po_set_reg_fixed_shape": (C.c_int, [C.c_int]),
+    "po_get_reg_fixed_shape": (C.c_int, []),
     "po_reg_pool_prewarm": (C.c_int, [C.c_int, C.c_int]),
     "po_reg_pool_release": (C.c_int, []),
     "po_debug_deferred_pairs": (C.c_longlong, [C.c_int]),
@@ -249,6 +251,16 @@ def set_chain_mode(mode="serial"):
 
 def get_chain_mode():
     return {v: k for k, v in CHAIN_MODES.items()}[int(load(False).po_get_chain_mode())]
+
+
+def set_reg_fixed_shape(on=True):
+    """po_set_reg_fixed_shape: whether pair launches of the default shape (ctc, beam_width 5, four bases) take the register-state
+    kernel's instantiation compiled for that shape (default) or the run-time kernel of every other shape; results are identical"""
+    check(load(False).po_set_reg_fixed_shape(1 if on else 0), "po_set_reg_fixed_shape")
+
+
+def get_reg_fixed_shape():
+    return bool(load(False).po_get_reg_fixed_shape())
 
 
 def reg_pool_prewarm(model="ctc", beam_width=5):

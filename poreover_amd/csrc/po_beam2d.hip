@@ -1678,7 +1678,7 @@ constexpr int X2_FB_BLOCKS = 64;   // workgroups of the beam2d_kernel pass over 
 // PO_REG_NEVER / PO_X2_DEFER_ODD only give the INITIAL value, read once when the library is first used, so that a workspace
 // size and the launch that follows always agree.  (Rounds 1 - 4 had two more kernels and routes — two pairs per wave, LDS
 // rings — which the register-state kernel replaced at every size: DESIGN.md, appendix.)
-struct B2Route { int route, defer_odd, debug_occ, no_order, reg_auto, chain_scan; };
+struct B2Route { int route, defer_odd, debug_occ, no_order, reg_auto, chain_scan, reg_fixed; };
 B2Route& b2_route() {
     static B2Route r = [] {
         B2Route x;
@@ -1688,6 +1688,10 @@ B2Route& b2_route() {
         x.no_order = getenv("PO_B2_NO_ORDER") ? 1 : 0;   // A/B: pairs taken in input order
         x.debug_occ = getenv("PO_DEBUG_OCC") ? 1 : 0;
         x.chain_scan = getenv("PO_CHAIN_CLOSED") ? PO_CHAIN_CLOSED_FORM : PO_CHAIN_SERIAL;   // (po_set_chain_mode)
+        {   // (po_set_reg_fixed_shape; PO_REG_FIXED_SHAPE=0: the run-time kernel for the default shape as well)
+            const char* e = getenv("PO_REG_FIXED_SHAPE");
+            x.reg_fixed = (e && atoi(e) == 0) ? 0 : 1;
+        }
         return x;
     }();
     return r;
@@ -1963,6 +1967,12 @@ extern "C" int po_set_chain_mode(int mode) {
     return PO_OK;
 }
 extern "C" int po_get_chain_mode(void) { return b2_route().chain_scan; }
+// Whether a launch of the default shape takes beam2d_reg_kernel's fixed-shape instantiation: see include/poreover_hip.h.
+extern "C" int po_set_reg_fixed_shape(int on) {
+    b2_route().reg_fixed = on ? 1 : 0;
+    return PO_OK;
+}
+extern "C" int po_get_reg_fixed_shape(void) { return b2_route().reg_fixed; }
 // profiling: a device counter that the pair beam kernels add their number of update_prob evaluations to
 extern "C" void po_b2_set_update_counter(unsigned long long* dev_counter) { g_b2_upd_counter = dev_counter; }
 // tests: pairs the register-state kernel (or its pre-pass) handed to beam2d_kernel on this device since the last reset, summed
@@ -2165,6 +2175,7 @@ extern "C" int po_launch_beam2d_geom(const double* y1, const int64_t* y1_off, co
         a.need_mono = 1;
         a.no_cum = 1;
         a.chain_scan = b2_route().chain_scan;
+        a.fixed_shape = b2_route().reg_fixed;
         a.order = nullptr;
         if (n > g.blocks && !b2_route().no_order) {   // more pairs than resident workgroups: longest first
             a.order = (int*)(w + g.off_order);

@@ -158,6 +158,8 @@ struct X2Args {
     int chain_scan;                   // beam2d_reg_kernel: PO_CHAIN_CLOSED_FORM (1; 2 = its guard at 3 nats) = a new element's window in closed
                                       // form (one exp, a prefix sum, one log per time: not the reference's rounding, inside its tolerance),
                                       // 0 = the serial chain (po_set_chain_mode)
+    int fixed_shape;                  // beam2d_reg_kernel: != 0 = a launch of the default shape (ctc, W = 5, A = 4, C = 5) takes the
+                                      // instantiation compiled for it (po_set_reg_fixed_shape), 0 = the run-time kernel for every shape
 };
 
 }  // namespace

@@ -61,6 +61,8 @@ constexpr int RK_NY = 32;     // y rows per read resident in LDS
 #endif
 constexpr int RK_NB = PO_REG_STAGE_NB;
 constexpr int RK_FRESH = INT_MIN / 2;
+// the shape of the FIXED instantiation of beam2d_reg_kernel: the default beam over four bases
+constexpr int RK_FX_W = 5, RK_FX_A = 4, RK_FX_C = RK_FX_A + 1;
 
 // What the tree model and the lane layout decide (update_prob: PrefixTree.h:518-531 ctc, :690-704 merge repeats, :600-632
 // flip-flop; the recurrences themselves are po_device.h::po_update, shared with every other beam kernel):
@@ -200,11 +202,18 @@ __device__ __forceinline__ double rk_g8_excl(double tot, double b0, double b1, d
 // SCAN: the new elements' chains in closed form (po_set_chain_mode(PO_CHAIN_CLOSED_FORM); the one-value model) — its own instantiation:
 // with both forms of the chain in one kernel the register allocation of EVERY phase suffered (the serial-only kernel ran at
 // 69 instead of 51 ms per 10 000 pairs with the closed form merely compiled in).
-template <int MODEL, int NR, bool COUNT = false, bool SCAN = false>
+// FIXED: the instantiation for ONE shape — the default beam, W = 5 over four bases (A = 4, C = 5) — with the three numbers
+// compile-time constants: slot arithmetic, candidate masks, trip counts and lane numbers fold, and the scalar registers that
+// carried them (and their spills, v_writelane / v_readlane in the VALU) go.  Where the constants allow more than folding — a
+// full beam's loops with immediate lane numbers, no hand-over for "more parents than stage slots" — the code says
+// `if constexpr (FIXED)`.  The arithmetic is the general kernel's, operation for operation (po_set_reg_fixed_shape is the
+// A/B switch).
+template <int MODEL, int NR, bool COUNT = false, bool SCAN = false, bool FIXED = false>
 __global__
 __launch_bounds__((64 * RegCfg<MODEL, NR>::WPG), (RegCfg<MODEL, NR>::WAVES))
 void beam2d_reg_kernel(X2Args a) {
     static_assert(!SCAN || RegCfg<MODEL, NR>::K == 1, "closed-form chains: the one-value model");
+    static_assert(!FIXED || (MODEL == PO_MODEL_CTC && NR == 1 && !COUNT && !SCAN), "the fixed shape: ctc, 32 slots, the serial chain");
     using Cfg = RegCfg<MODEL, NR>;
     constexpr int K = Cfg::K, KP = Cfg::KP, PC0 = Cfg::PC0, RK_YC = Cfg::YC, EB = Cfg::EB, RK_PS = Cfg::PS;
     constexpr int NS = Cfg::NS, WS = Cfg::WS, RK_NGL = Cfg::NGL, PF0N = Cfg::PF0N;
@@ -222,8 +231,26 @@ void beam2d_reg_kernel(X2Args a) {
     auto sm_pop = [&](SMask m) -> int { return (NR == 1) ? __popc((unsigned)m) : __popcll((unsigned long long)m); };
     auto sm_ctz = [&](SMask m) -> int { return (NR == 1) ? __builtin_ctz((unsigned)m) : (int)__builtin_ctzll((unsigned long long)m); };
     RegSmem<MODEL, NR, SCAN>& sm = gsm.w[(Cfg::WPG == 1) ? 0 : (int)(threadIdx.x >> 6)];
-    const int A = a.A, W = a.W, C = a.C;
+    const int A = FIXED ? RK_FX_A : a.A, W = FIXED ? RK_FX_W : a.W, C = FIXED ? RK_FX_C : a.C;
     const int divA = (65536 + A - 1) / A;   // x / A == (x * divA) >> 16 for the slot numbers divided here
+    auto div_A = [&](int x) -> int { return FIXED ? (x >> 2) : ((x * divA) >> 16); };   // (x >= 0: a slot number)
+    static_assert(RK_FX_A == 4, "div_A's shift");
+    // beam slots sel[] can name: the fixed shape's beam has W of them, never WS
+    constexpr int WSEL = FIXED ? RK_FX_W : WS;
+    static_assert(!FIXED || RK_PS >= RK_FX_W, "the fixed shape stages every parent a step can have");
+    // f(i) for the beam slots i = 0 .. n - 1, wave-uniform (the bodies are v_readlane and ballots).  The fixed shape's steady
+    // state is a full beam — n == W from the second table build of a pair on —: that case gets compile-time trips and immediate
+    // lane numbers, the first steps of a pair the loop.
+    auto each_beam = [&](int n, auto&& f) {
+        if constexpr (FIXED) {
+            if (__builtin_expect(n == RK_FX_W, 1)) {
+#pragma unroll
+                for (int i = 0; i < RK_FX_W; ++i) f(i);
+                return;
+            }
+        }
+        for (int i = 0; i < n; ++i) f(i);
+    };
     // ---- this wave's SLICE of the library's pool: value store + tree arena.  The pool has one slice per pair wave the device
     // can hold (po_beam2d.hip::reg_pool), shared by every launch of this kernel on the device — the waves of a pipelined job on
     // their streams, the next call — so a workspace no longer carries megabytes per resident pair.  A wave CLAIMS a free slice
@@ -262,7 +289,7 @@ void beam2d_reg_kernel(X2Args a) {
     // stops being an element; RK_FRESH = nothing stored.  See "the value store" below.
     int* const rowhdr = acrow + a.arena_cap;
     // nodes a slice's arena holds: a pair that needs more goes to beam2d_kernel (starve: the tests' way to get there)
-    const int arena_cap = (a.starve & 2) ? min((int)a.arena_cap, 1 + a.A + 24 * a.A) : (int)a.arena_cap;
+    const int arena_cap = (a.starve & 2) ? min((int)a.arena_cap, 1 + A + 24 * A) : (int)a.arena_cap;
     auto g_hi = [&](int r) -> int* { return r ? sm.g_hi1 : sm.g_hi0; };
 
 #ifdef PO_REG_TIMING
@@ -716,13 +743,13 @@ void beam2d_reg_kernel(X2Args a) {
             int nps = 0;
             auto pj = [&](int k) -> int { return (int)((pjb >> (4 * k)) & 15ull); };
             bool many = false;
-            for (int jj = 0; jj < nb; ++jj) {   // (wave-uniform)
-                if (__ballot(fresh_any && e_ps == jj) == 0ull) continue;
-                if (nps < RK_PS) {
+            each_beam(nb, [&](int jj) {   // (wave-uniform)
+                if (__ballot(fresh_any && e_ps == jj) == 0ull) return;
+                if (FIXED || nps < RK_PS) {   // (the fixed shape: nps <= W <= RK_PS)
                     pjb |= (unsigned long long)jj << (4 * nps);
                     nps++;
                 } else many = true;
-            }
+            });
             if (__builtin_expect(many, 0)) { KC(27, 1); return false; }
             int myk = 0;
             for (int k = 1; k < nps; ++k) myk = (e_ps == pj(k)) ? k : myk;   // (wave-uniform loop)
@@ -1034,13 +1061,13 @@ void beam2d_reg_kernel(X2Args a) {
             // ---- A. new beam lanes take their fields from the old slot sel[s]
             int mysel = sel[0];
 #pragma unroll
-            for (int i = 1; i < WS; ++i) mysel = (s == i) ? sel[i] : mysel;
+            for (int i = 1; i < WSEL; ++i) mysel = (s == i) ? sel[i] : mysel;
             const bool rb = s < nbn;                       // this lane is a beam slot of the new table
             const bool rc = !rb && s < nen;                // ... a child slot
-            const int j = rc ? (((s - nbn) * divA) >> 16) : 0, c = rc ? (s - nbn) - j * A : 0;
+            const int j = rc ? div_A(s - nbn) : 0, c = rc ? (s - nbn) - j * A : 0;
             int pj = sel[0];
 #pragma unroll
-            for (int i = 1; i < WS; ++i) pj = (j == i) ? sel[i] : pj;
+            for (int i = 1; i < WSEL; ++i) pj = (j == i) ? sel[i] : pj;
             const int srcb = rb ? mysel : 0;
             int n_id = __shfl(e_id, hb | srcb), n_row2 = __shfl(e_row2, hb | srcb), n_sym = __shfl(e_sym, hb | srcb);
             int n_fc = sm.f_fc[srcb], n_crow2 = sm.f_crow2[srcb], n_par = sm.f_par[srcb];
@@ -1131,10 +1158,10 @@ void beam2d_reg_kernel(X2Args a) {
                 if (p_isnew && lo_half && n_id < arena_cap) { apl[n_id] = po_pack_node(p_id, c); afc[n_id] = -1; acrow[n_id] = -1; }
             }
             // a child slot whose node is also a beam slot is the same node pushed twice (Beam::prune's std::unique)
-            for (int i = 0; i < nbn; ++i) {
+            each_beam(nbn, [&](int i) {
                 const int bid = __builtin_amdgcn_readlane(n_id, i);
                 if (rc && bid == n_id) n_alias = i;
-            }
+            });
             KT(42);
             // ---- D. which old slot continues here
             int src = -1;
@@ -1144,10 +1171,10 @@ void beam2d_reg_kernel(X2Args a) {
             }
             {   // the parent enters the beam: a child of it was an element only as a beam node
                 const bool look = !rb && rc && n_alias < 0 && pj >= nbo;
-                for (int i = 0; i < nbo; ++i) {   // (wave-uniform loop: v_readlane)
+                each_beam(nbo, [&](int i) {   // (wave-uniform loop: v_readlane)
                     const int oid = __builtin_amdgcn_readlane(e_id, i);
                     if (look && oid == n_id) src = i;
-                }
+                });
             }
             {   // (an old child slot that was an alias hands over to the beam slot that held the node)
                 const int oa = sm.f_alias[max(src, 0)];
@@ -1211,15 +1238,15 @@ void beam2d_reg_kernel(X2Args a) {
             nb = nbn; ne = nen;
             {   // (wave-uniform loops: v_readlane)
                 if (rb) n_ps = (n_par == 0) ? PS_ROOT : PS_FROZEN;
-                for (int i = 0; i < nbn; ++i) {
+                each_beam(nbn, [&](int i) {
                     const int bid = __builtin_amdgcn_readlane(e_id, i);
                     if (rb && n_par != 0 && bid == n_par) n_ps = i;
-                }
+                });
                 const bool fz = rb && n_ps == PS_FROZEN;
-                for (int i = 0; i < nbn; ++i) {
+                each_beam(nbn, [&](int i) {
                     const int bid = __builtin_amdgcn_readlane(e_id, i);
                     if (fz && bid == n_gpar) n_ps = nbn + A * i + sym_plast(e_sym);
-                }
+                });
             }
             e_ps = n_ps;
             KT(46);
@@ -1538,7 +1565,7 @@ void beam2d_reg_kernel(X2Args a) {
             if (!((smask >> s) & (SMask)1)) { rank = 64; neq = 0; }
             const int nbn = min(W, ncand);
 #pragma unroll
-            for (int jx = 0; jx < WS; ++jx) {
+            for (int jx = 0; jx < WSEL; ++jx) {
                 const SMask bj = smask_of(cand && rank == jx);
                 sel[jx] = (bj != 0) ? sm_ctz(bj) : 0;
             }
@@ -1558,7 +1585,7 @@ void beam2d_reg_kernel(X2Args a) {
                 }
                 rk_sync();
 #pragma unroll
-                for (int jx = 0; jx < WS; ++jx) sel[jx] = (jx < nbn) ? sm.tie.ord[jx] : 0;
+                for (int jx = 0; jx < WSEL; ++jx) sel[jx] = (jx < nbn) ? sm.tie.ord[jx] : 0;
                 rk_sync();
             }
             KT(7);
@@ -1629,6 +1656,14 @@ void reg_launch_model(const X2Args& a, int slots, hipStream_t stream) {
     if constexpr (RegCfg<MODEL, NR>::K == 1) {
         if (a.chain_scan && a.upd_count == nullptr) {   // (po_set_chain_mode(PO_CHAIN_CLOSED_FORM); the counting build is the serial chain's)
             hipLaunchKernelGGL((beam2d_reg_kernel<MODEL, NR, false, true>), grid, block, 0, stream, a);
+            return;
+        }
+    }
+    if constexpr (MODEL == PO_MODEL_CTC && NR == 1) {
+        // the default shape has its own instantiation (the constants folded: FIXED above); its resources are the general
+        // kernel's — reg_occupancy() sizes the slice pool from that one
+        if (a.fixed_shape && a.upd_count == nullptr && a.W == RK_FX_W && a.A == RK_FX_A && a.C == RK_FX_C) {
+            hipLaunchKernelGGL((beam2d_reg_kernel<MODEL, NR, false, false, true>), grid, block, 0, stream, a);
             return;
         }
     }
