@@ -26,6 +26,7 @@
 #define PO_LAE_BRANCHLESS 1
 #define PO_LAE_TRIM 1
 #include "po_device.h"
+#include "po_internal.h"
 
 namespace {
 

@@ -39,13 +39,15 @@
 //   * One workgroup per pair, thread = (read, element slot); the LDS layout is a compile-time struct
 //     per beam-width class (W <= 6 / 12 / 25 -> 64 / 128 / 256 threads).  Workgroups are persistent
 //     and pull pairs from an atomic queue.
+//
+// This file: beam2d_kernel, its workspace and its launch (and the logaddexp micro-benchmark).  The hidden method "grid" is
+// po_beam2d_grid.hip; which kernel a launch takes, and every process-wide setting, is po_beam2d_route.hip.
 #define PO_LAE_EARLY_TABLE 1   // (po_device.h; A/B in round 4: W = 10 -0.7 %, Bonito W = 5 -3 %, beam2d_kernel -1 %)
 #define PO_LAE_BRANCHLESS 1    // (... the clamp instead of the small-argument test, and the two-instruction forms: Bonito W = 5
 #define PO_LAE_TRIM 1          //  another -3 %, the others unchanged)
 #include <algorithm>
 #include <climits>
 #include <cstdio>
-#include <cstdlib>
 #include <mutex>
 #include <unordered_map>
 
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
         epoch++;
         if ((epoch & 0xffffu) == 0) { clear_slice(); epoch++; }   // (epoch 0 is what a cleared tag reads as)
         TK_START();
-        if (a.only_meta && a.only_meta[pi].y != X2_DEFERRED) continue;  // done by beam2d_reg_kernel
+        if (a.only_meta && a.only_meta[pi].y != REG_DEFERRED) continue;  // done by beam2d_reg_kernel
         if (a.retry_nomem) {
             if (a.status[pi] != PO_E_NOMEM) continue;                  // decoded (or refused for good) by the first pass
         } else
@@ -356,10 +358,6 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
             }
         };
         auto st_write = [&](int row, int rr, int t, int node, const double* v) {
-#ifdef PO_ABL_NOSTORE   // timing ablation only (results are wrong): keeps the value live, skips the store
-            if (v[0] == 12345.678) pool[0].tag = 1;
-            return;
-#endif
             Ent e;
             e.tag = make_tag(epoch, node, t);
 #pragma unroll
@@ -488,11 +486,7 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
                 const double pm = l_pm;
                 const int pt = l_pt;
                 td = l_td;
-#ifdef PO_ABL_NOREREAD   // timing ablation only (results are wrong)
-                if (true) { mx = pm; mt = pt; }
-#else
                 if (pm == PO_NEG_INF || (pt >= t0f && pt < t0)) { mx = pm; mt = pt; }
-#endif
                 else {
                     // the carried maximum's time has left the window
                     const Ent* rp = pool + ((size_t)l_row * 2 + r) * R;
@@ -513,21 +507,12 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
                         double pv = PO_NEG_INF;
                         const int te = min(td + 1, t0);
                         td = t0f;
-#ifdef PO_RR4
-                        for (int bt = t0f; bt < te; bt += 4) {
-                            double v8[4];
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) v8[q] = rp[(bt + q) & Rm].v[0];
-#pragma unroll
-                            for (int q = 0; q < 4; ++q) {
-#else
                         for (int bt = t0f; bt < te; bt += 8) {
                             double v8[8];
 #pragma unroll
                             for (int q = 0; q < 8; ++q) v8[q] = rp[(bt + q) & Rm].v[0];
 #pragma unroll
                             for (int q = 0; q < 8; ++q) {
-#endif
                                 const int tq = bt + q;
                                 if (tq < te) {
                                     if (v8[q] >= mx) { mx = v8[q]; mt = tq; }
@@ -640,11 +625,7 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
             {
                 const int nrow = min(len, k0 + yrows) - k0;  // this read's rows in the chunk (<= 0: none)
                 const double* src = yr_ + (int64_t)(t0 + k0) * C;
-#ifdef PO_ABL_NOYLOAD     // timing ablation only (results are wrong)
-                if (nrow * C > 1000000) sm.ybuf[r][s] = src[s];
-#else
                 for (int i = s; i < nrow * C; i += NCP) sm.ybuf[r][i] = src[i];
-#endif
             }
             b2_sync_lds<nthr>();  // y rows (and, first time, the seeds in xch[1]) -> visible to the iterations
             if (wm_pend) { mx = (wm_e.tag == wm_tag) ? wm_e.v[0] : PO_NEG_INF; wm_pend = false; }
@@ -679,9 +660,6 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
                     // direct 16-byte store per lane.  (Tried: buffering 8 iterations in LDS and flushing
                     // row-contiguous 128-byte bursts to cut L2 requests — the flush's extra instructions
                     // and LDS cost more than the coalescing saved: 22k vs 29k pairs/s.  DESIGN.md §3.3.)
-#ifdef PO_ABL_NOSTORE   // timing ablation only (results are wrong): keeps the value live, skips the store
-                    if (out[0] == 12345.678) pool[0].tag = 1;
-#else
                     if (t >= sfrom) {
                         Ent e;
                         // (t < 2^24 sits in the low word of the tag: a 32-bit add, no carry)
@@ -690,7 +668,6 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
                         for (int q = 0; q < K; ++q) e.v[q] = out[q];
                         myrow[(unsigned)(t & Rm)] = e;
                     }
-#endif
                     if (out[0] > self[0]) tr = t;   // the last time a value rose (folded into td after the loop)
 #pragma unroll
                     for (int q = 0; q < K; ++q) { self[q] = out[q]; sm.xch[k & 1][r][s][q] = out[q]; }
@@ -909,9 +886,6 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
                     }
                 }
                 same_beam = !b2_any<nthr>(viol);
-#ifdef PO_ABL_ALWAYSSAME   // timing ablation only (results are wrong): every prune keeps the beam
-                same_beam = true;
-#endif
             }
             if (same_beam) {
                 if (tid < nb) sm.stay[tid] = 1;
@@ -1212,340 +1186,8 @@ __global__ __launch_bounds__(B2_THREADS(WMAX), ((MODEL == PO_MODEL_CTC && WMAX <
 #endif
 }
 
-// (the pre-pass and the diagonal walk of the register-state kernel: po_beam2d_reg.hip; they are launched from this file)
-#include "po_beam2d_pre.h"
-
-// =================================================================================================
-// method "grid" (beam_search_2d_grid, BeamSearch2.h:33-184; hidden upstream option): ONE BEAM PER CELL.
-// Cell (u, v) of the band takes the beam of cell (u-1, v-1) — or the seed beam (the root's children) when
-// that cell was never visited — updates every node of it and every child at (read 0, u) and (read 1, v),
-// and keeps the W best by alpha0[u] + alpha1[v].  The cells are visited in row-major order and all beams
-// share one tree whose per-node time maps are overwritten by later visits, so the order is part of the
-// result: a pair is walked cell by cell by one workgroup, thread = (read, candidate slot); parallelism is
-// the candidates of a cell and the pairs of the batch.  Within a cell every update reads times u-1 / v-1
-// and writes u / v, so the candidates are independent; values live in the same tagged ring store as the
-// other methods' (R >= widest row band + 2), a row group is recycled when nothing written to it can be
-// read again (read 0: times < u-1; read 1: times < row start - 1, row starts must not move backwards),
-// and the beams of the previous row are kept in HBM (6 ints per node).
-namespace {
-enum { G_ID, G_ROW, G_PAR, G_PROW, G_SYM, G_DEPTH, G_COUNT };
-template <int MODEL, int WMAX>
-struct GridSmem {
-    static constexpr int K = (MODEL == PO_MODEL_CTC) ? 1 : 3;
-    static constexpr int NCM = WMAX * (PO_A + 1);
-    static constexpr int NCP = (NCM <= 32) ? 32 : 128;   // threads per read
-    static constexpr int NGL = 3072;   // row groups tracked per pair (GRID_NGL on the host side)
-    int e[G_COUNT][NCM];
-    int fc[WMAX], crow[WMAX], isnew[WMAX];
-    int dup[NCM];
-    int ord[NCM];           // prune with exact score ties: candidate slots in node-id order (po_stl_prune)
-    int sel[WMAX];
-    int g_owner[NGL], g_hi0[NGL], g_hi1[NGL];
-    int sh[8];
-    double sc[2][NCP];
-    unsigned long long nupd;
-    PoLaeTables lae;
-};
-}  // namespace
-#define GRID_THREADS(WM) ((WM) * (PO_A + 1) <= 32 ? 64 : 256)
-
-template <int MODEL, int WMAX>
-__global__ __launch_bounds__(GRID_THREADS(WMAX)) void beam2d_grid_kernel(B2Args a) {
-    using SM = GridSmem<MODEL, WMAX>;
-    static_assert(SM::NGL == 3072, "GRID_NGL");
-    constexpr int K = SM::K, NCP = SM::NCP, nthr = 2 * NCP;
-    using Ent = Entry<K>;
-    __shared__ SM sm;
-    const int tid = threadIdx.x;
-    const int r = tid / NCP, s = tid - r * NCP;
-    const int A = a.A, W = a.W, C = a.C;
-    const int divA = (65536 + A - 1) / A;
-    Ent* pool = (Ent*)(a.pool + (size_t)blockIdx.x * a.pool_bytes);
-    const long long pool_entries = (long long)(a.pool_bytes / sizeof(Ent));
-    int* apl = a.arena + (size_t)blockIdx.x * 3 * a.arena_cap;
-    int* afc = apl + a.arena_cap;
-    int* acrow = afc + a.arena_cap;
-    double* cum0 = a.cum + (size_t)blockIdx.x * 2 * a.tcap;
-    double* cum1 = cum0 + a.tcap;
-    const int CI = 1 + W * G_COUNT;                                     // ints per stored cell: n, then the entries
-    int* cellb = a.cellb + (size_t)blockIdx.x * 2 * a.vcap * CI;          // two rows of cells, indexed by column
-    unsigned epoch = 0;
-    po_lae_tables_load(&sm.lae, tid, nthr);
-    const PoLaeFast lae{&sm.lae};
-
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) sm.sh[0] = atomicAdd(a.queue, 1);
-        __syncthreads();
-        const int pi = sm.sh[0];
-        if (pi >= a.n) break;
-        epoch++;
-        if (a.use_pre_status && a.status[pi] != PO_OK) {
-            if (tid == 0) a.seq_len[pi] = 0;
-            continue;
-        }
-        const int64_t o1 = a.y1_off[pi], o2 = a.y2_off[pi];
-        const int U = (int)(a.y1_off[pi + 1] - o1), V = (int)(a.y2_off[pi + 1] - o2);
-        const double* yr_ = r ? a.y2 + o2 * C : a.y1 + o1 * C;
-        const int32_t* env = a.env ? a.env + 2 * o1 : nullptr;
-        int st = PO_OK;
-        if (U < 1 || V < 1 || U > a.tcap || V > a.vcap || V > a.tcap || U >= (1 << 24) || V >= (1 << 24)) st = PO_E_ARG;
-        int R = 32, NG = 0;
-        if (st == PO_OK) {
-            int bad = 0, unsup = 0, wmax = env ? 0 : V;
-            if (env)
-                for (int u = tid; u < U; u += nthr) {
-                    const int lo = env[2 * u], hi = env[2 * u + 1];
-                    if (lo < 0 || hi > V) bad = 1;                       // BeamSearch2.h reads y2 out of bounds there
-                    if (u > 0 && lo < env[2 * u - 2]) unsup = 1;         // a later row would read times the store has dropped
-                    wmax = max(wmax, hi - lo);
-                }
-            if (__syncthreads_or(bad)) st = PO_E_ENVELOPE;
-            if (__syncthreads_or(unsup) && st == PO_OK) st = PO_E_UNSUPPORTED;
-            if (st == PO_OK) {
-                if (tid == 0) sm.sh[1] = 0;
-                __syncthreads();
-                atomicMax(&sm.sh[1], wmax);
-                __syncthreads();
-                wmax = sm.sh[1];
-                while (R < wmax + 2) R <<= 1;
-                NG = (int)min((long long)SM::NGL, pool_entries / ((long long)PO_A * 2 * R));
-                if (NG < 2 * max(W, PO_A) + 4) st = PO_E_NOMEM;
-            }
-        }
-        if (st != PO_OK) {
-            if (tid == 0) { a.status[pi] = st; a.seq_len[pi] = 0; }
-            continue;
-        }
-        const int Rm = R - 1;
-        if (MODEL == PO_MODEL_CTC && s == 0) {   // blank prefix sums = the CTC root's alpha, serial in t
-            double* cw = r ? cum1 : cum0;
-            const int Tn = r ? V : U;
-            double acc = 0.0;
-            for (int t = 0; t < Tn; ++t) { acc += yr_[(int64_t)t * C + A]; cw[t] = acc; }
-        }
-        for (int g = tid; g < SM::NGL; g += nthr) { sm.g_owner[g] = -1; sm.g_hi0[g] = 0; sm.g_hi1[g] = 0; }
-        __syncthreads();
-        auto st_read = [&](int row, int rr, int t, int node, double* out) {
-            bool hit = false;
-            if (t >= 0 && row >= 0) {
-                const Ent e = pool[((size_t)row * 2 + rr) * R + (t & Rm)];
-                hit = (e.tag == make_tag(epoch, node, t));
-                if (hit) {
-#pragma unroll
-                    for (int k = 0; k < K; ++k) out[k] = e.v[k];
-                }
-            }
-            if (!hit) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) out[k] = PO_NEG_INF;
-            }
-        };
-        auto st_write = [&](int row, int rr, int t, int node, const double* v) {
-            Ent e;
-            e.tag = make_tag(epoch, node, t);
-#pragma unroll
-            for (int k = 0; k < K; ++k) e.v[k] = v[k];
-            pool[((size_t)row * 2 + rr) * R + (t & Rm)] = e;
-        };
-        auto root_at = [&](int rr, int t, double* out) {
-            if (MODEL == PO_MODEL_CTC) {
-                out[0] = (t < 0) ? 0.0 : (rr ? cum1 : cum0)[t];
-            } else {
-                double tmp[3];
-                root_values<MODEL>(t, 0.0, tmp);
-#pragma unroll
-                for (int k = 0; k < K; ++k) out[k] = tmp[k];
-            }
-        };
-        // tree: root = node 0, its children = nodes 1..A in row group 0, which is never recycled (the seed
-        // beam can come back at any cell); beam2d_seed (update at t = 0 on both reads)
-        if (tid == 0) {
-            apl[0] = po_pack_node(-1, A); afc[0] = 1; acrow[0] = 0;
-            sm.g_owner[0] = 0; sm.g_hi0[0] = 1; sm.g_hi1[0] = 1;
-            sm.sh[2] = 1 + A;   // next node id
-            sm.sh[3] = 1;       // group allocation cursor
-            sm.sh[4] = PO_OK;
-            sm.nupd = 0;
-        }
-        if (tid < A) { apl[1 + tid] = po_pack_node(0, tid); afc[1 + tid] = -1; acrow[1 + tid] = -1; }
-        if (s < A) {
-            double sp[3] = {PO_NEG_INF, PO_NEG_INF, PO_NEG_INF}, pp[3], out[3];
-            root_at(r, -1, pp);
-            const double ya = yr_[s], yb = (MODEL == PO_MODEL_FLIPFLOP) ? yr_[s + A] : yr_[A];
-            po_update<MODEL>(sp, pp, ya, yb, false, true, out, lae);
-            st_write(s, r, 0, 1 + s, out);
-        }
-        __syncthreads();
-
-        int prs = 0, pre = 0;   // the previous row's band
-        for (int u = 0; u < U && st == PO_OK; ++u) {
-            const int rs = env ? env[2 * u] : 0, re = env ? env[2 * u + 1] : V;
-            int* cur = cellb + (size_t)(u & 1) * a.vcap * CI;
-            const int* prv = cellb + (size_t)((u + 1) & 1) * a.vcap * CI;
-            for (int v = rs; v < re; ++v) {
-                // ---- 1. the predecessor's beam (BeamSearch2.h:137-146)
-                const bool hp = u > 0 && v > 0 && (v - 1) >= prs && (v - 1) < pre;
-                int nb = A;
-                if (hp) {
-                    const int* pc = prv + (size_t)(v - 1) * CI;
-                    nb = pc[0];
-                    if (tid < nb * G_COUNT) sm.e[tid % G_COUNT][tid / G_COUNT] = pc[1 + tid];
-                } else if (tid < A) {
-                    sm.e[G_ID][tid] = 1 + tid; sm.e[G_ROW][tid] = tid; sm.e[G_PAR][tid] = 0; sm.e[G_PROW][tid] = -1;
-                    sm.e[G_SYM][tid] = sym_pack(tid, A, true); sm.e[G_DEPTH][tid] = 1;
-                }
-                __syncthreads();
-                // ---- 2. expansion: children ids in beam order (ids break score ties), row groups
-                if (tid < nb) {
-                    const int id = sm.e[G_ID][tid];
-                    sm.fc[tid] = afc[id]; sm.crow[tid] = acrow[id];
-                }
-                __syncthreads();
-                if (tid == 0) {
-                    int next = sm.sh[2];
-                    for (int j = 0; j < nb; ++j) {
-                        const int id = sm.e[G_ID][j];
-                        int fcj = sm.fc[j], cr = sm.crow[j];
-                        sm.isnew[j] = fcj < 0;
-                        if (fcj < 0) {
-                            if ((long long)next + A > a.arena_cap || next + A >= (1 << 24)) { sm.sh[4] = PO_E_NOMEM; break; }
-                            fcj = next; next += A;
-                            afc[id] = fcj;
-                        }
-                        if (cr < 0 || cr >= NG || sm.g_owner[cr] != id) {   // children never stored, or their rows recycled
-                            int cursor = sm.sh[3], g = -1;
-                            for (int tries = 0; tries < NG; ++tries) {
-                                const int c = cursor;
-                                cursor = (cursor + 1 == NG) ? 0 : cursor + 1;
-                                if (c != 0 && (sm.g_owner[c] < 0 || (sm.g_hi0[c] <= u - 1 && sm.g_hi1[c] <= rs - 1))) { g = c; break; }
-                            }
-                            sm.sh[3] = cursor;
-                            if (g < 0) { sm.sh[4] = PO_E_NOMEM; break; }
-                            sm.g_owner[g] = id;
-                            cr = g;
-                            acrow[id] = g;
-                        }
-                        sm.g_hi0[cr] = u + 1; sm.g_hi1[cr] = v + 1;   // written below
-                        sm.fc[j] = fcj; sm.crow[j] = cr;
-                    }
-                    sm.sh[2] = next;
-                }
-                __syncthreads();
-                if (sm.sh[4] != PO_OK) { st = sm.sh[4]; break; }
-                // ---- 3. candidate table: slots [0, nb) the beam, then the children
-                const int ne = nb * (A + 1);
-                if (r == 0 && s >= nb && s < ne) {
-                    const int j = ((s - nb) * divA) >> 16, c = (s - nb) - j * A;
-                    const int id = sm.fc[j] + c;
-                    sm.e[G_ID][s] = id; sm.e[G_ROW][s] = sm.crow[j] * PO_A + c;
-                    sm.e[G_PAR][s] = sm.e[G_ID][j]; sm.e[G_PROW][s] = sm.e[G_ROW][j];
-                    sm.e[G_SYM][s] = sym_pack(c, sym_last(sm.e[G_SYM][j]), false);
-                    sm.e[G_DEPTH][s] = sm.e[G_DEPTH][j] + 1;
-                    if (sm.isnew[j]) { apl[id] = po_pack_node(sm.e[G_ID][j], c); afc[id] = -1; acrow[id] = -1; }
-                    int d = 0;
-                    for (int i = 0; i < nb; ++i) d |= (sm.e[G_ID][i] == id);   // Beam::prune dedupes by identity
-                    sm.dup[s] = d;
-                } else if (r == 0 && s < nb) {
-                    sm.dup[s] = 0;
-                    atomicMax(&sm.g_hi0[sm.e[G_ROW][s] / PO_A], u + 1);
-                    atomicMax(&sm.g_hi1[sm.e[G_ROW][s] / PO_A], v + 1);
-                }
-                __syncthreads();
-                // ---- 4. update_prob(node, 0, u) and (node, 1, v) of every candidate
-                if (s < ne) {
-                    const int id = sm.e[G_ID][s], row = sm.e[G_ROW][s], par = sm.e[G_PAR][s], sy = sm.e[G_SYM][s];
-                    const int t = r ? v : u;
-                    const int sym = sym_last(sy);
-                    double self[K], pp[K], out[K];
-                    st_read(row, r, t - 1, id, self);
-                    if (par == 0) root_at(r, t - 1, pp);
-                    else st_read(sm.e[G_PROW][s], r, t - 1, par, pp);
-                    const double* yrow = yr_ + (int64_t)t * C;
-                    const double ya = yrow[sym], yb = (MODEL == PO_MODEL_FLIPFLOP) ? yrow[sym + A] : yrow[A];
-                    po_update<MODEL>(self, pp, ya, yb, sym_plast(sy) == sym, ((sy >> 9) & 1) && t == 0, out, lae);
-                    st_write(row, r, t, id, out);
-                    sm.sc[r][s] = out[0];
-                }
-                if (tid == 0) sm.nupd += 2u * (unsigned)ne;
-                __syncthreads();
-                // ---- 5. prune: the W best of the distinct candidates by alpha0[u] + alpha1[v]; an exact tie that reaches
-                // into the beam (narrow bands: candidates that are all -inf) is resolved as libstdc++'s partial_sort / sort
-                // leave the creation-ordered candidates (po_device.h), like every other prune
-                const bool live = (r == 0) && s < ne && !sm.dup[s];
-                bool teq = false;
-                if (live) {
-                    const double my = sm.sc[0][s] + sm.sc[1][s];
-                    const int myid = sm.e[G_ID][s];
-                    int rank = 0, neq = 0;
-#pragma unroll 8
-                    for (int o = 0; o < ne; ++o) {   // (branch-free: the candidates' LDS reads go out in batches)
-                        const double so = sm.sc[0][o] + sm.sc[1][o];
-                        const int io = sm.e[G_ID][o];
-                        const int lv = sm.dup[o] ? 0 : 1;
-                        rank += lv & (((so > my) | (!(my > so) & (io < myid))) ? 1 : 0);
-                        neq += lv & ((so == my) ? 1 : 0);
-                    }
-                    if (rank < W) sm.sel[rank] = s;
-                    teq = (neq > 1) && (rank < W);
-                }
-                const int ncand = __syncthreads_count(live);
-                const int nn = min(W, ncand);
-                if (__syncthreads_or(teq)) {
-                    if (live) {
-                        const int myid = sm.e[G_ID][s];
-                        int pos = 0;
-                        for (int o = 0; o < ne; ++o) pos += (!sm.dup[o] && sm.e[G_ID][o] < myid) ? 1 : 0;
-                        sm.ord[pos] = s;
-                    }
-                    __syncthreads();
-                    if (tid == 0) {
-                        const double* s0 = sm.sc[0];
-                        const double* s1 = sm.sc[1];
-                        po_stl_prune<WMAX>(sm.ord, ncand, W, [&](int slot) { return s0[slot] + s1[slot]; });
-                        for (int j = 0; j < nn; ++j) sm.sel[j] = sm.ord[j];
-                    }
-                    __syncthreads();
-                }
-                // ---- 6. the cell's beam goes to HBM for cell (u+1, v+1)
-                int* cc = cur + (size_t)v * CI;
-                if (tid < nn * G_COUNT) cc[1 + tid] = sm.e[tid % G_COUNT][sm.sel[tid / G_COUNT]];
-                if (tid == 0) cc[0] = nn;
-                __syncthreads();
-            }
-            prs = rs; pre = re;
-        }
-        // ---- the top of the last cell's beam, or of the seed beam if (U-1, V-1) was never visited (:176-183)
-        __syncthreads();
-        if (tid == 0) {
-            int nout = 0;
-            if (st == PO_OK) {
-                int node = 1, depth = 1;
-                const int rsl = env ? env[2 * (U - 1)] : 0, rel = env ? env[2 * (U - 1) + 1] : V;
-                if (V - 1 >= rsl && V - 1 < rel) {
-                    const int* lc = cellb + (size_t)((U - 1) & 1) * a.vcap * CI + (size_t)(V - 1) * CI;
-                    node = lc[1 + G_ID]; depth = lc[1 + G_DEPTH];
-                }
-                nout = depth;
-                char* out = a.seq + a.seq_off[pi];
-                const int cap = (int)(a.seq_off[pi + 1] - a.seq_off[pi]);
-                if (nout > cap) { st = PO_E_CAP; nout = 0; }
-                else
-                    for (int i = nout - 1; i >= 0; --i) {
-                        const int pk = apl[node];
-                        out[i] = (char)((a.alphabet >> (8 * (po_node_last(pk) & 3))) & 0xffu);
-                        node = po_node_parent(pk);
-                    }
-            }
-            a.seq_len[pi] = nout;
-            a.status[pi] = st;
-            if (a.upd_count) { atomicAdd(a.upd_count, sm.nupd); atomicAdd(a.upd_count + 1, sm.nupd); }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// host side: geometry, workspace layout, launch
+// host side: geometry, workspace layout, launch (what runs it and with which settings: po_beam2d_route.hip)
 namespace {
 struct B2Geom {
     int threads, blocks, wclass;
@@ -1553,13 +1195,10 @@ struct B2Geom {
     size_t off_queue, off_state, off_pool, off_arena, off_cum, off_envt, off_order, total;
     unsigned long long magic;
 };
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 
 // device memory a pair-beam workspace may plan with (a fixed share of the board's memory: the size reported by
 // po_*_workspace_bytes and the size a launch expects must agree whatever else is allocated)
 size_t b2_mem_budget() { return po_dev_info().mem / 4; }
-
-int b2_num_cus() { return po_dev_info().cus; }
 
 // resident workgroups per CU of one kernel instance (registers and LDS decide), asked once from the runtime
 template <int MODEL, int WMAX>
@@ -1584,18 +1223,18 @@ B2Geom b2_geometry(int n, int64_t mr1, int64_t mr2, int W, int model, int method
     B2Geom g;
     const int K = (model == PO_MODEL_CTC) ? 1 : 3;
     g.wclass = W <= 6 ? 6 : (W <= 12 ? 12 : 25);
-    // the small passes (pairs handed back by the x2 kernel, retries after PO_E_NOMEM) run the W <= 6 class on the
+    // the small passes (pairs handed back by beam2d_reg_kernel, retries after PO_E_NOMEM) run the W <= 6 class on the
     // W <= 12 kernel (256 instead of 112 row groups) and the W <= 12 class on the W <= 25 kernel (768)
     if (max_blocks > 0 && g.wclass < 25) g.wclass = (g.wclass == 6) ? 12 : 25;
     g.threads = g.wclass == 6 ? 64 : (g.wclass == 12 ? 128 : 256);
     const int per_cu = b2_blocks_per_cu(model, g.wclass);
-    g.blocks = b2_num_cus() * per_cu;
+    g.blocks = po_dev_info().cus * per_cu;
     if (max_blocks > 0 && g.blocks > max_blocks) g.blocks = max_blocks;
     if (g.blocks > n) g.blocks = n > 0 ? n : 1;
     // (tried: as many workgroups as make the rounds even — 3 334 for 10 000 pairs instead of 4 096 + a 44 % third round:
     //  95.5k vs 108k pairs/s kernel-only; resident waves are worth more than an even tail)
     // value store per workgroup: 4 / 8 MB (one / three values per entry); four times that for the widest beam class
-    // and for the pass over the pairs the two-pairs-per-wave path handed back (max_blocks > 0: few workgroups, and
+    // and for the pass over the pairs beam2d_reg_kernel handed back (max_blocks > 0: few workgroups, and
     // those pairs are the ones with windows hundreds of frames wide, whose live rows grow with the window squared)
     // (the W <= 6 class, with 16 workgroups per CU, gets half of that on its direct path: its 112 row groups fit
     // windows up to 126 frames in it, and a pair that runs out is decoded again by the retry pass below)
@@ -1626,257 +1265,6 @@ B2Geom b2_geometry(int n, int64_t mr1, int64_t mr2, int W, int model, int method
     return g;
 }
 
-// The order in which a launch's persistent workgroups take their pairs: longest first (frames of both reads, 2048
-// classes, descending; within a class as the atomics fall).  The tail of a launch — the last pair of every workgroup,
-// running on a half-empty device — is then made of the SHORTEST pairs instead of whatever came last in the input:
-// worth a few percent on the bench's pairs (lengths within 10 %), most of the tail on real reads, whose lengths differ
-// tenfold.  Results do not depend on it (every pair is decoded by one workgroup, alone).  One workgroup: a histogram,
-// its prefix sums and a scatter, all in LDS.
-constexpr int ORD_BINS = 2048;
-__global__ __launch_bounds__(1024) void pair_order_kernel(const int64_t* y1_off, const int64_t* y2_off, int n, int* order) {
-    __shared__ int hist[ORD_BINS];
-    __shared__ int part[1024 / 64];
-    __shared__ long long cmax_s;
-    const int tid = threadIdx.x;
-    for (int b = tid; b < ORD_BINS; b += 1024) hist[b] = 0;
-    if (tid == 0) cmax_s = 1;
-    __syncthreads();
-    long long cm = 1;
-    for (int i = tid; i < n; i += 1024) cm = max(cm, (long long)((y1_off[i + 1] - y1_off[i]) + (y2_off[i + 1] - y2_off[i])));
-    atomicMax((unsigned long long*)&cmax_s, (unsigned long long)cm);
-    __syncthreads();
-    const long long cmax = cmax_s;
-    auto bin_of = [&](int i) -> int {
-        const long long c = (y1_off[i + 1] - y1_off[i]) + (y2_off[i + 1] - y2_off[i]);
-        const long long b = (max(c, 0ll) * (ORD_BINS - 1)) / cmax;
-        return ORD_BINS - 1 - (int)min(b, (long long)(ORD_BINS - 1));   // longest -> bin 0
-    };
-    for (int i = tid; i < n; i += 1024) atomicAdd(&hist[bin_of(i)], 1);
-    __syncthreads();
-    // exclusive prefix sums of the 2048 counts: two per thread, wave scan, wave totals through LDS
-    const int c0 = hist[2 * tid], c1 = hist[2 * tid + 1];
-    int v = c0 + c1;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o); if (lane >= o) v += t; }
-    if (lane == 63) part[wave] = v;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += part[w];
-    __syncthreads();
-    const int ex = base + v - (c0 + c1);
-    hist[2 * tid] = ex; hist[2 * tid + 1] = ex + c0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) order[atomicAdd(&hist[bin_of(i)], 1)] = i;
-}
-
-constexpr int X2_FB_BLOCKS = 64;   // workgroups of the beam2d_kernel pass over deferred pairs (16 / 32 MB of store each)
-// Kernel routing is a process-wide setting of the library (po_set_pair_route), not something a launch looks up in the
-// environment: PO_ROUTE_AUTO (the engine's choice: beam2d_reg_kernel wherever it applies — row_col with an envelope, W <= 12,
-// every tree model — and beam2d_kernel elsewhere), PO_ROUTE_REG (the same, named), PO_ROUTE_LEGACY (always beam2d_kernel) —
-// for the tests, which run the pair path on both kernels, and for A/B timing.  The environment variables PO_B2_LEGACY /
-// PO_REG_NEVER / PO_X2_DEFER_ODD only give the INITIAL value, read once when the library is first used, so that a workspace
-// size and the launch that follows always agree.  (Rounds 1 - 4 had two more kernels and routes — two pairs per wave, LDS
-// rings — which the register-state kernel replaced at every size: DESIGN.md, appendix.)
-struct B2Route { int route, defer_odd, debug_occ, no_order, reg_auto, chain_scan, reg_fixed; };
-B2Route& b2_route() {
-    static B2Route r = [] {
-        B2Route x;
-        x.route = getenv("PO_B2_LEGACY") ? PO_ROUTE_LEGACY : (getenv("PO_REG_FORCE") ? PO_ROUTE_REG : PO_ROUTE_AUTO);
-        x.reg_auto = getenv("PO_REG_NEVER") ? 0 : 1;      // A/B: beam2d_kernel for everything
-        x.defer_odd = getenv("PO_X2_DEFER_ODD") ? 1 : 0;
-        x.no_order = getenv("PO_B2_NO_ORDER") ? 1 : 0;   // A/B: pairs taken in input order
-        x.debug_occ = getenv("PO_DEBUG_OCC") ? 1 : 0;
-        x.chain_scan = getenv("PO_CHAIN_CLOSED") ? PO_CHAIN_CLOSED_FORM : PO_CHAIN_SERIAL;   // (po_set_chain_mode)
-        {   // (po_set_reg_fixed_shape; PO_REG_FIXED_SHAPE=0: the run-time kernel for the default shape as well)
-            const char* e = getenv("PO_REG_FIXED_SHAPE");
-            x.reg_fixed = (e && atoi(e) == 0) ? 0 : 1;
-        }
-        return x;
-    }();
-    return r;
-}
-void (*g_b2_mark_fwd)(int begin, hipStream_t stream) = nullptr;   // set through po_b2_set_mark
-// The register-state kernel (beam2d_reg_kernel, po_beam2d_reg.hip) with its batch-parallel pre-pass and walk kernels
-// (po_beam2d_pre.h): the engine's choice (PO_ROUTE_AUTO) for row_col with an envelope at every batch size, every tree
-// model, W <= 12.  PO_REG_NEVER / PO_ROUTE_LEGACY send everything to beam2d_kernel.
-struct RegGeom {
-    int blocks;        // pair waves (one-wave workgroups) of this launch
-    size_t off_queue, off_meta, off_nmain, off_sched, off_envt, off_order, off_fb, fb_bytes, total;
-};
-extern "C" int po_reg_slots_per_cu(int model, int wide);
-extern "C" int po_reg_max_elements(int wide);
-extern "C" int po_reg_ngl(int wide);
-extern "C" size_t po_reg_pool_bytes(int model, int wide);
-extern "C" void po_reg_launch(const void* x2args, int slots, int model, int wide, hipStream_t stream);
-// the 64-slot layout of the kernel (lane = element slot, the two reads one after the other): 7 <= W <= 12
-inline int reg_wide(int W) {
-    static const int force = getenv("PO_REG_FORCE_WIDE") ? 1 : 0;   // (experiments: the 64-slot layout for every width)
-    return (W > 6 || force) ? 1 : 0;
-}
-struct RegPool;
-RegPool* reg_pool(int model, int wide);
-bool reg_eligible(int n, int W, int A, int model, int method) {
-    const int rt = b2_route().route;
-    // (every tree model since round 5: the kernel is templated on the model's values per entry)
-    if (!(method == PO_METHOD_ROW_COL && W <= 12 && A >= 1 && W * (A + 1) <= po_reg_max_elements(reg_wide(W)))) return false;
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE && model != PO_MODEL_FLIPFLOP) return false;
-    if (!(rt == PO_ROUTE_REG || (rt == PO_ROUTE_AUTO && b2_route().reg_auto != 0))) return false;
-    // The route needs the library's slice pool (below).  It is made HERE — by the workspace-size query that precedes every
-    // launch, a host-side call — and not inside the enqueue-only launch (multi-GB hipMalloc calls, a memset and a
-    // copy on the null stream do not belong in a stream capture).  A pool that cannot be allocated is remembered as such: the size
-    // query then answers for beam2d_kernel and the launch takes that kernel — the two always agree.
-    {   // (a host without a device can only PLAN — the CPU tests' size queries: answer for the engine's route)
-        static const bool no_device = [] { int nd = 0; const bool none = hipGetDeviceCount(&nd) != hipSuccess || nd <= 0; (void)hipGetLastError(); return none; }();
-        if (no_device) return true;
-    }
-    return reg_pool(model, reg_wide(W)) != nullptr;
-}
-
-// ---- The library's SLICE POOL of the register-state kernel (one per device, tree model and lane layout; made at the first
-// launch that needs it, kept for the life of the process).  A slice = the value store of one pair wave (2 - 8 MB: 128 row
-// groups at R = 128) + its tree arena.  Rounds 1 - 4 carved these out of every call's workspace: 12 GB for a 10 000-pair call,
-// 28 GB per slot of a pipeline — and a hipMalloc of that size stalls for 0.5 - 2.5 s on this driver every now and then
-// (scripts/micro/malloc_cost.hip: never below 4 GB, one in three at 16 GB), which is what a process's FIRST call paid.
-// There are never more pair waves on the device than its register file and LDS admit, whatever the number of launches in
-// flight: ONE pool of that many slices serves them all, in chunks of at most 3.5 GB; a wave claims a slice when it starts
-// (po_beam2d_reg.hip).  The slices hold VALUES only (no tags, no epochs: presence is bookkeeping in the kernel), so nothing is ever
-// memset or cleared.  po_reg_pool_prewarm makes a pool ahead of the first launch, po_reg_pool_release frees the current device's.
-struct RegPool {
-    int nslices = 0, spc_log2 = 0;
-    size_t pool_bytes = 0, slice_bytes = 0;
-    long long arena_cap = 0;
-    char* chunk[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int* claim = nullptr;
-    char* words = nullptr;                       // the allocation claim / defer_count / tickets live in
-    unsigned long long* defer_count = nullptr;   // pairs handed to beam2d_kernel since the last reset (tests)
-    unsigned* tickets = nullptr;                 // {take, give} tickets of the ring of free slices (claim)
-};
-std::mutex g_reg_pool_mu;
-RegPool* g_reg_pools[PO_MAX_DEVICES][6] = {};
-bool g_reg_pool_failed[PO_MAX_DEVICES][6] = {};   // (sticky until po_reg_pool_release: the size query and the launch must agree)
-inline int reg_pool_key(int model, int wide) { return (model == PO_MODEL_CTC ? 0 : (model == PO_MODEL_MERGE ? 1 : 2)) * 2 + (wide ? 1 : 0); }
-RegPool* reg_pool(int model, int wide) {
-    const int dev = po_cur_device();
-    const int key = reg_pool_key(model, wide);
-    std::lock_guard<std::mutex> lk(g_reg_pool_mu);
-    if (g_reg_pools[dev][key]) return g_reg_pools[dev][key];
-    if (g_reg_pool_failed[dev][key]) return nullptr;
-    RegPool* p = new RegPool();
-    p->nslices = b2_num_cus() * po_reg_slots_per_cu(model, wide);
-    // (PO_REG_POOL_SLICES: a smaller pool — several processes sharing one board, each with its own 9 GB otherwise; launches
-    //  are cut to that many waves)
-    if (const char* e = getenv("PO_REG_POOL_SLICES")) { const int v = atoi(e); if (v >= 64 && v < p->nslices) p->nslices = v & ~1; }
-    p->pool_bytes = po_reg_pool_bytes(model, wide);
-    // tree nodes a slice's arena holds: four per node that ever enters the beam.  1 024 beam entries per beam slot is ~ 4 x what
-    // a T = 4000 pair makes; a pair that needs more is handed to beam2d_kernel (whose arenas are worst-case sized)
-    const long long WM = wide ? 12 : 6;
-    p->arena_cap = 1 + PO_A + (long long)PO_A * WM * 1024;
-    // (+ the row headers: one int per store row and read)
-    p->slice_bytes = al256(p->pool_bytes + sizeof(int) * 3 * (size_t)p->arena_cap + sizeof(int) * 2 * PO_A * (size_t)po_reg_ngl(wide));
-    int spc = 1;
-    while ((size_t)(2 * spc) * p->slice_bytes <= ((size_t)7 << 29) && 2 * spc <= p->nslices) spc *= 2;   // chunks of <= 3.5 GB
-    while ((p->nslices + spc - 1) / spc > 8) spc *= 2;
-    p->spc_log2 = 0;
-    while ((1 << p->spc_log2) < spc) ++p->spc_log2;
-    const int nchunks = (p->nslices + spc - 1) / spc;
-    bool ok = true;
-    for (int c = 0; c < nchunks && ok; ++c) {
-        const int here = std::min(spc, p->nslices - c * spc);
-        ok = hipMalloc((void**)&p->chunk[c], (size_t)here * p->slice_bytes) == hipSuccess;
-    }
-    // the ring of free slices (one int per slice), then — 256-byte aligned — the deferral counter and the two tickets
-    const size_t ring = al256(sizeof(int) * (size_t)p->nslices), words = ring + 256;
-    char* w = nullptr;
-    ok = ok && hipMalloc((void**)&w, words) == hipSuccess && hipMemset(w, 0, words) == hipSuccess;
-    if (ok) {   // every slice is free: ring word i holds slice i
-        std::vector<int> ids((size_t)p->nslices);
-        for (int i = 0; i < p->nslices; ++i) ids[(size_t)i] = i;
-        ok = hipMemcpy(w, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    if (!ok) {
-        (void)hipGetLastError();
-        for (auto c : p->chunk) if (c) (void)hipFree(c);
-        if (w) (void)hipFree(w);
-        delete p;
-        g_reg_pool_failed[dev][key] = true;
-        if (b2_route().debug_occ) fprintf(stderr, "[po] register-state kernel pool (model %d, %s layout) could not be allocated: beam2d_kernel serves the route\n", model, wide ? "64-slot" : "32-slot");
-        return nullptr;
-    }
-    p->words = w;
-    p->claim = (int*)w;
-    p->defer_count = (unsigned long long*)(w + ring);
-    p->tickets = (unsigned*)(w + ring + 128);
-    if (b2_route().debug_occ)
-        fprintf(stderr, "[po] register-state kernel pool (model %d, %s layout): %d slices of %.2f MB in %d chunk(s)\n", model, wide ? "64-slot" : "32-slot",
-                p->nslices, p->slice_bytes / 1048576.0, nchunks);
-    g_reg_pools[dev][key] = p;
-    return p;
-}
-// Per-call workspace of the route: the batch-sized arrays of the pre-pass and the walk, and the deferred-pairs pass.
-RegGeom reg_geometry(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int W, int model) {
-    (void)tr1;
-    RegGeom g;
-    g.blocks = b2_num_cus() * po_reg_slots_per_cu(model, reg_wide(W));
-    if (g.blocks > n) g.blocks = n > 0 ? n : 1;
-    const size_t np = (size_t)(n > 0 ? n : 1);
-    size_t o = 0;
-    g.off_queue = o; o += 256;
-    g.off_meta = o; o += al256(sizeof(int2) * np);
-    g.off_nmain = o; o += al256(sizeof(int) * np);
-    g.off_sched = o; o += al256(sizeof(int4) * (size_t)(tr2 > 0 ? tr2 : 1));
-    g.off_envt = o; o += al256(sizeof(int) * 2 * (size_t)tr2);
-    g.off_order = o; o += al256(sizeof(int) * np);   // the queue's order (pair_order_kernel)
-    g.off_fb = o;
-    g.fb_bytes = b2_geometry(n, mr1, mr2, W, model, PO_METHOD_ROW_COL, X2_FB_BLOCKS).total;
-    o += al256(g.fb_bytes);
-    g.total = o + 256;
-    return g;
-}
-
-// ---- grid method: one workgroup per pair in flight; per workgroup a value store, the tree arena, the blank
-// prefix sums and two rows of cell beams
-struct GridGeom {
-    int threads, blocks, wclass;
-    size_t pool_bytes, arena_cap, tcap, vcap, cell_ints;
-    size_t off_queue, off_pool, off_arena, off_cum, off_cell, total;
-};
-constexpr int GRID_NGL = 3072;
-GridGeom grid_geometry(int n, int64_t mr1, int64_t mr2, int W, int model, bool has_env) {
-    GridGeom g;
-    const int K = (model == PO_MODEL_CTC) ? 1 : 3;
-    g.wclass = W <= 6 ? 6 : 25;
-    g.threads = g.wclass == 6 ? 64 : 256;
-    // value store: with an envelope, room for every row group at bands up to 62 wide (R = 64; wider bands get
-    // fewer groups); without one a node keeps all V read-1 times (R >= V + 2), which only fits short reads
-    int64_t Rh = 64;
-    if (!has_env) while (Rh < mr2 + 2) Rh <<= 1;
-    g.pool_bytes = al256(std::min<size_t>((size_t)GRID_NGL * PO_A * 2 * (size_t)Rh * (K == 1 ? 16 : 32), (size_t)1 << 30));
-    // nodes: every beam node of every cell may be expanded; distinct ones per row are a few times W
-    const int64_t WM = W > PO_A ? W : PO_A;
-    g.arena_cap = (size_t)std::min<int64_t>((int64_t)1 << 24, 1 + PO_A + (int64_t)PO_A * WM * 8 * (mr1 + mr2 + 2));
-    g.tcap = (size_t)std::max(mr1, mr2);
-    g.vcap = (size_t)mr2;
-    g.cell_ints = 2 * g.vcap * (size_t)(1 + W * G_COUNT);
-    const size_t per_block = g.pool_bytes + sizeof(int) * 3 * g.arena_cap + sizeof(double) * 2 * g.tcap + sizeof(int) * g.cell_ints;
-    g.blocks = b2_num_cus() * (g.wclass == 6 ? 4 : 1);
-    g.blocks = (int)std::min<size_t>((size_t)g.blocks, std::max<size_t>(1, ((size_t)16 << 30) / per_block));  // <= 16 GB in all
-    if (g.blocks > n) g.blocks = n > 0 ? n : 1;
-    size_t o = 0;
-    g.off_queue = o; o += 256;
-    g.off_pool = o; o += g.pool_bytes * g.blocks;
-    g.off_arena = o; o += al256(sizeof(int) * 3 * g.arena_cap * g.blocks);
-    g.off_cum = o; o += al256(sizeof(double) * 2 * g.tcap * g.blocks);
-    g.off_cell = o; o += al256(sizeof(int) * g.cell_ints * g.blocks);
-    g.total = o + 256;
-    return g;
-}
-template <int MODEL>
-void grid_launch_w(const GridGeom& g, const B2Args& a, hipStream_t stream) {
-    if (g.wclass == 6) hipLaunchKernelGGL((beam2d_grid_kernel<MODEL, 6>), dim3(g.blocks), dim3(g.threads), 0, stream, a);
-    else hipLaunchKernelGGL((beam2d_grid_kernel<MODEL, 25>), dim3(g.blocks), dim3(g.threads), 0, stream, a);
-}
-
 template <int MODEL, int WMAX>
 void b2_launch(const B2Geom& g, const B2Args& a, hipStream_t stream) {
     if constexpr (WMAX == 6) {
@@ -1893,18 +1281,7 @@ void b2_launch_w(const B2Geom& g, const B2Args& a, hipStream_t stream) {
     else if (g.wclass == 12) b2_launch<MODEL, 12>(g, a, stream);
     else b2_launch<MODEL, 25>(g, a, stream);
 }
-}  // namespace
 
-extern "C" size_t po_beam2d_ws_bytes_impl(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, int W,
-                                          int model, int method) {
-    (void)C;
-    if (method == PO_METHOD_GRID) return grid_geometry(n, mr1, mr2, W, model, true).total;
-    if (method == PO_METHOD_GRID_NOENV) return grid_geometry(n, mr1, mr2, W, model, false).total;
-    if (reg_eligible(n, W, (model == PO_MODEL_FLIPFLOP) ? C / 2 : C - 1, model, method)) return reg_geometry(n, tr1, tr2, mr1, mr2, W, model).total;
-    return b2_geometry(n, mr1, mr2, W, model, method).total + b2_geometry(n, mr1, mr2, W, model, method, X2_FB_BLOCKS).total;
-}
-
-namespace {
 // The pair-beam kernels keep {magic, epoch} words per workgroup in the workspace instead of clearing their value
 // store per launch.  That is only sound while the same layout is used on the same memory: a caller that reuses one
 // buffer for waves of different geometry moves the sub-workspace, and state words of one layout can then survive
@@ -1929,68 +1306,7 @@ bool b2_ws_layout_changed(const void* ws, size_t off_state, size_t total, unsign
     }
     return !same;
 }
-unsigned long long* g_b2_upd_counter = nullptr;
-void (*g_b2_mark)(int begin, hipStream_t stream) = nullptr;   // profiling: brackets the main pair beam kernel
-}
-extern "C" void po_b2_set_mark(void (*f)(int, hipStream_t)) { g_b2_mark = f; g_b2_mark_fwd = f; }
-extern "C" int po_set_pair_route(int route, int defer_odd) {
-    if (route != PO_ROUTE_AUTO && route != PO_ROUTE_LEGACY && route != PO_ROUTE_REG) return PO_E_ARG;   // (PO_ROUTE_X2 / PO_ROUTE_RING: kernels retired in round 5)
-    b2_route().route = route;
-    b2_route().defer_odd = defer_odd & 7;   // bit 0: odd pairs are handed on; bits 1, 2: starve the row groups / the arena
-    return PO_OK;
-}
-// The slice pool ahead of time / given back (include/poreover_hip.h).
-extern "C" int po_reg_pool_prewarm(int model, int beam_width) {
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE && model != PO_MODEL_FLIPFLOP) return PO_E_ARG;
-    if (beam_width < 1 || beam_width > 12) return PO_E_ARG;
-    return reg_pool(model, reg_wide(beam_width)) ? PO_OK : PO_E_NOMEM;
-}
-extern "C" int po_reg_pool_release(void) {
-    if (hipDeviceSynchronize() != hipSuccess) return PO_E_HIP;   // (no pair wave may still hold a slice)
-    const int dev = po_cur_device();
-    std::lock_guard<std::mutex> lk(g_reg_pool_mu);
-    for (int k = 0; k < 6; ++k) {
-        g_reg_pool_failed[dev][k] = false;
-        RegPool* p = g_reg_pools[dev][k];
-        if (!p) continue;
-        for (auto c : p->chunk) if (c) (void)hipFree(c);
-        if (p->words) (void)hipFree(p->words);
-        delete p;
-        g_reg_pools[dev][k] = nullptr;
-    }
-    return PO_OK;
-}
-// How beam2d_reg_kernel computes a NEW element's window (po_beam2d_reg.hip, "closed form"): see include/poreover_hip.h.
-extern "C" int po_set_chain_mode(int mode) {
-    if (mode != PO_CHAIN_SERIAL && mode != PO_CHAIN_CLOSED_FORM && mode != PO_CHAIN_CLOSED_GUARD3) return PO_E_ARG;
-    b2_route().chain_scan = mode;
-    return PO_OK;
-}
-extern "C" int po_get_chain_mode(void) { return b2_route().chain_scan; }
-// Whether a launch of the default shape takes beam2d_reg_kernel's fixed-shape instantiation: see include/poreover_hip.h.
-extern "C" int po_set_reg_fixed_shape(int on) {
-    b2_route().reg_fixed = on ? 1 : 0;
-    return PO_OK;
-}
-extern "C" int po_get_reg_fixed_shape(void) { return b2_route().reg_fixed; }
-// profiling: a device counter that the pair beam kernels add their number of update_prob evaluations to
-extern "C" void po_b2_set_update_counter(unsigned long long* dev_counter) { g_b2_upd_counter = dev_counter; }
-// tests: pairs the register-state kernel (or its pre-pass) handed to beam2d_kernel on this device since the last reset, summed
-// over the pools in use (synchronises the device)
-extern "C" long long po_debug_deferred_pairs(int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    const int dev = po_cur_device();
-    long long tot = 0;
-    std::lock_guard<std::mutex> lk(g_reg_pool_mu);
-    for (RegPool* p : g_reg_pools[dev]) {
-        if (!p) continue;
-        unsigned long long v = 0;
-        if (hipMemcpy(&v, p->defer_count, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-        tot += (long long)v;
-        if (reset && hipMemset(p->defer_count, 0, sizeof(v)) != hipSuccess) return -1;
-    }
-    return tot;
-}
+}  // namespace
 
 // ---- logaddexp micro-benchmark: the peak rate of the specialised logaddexp on this device (4 independent
 // chains per lane, tables in LDS, every lane busy) — the compute ceiling the pair kernels are priced against
@@ -2010,7 +1326,7 @@ __global__ __launch_bounds__(256) void lae_peak_kernel(int iters, double* sink) 
 extern "C" int po_launch_lae_peak(int iters, double* lae_per_s, hipStream_t stream) {
     double* sink = nullptr;
     if (hipMalloc((void**)&sink, 8) != hipSuccess) return PO_E_HIP;
-    const int blocks = b2_num_cus() * 8;
+    const int blocks = po_dev_info().cus * 8;
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     hipLaunchKernelGGL(lae_peak_kernel, dim3(blocks), dim3(256), 0, stream, 64, sink);  // warm-up
@@ -2025,37 +1341,32 @@ extern "C" int po_launch_lae_peak(int iters, double* lae_per_s, hipStream_t stre
     return rc;
 }
 
-namespace {
-int b2_launch_legacy(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, const int32_t* env,
-                     int n, int C, int A, uint32_t alphabet, int W, int model, int method, int64_t mr1, int64_t mr2,
-                     char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status, int use_pre_status, void* ws,
-                     size_t ws_bytes, hipStream_t stream, int max_blocks, const int2* only_meta, int retry = 0,
-                     const int* retry_flag = nullptr) {
-    const B2Geom g = b2_geometry(n, mr1, mr2, W, model, method, max_blocks);
+size_t po_b2_legacy_ws_bytes(int n, int64_t mr1, int64_t mr2, int W, int model, int method, int max_blocks) {
+    return b2_geometry(n, mr1, mr2, W, model, method, max_blocks).total;
+}
+
+int po_b2_launch_legacy(const PoB2Call& c, void* ws, size_t ws_bytes, int max_blocks, const int2* only_meta, int retry, const int* retry_flag) {
+    const B2Geom g = b2_geometry(c.n, c.mr1, c.mr2, c.W, c.model, c.method, max_blocks);
     if (ws_bytes < g.total) return PO_E_CAP;
     // direct path: a second, small pass (64 workgroups, four times the store) decodes the pairs whose live rows did
     // not fit the first one's store — windows hundreds of frames wide; an empty pass costs its 1 GB memset
     if (max_blocks == 0 && !retry) {
-        const size_t rb = b2_geometry(n, mr1, mr2, W, model, method, X2_FB_BLOCKS).total;
+        const size_t rb = b2_geometry(c.n, c.mr1, c.mr2, c.W, c.model, c.method, REG_FB_BLOCKS).total;
         if (ws_bytes < g.total + rb) return PO_E_CAP;
     }
+    hipStream_t stream = c.stream;
     char* w = (char*)ws;
-    B2Args a;
-    a.y1 = y1; a.y1_off = y1_off; a.y2 = y2; a.y2_off = y2_off; a.env = env;
-    a.n = n; a.A = A; a.W = W; a.C = C; a.method = method; a.alphabet = alphabet;
-    a.seq = seq; a.seq_off = seq_off; a.seq_len = seq_len; a.status = status;
-    a.use_pre_status = use_pre_status;
+    B2Args a = {};
+    b2_caller_args(a, c);
+    a.method = c.method;
     a.queue = (int*)(w + g.off_queue);
     a.pool = w + g.off_pool; a.pool_bytes = g.pool_bytes;
     a.arena = (int*)(w + g.off_arena); a.arena_cap = (long long)g.arena_cap;
     a.cum = (double*)(w + g.off_cum); a.tcap = (long long)g.tcap;
     a.envt = (int*)(w + g.off_envt); a.vcap = (long long)g.vcap;
-    a.dbg = nullptr;
     a.only_meta = only_meta;
-    a.cellb = nullptr;
     a.retry_nomem = retry;
     a.retry_flag = retry_flag;
-    a.upd_count = g_b2_upd_counter;
     a.wgstate = (unsigned long long*)(w + g.off_state);
     a.magic = g.magic;
 #ifdef PO_B2_TIMING
@@ -2070,17 +1381,17 @@ int b2_launch_legacy(const double* y1, const int64_t* y1_off, const double* y2, 
     if (b2_ws_layout_changed(ws, g.off_state, g.total, g.magic) &&
         po_zero_async(w + g.off_state, sizeof(unsigned long long) * 2 * (size_t)g.blocks, stream) != hipSuccess)
         return PO_E_HIP;
-    a.order = nullptr;
-    if (n > g.blocks && !only_meta && !retry && !b2_route().no_order) {   // more pairs than resident workgroups: the order of the queue matters
+    if (c.n > g.blocks && !only_meta && !retry && c.order) {   // more pairs than resident workgroups: the order of the queue matters
         a.order = (int*)(w + g.off_order);
-        hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), 0, stream, y1_off, y2_off, n, (int*)(w + g.off_order));
+        c.order(c.y1_off, c.y2_off, c.n, (int*)(w + g.off_order), stream);
     }
-    if (g_b2_mark && !only_meta && !retry) g_b2_mark(1, stream);
-    if (model == PO_MODEL_CTC) b2_launch_w<PO_MODEL_CTC>(g, a, stream);
-    else if (model == PO_MODEL_MERGE) b2_launch_w<PO_MODEL_MERGE>(g, a, stream);
-    else if (model == PO_MODEL_FLIPFLOP) b2_launch_w<PO_MODEL_FLIPFLOP>(g, a, stream);
+    const bool marked = c.mark && !only_meta && !retry;
+    if (marked) c.mark(1, stream);
+    if (c.model == PO_MODEL_CTC) b2_launch_w<PO_MODEL_CTC>(g, a, stream);
+    else if (c.model == PO_MODEL_MERGE) b2_launch_w<PO_MODEL_MERGE>(g, a, stream);
+    else if (c.model == PO_MODEL_FLIPFLOP) b2_launch_w<PO_MODEL_FLIPFLOP>(g, a, stream);
     else return PO_E_ARG;
-    if (g_b2_mark && !only_meta && !retry) g_b2_mark(0, stream);
+    if (marked) c.mark(0, stream);
 #ifdef PO_B2_TIMING
     {
         long long h[37];
@@ -2095,136 +1406,6 @@ int b2_launch_legacy(const double* y1, const int64_t* y1_off, const double* y2, 
     }
 #endif
     if (max_blocks == 0 && !retry)
-        return b2_launch_legacy(y1, y1_off, y2, y2_off, env, n, C, A, alphabet, W, model, method, mr1, mr2, seq, seq_off, seq_len,
-                                status, use_pre_status, (char*)ws + g.total, ws_bytes - g.total, stream, X2_FB_BLOCKS, nullptr, 1,
-                                a.queue + 8);
+        return po_b2_launch_legacy(c, (char*)ws + g.total, ws_bytes - g.total, REG_FB_BLOCKS, nullptr, 1, a.queue + 8);
     return PO_OK;
-}
-}  // namespace
-
-extern "C" int po_launch_beam2d_geom(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off,
-                                     const int32_t* env, int n, int C, int A, uint32_t alphabet, int W, int model,
-                                     int method, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, char* seq,
-                                     const int64_t* seq_off, int32_t* seq_len, int32_t* status, int use_pre_status,
-                                     void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (n <= 0) return PO_OK;
-    if (A < 1 || A > PO_A || W < 1 || W > 25) return PO_E_ARG;
-    if (method != PO_METHOD_ROW_COL && method != PO_METHOD_ROW && method != PO_METHOD_GRID) return PO_E_ARG;
-    if ((model == PO_MODEL_FLIPFLOP) ? (C != 2 * A) : (C != A + 1)) return PO_E_ARG;
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE && model != PO_MODEL_FLIPFLOP) return PO_E_ARG;
-    // without an envelope the reference's dispatcher knows "row" and sends everything else to grid (BeamSearch.h:441-458)
-    if (method == PO_METHOD_GRID || (!env && method != PO_METHOD_ROW)) {
-        const GridGeom g = grid_geometry(n, mr1, mr2, W, model, env != nullptr);
-        if (ws_bytes < g.total) return PO_E_CAP;
-        char* w = (char*)ws;
-        B2Args a;
-        a.y1 = y1; a.y1_off = y1_off; a.y2 = y2; a.y2_off = y2_off; a.env = env;
-        a.n = n; a.A = A; a.W = W; a.C = C; a.method = PO_METHOD_GRID; a.alphabet = alphabet;
-        a.seq = seq; a.seq_off = seq_off; a.seq_len = seq_len; a.status = status;
-        a.use_pre_status = use_pre_status;
-        a.queue = (int*)(w + g.off_queue);
-        a.pool = w + g.off_pool; a.pool_bytes = g.pool_bytes;
-        a.arena = (int*)(w + g.off_arena); a.arena_cap = (long long)g.arena_cap;
-        a.cum = (double*)(w + g.off_cum); a.tcap = (long long)g.tcap;
-        a.envt = nullptr; a.vcap = (long long)g.vcap;
-        a.cellb = (int*)(w + g.off_cell);
-        a.retry_nomem = 0;
-        a.retry_flag = nullptr;
-        a.order = nullptr;
-        a.dbg = nullptr; a.only_meta = nullptr;
-        a.upd_count = g_b2_upd_counter;
-        a.wgstate = nullptr; a.magic = 0;   // (the grid kernel clears its store per launch)
-        if (po_zero_async(w + g.off_queue, 256, stream) != hipSuccess) return PO_E_HIP;
-        if (po_zero_async(w + g.off_pool, g.pool_bytes * g.blocks, stream) != hipSuccess) return PO_E_HIP;
-        if (model == PO_MODEL_CTC) grid_launch_w<PO_MODEL_CTC>(g, a, stream);
-        else if (model == PO_MODEL_MERGE) grid_launch_w<PO_MODEL_MERGE>(g, a, stream);
-        else grid_launch_w<PO_MODEL_FLIPFLOP>(g, a, stream);
-        return PO_OK;
-    }
-    if (reg_eligible(n, W, A, model, method)) {
-        const RegGeom g = reg_geometry(n, tr1, tr2, mr1, mr2, W, model);
-        if (ws_bytes < g.total) return PO_E_CAP;
-        RegPool* const rp = reg_pool(model, reg_wide(W));   // (made by the size query before this launch: reg_eligible)
-        if (!rp) return PO_E_NOMEM;                          // (cannot happen: eligibility said it exists)
-        char* w = (char*)ws;
-        X2Args a;
-        a.y1 = y1; a.y1_off = y1_off; a.y2 = y2; a.y2_off = y2_off; a.env = env;
-        a.n = n; a.A = A; a.W = W; a.C = C; a.alphabet = alphabet;
-        a.seq = seq; a.seq_off = seq_off; a.seq_len = seq_len; a.status = status; a.use_pre_status = use_pre_status;
-        a.queue = (int*)(w + g.off_queue);
-        a.meta = (int2*)(w + g.off_meta);
-        a.nmain = (int*)(w + g.off_nmain);
-        a.sched = (int4*)(w + g.off_sched);
-        a.envt = (int*)(w + g.off_envt);
-        a.cum1 = nullptr; a.cum2 = nullptr;   // (the kernel adds the ctc root's alpha up as its scans pass the times)
-        a.pool = nullptr; a.pool_bytes = rp->pool_bytes;
-        a.arena = nullptr; a.arena_cap = rp->arena_cap;
-        for (int c = 0; c < 8; ++c) a.slice_chunk[c] = rp->chunk[c];
-        a.slice_spc_log2 = rp->spc_log2; a.nslices = rp->nslices; a.slice_bytes = rp->slice_bytes; a.slice_claim = rp->claim;
-        a.slice_tickets = rp->tickets;
-        a.defer_count = rp->defer_count;
-        {   // PO_REG_PERSIST=0 / 1 pins the launch form (A/B)
-            static const int env = [] { const char* e = getenv("PO_REG_PERSIST"); return e ? atoi(e) : -1; }();
-            a.persist = env >= 0 ? (env != 0) : 1;
-        }
-        a.starve = (b2_route().defer_odd >> 1) & 3;
-        a.wgstate = nullptr; a.magic = 0;   // (beam2d_kernel's epoch-tagged slices; this kernel's store is tag-free)
-        a.dbg = nullptr;
-        a.upd_count = g_b2_upd_counter;
-        a.defer_odd = b2_route().defer_odd & 1;
-        a.need_mono = 1;
-        a.no_cum = 1;
-        a.chain_scan = b2_route().chain_scan;
-        a.fixed_shape = b2_route().reg_fixed;
-        a.order = nullptr;
-        if (n > g.blocks && !b2_route().no_order) {   // more pairs than resident workgroups: longest first
-            a.order = (int*)(w + g.off_order);
-            hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(1024), 0, stream, y1_off, y2_off, n, (int*)(w + g.off_order));
-        }
-        const int grid = a.persist ? std::min(g.blocks, rp->nslices) : n;
-        a.pre_vcols = 0;
-        a.ngl = po_reg_ngl(reg_wide(W));
-        if (po_zero_async(w + g.off_queue, 256, stream) != hipSuccess) return PO_E_HIP;
-        if (model == PO_MODEL_CTC) hipLaunchKernelGGL(beam2d_prepass_kernel<PO_MODEL_CTC>, dim3(n), dim3(64), 0, stream, a);
-        else if (model == PO_MODEL_MERGE) hipLaunchKernelGGL(beam2d_prepass_kernel<PO_MODEL_MERGE>, dim3(n), dim3(64), 0, stream, a);
-        else hipLaunchKernelGGL(beam2d_prepass_kernel<PO_MODEL_FLIPFLOP>, dim3(n), dim3(64), 0, stream, a);
-        hipLaunchKernelGGL(beam2d_walk_kernel, dim3(n), dim3(64), 0, stream, a);
-        if (g_b2_mark_fwd) g_b2_mark_fwd(1, stream);
-        po_reg_launch(&a, grid, model, reg_wide(W), stream);
-        if (g_b2_mark_fwd) g_b2_mark_fwd(0, stream);
-        // pairs the pre-pass or the kernel deferred (tier-2 row groups exhausted, windows beyond the store's ring):
-        // one small pass of beam2d_kernel, a no-op when there are none
-        return b2_launch_legacy(y1, y1_off, y2, y2_off, env, n, C, A, alphabet, W, model, method, mr1, mr2, seq, seq_off,
-                                seq_len, status, use_pre_status, w + g.off_fb, g.fb_bytes, stream, X2_FB_BLOCKS, a.meta, 0, a.queue + 16);
-    }
-    return b2_launch_legacy(y1, y1_off, y2, y2_off, env, n, C, A, alphabet, W, model, method, mr1, mr2, seq, seq_off, seq_len,
-                            status, use_pre_status, ws, ws_bytes, stream, 0, nullptr);
-}
-
-// max rows are not part of the device-pointer ABI: read them back from the offset arrays
-extern "C" int po_launch_beam2d(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off,
-                                const int32_t* env, int n, int C, int A, uint32_t alphabet, int W, int model,
-                                int method, char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status,
-                                void* ws, size_t ws_bytes, hipStream_t stream) {
-    if (n <= 0) return PO_OK;
-    int64_t* h = (int64_t*)malloc(sizeof(int64_t) * 2 * (size_t)(n + 1));
-    if (!h) return PO_E_NOMEM;
-    int rc = PO_OK;
-    if (hipMemcpyAsync(h, y1_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(h + n + 1, y2_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess)
-        rc = PO_E_HIP;
-    int64_t m1 = 0, m2 = 0, tr1 = 0, tr2 = 0;
-    if (rc == PO_OK) {
-        for (int i = 0; i < n; ++i) {
-            m1 = std::max<int64_t>(m1, h[i + 1] - h[i]);
-            m2 = std::max<int64_t>(m2, h[n + 1 + i + 1] - h[n + 1 + i]);
-        }
-        tr1 = h[n] - h[0];
-        tr2 = h[n + 1 + n] - h[n + 1];
-    }
-    free(h);
-    if (rc != PO_OK) return rc;
-    return po_launch_beam2d_geom(y1, y1_off, y2, y2_off, env, n, C, A, alphabet, W, model, method, tr1, tr2, m1, m2, seq,
-                                 seq_off, seq_len, status, 0, ws, ws_bytes, stream);
 }

@@ -1,11 +1,24 @@
-// Shared by the pair-beam translation units (po_beam2d.hip, po_beam2d_reg.hip): the tagged value store entry, kernel
-// argument blocks, element-table field names and the wave-level hand-over helpers.  Everything sits in an anonymous
-// namespace: each translation unit gets its own copy.
+// Shared by the pair-beam translation units (po_beam2d.hip, po_beam2d_grid.hip, po_beam2d_route.hip, po_beam2d_reg.hip): the
+// tagged value store entry, kernel argument blocks, element-table field names and the wave-level hand-over helpers.  Everything
+// but the po_reg_* prototypes sits in an anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "po_device.h"
+#ifndef PO_EMU
+#include "po_internal.h"
+#endif
+
+// The C entry points of po_beam2d_reg.hip, called by po_beam2d_route.hip.  The argument block is a RegArgs (below): a const void*
+// here, because the struct is a type of its own in every translation unit.  wide != 0: the 64-slot layout (7 <= W <= 12).
+extern "C" int po_reg_slots_per_cu(int model, int wide);
+extern "C" int po_reg_max_elements(int wide);
+extern "C" int po_reg_ngl(int wide);
+extern "C" size_t po_reg_pool_bytes(int model, int wide);
+extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wide, hipStream_t stream);
+// ... and between the two objects po_beam2d_reg.hip is compiled to (PO_REG_TU)
+extern "C" __attribute__((visibility("hidden"))) int po_reg_wide_occupancy(int mi);
+extern "C" __attribute__((visibility("hidden"))) void po_reg_wide_launch(const void* regargs, int slots, int model, hipStream_t stream);
 
 namespace {
-
 
 
 template <int K>
@@ -34,7 +47,7 @@ struct B2Args {
     double* cum; long long tcap;       // 2 arrays of tcap doubles: blank prefix sums of each read
     int* envt; long long vcap;         // 2 * vcap ints: transposed envelope
     long long* dbg;                    // optional phase cycle counters (PO_B2_TIMING builds)
-    const int2* only_meta;             // non-NULL: decode only the pairs the two-pairs-per-wave path deferred (meta.y == -2)
+    const int2* only_meta;             // non-NULL: decode only the pairs beam2d_reg_kernel or its pre-pass deferred (meta.y == REG_DEFERRED)
     int* cellb;                        // grid method: two rows of per-cell beams per workgroup (2 * vcap * (1 + 6 W) ints)
     int retry_nomem;                   // second pass with a larger store: decode only the pairs the first one gave PO_E_NOMEM
     const int* order;                  // optional: the pair the q-th queue ticket stands for (longest first)
@@ -43,13 +56,25 @@ struct B2Args {
     unsigned long long* wgstate;       // per workgroup {magic, epoch counter}: what its slice of the value store was last tagged with
     unsigned long long magic;          // names this workspace geometry: a slice whose state word differs is cleared before use
 };
+#ifndef PO_EMU
+// The caller's side of an argument block (B2Args, RegArgs) from a PoB2Call (po_internal.h); the rest is the launch's to fill in.
+template <class Args>
+inline void b2_caller_args(Args& a, const PoB2Call& c) {
+    a.y1 = c.y1; a.y1_off = c.y1_off; a.y2 = c.y2; a.y2_off = c.y2_off; a.env = c.env;
+    a.n = c.n; a.A = c.A; a.W = c.W; a.C = c.C; a.alphabet = c.alphabet;
+    a.seq = c.seq; a.seq_off = c.seq_off; a.seq_len = c.seq_len; a.status = c.status;
+    a.use_pre_status = c.use_pre_status;
+    a.upd_count = c.upd_count;
+}
+#endif
 
 // F_PSLOT of an element whose parent does not move in the scan: a frozen parent (its values are read from
 // its ring row in the store), or the root (closed form / blank prefix sums)
 constexpr int PS_FROZEN = -1, PS_ROOT = -2;
-// meta.y of a pair the two-pairs-per-wave kernel hands to beam2d_kernel (window too wide for its store
+// meta.y of a pair beam2d_reg_kernel or its pre-pass hands to beam2d_kernel (window too wide for its store
 // geometry, or its row-group table ran out)
-constexpr int X2_DEFERRED = -2;
+constexpr int REG_DEFERRED = -2;
+constexpr int REG_FB_BLOCKS = 64;   // workgroups of the beam2d_kernel pass over deferred pairs (16 / 32 MB of store each)
 
 // LDS hand-over between iterations.  One wave per workgroup: a wave's LDS operations execute in order,
 // only the compiler needs fencing.  More waves: LDS-only barrier (outstanding stores are not waited for).
@@ -114,8 +139,9 @@ __device__ __forceinline__ int sym_pack(int last, int plast, bool rootpar) { ret
 __device__ __forceinline__ int sym_last(int s) { return s & 7; }
 __device__ __forceinline__ int sym_plast(int s) { return (s >> 4) & 7; }
 
-
-struct X2Args {
+// The argument block of beam2d_reg_kernel and of its pre-pass and walk kernels (po_beam2d_pre.h).  The kernel takes monotone
+// envelopes only (what build_envelope makes): the pre-pass defers every other pair.
+struct RegArgs {
     const double* y1; const int64_t* y1_off;
     const double* y2; const int64_t* y2_off;
     const int32_t* env;
@@ -129,17 +155,19 @@ struct X2Args {
                                    // end}, at the pair's read-1 row offset (a pair has at most min(U, V) main steps)
     int* nmain;                    // per pair: number of main steps
     int* envt;                     // transposed envelope: 2 ints per read-1 row of the batch
-    double* cum1; double* cum2;    // blank prefix sums at the batch row offsets (CTC root)
-    char* pool; size_t pool_bytes; // value store per half-wave
-    int* arena; long long arena_cap;  // per half-wave: 3 int arrays
+    // (The layout of this block is load-bearing: beam2d_reg_kernel sits at exactly 128 VGPRs and its kernarg offsets are part of
+    //  what was measured, so the fields no kernel reads — cum1, cum2, pool, arena, need_mono, pre_vcols, wgstate, magic, no_cum — stay.)
+    double* cum1; double* cum2;
+    char* pool; size_t pool_bytes; // value store of a pair wave's slice ...
+    int* arena; long long arena_cap;  // ... and the nodes of its tree arena (3 int arrays)
     long long* dbg;
     int defer_odd;                    // test hook (PO_X2_DEFER_ODD): hand every odd pair to beam2d_kernel
-    int need_mono;                    // the main kernel takes monotone envelopes only (beam2d_reg_kernel): others are deferred
+    int need_mono;
     const int* order;                 // optional: the pair the q-th queue ticket stands for (longest first, pair_order_kernel)
-    int pre_vcols;                    // pre-pass: columns its LDS table holds
+    int pre_vcols;
     int ngl;                          // row groups the main kernel tracks per pair
     unsigned long long* upd_count;    // optional (po_profile_update_counter): update_prob evaluations {of the reference's schedule, executed}
-    unsigned long long* wgstate;      // (unused since round 5: beam2d_reg_kernel's store carries no tags; kept for the argument block's layout)
+    unsigned long long* wgstate;
     unsigned long long magic;
     int reg_slots;                    // beam2d_reg_kernel: pair waves of the launch
     // beam2d_reg_kernel: the library's pool of slices {value store of pool_bytes | tree arena: 3 x arena_cap ints}, one per
@@ -154,7 +182,7 @@ struct X2Args {
     unsigned long long* defer_count;  // pairs handed to beam2d_kernel, counted for the tests (po_debug_deferred_pairs)
     int starve;                       // test hook (po_set_pair_route's defer_odd bits 1, 2): bit 0 = a dozen row groups only,
                                       // bit 1 = a tree arena of a few nodes only — every hand-over reason can be forced
-    int no_cum;                       // pre-pass: leave the blank prefix sums out (beam2d_reg_kernel adds the root's alpha up as it goes)
+    int no_cum;
     int chain_scan;                   // beam2d_reg_kernel: PO_CHAIN_CLOSED_FORM (1; 2 = its guard at 3 nats) = a new element's window in closed
                                       // form (one exp, a prefix sum, one log per time: not the reference's rounding, inside its tolerance),
                                       // 0 = the serial chain (po_set_chain_mode)

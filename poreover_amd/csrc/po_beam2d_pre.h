@@ -1,6 +1,6 @@
-// Per-pair pre-pass and diagonal walk of the row_col pair beam search for the register-state kernel (po_beam2d_reg.hip,
-// launched through po_beam2d.hip's host code).  Kept in a
-// header of their own so that tools/simt_emu can run them on the CPU next to the kernel under development.
+// Per-pair pre-pass and diagonal walk of the row_col pair beam search for the register-state kernel (po_beam2d_reg.hip;
+// compiled in and launched from po_beam2d_route.hip).  Kept in a header of their own so that tools/simt_emu can run them on
+// the CPU next to the kernel under development.
 #pragma once
 #include "po_beam2d_common.h"
 
@@ -12,7 +12,7 @@
 // place in HBM: on a monotone envelope every column is written by exactly one row per bound.  (The ctc root's blank prefix
 // sums were added up here through round 4; beam2d_reg_kernel adds them up as its scans pass the times.)
 template <int MODEL>
-__global__ __launch_bounds__(64) void beam2d_prepass_kernel(X2Args a) {
+__global__ __launch_bounds__(64) void beam2d_prepass_kernel(RegArgs a) {
     constexpr int K = (MODEL == PO_MODEL_CTC) ? 1 : 3;
     constexpr int nthr = 64;
     const int pi = blockIdx.x, tid = threadIdx.x;
@@ -64,20 +64,6 @@ __global__ __launch_bounds__(64) void beam2d_prepass_kernel(X2Args a) {
                 envt[2 * x + 1] = c ? a_ + c : -1;
                 wmax = max(wmax, c);
             }
-        } else if (st == PO_OK && !a.need_mono) {   // (a caller's own envelope, and a launch that takes it: integer atomics, order-free)
-            for (int x = tid; x < V; x += nthr) { envt[2 * x] = 0x7fffffff; envt[2 * x + 1] = 0; }
-            __syncthreads();
-            for (int u = tid; u < U; u += nthr) {
-                const int lo = env[2 * u], hi = env[2 * u + 1];
-                for (int x = lo; x < hi; ++x) { atomicMin(&envt[2 * x], u); atomicAdd(&envt[2 * x + 1], 1); }
-            }
-            __syncthreads();
-            for (int x = tid; x < V; x += nthr) {
-                const int c = envt[2 * x + 1], f = envt[2 * x];
-                envt[2 * x] = c ? f : -1;
-                envt[2 * x + 1] = c ? f + c : -1;
-                wmax = max(wmax, c);
-            }
         }
         if (st == PO_OK) {
 #pragma unroll
@@ -91,13 +77,13 @@ __global__ __launch_bounds__(64) void beam2d_prepass_kernel(X2Args a) {
             // too few row groups for this window width here, or (test hook) odd pairs: beam2d_kernel takes it
             // ... or an envelope whose row starts / ends move backwards, for a kernel that builds on windows that only
             // move forward (what build_envelope makes; anything else is a caller's own array)
-            else if (min((long long)a.ngl, ng) < 8 * max(W, PO_A) || ((a.defer_odd & 1) && (pi & 1)) || (a.need_mono && !mono)) R = X2_DEFERRED;
+            else if (min((long long)a.ngl, ng) < 8 * max(W, PO_A) || ((a.defer_odd & 1) && (pi & 1)) || !mono) R = REG_DEFERRED;
         }
     }
     if (tid == 0) {
         a.meta[pi] = make_int2(st, R);
         a.nmain[pi] = 0;
-        if (st == PO_OK && R == X2_DEFERRED) {   // the pass over the deferred pairs has something to do
+        if (st == PO_OK && R == REG_DEFERRED) {   // the pass over the deferred pairs has something to do
             a.queue[16] = 1;
             if (a.defer_count) atomicAdd(a.defer_count, 1ull);
         }
@@ -108,7 +94,7 @@ __global__ __launch_bounds__(64) void beam2d_prepass_kernel(X2Args a) {
 // and records the main steps, so the beam kernel neither reads the envelope nor loops over catch-up steps.
 // Lane l caches envelope row ubase + l / column vbase + l; the walk reads them with v_readlane and refills a
 // cache when it is left (one global round trip per <= 64 steps).  No LDS: many waves per CU hide its latency.
-__global__ __launch_bounds__(64) void beam2d_walk_kernel(X2Args a) {
+__global__ __launch_bounds__(64) void beam2d_walk_kernel(RegArgs a) {
     const int pi = blockIdx.x, lane = threadIdx.x;
     const int2 mt = a.meta[pi];
     if (mt.x != PO_OK || mt.y < 0) return;   // refused, skipped upstream or deferred: no schedule needed

@@ -211,7 +211,7 @@ __device__ __forceinline__ double rk_g8_excl(double tot, double b0, double b1, d
 template <int MODEL, int NR, bool COUNT = false, bool SCAN = false, bool FIXED = false>
 __global__
 __launch_bounds__((64 * RegCfg<MODEL, NR>::WPG), (RegCfg<MODEL, NR>::WAVES))
-void beam2d_reg_kernel(X2Args a) {
+void beam2d_reg_kernel(RegArgs a) {
     static_assert(!SCAN || RegCfg<MODEL, NR>::K == 1, "closed-form chains: the one-value model");
     static_assert(!FIXED || (MODEL == PO_MODEL_CTC && NR == 1 && !COUNT && !SCAN), "the fixed shape: ctc, 32 slots, the serial chain");
     using Cfg = RegCfg<MODEL, NR>;
@@ -252,7 +252,7 @@ void beam2d_reg_kernel(X2Args a) {
         for (int i = 0; i < n; ++i) f(i);
     };
     // ---- this wave's SLICE of the library's pool: value store + tree arena.  The pool has one slice per pair wave the device
-    // can hold (po_beam2d.hip::reg_pool), shared by every launch of this kernel on the device — the waves of a pipelined job on
+    // can hold (po_beam2d_route.hip::reg_pool), shared by every launch of this kernel on the device — the waves of a pipelined job on
     // their streams, the next call — so a workspace no longer carries megabytes per resident pair.  A wave CLAIMS a free slice
     // when it starts and gives it back when the queue is empty.  The hand-over between waves is an agent-scope release /
     // acquire pair (per-XCD L2s are not coherent, a CU's L1 is never refreshed by another CU's stores): once per wave's lifetime.
@@ -315,7 +315,7 @@ void beam2d_reg_kernel(X2Args a) {
         pi = __builtin_amdgcn_readfirstlane(pi);
         if (pi >= a.n) break;
         const int2 m = a.meta[pi];
-        if (__builtin_expect(m.y == X2_DEFERRED, 0)) continue;                 // beam2d_kernel decodes it after this kernel
+        if (__builtin_expect(m.y == REG_DEFERRED, 0)) continue;                 // beam2d_kernel decodes it after this kernel
         if (__builtin_expect(m.x != PO_OK || m.y < 0, 0)) {                    // refused by the pre-pass, or skipped upstream
             if (lane == 0) {
                 a.seq_len[pi] = 0;
@@ -332,7 +332,7 @@ void beam2d_reg_kernel(X2Args a) {
         const int nmain = a.nmain[pi];
         const int R2 = m.y, Rm2 = R2 - 1;
         if (__builtin_expect(R2 > 256, 0)) {   // windows of 255 frames and more: the packed walk records below keep a window's length in 8 bits
-            if (lane == 0) { a.meta[pi] = make_int2(PO_OK, X2_DEFERRED); a.queue[16] = 1; if (a.defer_count) atomicAdd(a.defer_count, 1ull); }
+            if (lane == 0) { a.meta[pi] = make_int2(PO_OK, REG_DEFERRED); a.queue[16] = 1; if (a.defer_count) atomicAdd(a.defer_count, 1ull); }
             continue;
         }
         const int NG = (int)min((long long)((a.starve & 1) ? 12 : RK_NGL), pool_entries / ((long long)PO_A * 2 * R2));
@@ -1594,7 +1594,7 @@ void beam2d_reg_kernel(X2Args a) {
         KT(6);
         // ---------------------------------------------------------------- label of the top node
         if (st == PO_E_NOMEM && lane == 0) {   // out of row groups (or a window end moved back): beam2d_kernel takes the pair
-            a.meta[pi] = make_int2(PO_OK, X2_DEFERRED);
+            a.meta[pi] = make_int2(PO_OK, REG_DEFERRED);
             a.queue[16] = 1;
             if (a.defer_count) atomicAdd(a.defer_count, 1ull);
         } else if (lane == 0) {
@@ -1650,7 +1650,7 @@ int reg_occupancy() {
     return nblk;
 }
 template <int MODEL, int NR>
-void reg_launch_model(const X2Args& a, int slots, hipStream_t stream) {
+void reg_launch_model(const RegArgs& a, int slots, hipStream_t stream) {
     constexpr int WPG = RegCfg<MODEL, NR>::WPG;
     const dim3 grid((slots + WPG - 1) / WPG), block(64 * WPG);   // (a.reg_slots = slots: the waves beyond it leave at once)
     if constexpr (RegCfg<MODEL, NR>::K == 1) {
@@ -1672,17 +1672,15 @@ void reg_launch_model(const X2Args& a, int slots, hipStream_t stream) {
 }
 }  // namespace
 // PO_REG_TU — poreover_amd/build.py compiles this file TWICE: 1 = the 32-slot kernels and the C entry points, 2 = the 64-slot kernels
-// behind the two functions below (undefined: one translation unit with everything — the tools' and the emulator's build).  Two
-// objects because they are compiled with different scheduler options (build.py: -amdgpu-use-amdgpu-trackers gains 1 % on the 32-slot
+// behind po_reg_wide_occupancy and po_reg_wide_launch (hidden symbols, declared in po_beam2d_common.h).  Undefined: one translation
+// unit with everything — the tools' and the emulator's build.  Two objects because they are compiled with different scheduler options (build.py: -amdgpu-use-amdgpu-trackers gains 1 % on the 32-slot
 // one-value kernel and loses 1.5 % on the 64-slot one, profiles/r06_ab_compiler_flags.txt) and the option is per translation unit.
-extern "C" __attribute__((visibility("hidden"))) int po_reg_wide_occupancy(int mi);
-extern "C" __attribute__((visibility("hidden"))) void po_reg_wide_launch(const void* x2args, int slots, int model, hipStream_t stream);
 #if !defined(PO_REG_TU) || PO_REG_TU == 2
 extern "C" int po_reg_wide_occupancy(int mi) {
     return mi == 0 ? reg_occupancy<PO_MODEL_CTC, 2>() : (mi == 1 ? reg_occupancy<PO_MODEL_MERGE, 2>() : reg_occupancy<PO_MODEL_FLIPFLOP, 2>());
 }
-extern "C" void po_reg_wide_launch(const void* x2args, int slots, int model, hipStream_t stream) {
-    const X2Args& a = *(const X2Args*)x2args;
+extern "C" void po_reg_wide_launch(const void* regargs, int slots, int model, hipStream_t stream) {
+    const RegArgs& a = *(const RegArgs*)regargs;
     if (model == PO_MODEL_CTC) reg_launch_model<PO_MODEL_CTC, 2>(a, slots, stream);
     else if (model == PO_MODEL_MERGE) reg_launch_model<PO_MODEL_MERGE, 2>(a, slots, stream);
     else reg_launch_model<PO_MODEL_FLIPFLOP, 2>(a, slots, stream);
@@ -1708,8 +1706,8 @@ extern "C" int po_reg_ngl(int wide) { return wide ? 2 * PO_REG_NGL : PO_REG_NGL;
 // for the wide form
 extern "C" size_t po_reg_pool_bytes(int model, int wide) { return (size_t)(model == PO_MODEL_CTC ? 1 : 3) << (wide ? 21 : 20); }
 // `slots` pair slots (one-wave workgroups), each with its own store slice and arena
-extern "C" void po_reg_launch(const void* x2args, int slots, int model, int wide, hipStream_t stream) {
-    X2Args a = *(const X2Args*)x2args;
+extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wide, hipStream_t stream) {
+    RegArgs a = *(const RegArgs*)regargs;
     a.reg_slots = slots;
 #ifdef PO_REG_TIMING
     static long long* dbg = nullptr;

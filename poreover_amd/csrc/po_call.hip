@@ -26,7 +26,8 @@
 
 #include "po_call_kernels.h"
 
-extern "C" void po_set_error(const char* msg);
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 
@@ -47,8 +48,6 @@ int call_hip(hipError_t e, const char* what) {
 
 // the model checked against the weights' length; returns the widest activation (channels) or a PO_E_* code
 int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) { return check_model_for(L, nl, nweights, call_fail); }
-
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 
 size_t ws_bytes_for(int64_t M, int64_t wmax) {
     return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G * 4);

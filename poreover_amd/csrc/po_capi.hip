@@ -9,55 +9,8 @@
 #include <vector>
 
 #include "../../include/poreover_hip.h"
-
-extern "C" {
-int po_launch_viterbi(const double*, const int64_t*, int, int, int, uint32_t, int, int8_t*, char*, const int64_t*, int32_t*,
-                      int32_t*, int32_t*, int8_t*, int8_t*, hipStream_t);
-int po_launch_beam1d(const double*, const int64_t*, int, int, int, uint32_t, int, int, int*, int*, char*, const int64_t*,
-                     int32_t*, int32_t*, hipStream_t);
-int64_t po_beam1d_arena_nodes(int, int64_t, int);
-size_t po_beam2d_ws_bytes_impl(int, int64_t, int64_t, int64_t, int64_t, int, int, int, int);
-int po_launch_beam2d(const double*, const int64_t*, const double*, const int64_t*, const int32_t*, int, int,
-                     int, uint32_t, int, int, int, char*, const int64_t*, int32_t*, int32_t*, void*, size_t, hipStream_t);
-size_t po_pair_ws_bytes_impl(int, int64_t, int64_t, int64_t, int64_t, int, const po_pair_options*);
-size_t po_lattice_ws_bytes(int, int64_t, int64_t, int, int);
-size_t po_prefix_ws_bytes(int, int64_t);
-size_t po_gamma_ws_bytes(int, int64_t, int64_t, int64_t);
-size_t po_pair_prefix_ws_bytes(int, int64_t);
-int po_launch_forward_vec(const double*, const int64_t*, int, int, int, int, int, const double*, double*, hipStream_t);
-int po_launch_pair_prefix_search(const double*, const int64_t*, const double*, const int64_t*, const double*, const int64_t*, int, int,
-                                 int, uint32_t, int, int64_t, char*, const int64_t*, int32_t*, double*, int32_t*, void*, size_t,
-                                 hipStream_t);
-void po_b2_set_update_counter(unsigned long long*);
-void po_b2_set_mark(void (*)(int, hipStream_t));
-int po_launch_lae_peak(int, double*, hipStream_t);
-int po_launch_pair_decode_from_1d(const double*, const int64_t*, const double*, const int64_t*, int, int, const po_pair_options*,
-                                  int64_t, int64_t, int64_t, int64_t, const int32_t*, const int32_t*, char*, const int64_t*,
-                                  int32_t*, int32_t*, double*, int32_t*, char*, const int64_t*, int32_t*, int32_t*, void*, size_t,
-                                  hipStream_t);
-int po_launch_gamma(const double*, const int64_t*, const double*, const int64_t*, const int32_t*, const int64_t*, int, int, int,
-                    int64_t, int64_t, int64_t, double*, double*, const int64_t*, int32_t*, void*, size_t, hipStream_t);
-int po_launch_ingest(const void*, const int64_t*, int, int, int, const int*, int, int64_t, double*, hipStream_t);
-size_t po_align_ws_bytes(int, int64_t, int64_t, int);
-int po_launch_align(const char*, const int64_t*, int, int, int64_t, int64_t, char*, char*, const int64_t*, int32_t*, int32_t*,
-                    void*, size_t, hipStream_t);
-int po_launch_nw_matrix(const char*, const int64_t*, int, int, int, int, int32_t*, const int64_t*, int32_t*, hipStream_t);
-int po_launch_align_scores(const char*, const int64_t*, int, int, int, int, int, int64_t, int64_t, char*, char*, const int64_t*,
-                           int32_t*, int32_t*, void*, size_t, hipStream_t);
-size_t po_envelope_ws_bytes(int, int64_t);
-int po_launch_envelope(const char*, const char*, const int64_t*, const int32_t*, int, const int32_t*, const int64_t*,
-                       const int32_t*, const int64_t*, const int32_t*, const int32_t*, int, int64_t, int32_t*,
-                       const int64_t*, int32_t*, void*, size_t, hipStream_t);
-int po_launch_prefix_search(const double*, const int64_t*, int, int, int, uint32_t, int64_t, char*, const int64_t*, int32_t*,
-                            double*, int32_t*, void*, size_t, hipStream_t);
-int po_launch_forward(const double*, const int64_t*, int, int, int, uint32_t, int, const char*, const int64_t*, int64_t,
-                      double*, int32_t*, void*, size_t, hipStream_t);
-int po_launch_acceptor(const double*, const int64_t*, int, int, int, uint32_t, int, const char*, const int64_t*, int64_t,
-                       int64_t, int32_t*, int32_t*, void*, size_t, hipStream_t);
-int po_launch_pair_decode(const double*, const int64_t*, const double*, const int64_t*, int, int,
-                          const po_pair_options*, char*, const int64_t*, int32_t*, int32_t*, double*, int32_t*,
-                          char*, const int64_t*, int32_t*, int32_t*, void*, size_t, hipStream_t);
-}
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 thread_local std::string g_err;
@@ -70,7 +23,6 @@ int fail_hip(hipError_t e, const char* what) {
         hipError_t e_ = (x);                           \
         if (e_ != hipSuccess) return fail_hip(e_, #x); \
     } while (0)
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 // alphabet string -> (A, packed bytes); NULL means "ACGT"
 inline int pack_alphabet(const char* a, uint32_t* packed) {
     if (!a) a = "ACGT";
@@ -110,7 +62,7 @@ struct ProfScope {
         }
     }
 };
-// brackets the main pair beam kernel (called from po_beam2d.hip around its launch)
+// brackets the main pair beam kernel (handed to the pair beam launches by po_beam2d_route.hip)
 hipEvent_t g_mark_a = nullptr;
 void b2_mark(int begin, hipStream_t s) {
     if (!g_prof_on) return;

@@ -19,6 +19,8 @@
 #include <algorithm>
 
 #include "po_device.h"
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 constexpr int GM_THREADS = 256;
@@ -133,10 +135,6 @@ __global__ __launch_bounds__(GM_THREADS) void pair_gamma_kernel(GMArgs a) {
             dst[i] = G(g, u, v);
         }
     }
-}
-
-namespace {
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 }
 
 extern "C" size_t po_gamma_ws_bytes(int n, int64_t max_cells, int64_t max_rows1, int64_t max_rows2) {

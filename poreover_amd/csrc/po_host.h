@@ -11,6 +11,9 @@
 
 constexpr int PO_MAX_DEVICES = 64;
 
+// workspace regions start on 256-byte boundaries
+inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
+
 inline int po_cur_device() {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PO_MAX_DEVICES) dev = 0;

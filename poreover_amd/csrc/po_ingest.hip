@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "po_device.h"
+#include "po_internal.h"
 
 namespace {
 struct IGArgs {

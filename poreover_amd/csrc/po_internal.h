@@ -1,0 +1,135 @@
+// Entry points that one translation unit of the library defines and another calls, declared ONCE: the defining file and every
+// calling file include this header, so a definition that drifts from its callers is a compile error (clang rejects conflicting
+// declarations of a C-linkage function) instead of a call that links and passes garbage.  The public C-ABI is
+// include/poreover_hip.h; what is here is internal.  (po_reg_*: po_beam2d_common.h, next to the argument block they take.)
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/poreover_hip.h"
+
+extern "C" {
+// po_capi.hip
+void po_set_error(const char* msg);
+void po_prof_stage(int kernel, hipStream_t s, int begin, void** tok);
+
+// po_viterbi.hip
+int po_launch_viterbi(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int kind, int8_t* path,
+                      char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* map, int32_t* status, int8_t* ff_ptr,
+                      int8_t* ff_path, hipStream_t stream);
+int po_launch_viterbi_strided(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int kind,
+                              int8_t* path, char* seq, const int64_t* seq_off, int so_base, int so_stride, int32_t* seq_len,
+                              int32_t* map, int32_t* status, int8_t* ff_ptr, int8_t* ff_path, hipStream_t stream);
+
+// po_beam1d.hip
+int po_launch_beam1d(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int W, int model,
+                     int* arena_pl, int* arena_fc, char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status,
+                     hipStream_t stream);
+int64_t po_beam1d_arena_nodes(int n, int64_t total_rows, int W);
+
+// po_beam2d.hip
+int po_launch_lae_peak(int iters, double* lae_per_s, hipStream_t stream);
+
+// po_beam2d_route.hip
+size_t po_beam2d_ws_bytes_impl(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, int W, int model, int method);
+int po_launch_beam2d(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, const int32_t* env,
+                     int n, int C, int A, uint32_t alphabet, int W, int model, int method, char* seq, const int64_t* seq_off,
+                     int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+void po_b2_set_update_counter(unsigned long long* dev_counter);
+void po_b2_set_mark(void (*f)(int, hipStream_t));
+int po_launch_beam2d_geom(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, const int32_t* env,
+                          int n, int C, int A, uint32_t alphabet, int W, int model, int method, int64_t tr1, int64_t tr2,
+                          int64_t mr1, int64_t mr2, char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status,
+                          int use_pre_status, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// po_pair.hip
+size_t po_pair_ws_bytes_impl(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, const po_pair_options* opt);
+int po_launch_pair_decode_from_1d(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n,
+                                  int C, const po_pair_options* opt, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                                  const int32_t* map1, const int32_t* map2, char* seq1d, const int64_t* seq1d_off,
+                                  int32_t* len1, int32_t* len2, double* identity, int32_t* env_out, char* seq,
+                                  const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes,
+                                  hipStream_t stream);
+size_t po_align_ws_bytes(int n, int64_t max_len1, int64_t max_len2, int band);
+int po_launch_align(const char* seqs, const int64_t* seq_off, int n, int band, int64_t max_len1, int64_t max_len2, char* aln1,
+                    char* aln2, const int64_t* aln_off, int32_t* ncol, int32_t* status, void* ws, size_t ws_bytes,
+                    hipStream_t stream);
+int po_launch_nw_matrix(const char* seqs, const int64_t* seq_off, int n, int match, int mismatch, int gap, int32_t* dp,
+                        const int64_t* dp_off, int32_t* status, hipStream_t stream);
+int po_launch_align_scores(const char* seqs, const int64_t* seq_off, int n, int band, int match, int mismatch, int gap,
+                           int64_t max_len1, int64_t max_len2, char* aln1, char* aln2, const int64_t* aln_off, int32_t* ncol,
+                           int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t po_envelope_ws_bytes(int n, int64_t max_ncol);
+int po_launch_envelope(const char* aln1, const char* aln2, const int64_t* aln_off, const int32_t* ncol, int n,
+                       const int32_t* map1, const int64_t* map1_off, const int32_t* map2, const int64_t* map2_off,
+                       const int32_t* U, const int32_t* V, int padding, int64_t max_ncol, int32_t* env, const int64_t* env_off,
+                       int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+int po_launch_pair_decode(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                          const po_pair_options* opt, char* seq1d, const int64_t* seq1d_off, int32_t* len1, int32_t* len2,
+                          double* identity, int32_t* env_out, char* seq, const int64_t* seq_off, int32_t* seq_len,
+                          int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                               const po_pair_options* opt, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                               const int32_t* ext_map1, const int32_t* ext_map2, char* seq1d, const int64_t* seq1d_off,
+                               int32_t* len1, int32_t* len2, double* identity, int32_t* env_out, char* seq,
+                               const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes,
+                               hipStream_t stream);
+
+// po_lattice.hip
+size_t po_lattice_ws_bytes(int n, int64_t max_rows, int64_t max_label, int model, int acceptor);
+int po_launch_forward(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int model,
+                      const char* labels, const int64_t* label_off, int64_t max_rows, double* out, int32_t* status, void* ws,
+                      size_t ws_bytes, hipStream_t stream);
+int po_launch_acceptor(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int band,
+                       const char* labels, const int64_t* label_off, int64_t max_rows, int64_t max_label, int32_t* path,
+                       int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// po_prefix.hip
+size_t po_prefix_ws_bytes(int n, int64_t max_rows);
+size_t po_pair_prefix_ws_bytes(int n, int64_t max_rows);
+int po_launch_forward_vec(const double* y, const int64_t* y_off, int n, int C, int s, int i, int flavor, const double* previous,
+                          double* out, hipStream_t stream);
+int po_launch_pair_prefix_search(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off,
+                                 const double* gm, const int64_t* gm_off, int n, int C, int A, uint32_t alphabet, int flavor,
+                                 int64_t max_rows, char* seq, const int64_t* seq_off, int32_t* seq_len, double* logp,
+                                 int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream);
+int po_launch_prefix_search(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int64_t max_rows,
+                            char* seq, const int64_t* seq_off, int32_t* seq_len, double* logp, int32_t* status, void* ws,
+                            size_t ws_bytes, hipStream_t stream);
+
+// po_gamma.hip
+size_t po_gamma_ws_bytes(int n, int64_t max_cells, int64_t max_rows1, int64_t max_rows2);
+int po_launch_gamma(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, const int32_t* env,
+                    const int64_t* env_off, int n, int C, int flavor, int64_t max_cells, int64_t max_rows1, int64_t max_rows2,
+                    double* out, double* dense_out, const int64_t* dense_off, int32_t* status, void* ws, size_t ws_bytes,
+                    hipStream_t stream);
+
+// po_ingest.hip
+int po_launch_ingest(const void* src, const int64_t* row_off, int n, int C, int mode, const int* perm, int reverse,
+                     int64_t total_rows, double* out, hipStream_t stream);
+}  // extern "C"
+
+// ---- The pair-beam launch layer: po_beam2d_route.hip owns every process-wide setting and chooses the kernel family; po_beam2d.hip and
+// po_beam2d_grid.hip plan the workspace of their kernel and launch it, with what they need of the settings in a PoB2Call.  C++
+// linkage and hidden: no part of the library's symbol table.
+#define PO_HIDDEN __attribute__((visibility("hidden")))
+struct PoB2Call {   // po_launch_beam2d_geom's arguments ...
+    const double* y1; const int64_t* y1_off; const double* y2; const int64_t* y2_off; const int32_t* env;
+    int n, C, A; uint32_t alphabet; int W, model, method;
+    int64_t mr1, mr2;
+    char* seq; const int64_t* seq_off; int32_t* seq_len; int32_t* status; int use_pre_status;
+    hipStream_t stream;
+    // ... and the route's settings.  order: writes the queue's order (longest pair first), or NULL: input order
+    void (*order)(const int64_t* y1_off, const int64_t* y2_off, int n, int* order, hipStream_t stream);
+    unsigned long long* upd_count;                  // profiling: device counter of update_prob evaluations, or NULL
+    void (*mark)(int begin, hipStream_t stream);    // profiling: brackets the main pair beam kernel, or NULL
+};
+// beam2d_kernel.  max_blocks > 0: the small pass (that many workgroups at most, the larger store) over the pairs another kernel handed on
+PO_HIDDEN size_t po_b2_legacy_ws_bytes(int n, int64_t mr1, int64_t mr2, int W, int model, int method, int max_blocks);
+PO_HIDDEN int po_b2_launch_legacy(const PoB2Call& c, void* ws, size_t ws_bytes, int max_blocks, const int2* only_meta, int retry = 0,
+                                  const int* retry_flag = nullptr);
+// beam2d_grid_kernel
+PO_HIDDEN size_t po_b2_grid_ws_bytes(int n, int64_t mr1, int64_t mr2, int W, int model, bool has_env);
+PO_HIDDEN int po_b2_launch_grid(const PoB2Call& c, void* ws, size_t ws_bytes);

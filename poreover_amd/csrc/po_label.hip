@@ -30,7 +30,8 @@
 
 #include "../../include/poreover_hip.h"
 
-extern "C" void po_set_error(const char* msg);
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 
@@ -411,7 +412,6 @@ int lb_fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return lb_fail(PO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 inline bool lb_fast(int band) { return band >= 1 && band <= LB_FAST_MAX_B; }
 inline int lb_fast_ns(int band) { return (2 * band + 2 <= 64) ? 1 : 2; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -19,6 +19,8 @@
 #include <cstdlib>
 
 #include "po_device.h"
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 constexpr int LT_THREADS = 256;
@@ -299,10 +301,6 @@ __global__ __launch_bounds__(LT_THREADS) void acceptor_cy_kernel(LTArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-namespace {
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-}
-
 extern "C" size_t po_lattice_ws_bytes(int n, int64_t max_rows, int64_t max_label, int model, int acceptor) {
     const int K = (model == PO_MODEL_CTC) ? 1 : 3;
     size_t b = al256(sizeof(double) * 2 * (size_t)max_rows * K) * (size_t)(n > 0 ? n : 1);

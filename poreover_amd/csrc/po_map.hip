@@ -28,7 +28,7 @@
 #include "../../include/poreover_hip.h"
 #include "po_host.h"
 
-extern "C" void po_set_error(const char* msg);
+#include "po_internal.h"
 
 namespace {
 

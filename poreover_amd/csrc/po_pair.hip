@@ -28,6 +28,7 @@
 #define PO_WANT_ZERO_KERNEL 1
 #include "po_device.h"
 #include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 
@@ -757,15 +758,6 @@ __global__ __launch_bounds__(NT) void pair_prep_kernel(PPArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-extern "C" {
-int po_launch_viterbi_strided(const double*, const int64_t*, int, int, int, uint32_t, int, int8_t*, char*,
-                              const int64_t*, int, int, int32_t*, int32_t*, int32_t*, int8_t*, int8_t*, hipStream_t);
-size_t po_beam2d_ws_bytes_impl(int, int64_t, int64_t, int64_t, int64_t, int, int, int, int);
-int po_launch_beam2d_geom(const double*, const int64_t*, const double*, const int64_t*, const int32_t*, int, int, int,
-                          uint32_t, int, int, int, int64_t, int64_t, int64_t, int64_t, char*, const int64_t*, int32_t*, int32_t*,
-                          int, void*, size_t, hipStream_t);
-void po_prof_stage(int kernel, hipStream_t s, int begin, void** tok);
-}
 
 // which kernel aligns with a band: process-wide like po_set_pair_route, initial value from PO_PP_LEGACY (read once)
 static std::atomic<int> g_pp_legacy{-1};
@@ -802,8 +794,6 @@ void pp_launch(PPArgs a, int blocks, int one_wave, hipStream_t stream, long long
 }  // namespace
 
 namespace {
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // ints of DP slice the skewed-wavefront kernel needs for basecalls of at most l1 x l2 bases: one flag row of 64 dwords
 // per (row, column block) pair it visits plus the 63 drain steps of every block.  A row's visited columns
 // [start(i-1), end(i)] span at most 2 band + 1 cells plus the band's move from one row to the next (l2 in all).
@@ -1029,10 +1019,6 @@ extern "C" size_t po_align_ws_bytes(int n, int64_t max_len1, int64_t max_len2, i
            al256(2 * (size_t)(max_len1 + max_len2 + 16) * blocks) + 256;
 }
 
-extern "C" int po_launch_align_scores(const char* seqs, const int64_t* seq_off, int n, int band, int match, int mismatch,
-                                      int gap, int64_t max_len1, int64_t max_len2, char* aln1, char* aln2,
-                                      const int64_t* aln_off, int32_t* ncol, int32_t* status, void* ws, size_t ws_bytes,
-                                      hipStream_t stream);
 extern "C" int po_launch_align(const char* seqs, const int64_t* seq_off, int n, int band, int64_t max_len1,
                                int64_t max_len2, char* aln1, char* aln2, const int64_t* aln_off, int32_t* ncol,
                                int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream) {

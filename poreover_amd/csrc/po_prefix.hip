@@ -22,6 +22,8 @@
 #include <cstdlib>
 
 #include "po_device.h"
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 constexpr int PS_THREADS = 256;
@@ -168,10 +170,6 @@ __global__ __launch_bounds__(PS_THREADS) void prefix_search_kernel(PSArgs a) {
         a.logp[pi] = shd[0];
         a.status[pi] = st;
     }
-}
-
-namespace {
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 }
 
 extern "C" size_t po_prefix_ws_bytes(int n, int64_t max_rows) { return al256((size_t)max_rows + 8) * (size_t)(n > 0 ? n : 1) + 256; }

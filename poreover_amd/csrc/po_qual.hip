@@ -26,7 +26,8 @@
 
 #include "../../include/poreover_hip.h"
 
-extern "C" void po_set_error(const char* msg);
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
 
@@ -388,7 +389,6 @@ int q_fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return q_fail(PO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
-inline size_t q_al256(size_t b) { return (b + 255) & ~size_t(255); }
 inline int q_per_state(int model) { return model == PO_MODEL_MERGE ? 14 : 8; }   // doubles of state per ring index (the last: two ints)
 inline int q_nb(int model) { return model == PO_MODEL_MERGE ? 2 : 1; }
 
@@ -423,7 +423,7 @@ size_t po_qual_workspace_bytes(int n, int64_t total_rows, int64_t max_rows, int6
     if (band_size >= 1) cells = std::min(cells, ((double)total_rows + (double)n) * (2.0 * band_size + 2.0));
     const double beta = cells * q_nb(model) * 8.0;
     const double st = ((double)total_labels + (double)n) * q_per_state(model) * 8.0;
-    return q_al256((size_t)beta + 8) + q_al256((size_t)st + 8) + q_al256(sizeof(QDesc) * (size_t)n) + 256;
+    return al256((size_t)beta + 8) + al256((size_t)st + 8) + al256(sizeof(QDesc) * (size_t)n) + 256;
 }
 
 int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
@@ -490,7 +490,7 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
             if (cls[i] == c) sorted.push_back(desc[i]);
         first[c + 1] = (int)sorted.size();
     }
-    const size_t b_beta = q_al256((size_t)nbeta * 8 + 8), b_st = q_al256((size_t)nst * 8 + 8), b_desc = q_al256(sizeof(QDesc) * (size_t)n);
+    const size_t b_beta = al256((size_t)nbeta * 8 + 8), b_st = al256((size_t)nst * 8 + 8), b_desc = al256(sizeof(QDesc) * (size_t)n);
     if (ws_bytes < b_beta + b_st + b_desc) return q_fail(PO_E_CAP, "po_qual_batch: workspace too small");
     a.beta = (double*)ws;
     a.st = (double*)((char*)ws + b_beta);

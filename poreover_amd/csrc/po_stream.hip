@@ -39,19 +39,10 @@
 #include <vector>
 
 #include "../../include/poreover_hip.h"
-
-extern "C" {
-size_t po_pair_ws_bytes_impl(int, int64_t, int64_t, int64_t, int64_t, int, const po_pair_options*);
-int po_launch_pair_decode_geom(const double*, const int64_t*, const double*, const int64_t*, int, int, const po_pair_options*,
-                               int64_t, int64_t, int64_t, int64_t, const int32_t*, const int32_t*, char*, const int64_t*,
-                               int32_t*, int32_t*, double*, int32_t*, char*, const int64_t*, int32_t*, int32_t*, void*, size_t,
-                               hipStream_t);
-int po_launch_ingest(const void*, const int64_t*, int, int, int, const int*, int, int64_t, double*, hipStream_t);
-void po_set_error(const char* msg);
-}
+#include "po_host.h"
+#include "po_internal.h"
 
 namespace {
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
 inline double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }

@@ -35,7 +35,7 @@
 
 #include "po_call_kernels.h"
 
-extern "C" void po_set_error(const char* msg);
+#include "po_internal.h"
 
 namespace {
 

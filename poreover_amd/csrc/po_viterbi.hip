@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "po_device.h"
+#include "po_internal.h"
 
 #define VT_THREADS 256
 #define VT_WAVES (VT_THREADS / PO_WAVE)
@@ -341,12 +342,6 @@ __global__ __launch_bounds__(VT_THREADS) void flipflop_compact_kernel(
         if (status[r] == PO_OK) status[r] = st;
     }
 }
-
-extern "C" int po_launch_viterbi_strided(const double* y, const int64_t* y_off, int n, int C, int A,
-                                         uint32_t alphabet, int kind, int8_t* path, char* seq,
-                                         const int64_t* seq_off, int so_base, int so_stride, int32_t* seq_len,
-                                         int32_t* map, int32_t* status, int8_t* ff_ptr, int8_t* ff_path,
-                                         hipStream_t stream);
 
 extern "C" int po_launch_viterbi(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet,
                                  int kind, int8_t* path, char* seq, const int64_t* seq_off, int32_t* seq_len,

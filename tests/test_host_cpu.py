@@ -57,6 +57,50 @@ def test_build_objects_cover_every_source():
     assert "PO_REG_TU == 1" in src and "PO_REG_TU == 2" in src and "po_reg_wide_launch" in src
 
 
+def _po_prototypes(text):
+    """(declared, defined): the po_* functions a C++ source declares with a prototype / defines with a body"""
+    text = re.sub(r"//[^\n]*|/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r'"(?:[^"\\\n]|\\.)*"', '""', text)
+    text = re.sub(r"^[ \t]*#[^\n]*", ";", text, flags=re.M)   # (a preprocessor line ends what came before it)
+    declared, defined = set(), set()
+    # a statement that starts with type words (no operator, no parenthesis, no keyword of a call site) and names a po_* function
+    for m in re.finditer(r'(?:^|[;{}])\s*((?:extern\s+""\s+)?(?:__attribute__\(\(\w+\(""\)\)\)\s+)?[A-Za-z_][\w\s\*&:<>]*?[\s\*&])(po_\w+)\s*\(', text):
+        if re.search(r"\b(return|else|case|do|new|delete|throw|goto|typedef|using)\b", m.group(1)):
+            continue
+        i, depth = m.end(), 1
+        while depth:
+            depth += (text[i] == "(") - (text[i] == ")")
+            i += 1
+        rest = text[i:].lstrip()
+        if rest.startswith(";"):
+            declared.add(m.group(2))
+        elif rest.startswith("{"):
+            defined.add(m.group(2))
+    return declared, defined
+
+
+def test_no_hand_copied_prototypes():
+    """No .hip file under csrc/ declares a po_* function that it neither defines nor gets from a header: entry points that one
+    translation unit defines and another calls are declared once, in po_internal.h (po_reg_*: po_beam2d_common.h), which the
+    defining file includes as well — so a signature that drifts stops the build instead of corrupting arguments."""
+    import glob
+    from poreover_amd import build
+    csrc = os.path.join(os.path.dirname(build.__file__), "csrc")
+    assert _po_prototypes('extern "C" int po_x(int);\nint f() { return po_y(1); }\nvoid po_z(int a) {\n}\nstatic int po_w(void* p);')[0] == {"po_x", "po_w"}
+    offenders, in_headers = {}, set()
+    for f in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        declared, defined = _po_prototypes(open(f).read())
+        if declared - defined:
+            offenders[os.path.basename(f)] = sorted(declared - defined)
+    for f in glob.glob(os.path.join(csrc, "*.h")):
+        in_headers |= _po_prototypes(open(f).read())[0]
+    assert not offenders, offenders
+    # ... and the header is where they went: what the route file needs of the kernel files, what the C-ABI needs of everyone
+    for name in ("po_launch_beam2d_geom", "po_beam2d_ws_bytes_impl", "po_pair_ws_bytes_impl", "po_launch_viterbi_strided", "po_set_error",
+                 "po_prof_stage", "po_reg_launch", "po_b2_launch_legacy", "po_b2_launch_grid"):
+        assert name in in_headers, name
+
+
 def test_product_never_imports_oracle():
     bad = []
     for root, _, files in os.walk(os.path.join(REPO, "poreover_amd")):

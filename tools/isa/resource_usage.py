@@ -9,11 +9,9 @@ SRC = sorted(_build.OBJECTS)
 print("# kernel resource usage, hipcc -O3 --offload-arch=gfx950 -S (code-object metadata), the sources of this commit")
 print("# kernel | VGPRs | AGPRs | SGPRs | SGPR spills | VGPR spills | scratch B/lane | LDS B/block | waves/SIMD (512 / VGPRs, at most 8)")
 for oname, sname, extra in SRC:
-    src = os.path.join(ROOT, "poreover_amd", "csrc", sname)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "x.s")
-        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value", "-Wno-unused-function",
-                        *extra, "-S", "--cuda-device-only", "-o", out, src], check=True, stderr=subprocess.DEVNULL)
+        subprocess.run(_build.compile_cmd(oname) + ["-S", "--cuda-device-only", "-o", out], check=True, stderr=subprocess.DEVNULL)
         txt = open(out).read()
     meta = txt[txt.index("amdhsa.kernels:"):] if "amdhsa.kernels:" in txt else ""
     print("## " + oname + ((" (" + sname + " " + " ".join(extra) + ")") if extra else ""))

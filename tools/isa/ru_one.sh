@@ -1,8 +1,11 @@
 #!/bin/bash
-# resource usage of ONE translation unit (default: the register-state pair kernel): tools/isa/ru_one.sh [file.hip] [extra hipcc flags]
-f=${1:-poreover_amd/csrc/po_beam2d_reg.hip}; shift
+# resource usage of ONE object of the library (default: the register-state pair kernel), compiled as the product compiles it
+# (poreover_amd/build.py --cmd): tools/isa/ru_one.sh [OBJECT] [extra hipcc flags]     OBJECT: po_pair, po_beam2d_reg_wide.hip, ...
+# po_beam2d_reg is the library's object of that name, i.e. the 32-slot kernels only (the 64-slot ones: po_beam2d_reg_wide); all
+# fifteen instantiations in one listing, as this script gave before it took the product's options: po_beam2d_reg -UPO_REG_TU
+f=$(basename ${1:-po_beam2d_reg.hip}); shift
 cd $(dirname $0)/../..
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wno-unused-value -S --cuda-device-only "$@" -o /tmp/ru_one.s $f 2>/dev/null
+eval "$(python3 poreover_amd/build.py --cmd $f "$@") -S --cuda-device-only -o /tmp/ru_one.s" 2>/dev/null
 python3 - <<'PY'
 import re,subprocess
 txt=open('/tmp/ru_one.s').read()
