@@ -281,7 +281,16 @@ int po_pair_decode_batch(const double* y1, const int64_t* y1_off, const double* 
                          size_t ws_bytes, void* stream);
 
 /* ---- host-buffer conveniences (numpy callers): allocate, copy in, launch, copy out, free ----
- * Same semantics as the device-pointer forms with every pointer a HOST pointer; synchronous. */
+ * Same semantics as the device-pointer forms with every pointer a HOST pointer; synchronous.
+ * INPUT offset tables (y_off_h, y1_off_h, y2_off_h, label_off_h, and the tables of sequences, alignments, maps and
+ * envelopes that a call reads) need not start at 0: a call may be given items k..k+n of a larger batch as off + k and the
+ * batch's own data pointers.  Arrays with one entry per row or per label of an input (env_h of po_beam2d_batch_h, the frame
+ * maps of po_pair_decode_from_1d_batch_h, guide_h) are read at the same offsets, and po_label_align_batch_h / po_qual_batch_h
+ * write map_h / odds_h at label_off_h[0] on, the labels' own places.  (previous_h of po_forward_vec_batch_h is the
+ * exception: the n items' rows from previous_h[0] on.)  Every other output starts at element 0 of its array, and OUTPUT
+ * offset tables (seq_off_h, seq1d_off_h, aln_off_h, env_off_h of po_envelope_batch_h, dense_off_h, dp_off_h) start at 0.
+ * Three calls require row_off_h[0] / off_h[0] == 0 on input and answer PO_E_ARG otherwise: po_ingest_batch_h,
+ * po_decode_1d_batch_h and po_map_sketch_h (as do the mapper's po_map_batch_h and po_map_pairs_h further down). */
 int po_ingest_batch_h(const void* src_h, const int64_t* row_off_h, int n, int C, int mode, const int* perm_h,
                       int reverse, double* out_h);
 /* `poreover decode` for a batch of traces in one call (decode.py:114-192: model_from_trace + viterbi_decode /

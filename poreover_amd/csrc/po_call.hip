@@ -31,24 +31,6 @@
 
 namespace {
 
-thread_local std::string g_call_err;
-int call_fail(int code, const std::string& msg) {
-    g_call_err = msg;
-    po_set_error(msg.c_str());
-    return code;
-}
-int call_hip(hipError_t e, const char* what) {
-    return call_fail(PO_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define CALLCHK(x)                                      \
-    do {                                                \
-        hipError_t e_ = (x);                            \
-        if (e_ != hipSuccess) return call_hip(e_, #x);  \
-    } while (0)
-
-// the model checked against the weights' length; returns the widest activation (channels) or a PO_E_* code
-int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) { return check_model_for(L, nl, nweights, call_fail); }
-
 size_t ws_bytes_for(int64_t M, int64_t wmax) {
     return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G * 4);
 }
@@ -72,17 +54,16 @@ size_t po_call_workspace_bytes(int n, int T, const po_call_layer* layers_h, int 
 int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers_h, int n_layers, const float* weights,
                   int64_t n_weights, float* probs, float* logits, void* ws, size_t ws_bytes, void* stream_,
                   float* stage_ms_h) {
-    g_call_err.clear();
     po_set_error("");
-    if (n < 0 || T < 1 || !signal || !weights || !probs) return call_fail(PO_E_ARG, "po_call_batch: null argument or T < 1");
+    if (n < 0 || T < 1 || !signal || !weights || !probs) return po_fail(PO_E_ARG, "po_call_batch: null argument or T < 1");
     int64_t nw;
     const int64_t wmax = check_model(layers_h, n_layers, &nw);
     if (wmax < 0) return (int)wmax;
-    if (nw != n_weights) return call_fail(PO_E_ARG, "po_call_batch: the model has " + std::to_string(nw) + " weights, " +
-                                                        std::to_string(n_weights) + " given");
+    if (nw != n_weights) return po_fail(PO_E_ARG, "po_call_batch: the model has " + std::to_string(nw) + " weights, " +
+                                        std::to_string(n_weights) + " given");
     if (n == 0) return PO_OK;
     const int64_t M = (int64_t)n * T;
-    if (!ws || ws_bytes < ws_bytes_for(M, wmax)) return call_fail(PO_E_CAP, "po_call_batch: workspace too small");
+    if (!ws || ws_bytes < ws_bytes_for(M, wmax)) return po_fail(PO_E_CAP, "po_call_batch: workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
     char* p = (char*)ws;
     float* act[2] = {(float*)p, (float*)(p + al256((size_t)M * wmax * 4))};
@@ -92,15 +73,15 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
         if (!stage_ms_h) return PO_OK;
         Stage s;
         s.kind = kind;
-        CALLCHK(hipEventCreate(&s.a));
-        CALLCHK(hipEventCreate(&s.b));
+        PO_HIPCHK(hipEventCreate(&s.a));
+        PO_HIPCHK(hipEventCreate(&s.b));
         st.push_back(s);
-        CALLCHK(hipEventRecord(s.a, stream));
+        PO_HIPCHK(hipEventRecord(s.a, stream));
         return PO_OK;
     };
     auto end = [&]() -> int {
         if (!stage_ms_h) return PO_OK;
-        CALLCHK(hipEventRecord(st.back().b, stream));
+        PO_HIPCHK(hipEventRecord(st.back().b, stream));
         return PO_OK;
     };
     const float* x = signal;
@@ -155,12 +136,12 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
     }
     if (rc == PO_OK) {
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = call_hip(e, "po_call_batch: launch");
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_call_batch: launch");
     }
     if (stage_ms_h) {
         if (rc == PO_OK) {
             const hipError_t e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) rc = call_hip(e, "po_call_batch: hipStreamSynchronize");
+            if (e != hipSuccess) rc = po_fail_hip(e, "po_call_batch: hipStreamSynchronize");
         }
         for (auto& s : st) {
             float ms = 0.f;
@@ -174,14 +155,13 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
 
 int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* layers_h, int n_layers,
                     const float* weights_h, int64_t n_weights, float* probs_h, float* logits_h, float* stage_ms_h) {
-    g_call_err.clear();
     po_set_error("");
-    if (n < 0 || T < 1 || !signal_h || !weights_h || !probs_h) return call_fail(PO_E_ARG, "po_call_batch_h: null argument or T < 1");
+    if (n < 0 || T < 1 || !signal_h || !weights_h || !probs_h) return po_fail(PO_E_ARG, "po_call_batch_h: null argument or T < 1");
     int64_t nw;
     const int64_t wmax = check_model(layers_h, n_layers, &nw);
     if (wmax < 0) return (int)wmax;
-    if (nw != n_weights) return call_fail(PO_E_ARG, "po_call_batch_h: the model has " + std::to_string(nw) + " weights, " +
-                                                        std::to_string(n_weights) + " given");
+    if (nw != n_weights) return po_fail(PO_E_ARG, "po_call_batch_h: the model has " + std::to_string(nw) + " weights, " +
+                                        std::to_string(n_weights) + " given");
     if (n == 0) return PO_OK;
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + 4, 0.f);
     // windows per pass: as many as ~4 GiB of workspace holds, a whole number of recurrence tiles (a window's bits do
@@ -191,41 +171,23 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
     if (chunk >= RT) chunk = chunk / RT * RT;
     chunk = std::min(chunk, n);
     const int64_t Mc = (int64_t)chunk * T;
-    float *dw = nullptr, *dsig = nullptr, *dprob = nullptr, *dlog = nullptr;
-    void* dws = nullptr;
     const size_t wsb = ws_bytes_for(Mc, wmax);
-    int rc = PO_OK;
-    hipError_t e;
-    if ((e = hipMalloc(&dw, (size_t)n_weights * 4)) != hipSuccess ||
-        (e = hipMalloc(&dsig, (size_t)Mc * 4)) != hipSuccess ||
-        (e = hipMalloc(&dprob, (size_t)Mc * NOUT * 4)) != hipSuccess ||
-        (logits_h && (e = hipMalloc(&dlog, (size_t)Mc * NOUT * 4)) != hipSuccess) ||
-        (e = hipMalloc(&dws, wsb)) != hipSuccess) {
-        rc = call_hip(e, "po_call_batch_h: hipMalloc");
-    }
-    if (rc == PO_OK && (e = hipMemcpy(dw, weights_h, (size_t)n_weights * 4, hipMemcpyHostToDevice)) != hipSuccess)
-        rc = call_hip(e, "po_call_batch_h: hipMemcpy (weights)");
-    for (int w0 = 0; rc == PO_OK && w0 < n; w0 += chunk) {
+    PoDev dw, dsig, dprob, dlog, dws;   // (dlog stays NULL without a logits output)
+    PO_HIPCHK(dw.up(weights_h, (size_t)n_weights * 4));
+    PO_HIPCHK(dsig.up(nullptr, (size_t)Mc * 4));
+    PO_HIPCHK(dprob.up(nullptr, (size_t)Mc * NOUT * 4));
+    if (logits_h) PO_HIPCHK(dlog.up(nullptr, (size_t)Mc * NOUT * 4));
+    PO_HIPCHK(dws.up(nullptr, wsb));
+    for (int w0 = 0; w0 < n; w0 += chunk) {
         const int nc = std::min(chunk, n - w0);
-        const int64_t M = (int64_t)nc * T;
-        if ((e = hipMemcpy(dsig, signal_h + (int64_t)w0 * T, (size_t)M * 4, hipMemcpyHostToDevice)) != hipSuccess) {
-            rc = call_hip(e, "po_call_batch_h: hipMemcpy (signal)");
-            break;
-        }
-        rc = po_call_batch(dsig, nc, T, layers_h, n_layers, dw, n_weights, dprob, dlog, dws, wsb, nullptr, stage_ms_h);
-        if (rc != PO_OK) break;
-        if ((e = hipMemcpy(probs_h + (int64_t)w0 * T * NOUT, dprob, (size_t)M * NOUT * 4, hipMemcpyDeviceToHost)) != hipSuccess ||
-            (logits_h && (e = hipMemcpy(logits_h + (int64_t)w0 * T * NOUT, dlog, (size_t)M * NOUT * 4, hipMemcpyDeviceToHost)) != hipSuccess))
-            rc = call_hip(e, "po_call_batch_h: hipMemcpy (outputs)");
+        const size_t M = (size_t)nc * T;
+        PO_HIPCHK(hipMemcpy(dsig, signal_h + (int64_t)w0 * T, M * 4, hipMemcpyHostToDevice));
+        const int rc = po_call_batch(dsig, nc, T, layers_h, n_layers, dw, n_weights, dprob, dlog, dws, wsb, nullptr, stage_ms_h);
+        if (rc != PO_OK) return rc;
+        PO_HIPCHK(dprob.down(probs_h + (int64_t)w0 * T * NOUT, M * NOUT * 4));
+        if (logits_h) PO_HIPCHK(dlog.down(logits_h + (int64_t)w0 * T * NOUT, M * NOUT * 4));
     }
-    std::string keep = rc == PO_OK ? std::string() : g_call_err;
-    (void)hipFree(dw);
-    (void)hipFree(dsig);
-    (void)hipFree(dprob);
-    if (dlog) (void)hipFree(dlog);
-    (void)hipFree(dws);
-    if (rc != PO_OK) po_set_error(keep.c_str());
-    return rc;
+    return PO_OK;
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // unit that includes this gets its own copy.  What they compute, and how, is described in po_call.hip.
 #pragma once
 #include "po_device.h"
+#include "po_hostbuf.h"
 
 namespace {
 
@@ -201,33 +202,32 @@ __global__ __launch_bounds__(256) void dense_softmax_kernel(const float* __restr
     }
 }
 
-// the model checked against the weights' length; returns the widest activation (channels) or fail(PO_E_*, message)'s code
-template <class Fail>
-int64_t check_model_for(const po_call_layer* L, int nl, int64_t* nweights, Fail fail) {
-    if (!L || nl < 1) return fail(PO_E_ARG, "po_call: empty model");
+// the model checked against the weights' length; returns the widest activation (channels) or po_fail(PO_E_*, message)'s code
+int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
+    if (!L || nl < 1) return po_fail(PO_E_ARG, "po_call: empty model");
     int64_t wmax = 1, nw = 0;
     int cin = 1;
     for (int k = 0; k < nl; ++k) {
         const po_call_layer& l = L[k];
-        if (l.cin != cin) return fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " takes " + std::to_string(l.cin) +
-                                                         " channels, its input has " + std::to_string(cin));
+        if (l.cin != cin) return po_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " takes " + std::to_string(l.cin) +
+                                         " channels, its input has " + std::to_string(cin));
         if (l.kind == PO_CALL_CONV) {
-            if (l.cout < 1 || l.kernel < 1 || l.kernel > 64) return fail(PO_E_ARG, "po_call: conv filters / kernel size");
+            if (l.cout < 1 || l.kernel < 1 || l.kernel > 64) return po_fail(PO_E_ARG, "po_call: conv filters / kernel size");
             nw += (int64_t)l.kernel * l.cin * l.cout + l.cout;
         } else if (l.kind == PO_CALL_BIGRU || l.kind == PO_CALL_GRU || l.kind == PO_CALL_GRU_BACK) {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
-            if (l.cout != nd * H) return fail(PO_E_UNSUPPORTED, "po_call: GRU layers have 128 units per direction");
+            if (l.cout != nd * H) return po_fail(PO_E_UNSUPPORTED, "po_call: GRU layers have 128 units per direction");
             nw += nd * ((int64_t)l.cin * G + (int64_t)H * G + 2 * G);
         } else if (l.kind == PO_CALL_DENSE) {
-            if (k != nl - 1 || l.cout != NOUT) return fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
+            if (k != nl - 1 || l.cout != NOUT) return po_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
             nw += (int64_t)l.cin * NOUT + NOUT;
         } else {
-            return fail(PO_E_ARG, "po_call: layer kind " + std::to_string(l.kind));
+            return po_fail(PO_E_ARG, "po_call: layer kind " + std::to_string(l.kind));
         }
         cin = l.cout;
         wmax = std::max<int64_t>(wmax, l.cout);
     }
-    if (L[nl - 1].kind != PO_CALL_DENSE) return fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
+    if (L[nl - 1].kind != PO_CALL_DENSE) return po_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
     *nweights = nw;
     return wmax;
 }

@@ -9,20 +9,18 @@
 #include <vector>
 
 #include "../../include/poreover_hip.h"
-#include "po_host.h"
-#include "po_internal.h"
+#include "po_hostbuf.h"
 
 namespace {
-thread_local std::string g_err;
-int fail_hip(hipError_t e, const char* what) {
-    g_err = std::string(what) + ": " + hipGetErrorString(e);
-    return PO_E_HIP;
+thread_local std::string g_err;   // the one error message of a thread: po_last_error reads it, po_fail / po_set_error write it
+}  // namespace
+int po_fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
 }
-#define HIPCHK(x)                                      \
-    do {                                               \
-        hipError_t e_ = (x);                           \
-        if (e_ != hipSuccess) return fail_hip(e_, #x); \
-    } while (0)
+int po_fail_hip(hipError_t e, const char* what) { return po_fail(PO_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+
+namespace {
 // alphabet string -> (A, packed bytes); NULL means "ACGT"
 inline int pack_alphabet(const char* a, uint32_t* packed) {
     if (!a) a = "ACGT";
@@ -103,7 +101,7 @@ int po_device_count(void) {
 
 int po_set_device(int device) {
     g_err.clear();
-    HIPCHK(hipSetDevice(device));
+    PO_HIPCHK(hipSetDevice(device));
     return PO_OK;
 }
 
@@ -114,7 +112,7 @@ void po_set_error(const char* msg) { g_err = msg ? msg : ""; }
 int po_device_info(int device, char* name, int name_cap, int* cus, int* clock_khz, size_t* total_mem) {
     g_err.clear();
     hipDeviceProp_t p;
-    HIPCHK(hipGetDeviceProperties(&p, device));
+    PO_HIPCHK(hipGetDeviceProperties(&p, device));
     if (name && name_cap > 0) { std::strncpy(name, p.name, name_cap - 1); name[name_cap - 1] = 0; }
     if (cus) *cus = p.multiProcessorCount;
     if (clock_khz) *clock_khz = p.clockRate;
@@ -129,13 +127,11 @@ int po_ingest_batch(const void* src, const int64_t* row_off, int n, int C, int m
     if (n < 0 || !src || !row_off || !out) { g_err = "po_ingest_batch: null argument"; return PO_E_ARG; }
     if (n == 0) return PO_OK;
     int64_t ends[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&ends[0], row_off, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], row_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    PO_HIPCHK(po_read_ends(row_off, n, (hipStream_t)stream, ends));
     if (ends[0] != 0) { g_err = "po_ingest_batch: row_off[0] must be 0"; return PO_E_ARG; }
     int rc = po_launch_ingest(src, row_off, n, C, mode, perm_h, reverse, ends[1], out, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_ingest_batch: bad C / mode / permutation"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -159,9 +155,7 @@ int po_viterbi_batch(const double* y, const int64_t* y_off, int n, int C, const 
     if (kind == PO_KIND_FLIPFLOP) {
         if (!ws) { g_err = "po_viterbi_batch: flip-flop needs a workspace"; return PO_E_CAP; }
         int64_t ends[2] = {0, 0};  // total rows, to split and bounds-check the workspace
-        HIPCHK(hipMemcpyAsync(&ends[0], y_off, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIPCHK(hipMemcpyAsync(&ends[1], y_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        PO_HIPCHK(po_read_ends(y_off, n, (hipStream_t)stream, ends));
         const size_t rows = (size_t)(ends[1] - ends[0]);
         if (ws_bytes < al256(rows * 8) + al256(rows)) { g_err = "po_viterbi_batch: workspace too small"; return PO_E_CAP; }
         ff_ptr = (int8_t*)ws;
@@ -171,7 +165,7 @@ int po_viterbi_batch(const double* y, const int64_t* y_off, int n, int C, const 
     int rc = po_launch_viterbi(y, y_off, n, C, A, ap, kind, path, seq, seq_off, seq_len, map, status, ff_ptr, ff_path,
                                (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_viterbi_batch: unsupported C/kind"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -200,14 +194,12 @@ int po_beam1d_batch(const double* y, const int64_t* y_off, int n, int C, const c
     int* afc = (int*)((char*)ws + half);
     // total rows, for the capacity check (one small D2H; the rest of the call stays asynchronous)
     int64_t ends[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(&ends[0], y_off, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipMemcpyAsync(&ends[1], y_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    PO_HIPCHK(po_read_ends(y_off, n, (hipStream_t)stream, ends));
     if (sizeof(int) * (size_t)po_beam1d_arena_nodes(n, ends[1] - ends[0], W) > half) { g_err = "po_beam1d_batch: workspace too small"; return PO_E_CAP; }
     ProfScope ps(PO_K_BEAM1D, (hipStream_t)stream);
     int rc = po_launch_beam1d(y, y_off, n, C, A, ap, W, model, apl, afc, seq, seq_off, seq_len, status, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_beam1d_batch: unsupported C/model/beam_width"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -231,18 +223,16 @@ int po_beam2d_batch(const double* y1, const int64_t* y1_off, const double* y2, c
     int rc = po_launch_beam2d(y1, y1_off, y2, y2_off, env, n, C, A, ap, W, model, method, seq, seq_off, seq_len, status,
                               ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_beam2d_batch: launch refused"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
 // -------------------------------------------------------------------------------- forward / acceptor
 namespace {
-// max rows / max label length of a batch, read back from the device offset tables
+// the largest item of each of two device offset tables (rows and labels, or the two reads of a pair), read back
 int batch_maxima(const int64_t* y_off, const int64_t* label_off, int n, hipStream_t s, int64_t* mr, int64_t* ml) {
     std::vector<int64_t> h(2 * (size_t)(n + 1));
-    HIPCHK(hipMemcpyAsync(h.data(), y_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(h.data() + n + 1, label_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    PO_HIPCHK(po_read_tables(y_off, label_off, n, s, h.data()));
     *mr = 0; *ml = 0;
     for (int i = 0; i < n; ++i) {
         *mr = std::max<int64_t>(*mr, h[i + 1] - h[i]);
@@ -269,7 +259,7 @@ int po_forward_batch(const double* y, const int64_t* y_off, int n, int C, const 
     if (rc != PO_OK) return rc;
     rc = po_launch_forward(y, y_off, n, C, A, ap, model, labels, label_off, mr, logp, status, ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_forward_batch: unsupported C/model or workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -293,7 +283,7 @@ int po_viterbi_acceptor_batch(const double* y, const int64_t* y_off, int n, int 
     rc = po_launch_acceptor(y, y_off, n, C, A, ap, band_size, labels, label_off, mr, ml, path, status, ws, ws_bytes,
                             (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_viterbi_acceptor_batch: unsupported C or workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -311,14 +301,14 @@ int po_prefix_search_batch(const double* y, const int64_t* y_off, int n, int C, 
     if (A < 0) { g_err = "po_prefix_search_batch: alphabet must have 1..4 symbols"; return PO_E_ARG; }
     if (n == 0) return PO_OK;
     std::vector<int64_t> h((size_t)n + 1);
-    HIPCHK(hipMemcpyAsync(h.data(), y_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    PO_HIPCHK(hipMemcpyAsync(h.data(), y_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PO_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     int64_t mr = 0;
     for (int i = 0; i < n; ++i) mr = std::max<int64_t>(mr, h[i + 1] - h[i]);
     int rc = po_launch_prefix_search(y, y_off, n, C, A, ap, mr, seq, seq_off, seq_len, logp, status, ws, ws_bytes,
                                      (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_prefix_search_batch: unsupported C / window longer than the LDS rows / workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -332,13 +322,13 @@ int po_align_batch(const char* seqs, const int64_t* seq_off, int n, int band_wid
     if (n < 0 || !seqs || !seq_off || !aln1 || !aln2 || !aln_off || !ncol || !status || !ws) { g_err = "po_align_batch: null argument"; return PO_E_ARG; }
     if (n == 0) return PO_OK;
     std::vector<int64_t> h(2 * (size_t)n + 1);
-    HIPCHK(hipMemcpyAsync(h.data(), seq_off, sizeof(int64_t) * (2 * n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    PO_HIPCHK(hipMemcpyAsync(h.data(), seq_off, sizeof(int64_t) * (2 * n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PO_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     int64_t m1 = 0, m2 = 0;
     for (int i = 0; i < n; ++i) { m1 = std::max<int64_t>(m1, h[2 * i + 1] - h[2 * i]); m2 = std::max<int64_t>(m2, h[2 * i + 2] - h[2 * i + 1]); }
     int rc = po_launch_align(seqs, seq_off, n, band_width, m1, m2, aln1, aln2, aln_off, ncol, status, ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_align_batch: workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -354,14 +344,14 @@ int po_envelope_batch(const char* aln1, const char* aln2, const int64_t* aln_off
         !env_off || !status || !ws) { g_err = "po_envelope_batch: null argument"; return PO_E_ARG; }
     if (n == 0) return PO_OK;
     std::vector<int32_t> h((size_t)n);
-    HIPCHK(hipMemcpyAsync(h.data(), ncol, sizeof(int32_t) * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    PO_HIPCHK(hipMemcpyAsync(h.data(), ncol, sizeof(int32_t) * n, hipMemcpyDeviceToHost, (hipStream_t)stream));
+    PO_HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     int64_t mc = 0;
     for (int i = 0; i < n; ++i) mc = std::max<int64_t>(mc, h[i]);
     int rc = po_launch_envelope(aln1, aln2, aln_off, ncol, n, map1, map1_off, map2, map2_off, U, V, padding, mc, env,
                                 env_off, status, ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_envelope_batch: workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -377,16 +367,13 @@ int po_pair_gamma_batch(const double* y1, const int64_t* y1_off, const double* y
     if (n < 0 || !y1 || !y1_off || !y2 || !y2_off || !gamma00 || !status || !ws || (env && !env_off) ||
         (dense_out && !dense_off)) { g_err = "po_pair_gamma_batch: null argument"; return PO_E_ARG; }
     if (n == 0) return PO_OK;
-    std::vector<int64_t> h(2 * (size_t)(n + 1));
-    HIPCHK(hipMemcpyAsync(h.data(), y1_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipMemcpyAsync(h.data() + n + 1, y2_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, (hipStream_t)stream));
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     int64_t m1 = 0, m2 = 0;
-    for (int i = 0; i < n; ++i) { m1 = std::max<int64_t>(m1, h[i + 1] - h[i]); m2 = std::max<int64_t>(m2, h[n + 1 + i + 1] - h[n + 1 + i]); }
-    int rc = po_launch_gamma(y1, y1_off, y2, y2_off, env, env_off, n, C, flavor, max_cells, m1, m2, gamma00, dense_out,
+    int rc = batch_maxima(y1_off, y2_off, n, (hipStream_t)stream, &m1, &m2);
+    if (rc != PO_OK) return rc;
+    rc = po_launch_gamma(y1, y1_off, y2, y2_off, env, env_off, n, C, flavor, max_cells, m1, m2, gamma00, dense_out,
                              dense_off, status, ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_pair_gamma_batch: bad C or workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -407,42 +394,40 @@ int po_pair_decode_batch(const double* y1, const int64_t* y1_off, const double* 
     int rc = po_launch_pair_decode(y1, y1_off, y2, y2_off, n, C, opt, seq1d, seq1d_off, len1, len2, identity,
                                    env_out, seq, seq_off, seq_len, status, ws, ws_bytes, (hipStream_t)stream);
     if (rc != PO_OK) { g_err = "po_pair_decode_batch: launch refused"; return rc; }
-    HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
 // -------------------------------------------------------------------------------- host-buffer forms
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t b) { return hipMalloc(&p, b ? b : 16) == hipSuccess ? 0 : -1; }
-};
-#define UP(buf, src, bytes)                                                                      \
-    do {                                                                                         \
-        if ((buf).alloc(bytes)) { g_err = "hipMalloc failed"; return PO_E_HIP; }                 \
-        if ((src) && (bytes)) HIPCHK(hipMemcpy((buf).p, (src), (bytes), hipMemcpyHostToDevice)); \
-    } while (0)
-#define DOWN(dst, buf, bytes)                                                                      \
-    do {                                                                                           \
-        if ((dst) && (bytes)) HIPCHK(hipMemcpy((dst), (buf).p, (bytes), hipMemcpyDeviceToHost));   \
-    } while (0)
-}  // namespace
+// Every twin is its arrays going up (po_hostbuf.h), one launch on the null stream, hipDeviceSynchronize, its outputs coming down;
+// a return on the way frees what was allocated.  Input tables are rebased by PoRagged; output tables start at 0.
+static size_t ingest_elem_bytes(int mode) { return mode == PO_INGEST_LOGITS_F32 ? 4 : (mode == PO_INGEST_TRACE_U8 ? 1 : 8); }
+
+// stored cells of the largest gamma DP of a batch: the dense box, or the envelope's rows (Gamma.h: end - start + 1 each)
+static int64_t gamma_max_cells(const PoRagged& r1, const PoRagged& r2, const int32_t* env_h, const int64_t* env_off_h, int n) {
+    int64_t mc = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t U = r1.off[i + 1] - r1.off[i], V = r2.off[i + 1] - r2.off[i];
+        int64_t cells = env_h ? 0 : (U + 1) * (V + 1);
+        if (env_h) for (int64_t u = 0; u <= U; ++u) { const int64_t w = (int64_t)env_h[2 * (env_off_h[i] + u) + 1] - env_h[2 * (env_off_h[i] + u)] + 1; cells += w > 0 ? w : 0; }
+        mc = std::max(mc, cells);
+    }
+    return mc;
+}
 
 int po_ingest_batch_h(const void* src_h, const int64_t* row_off_h, int n, int C, int mode, const int* perm_h, int reverse,
                       double* out_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = row_off_h[n];
-    const size_t esz = mode == PO_INGEST_LOGITS_F32 ? 4 : (mode == PO_INGEST_TRACE_U8 ? 1 : 8);
-    DevBuf s, ro, o;
-    UP(s, src_h, esz * (size_t)rows * C);
-    UP(ro, row_off_h, sizeof(int64_t) * (n + 1));
-    UP(o, nullptr, sizeof(double) * (size_t)rows * C);
-    int rc = po_ingest_batch(s.p, (const int64_t*)ro.p, n, C, mode, perm_h, reverse, (double*)o.p, nullptr);
+    const size_t rows = (size_t)row_off_h[n];
+    PoDev s, ro, o;
+    PO_HIPCHK(s.up(src_h, ingest_elem_bytes(mode) * rows * C));
+    PO_HIPCHK(ro.up(row_off_h, sizeof(int64_t) * (n + 1)));
+    PO_HIPCHK(o.up(nullptr, sizeof(double) * rows * C));
+    int rc = po_ingest_batch(s, ro, n, C, mode, perm_h, reverse, o, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(out_h, o, sizeof(double) * (size_t)rows * C);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(o.down(out_h, sizeof(double) * rows * C));
     return PO_OK;
 }
 
@@ -452,31 +437,23 @@ int po_viterbi_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, 
                        int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = y_off_h[n] - y_off_h[0];
-    const int64_t seqb = seq_off_h[n];
-    DevBuf y, yo, so, sq, sl, st, pt, mp, ws;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    UP(pt, nullptr, (size_t)rows);
-    UP(mp, nullptr, sizeof(int32_t) * rows);
-    const size_t wsb = po_viterbi_workspace_bytes(n, rows, C, kind);
-    UP(ws, nullptr, wsb);
-    int rc = po_viterbi_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, kind, (int8_t*)pt.p, (char*)sq.p,
-                              (const int64_t*)so.p, (int32_t*)sl.p, map_h ? (int32_t*)mp.p : nullptr,
-                              (int32_t*)st.p, ws.p, wsb, nullptr);
+    const PoRagged r(y_off_h, n);
+    PoRows y;
+    PoSeqOut out;
+    PoDev pt, mp, ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(out.up(seq_off_h, n));
+    PO_HIPCHK(pt.up(nullptr, (size_t)r.total));
+    PO_HIPCHK(mp.up(nullptr, sizeof(int32_t) * r.total));
+    const size_t wsb = po_viterbi_workspace_bytes(n, r.total, C, kind);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_viterbi_batch(y.data, y.off, n, C, alphabet, kind, pt, out.seq, out.off, out.len,
+                              map_h ? mp.as<int32_t>() : nullptr, out.status, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
-    DOWN(path_h, pt, (size_t)rows);
-    DOWN(map_h, mp, sizeof(int32_t) * rows);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
+    PO_HIPCHK(pt.down(path_h, (size_t)r.total));
+    PO_HIPCHK(mp.down(map_h, sizeof(int32_t) * r.total));
     return PO_OK;
 }
 
@@ -487,38 +464,27 @@ int po_decode_1d_batch_h(const void* src_h, const int64_t* row_off_h, int n, int
                          int32_t* seq_len_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    if (!src_h || !row_off_h || !seq_h || !seq_off_h || !seq_len_h || !status_h) { g_err = "po_decode_1d_batch_h: null argument"; return PO_E_ARG; }
-    if (in_mode < 0 || in_mode > 2 || row_off_h[0] != 0) { g_err = "po_decode_1d_batch_h: bad input mode / offsets"; return PO_E_ARG; }
-    const int64_t rows = row_off_h[n];
-    const size_t esz = in_mode == PO_INGEST_LOGITS_F32 ? 4 : (in_mode == PO_INGEST_TRACE_U8 ? 1 : 8);
-    int64_t mx = 0;
-    for (int i = 0; i < n; ++i) mx = std::max<int64_t>(mx, row_off_h[i + 1] - row_off_h[i]);
-    DevBuf src, ro, y, so, sq, sl, st, ws;
-    UP(src, src_h, esz * (size_t)rows * C);
-    UP(ro, row_off_h, sizeof(int64_t) * (n + 1));
-    UP(y, nullptr, sizeof(double) * (size_t)rows * C);
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seq_off_h[n]);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    int rc = po_launch_ingest(src.p, (const int64_t*)ro.p, n, C, in_mode, perm_h, reverse, rows, (double*)y.p, nullptr);
-    if (rc != PO_OK) { g_err = "po_decode_1d_batch_h: bad C / mode / permutation"; return rc; }
-    if (beam_width <= 0) {
-        const size_t wsb = po_viterbi_workspace_bytes(n, rows, C, kind);
-        UP(ws, nullptr, wsb);
-        rc = po_viterbi_batch((const double*)y.p, (const int64_t*)ro.p, n, C, alphabet, kind, nullptr, (char*)sq.p,
-                              (const int64_t*)so.p, (int32_t*)sl.p, nullptr, (int32_t*)st.p, ws.p, wsb, nullptr);
-    } else {
-        const size_t wsb = po_beam1d_workspace_bytes(n, rows, mx, C, beam_width, model);
-        UP(ws, nullptr, wsb);
-        rc = po_beam1d_batch((const double*)y.p, (const int64_t*)ro.p, n, C, alphabet, beam_width, model, (char*)sq.p,
-                             (const int64_t*)so.p, (int32_t*)sl.p, (int32_t*)st.p, ws.p, wsb, nullptr);
-    }
+    if (!src_h || !row_off_h || !seq_h || !seq_off_h || !seq_len_h || !status_h) return po_fail(PO_E_ARG, "po_decode_1d_batch_h: null argument");
+    if (in_mode < 0 || in_mode > 2 || row_off_h[0] != 0) return po_fail(PO_E_ARG, "po_decode_1d_batch_h: bad input mode / offsets");
+    const PoRagged r(row_off_h, n);
+    PoRows src;
+    PoSeqOut out;
+    PoDev y, ws;
+    PO_HIPCHK(src.up(src_h, r, ingest_elem_bytes(in_mode) * C));
+    PO_HIPCHK(y.up(nullptr, sizeof(double) * (size_t)r.total * C));
+    PO_HIPCHK(out.up(seq_off_h, n));
+    int rc = po_launch_ingest(src.data, src.off, n, C, in_mode, perm_h, reverse, r.total, y, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_decode_1d_batch_h: bad C / mode / permutation");
+    const size_t wsb = beam_width <= 0 ? po_viterbi_workspace_bytes(n, r.total, C, kind)
+                                       : po_beam1d_workspace_bytes(n, r.total, r.max, C, beam_width, model);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    rc = beam_width <= 0 ? po_viterbi_batch(y, src.off, n, C, alphabet, kind, nullptr, out.seq, out.off, out.len, nullptr,
+                                            out.status, ws, wsb, nullptr)
+                         : po_beam1d_batch(y, src.off, n, C, alphabet, beam_width, model, out.seq, out.off, out.len, out.status,
+                                           ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seq_off_h[n]);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
     return PO_OK;
 }
 
@@ -527,28 +493,18 @@ int po_beam1d_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, c
                       const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = y_off_h[n] - y_off_h[0];
-    const int64_t seqb = seq_off_h[n];
-    int64_t mx = 0;
-    for (int i = 0; i < n; ++i) mx = std::max<int64_t>(mx, y_off_h[i + 1] - y_off_h[i]);
-    DevBuf y, yo, so, sq, sl, st, ws;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_beam1d_workspace_bytes(n, rows, mx, C, W, model);
-    UP(ws, nullptr, wsb);
-    int rc = po_beam1d_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, W, model, (char*)sq.p,
-                             (const int64_t*)so.p, (int32_t*)sl.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    const PoRagged r(y_off_h, n);
+    PoRows y;
+    PoSeqOut out;
+    PoDev ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(out.up(seq_off_h, n));
+    const size_t wsb = po_beam1d_workspace_bytes(n, r.total, r.max, C, W, model);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_beam1d_batch(y.data, y.off, n, C, alphabet, W, model, out.seq, out.off, out.len, out.status, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
     return PO_OK;
 }
 
@@ -557,39 +513,24 @@ int po_pair_gamma_batch_h(const double* y1_h, const int64_t* y1_off_h, const dou
                           double* dense_out_h, const int64_t* dense_off_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t r1 = y1_off_h[n] - y1_off_h[0], r2 = y2_off_h[n] - y2_off_h[0];
-    int64_t m1 = 0, m2 = 0, mc = 0;
-    for (int i = 0; i < n; ++i) {
-        const int64_t U = y1_off_h[i + 1] - y1_off_h[i], V = y2_off_h[i + 1] - y2_off_h[i];
-        m1 = std::max(m1, U); m2 = std::max(m2, V);
-        int64_t cells = 0;
-        if (env_h) for (int64_t u = 0; u <= U; ++u) { const int64_t w = env_h[2 * (env_off_h[i] + u) + 1] - env_h[2 * (env_off_h[i] + u)] + 1; cells += w > 0 ? w : 0; }
-        else cells = (U + 1) * (V + 1);
-        mc = std::max(mc, cells);
-    }
-    DevBuf a, ao, b, bo, ev, eo, g0, dn, dof, st, ws;
-    UP(a, y1_h + y1_off_h[0] * C, sizeof(double) * r1 * C);
-    UP(b, y2_h + y2_off_h[0] * C, sizeof(double) * r2 * C);
-    std::vector<int64_t> o1(y1_off_h, y1_off_h + n + 1), o2(y2_off_h, y2_off_h + n + 1);
-    for (auto& o : o1) o -= y1_off_h[0];
-    for (auto& o : o2) o -= y2_off_h[0];
-    UP(ao, o1.data(), sizeof(int64_t) * (n + 1));
-    UP(bo, o2.data(), sizeof(int64_t) * (n + 1));
-    if (env_h) { UP(ev, env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n]); UP(eo, env_off_h, sizeof(int64_t) * (n + 1)); }
-    UP(g0, nullptr, sizeof(double) * n);
-    if (dense_out_h) { UP(dn, nullptr, sizeof(double) * (size_t)dense_off_h[n]); UP(dof, dense_off_h, sizeof(int64_t) * (n + 1)); }
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_pair_gamma_workspace_bytes(n, mc, m1, m2);
-    UP(ws, nullptr, wsb);
-    int rc = po_pair_gamma_batch((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p, (const int64_t*)bo.p,
-                                 env_h ? (const int32_t*)ev.p : nullptr, env_h ? (const int64_t*)eo.p : nullptr, n, C, flavor,
-                                 mc, (double*)g0.p, dense_out_h ? (double*)dn.p : nullptr,
-                                 dense_out_h ? (const int64_t*)dof.p : nullptr, (int32_t*)st.p, ws.p, wsb, nullptr);
+    const PoRagged r1(y1_off_h, n), r2(y2_off_h, n);
+    const int64_t mc = gamma_max_cells(r1, r2, env_h, env_off_h, n);
+    PoRows a, b;
+    PoDev ev, eo, g0, dn, dof, st, ws;   // (ev, eo and dn, dof stay NULL without an envelope / a dense output)
+    PO_HIPCHK(a.up(y1_h, r1, sizeof(double) * C));
+    PO_HIPCHK(b.up(y2_h, r2, sizeof(double) * C));
+    if (env_h) { PO_HIPCHK(ev.up(env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n])); PO_HIPCHK(eo.up(env_off_h, sizeof(int64_t) * (n + 1))); }
+    PO_HIPCHK(g0.up(nullptr, sizeof(double) * n));
+    if (dense_out_h) { PO_HIPCHK(dn.up(nullptr, sizeof(double) * (size_t)dense_off_h[n])); PO_HIPCHK(dof.up(dense_off_h, sizeof(int64_t) * (n + 1))); }
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_pair_gamma_workspace_bytes(n, mc, r1.max, r2.max);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_pair_gamma_batch(a.data, a.off, b.data, b.off, ev, eo, n, C, flavor, mc, g0, dn, dof, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(gamma00_h, g0, sizeof(double) * n);
-    if (dense_out_h) DOWN(dense_out_h, dn, sizeof(double) * (size_t)dense_off_h[n]);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(g0.down(gamma00_h, sizeof(double) * n));
+    if (dense_out_h) PO_HIPCHK(dn.down(dense_out_h, sizeof(double) * (size_t)dense_off_h[n]));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 
@@ -601,62 +542,38 @@ int po_pair_prefix_search_env_batch_h(const double* y1_h, const int64_t* y1_off_
     if (n <= 0) return PO_OK;
     uint32_t ap = 0;
     const int A = pack_alphabet(alphabet, &ap);
-    if (A < 0) { g_err = "po_pair_prefix_search_env_batch_h: alphabet must have 1..4 symbols"; return PO_E_ARG; }
-    const int64_t r1 = y1_off_h[n] - y1_off_h[0], r2 = y2_off_h[n] - y2_off_h[0];
-    int64_t m1 = 0, m2 = 0, mc = 0;
-    std::vector<int64_t> dof((size_t)n + 1, 0);
-    for (int i = 0; i < n; ++i) {
-        const int64_t U = y1_off_h[i + 1] - y1_off_h[i], V = y2_off_h[i + 1] - y2_off_h[i];
-        m1 = std::max(m1, U); m2 = std::max(m2, V);
-        int64_t cells = (U + 1) * (V + 1);
-        if (env_h) {   // stored cells of the envelope DP: sum over rows of end - start + 1
-            cells = 0;
-            for (int64_t u = 0; u <= U; ++u) { const int64_t w = (int64_t)env_h[2 * (env_off_h[i] + u) + 1] - env_h[2 * (env_off_h[i] + u)] + 1; cells += w > 0 ? w : 0; }
-        }
-        mc = std::max(mc, cells);
-        dof[i + 1] = dof[i] + (U + 1) * (V + 1);
-    }
-    DevBuf a, ao, b, bo, g0, dn, dfo, st, st2, ws, so, sq, sl, lp, ws2, ev, eo;
-    if (env_h) { UP(ev, env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n]); UP(eo, env_off_h, sizeof(int64_t) * (n + 1)); }
-    UP(a, y1_h + y1_off_h[0] * C, sizeof(double) * r1 * C);
-    UP(b, y2_h + y2_off_h[0] * C, sizeof(double) * r2 * C);
-    std::vector<int64_t> o1(y1_off_h, y1_off_h + n + 1), o2(y2_off_h, y2_off_h + n + 1);
-    for (auto& o : o1) o -= y1_off_h[0];
-    for (auto& o : o2) o -= y2_off_h[0];
-    UP(ao, o1.data(), sizeof(int64_t) * (n + 1));
-    UP(bo, o2.data(), sizeof(int64_t) * (n + 1));
-    UP(g0, nullptr, sizeof(double) * n);
-    UP(dn, nullptr, sizeof(double) * (size_t)dof[n]);
-    UP(dfo, dof.data(), sizeof(int64_t) * (n + 1));
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_pair_gamma_workspace_bytes(n, mc, m1, m2);
-    UP(ws, nullptr, wsb);
+    if (A < 0) return po_fail(PO_E_ARG, "po_pair_prefix_search_env_batch_h: alphabet must have 1..4 symbols");
+    const PoRagged r1(y1_off_h, n), r2(y2_off_h, n);
+    const int64_t mc = gamma_max_cells(r1, r2, env_h, env_off_h, n);
+    std::vector<int64_t> dof((size_t)n + 1, 0);   // gamma goes to the search as full (U + 1) x (V + 1) matrices
+    for (int i = 0; i < n; ++i) dof[i + 1] = dof[i] + (r1.off[i + 1] - r1.off[i] + 1) * (r2.off[i + 1] - r2.off[i] + 1);
+    PoRows a, b;
+    PoSeqOut out;
+    PoDev ev, eo, g0, dn, dfo, st, ws, ws2;
+    if (env_h) { PO_HIPCHK(ev.up(env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n])); PO_HIPCHK(eo.up(env_off_h, sizeof(int64_t) * (n + 1))); }
+    PO_HIPCHK(a.up(y1_h, r1, sizeof(double) * C));
+    PO_HIPCHK(b.up(y2_h, r2, sizeof(double) * C));
+    PO_HIPCHK(g0.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(dn.up(nullptr, sizeof(double) * (size_t)dof[n]));
+    PO_HIPCHK(dfo.up(dof.data(), sizeof(int64_t) * (n + 1)));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_pair_gamma_workspace_bytes(n, mc, r1.max, r2.max);
+    PO_HIPCHK(ws.up(nullptr, wsb));
     // gamma: dense (the Python paths' flavour), or the envelope DP of Gamma.h (its own arithmetic: logaddexp, -inf)
     // written out as a full matrix with -inf outside the stored ranges
-    int rc = po_pair_gamma_batch((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p, (const int64_t*)bo.p,
-                                 env_h ? (const int32_t*)ev.p : nullptr, env_h ? (const int64_t*)eo.p : nullptr, n, C,
-                                 env_h ? 0 : flavor, mc, (double*)g0.p, (double*)dn.p, (const int64_t*)dfo.p,
-                                 (int32_t*)st.p, ws.p, wsb, nullptr);
+    int rc = po_pair_gamma_batch(a.data, a.off, b.data, b.off, ev, eo, n, C, env_h ? 0 : flavor, mc, g0, dn, dfo, st, ws, wsb,
+                                 nullptr);
     if (rc != PO_OK) return rc;
-    const int64_t seqb = seq_off_h[n];
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(lp, nullptr, sizeof(double) * n);
-    UP(st2, nullptr, sizeof(int32_t) * n);
-    const int64_t mr = std::max(m1, m2);
+    PO_HIPCHK(out.up(seq_off_h, n, true));
+    const int64_t mr = std::max(r1.max, r2.max);
     const size_t wsb2 = po_pair_prefix_ws_bytes(n, mr);
-    UP(ws2, nullptr, wsb2);
-    rc = po_launch_pair_prefix_search((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p, (const int64_t*)bo.p,
-                                      (const double*)dn.p, (const int64_t*)dfo.p, n, C, A, ap, flavor, mr, (char*)sq.p,
-                                      (const int64_t*)so.p, (int32_t*)sl.p, (double*)lp.p, (int32_t*)st2.p, ws2.p, wsb2, nullptr);
-    if (rc != PO_OK) { g_err = "po_pair_prefix_search_env_batch_h: box too long for the LDS rows, or bad C"; return rc; }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(logp_h, lp, sizeof(double) * n);
-    DOWN(status_h, st2, sizeof(int32_t) * n);
+    PO_HIPCHK(ws2.up(nullptr, wsb2));
+    rc = po_launch_pair_prefix_search(a.data, a.off, b.data, b.off, dn, dfo, n, C, A, ap, flavor, mr, out.seq, out.off, out.len,
+                                      out.logp, out.status, ws2, wsb2, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_prefix_search_env_batch_h: box too long for the LDS rows, or bad C");
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h, logp_h));
     return PO_OK;
 }
 
@@ -671,21 +588,18 @@ int po_forward_vec_batch_h(const double* y_h, const int64_t* y_off_h, int n, int
                            const double* previous_h, double* out_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    if (!y_h || !y_off_h || !out_h) { g_err = "po_forward_vec_batch_h: null argument"; return PO_E_ARG; }
-    const int64_t rows = y_off_h[n] - y_off_h[0];
-    DevBuf y, yo, pv, out;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    if (previous_h) UP(pv, previous_h, sizeof(double) * rows);
-    UP(out, nullptr, sizeof(double) * rows);
-    int rc = po_launch_forward_vec((const double*)y.p, (const int64_t*)yo.p, n, C, s, i, flavor,
-                                   previous_h ? (const double*)pv.p : nullptr, (double*)out.p, nullptr);
-    if (rc != PO_OK) { g_err = "po_forward_vec_batch_h: bad symbol / label length, or previous row missing"; return rc; }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(out_h, out, sizeof(double) * rows);
+    if (!y_h || !y_off_h || !out_h) return po_fail(PO_E_ARG, "po_forward_vec_batch_h: null argument");
+    const PoRagged r(y_off_h, n);
+    PoRows y;
+    PoDev pv, out;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    if (previous_h) PO_HIPCHK(pv.up(previous_h, sizeof(double) * r.total));   // (the n items' rows from previous_h[0] on)
+    PO_HIPCHK(out.up(nullptr, sizeof(double) * r.total));
+    int rc = po_launch_forward_vec(y.data, y.off, n, C, s, i, flavor, pv, out, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_forward_vec_batch_h: bad symbol / label length, or previous row missing");
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(out_h, sizeof(double) * r.total));
     return PO_OK;
 }
 
@@ -699,26 +613,24 @@ int po_align_scores_batch_h(const char* seqs_h, const int64_t* seq_off_h, int n,
         m1 = std::max<int64_t>(m1, seq_off_h[2 * i + 1] - seq_off_h[2 * i]);
         m2 = std::max<int64_t>(m2, seq_off_h[2 * i + 2] - seq_off_h[2 * i + 1]);
     }
-    DevBuf sq, so, a1, a2, ao, nc, st, ws;
-    UP(sq, seqs_h, (size_t)seq_off_h[2 * n]);
-    UP(so, seq_off_h, sizeof(int64_t) * (2 * n + 1));
-    UP(a1, nullptr, (size_t)aln_off_h[n]);
-    UP(a2, nullptr, (size_t)aln_off_h[n]);
-    UP(ao, aln_off_h, sizeof(int64_t) * (n + 1));
-    UP(nc, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
+    PoDev sq, so, a1, a2, ao, nc, st, ws;
+    PO_HIPCHK(sq.up(seqs_h, (size_t)seq_off_h[2 * n]));
+    PO_HIPCHK(so.up(seq_off_h, sizeof(int64_t) * (2 * n + 1)));
+    PO_HIPCHK(a1.up(nullptr, (size_t)aln_off_h[n]));
+    PO_HIPCHK(a2.up(nullptr, (size_t)aln_off_h[n]));
+    PO_HIPCHK(ao.up(aln_off_h, sizeof(int64_t) * (n + 1)));
+    PO_HIPCHK(nc.up(nullptr, sizeof(int32_t) * n));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
     const size_t wsb = po_align_workspace_bytes(n, m1, m2, band_width);
-    UP(ws, nullptr, wsb);
-    int rc = po_launch_align_scores((const char*)sq.p, (const int64_t*)so.p, n, band_width, match, mismatch, gap_cost, m1, m2,
-                                    (char*)a1.p, (char*)a2.p, (const int64_t*)ao.p, (int32_t*)nc.p, (int32_t*)st.p, ws.p, wsb,
-                                    nullptr);
-    if (rc != PO_OK) { g_err = "po_align_scores_batch_h: workspace too small"; return rc; }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(aln1_h, a1, (size_t)aln_off_h[n]);
-    DOWN(aln2_h, a2, (size_t)aln_off_h[n]);
-    DOWN(ncol_h, nc, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_launch_align_scores(sq, so, n, band_width, match, mismatch, gap_cost, m1, m2, a1, a2, ao, nc, st, ws, wsb, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_align_scores_batch_h: workspace too small");
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(a1.down(aln1_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(a2.down(aln2_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(nc.down(ncol_h, sizeof(int32_t) * n));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 
@@ -732,18 +644,17 @@ int po_nw_matrix_batch_h(const char* seqs_h, const int64_t* seq_off_h, int n, in
                          const int64_t* dp_off_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    DevBuf sq, so, dp, dpo, st;
-    UP(sq, seqs_h, (size_t)seq_off_h[2 * n]);
-    UP(so, seq_off_h, sizeof(int64_t) * (2 * n + 1));
-    UP(dp, nullptr, sizeof(int32_t) * (size_t)dp_off_h[n]);
-    UP(dpo, dp_off_h, sizeof(int64_t) * (n + 1));
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const int rc = po_launch_nw_matrix((const char*)sq.p, (const int64_t*)so.p, n, match, mismatch, gap_cost, (int32_t*)dp.p,
-                                       (const int64_t*)dpo.p, (int32_t*)st.p, nullptr);
+    PoDev sq, so, dp, dpo, st;
+    PO_HIPCHK(sq.up(seqs_h, (size_t)seq_off_h[2 * n]));
+    PO_HIPCHK(so.up(seq_off_h, sizeof(int64_t) * (2 * n + 1)));
+    PO_HIPCHK(dp.up(nullptr, sizeof(int32_t) * (size_t)dp_off_h[n]));
+    PO_HIPCHK(dpo.up(dp_off_h, sizeof(int64_t) * (n + 1)));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const int rc = po_launch_nw_matrix(sq, so, n, match, mismatch, gap_cost, dp, dpo, st, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(dp_h, dp, sizeof(int32_t) * (size_t)dp_off_h[n]);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(dp.down(dp_h, sizeof(int32_t) * (size_t)dp_off_h[n]));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 
@@ -760,30 +671,28 @@ int po_envelope_batch_h(const char* aln1_h, const char* aln2_h, const int64_t* a
     if (n <= 0) return PO_OK;
     int64_t mc = 0;
     for (int i = 0; i < n; ++i) mc = std::max<int64_t>(mc, ncol_h[i]);
-    DevBuf a1, a2, ao, nc, m1, m1o, m2, m2o, u, v, ev, eo, st, ws;
-    UP(a1, aln1_h, (size_t)aln_off_h[n]);
-    UP(a2, aln2_h, (size_t)aln_off_h[n]);
-    UP(ao, aln_off_h, sizeof(int64_t) * (n + 1));
-    UP(nc, ncol_h, sizeof(int32_t) * n);
-    UP(m1, map1_h, sizeof(int32_t) * (size_t)map1_off_h[n]);
-    UP(m1o, map1_off_h, sizeof(int64_t) * (n + 1));
-    UP(m2, map2_h, sizeof(int32_t) * (size_t)map2_off_h[n]);
-    UP(m2o, map2_off_h, sizeof(int64_t) * (n + 1));
-    UP(u, U_h, sizeof(int32_t) * n);
-    UP(v, V_h, sizeof(int32_t) * n);
-    UP(ev, nullptr, sizeof(int32_t) * 2 * (size_t)env_off_h[n]);
-    UP(eo, env_off_h, sizeof(int64_t) * (n + 1));
-    UP(st, nullptr, sizeof(int32_t) * n);
+    const size_t tab = sizeof(int64_t) * (n + 1), per = sizeof(int32_t) * n;
+    PoDev a1, a2, ao, nc, m1, m1o, m2, m2o, u, v, ev, eo, st, ws;
+    PO_HIPCHK(a1.up(aln1_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(a2.up(aln2_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(ao.up(aln_off_h, tab));
+    PO_HIPCHK(nc.up(ncol_h, per));
+    PO_HIPCHK(m1.up(map1_h, sizeof(int32_t) * (size_t)map1_off_h[n]));
+    PO_HIPCHK(m1o.up(map1_off_h, tab));
+    PO_HIPCHK(m2.up(map2_h, sizeof(int32_t) * (size_t)map2_off_h[n]));
+    PO_HIPCHK(m2o.up(map2_off_h, tab));
+    PO_HIPCHK(u.up(U_h, per));
+    PO_HIPCHK(v.up(V_h, per));
+    PO_HIPCHK(ev.up(nullptr, sizeof(int32_t) * 2 * (size_t)env_off_h[n]));
+    PO_HIPCHK(eo.up(env_off_h, tab));
+    PO_HIPCHK(st.up(nullptr, per));
     const size_t wsb = po_envelope_workspace_bytes(n, mc);
-    UP(ws, nullptr, wsb);
-    int rc = po_envelope_batch((const char*)a1.p, (const char*)a2.p, (const int64_t*)ao.p, (const int32_t*)nc.p, n,
-                               (const int32_t*)m1.p, (const int64_t*)m1o.p, (const int32_t*)m2.p, (const int64_t*)m2o.p,
-                               (const int32_t*)u.p, (const int32_t*)v.p, padding, (int32_t*)ev.p, (const int64_t*)eo.p,
-                               (int32_t*)st.p, ws.p, wsb, nullptr);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_envelope_batch(a1, a2, ao, nc, n, m1, m1o, m2, m2o, u, v, padding, ev, eo, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(env_h, ev, sizeof(int32_t) * 2 * (size_t)env_off_h[n]);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(ev.down(env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n]));
+    PO_HIPCHK(st.down(status_h, per));
     return PO_OK;
 }
 
@@ -791,30 +700,18 @@ int po_prefix_search_batch_h(const double* y_h, const int64_t* y_off_h, int n, i
                              const int64_t* seq_off_h, int32_t* seq_len_h, double* logp_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = y_off_h[n] - y_off_h[0];
-    const int64_t seqb = seq_off_h[n];
-    int64_t mx = 0;
-    for (int i = 0; i < n; ++i) mx = std::max<int64_t>(mx, y_off_h[i + 1] - y_off_h[i]);
-    DevBuf y, yo, so, sq, sl, lp, st, ws;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(lp, nullptr, sizeof(double) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_prefix_search_workspace_bytes(n, mx);
-    UP(ws, nullptr, wsb);
-    int rc = po_prefix_search_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, (char*)sq.p,
-                                    (const int64_t*)so.p, (int32_t*)sl.p, (double*)lp.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    const PoRagged r(y_off_h, n);
+    PoRows y;
+    PoSeqOut out;
+    PoDev ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(out.up(seq_off_h, n, true));
+    const size_t wsb = po_prefix_search_workspace_bytes(n, r.max);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_prefix_search_batch(y.data, y.off, n, C, alphabet, out.seq, out.off, out.len, out.logp, out.status, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(logp_h, lp, sizeof(double) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h, logp_h));
     return PO_OK;
 }
 
@@ -822,27 +719,20 @@ int po_forward_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, 
                        const char* labels_h, const int64_t* label_off_h, double* logp_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = y_off_h[n] - y_off_h[0], nl = label_off_h[n] - label_off_h[0];
-    int64_t mx = 0;
-    for (int i = 0; i < n; ++i) mx = std::max<int64_t>(mx, y_off_h[i + 1] - y_off_h[i]);
-    DevBuf y, yo, lb, lo, out, st, ws;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1), lof(label_off_h, label_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    for (auto& o : lof) o -= label_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    UP(lb, labels_h + label_off_h[0], (size_t)nl);
-    UP(lo, lof.data(), sizeof(int64_t) * (n + 1));
-    UP(out, nullptr, sizeof(double) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_forward_workspace_bytes(n, mx, model);
-    UP(ws, nullptr, wsb);
-    int rc = po_forward_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, model, (const char*)lb.p,
-                              (const int64_t*)lo.p, (double*)out.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    const PoRagged r(y_off_h, n), l(label_off_h, n);
+    PoRows y, lb;
+    PoDev out, st, ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(lb.up(labels_h, l, 1));
+    PO_HIPCHK(out.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_forward_workspace_bytes(n, r.max, model);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_forward_batch(y.data, y.off, n, C, alphabet, model, lb.data, lb.off, out, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(logp_h, out, sizeof(double) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(logp_h, sizeof(double) * n));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 
@@ -851,31 +741,20 @@ int po_viterbi_acceptor_batch_h(const double* y_h, const int64_t* y_off_h, int n
                                 int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t rows = y_off_h[n] - y_off_h[0], nl = label_off_h[n] - label_off_h[0];
-    int64_t mx = 0, ml = 0;
-    for (int i = 0; i < n; ++i) {
-        mx = std::max<int64_t>(mx, y_off_h[i + 1] - y_off_h[i]);
-        ml = std::max<int64_t>(ml, label_off_h[i + 1] - label_off_h[i]);
-    }
-    DevBuf y, yo, lb, lo, pt, st, ws;
-    UP(y, y_h + y_off_h[0] * C, sizeof(double) * rows * C);
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1), lof(label_off_h, label_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    for (auto& o : lof) o -= label_off_h[0];
-    UP(yo, off.data(), sizeof(int64_t) * (n + 1));
-    UP(lb, labels_h + label_off_h[0], (size_t)nl);
-    UP(lo, lof.data(), sizeof(int64_t) * (n + 1));
-    UP(pt, nullptr, sizeof(int32_t) * rows);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    const size_t wsb = po_viterbi_acceptor_workspace_bytes(n, mx, ml);
-    UP(ws, nullptr, wsb);
-    int rc = po_viterbi_acceptor_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, band_size,
-                                       (const char*)lb.p, (const int64_t*)lo.p, (int32_t*)pt.p, (int32_t*)st.p, ws.p,
-                                       wsb, nullptr);
+    const PoRagged r(y_off_h, n), l(label_off_h, n);
+    PoRows y, lb;
+    PoDev pt, st, ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(lb.up(labels_h, l, 1));
+    PO_HIPCHK(pt.up(nullptr, sizeof(int32_t) * r.total));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_viterbi_acceptor_workspace_bytes(n, r.max, l.max);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_viterbi_acceptor_batch(y.data, y.off, n, C, alphabet, band_size, lb.data, lb.off, pt, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(path_h, pt, sizeof(int32_t) * rows);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(pt.down(path_h, sizeof(int32_t) * r.total));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 
@@ -883,7 +762,7 @@ int po_viterbi_acceptor_cy_batch_h(const double* y_h, const int64_t* y_off_h, in
                                    int band_size, const char* labels_h, const int64_t* label_off_h, int32_t* path_h,
                                    int32_t* status_h) {
     g_err.clear();
-    if (band_size < 0) { g_err = "po_viterbi_acceptor_cy_batch_h: negative band"; return PO_E_ARG; }
+    if (band_size < 0) return po_fail(PO_E_ARG, "po_viterbi_acceptor_cy_batch_h: negative band");
     return po_viterbi_acceptor_batch_h(y_h, y_off_h, n, C, alphabet, -(band_size + 1), labels_h, label_off_h, path_h, status_h);
 }
 
@@ -893,38 +772,72 @@ int po_beam2d_batch_h(const double* y1_h, const int64_t* y1_off_h, const double*
                       const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h) {
     g_err.clear();
     if (n <= 0) return PO_OK;
-    const int64_t r1 = y1_off_h[n] - y1_off_h[0], r2 = y2_off_h[n] - y2_off_h[0];
-    const int64_t seqb = seq_off_h[n];
-    int64_t m1 = 0, m2 = 0;
-    for (int i = 0; i < n; ++i) {
-        m1 = std::max<int64_t>(m1, y1_off_h[i + 1] - y1_off_h[i]);
-        m2 = std::max<int64_t>(m2, y2_off_h[i + 1] - y2_off_h[i]);
-    }
-    DevBuf a, ao, b, bo, ev, so, sq, sl, st, ws;
-    UP(a, y1_h + y1_off_h[0] * C, sizeof(double) * r1 * C);
-    UP(b, y2_h + y2_off_h[0] * C, sizeof(double) * r2 * C);
-    std::vector<int64_t> o1(y1_off_h, y1_off_h + n + 1), o2(y2_off_h, y2_off_h + n + 1);
-    for (auto& o : o1) o -= y1_off_h[0];
-    for (auto& o : o2) o -= y2_off_h[0];
-    UP(ao, o1.data(), sizeof(int64_t) * (n + 1));
-    UP(bo, o2.data(), sizeof(int64_t) * (n + 1));
-    if (env_h) UP(ev, env_h + 2 * y1_off_h[0], sizeof(int32_t) * 2 * r1);
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
+    const PoRagged r1(y1_off_h, n), r2(y2_off_h, n);
+    PoRows a, b;
+    PoSeqOut out;
+    PoDev ev, ws;
+    PO_HIPCHK(a.up(y1_h, r1, sizeof(double) * C));
+    PO_HIPCHK(b.up(y2_h, r2, sizeof(double) * C));
+    if (env_h) PO_HIPCHK(ev.up(env_h + 2 * r1.base, sizeof(int32_t) * 2 * r1.total));   // one [start, end) per row of read 1
+    PO_HIPCHK(out.up(seq_off_h, n));
     // (without an envelope everything but "row" runs the grid method, as in the reference's dispatcher)
-    const size_t wsb = po_beam2d_workspace_bytes(n, r1, r2, m1, m2, C, W, model,
+    const size_t wsb = po_beam2d_workspace_bytes(n, r1.total, r2.total, r1.max, r2.max, C, W, model,
                                                  (!env_h && method != PO_METHOD_ROW) ? PO_METHOD_GRID_NOENV : method);
-    UP(ws, nullptr, wsb);
-    int rc = po_beam2d_batch((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p, (const int64_t*)bo.p,
-                             env_h ? (const int32_t*)ev.p : nullptr, n, C, alphabet, W, model, method, (char*)sq.p,
-                             (const int64_t*)so.p, (int32_t*)sl.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc = po_beam2d_batch(a.data, a.off, b.data, b.off, ev, n, C, alphabet, W, model, method, out.seq, out.off, out.len,
+                             out.status, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
+    return PO_OK;
+}
+
+// The two pair-decode twins.  from_1d: the caller's 1-D basecalls, lengths and frame maps go up and po_launch_pair_decode_from_1d
+// runs; otherwise the basecalls are outputs of po_pair_decode_batch, allocated here and brought down with the rest.
+static int pair_decode_h(bool from_1d, const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n,
+                  int C, const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
+                  const int32_t* map1_h, const int32_t* map2_h, double* identity_h, int32_t* env_out_h, char* seq_h,
+                  const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h) {
+    g_err.clear();
+    if (n <= 0) return PO_OK;
+    const PoRagged r1(y1_off_h, n), r2(y2_off_h, n);
+    const size_t s1b = (size_t)seq1d_off_h[2 * n], per = sizeof(int32_t) * n;
+    PoRows a, b;
+    PoSeqOut out;
+    PoDev s1o, s1, l1, l2, mp1, mp2, idn, ev, ws;
+    PO_HIPCHK(a.up(y1_h, r1, sizeof(double) * C));
+    PO_HIPCHK(b.up(y2_h, r2, sizeof(double) * C));
+    PO_HIPCHK(out.up(seq_off_h, n));
+    PO_HIPCHK(s1o.up(seq1d_off_h, sizeof(int64_t) * (2 * n + 1)));
+    PO_HIPCHK(s1.up(from_1d ? seq1d_h : nullptr, s1b));
+    PO_HIPCHK(l1.up(from_1d ? len1_h : nullptr, per));
+    PO_HIPCHK(l2.up(from_1d ? len2_h : nullptr, per));
+    if (from_1d) PO_HIPCHK(mp1.up(map1_h + r1.base, sizeof(int32_t) * r1.total));   // one frame per base, at the read's rows
+    if (from_1d) PO_HIPCHK(mp2.up(map2_h + r2.base, sizeof(int32_t) * r2.total));
+    PO_HIPCHK(idn.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(ev.up(nullptr, sizeof(int32_t) * 2 * r1.total));
+    const size_t wsb = po_pair_decode_workspace_bytes(n, r1.total, r2.total, r1.max, r2.max, C, opt);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    int rc;
+    if (from_1d) {
+        rc = po_launch_pair_decode_from_1d(a.data, a.off, b.data, b.off, n, C, opt, r1.total, r2.total, r1.max, r2.max, mp1, mp2,
+                                           s1, s1o, l1, l2, idn, ev, out.seq, out.off, out.len, out.status, ws, wsb, nullptr);
+        if (rc != PO_OK) return po_fail(rc, "po_pair_decode_from_1d_batch_h: launch refused");
+        PO_HIPCHK(hipGetLastError());
+    } else {
+        rc = po_pair_decode_batch(a.data, a.off, b.data, b.off, n, C, opt, s1, s1o, l1, l2, idn, ev, out.seq, out.off, out.len,
+                                  out.status, ws, wsb, nullptr);
+        if (rc != PO_OK) return rc;
+    }
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
+    if (!from_1d) {
+        PO_HIPCHK(s1.down(seq1d_h, s1b));
+        PO_HIPCHK(l1.down(len1_h, per));
+        PO_HIPCHK(l2.down(len2_h, per));
+    }
+    PO_HIPCHK(idn.down(identity_h, sizeof(double) * n));
+    PO_HIPCHK(ev.down(env_out_h, sizeof(int32_t) * 2 * r1.total));
     return PO_OK;
 }
 
@@ -933,51 +846,9 @@ int po_pair_decode_from_1d_batch_h(const double* y1_h, const int64_t* y1_off_h, 
                                    const int64_t* seq1d_off_h, const int32_t* len1_h, const int32_t* len2_h,
                                    const int32_t* map1_h, const int32_t* map2_h, double* identity_h, int32_t* env_out_h,
                                    char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h) {
-    g_err.clear();
-    if (n <= 0) return PO_OK;
-    const int64_t r1 = y1_off_h[n] - y1_off_h[0], r2 = y2_off_h[n] - y2_off_h[0];
-    const int64_t seqb = seq_off_h[n], s1b = seq1d_off_h[2 * n];
-    int64_t m1 = 0, m2 = 0;
-    for (int i = 0; i < n; ++i) {
-        m1 = std::max<int64_t>(m1, y1_off_h[i + 1] - y1_off_h[i]);
-        m2 = std::max<int64_t>(m2, y2_off_h[i + 1] - y2_off_h[i]);
-    }
-    DevBuf a, ao, b, bo, so, sq, sl, st, s1o, s1, l1, l2, idn, ev, mp1, mp2, ws;
-    UP(a, y1_h + y1_off_h[0] * C, sizeof(double) * r1 * C);
-    UP(b, y2_h + y2_off_h[0] * C, sizeof(double) * r2 * C);
-    std::vector<int64_t> o1(y1_off_h, y1_off_h + n + 1), o2(y2_off_h, y2_off_h + n + 1);
-    for (auto& o : o1) o -= y1_off_h[0];
-    for (auto& o : o2) o -= y2_off_h[0];
-    UP(ao, o1.data(), sizeof(int64_t) * (n + 1));
-    UP(bo, o2.data(), sizeof(int64_t) * (n + 1));
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    UP(s1o, seq1d_off_h, sizeof(int64_t) * (2 * n + 1));
-    UP(s1, seq1d_h, (size_t)s1b);
-    UP(l1, len1_h, sizeof(int32_t) * n);
-    UP(l2, len2_h, sizeof(int32_t) * n);
-    UP(mp1, map1_h + y1_off_h[0], sizeof(int32_t) * r1);
-    UP(mp2, map2_h + y2_off_h[0], sizeof(int32_t) * r2);
-    UP(idn, nullptr, sizeof(double) * n);
-    UP(ev, nullptr, sizeof(int32_t) * 2 * r1);
-    const size_t wsb = po_pair_decode_workspace_bytes(n, r1, r2, m1, m2, C, opt);
-    UP(ws, nullptr, wsb);
-    int rc = po_launch_pair_decode_from_1d((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p, (const int64_t*)bo.p, n,
-                                           C, opt, r1, r2, m1, m2, (const int32_t*)mp1.p, (const int32_t*)mp2.p, (char*)s1.p,
-                                           (const int64_t*)s1o.p, (int32_t*)l1.p, (int32_t*)l2.p, (double*)idn.p,
-                                           (int32_t*)ev.p, (char*)sq.p, (const int64_t*)so.p, (int32_t*)sl.p, (int32_t*)st.p,
-                                           ws.p, wsb, nullptr);
-    if (rc != PO_OK) { g_err = "po_pair_decode_from_1d_batch_h: launch refused"; return rc; }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
-    DOWN(identity_h, idn, sizeof(double) * n);
-    DOWN(env_out_h, ev, sizeof(int32_t) * 2 * r1);
-    return PO_OK;
+    return pair_decode_h(true, y1_h, y1_off_h, y2_h, y2_off_h, n, C, opt, const_cast<char*>(seq1d_h), seq1d_off_h,
+                         const_cast<int32_t*>(len1_h), const_cast<int32_t*>(len2_h), map1_h, map2_h, identity_h, env_out_h, seq_h,
+                         seq_off_h, seq_len_h, status_h);
 }
 
 int po_pair_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h,
@@ -985,50 +856,8 @@ int po_pair_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const do
                            const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h,
                            int32_t* env_out_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h,
                            int32_t* status_h) {
-    g_err.clear();
-    if (n <= 0) return PO_OK;
-    const int64_t r1 = y1_off_h[n] - y1_off_h[0], r2 = y2_off_h[n] - y2_off_h[0];
-    const int64_t seqb = seq_off_h[n], s1b = seq1d_off_h[2 * n];
-    int64_t m1 = 0, m2 = 0;
-    for (int i = 0; i < n; ++i) {
-        m1 = std::max<int64_t>(m1, y1_off_h[i + 1] - y1_off_h[i]);
-        m2 = std::max<int64_t>(m2, y2_off_h[i + 1] - y2_off_h[i]);
-    }
-    DevBuf a, ao, b, bo, so, sq, sl, st, s1o, s1, l1, l2, idn, ev, ws;
-    UP(a, y1_h + y1_off_h[0] * C, sizeof(double) * r1 * C);
-    UP(b, y2_h + y2_off_h[0] * C, sizeof(double) * r2 * C);
-    std::vector<int64_t> o1(y1_off_h, y1_off_h + n + 1), o2(y2_off_h, y2_off_h + n + 1);
-    for (auto& o : o1) o -= y1_off_h[0];
-    for (auto& o : o2) o -= y2_off_h[0];
-    UP(ao, o1.data(), sizeof(int64_t) * (n + 1));
-    UP(bo, o2.data(), sizeof(int64_t) * (n + 1));
-    UP(so, seq_off_h, sizeof(int64_t) * (n + 1));
-    UP(sq, nullptr, (size_t)seqb);
-    UP(sl, nullptr, sizeof(int32_t) * n);
-    UP(st, nullptr, sizeof(int32_t) * n);
-    UP(s1o, seq1d_off_h, sizeof(int64_t) * (2 * n + 1));
-    UP(s1, nullptr, (size_t)s1b);
-    UP(l1, nullptr, sizeof(int32_t) * n);
-    UP(l2, nullptr, sizeof(int32_t) * n);
-    UP(idn, nullptr, sizeof(double) * n);
-    UP(ev, nullptr, sizeof(int32_t) * 2 * r1);
-    const size_t wsb = po_pair_decode_workspace_bytes(n, r1, r2, m1, m2, C, opt);
-    UP(ws, nullptr, wsb);
-    int rc = po_pair_decode_batch((const double*)a.p, (const int64_t*)ao.p, (const double*)b.p,
-                                  (const int64_t*)bo.p, n, C, opt, (char*)s1.p, (const int64_t*)s1o.p,
-                                  (int32_t*)l1.p, (int32_t*)l2.p, (double*)idn.p, (int32_t*)ev.p, (char*)sq.p,
-                                  (const int64_t*)so.p, (int32_t*)sl.p, (int32_t*)st.p, ws.p, wsb, nullptr);
-    if (rc != PO_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
-    DOWN(seq_h, sq, (size_t)seqb);
-    DOWN(seq_len_h, sl, sizeof(int32_t) * n);
-    DOWN(status_h, st, sizeof(int32_t) * n);
-    DOWN(seq1d_h, s1, (size_t)s1b);
-    DOWN(len1_h, l1, sizeof(int32_t) * n);
-    DOWN(len2_h, l2, sizeof(int32_t) * n);
-    DOWN(identity_h, idn, sizeof(double) * n);
-    DOWN(env_out_h, ev, sizeof(int32_t) * 2 * r1);
-    return PO_OK;
+    return pair_decode_h(false, y1_h, y1_off_h, y2_h, y2_off_h, n, C, opt, seq1d_h, seq1d_off_h, len1_h, len2_h, nullptr, nullptr,
+                         identity_h, env_out_h, seq_h, seq_off_h, seq_len_h, status_h);
 }
 
 // -------------------------------------------------------------------------------- events / profile
@@ -1038,13 +867,13 @@ void* po_event_create(void) {
 }
 int po_event_record(void* ev, void* stream) {
     g_err.clear();
-    HIPCHK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream));
+    PO_HIPCHK(hipEventRecord((hipEvent_t)ev, (hipStream_t)stream));
     return PO_OK;
 }
 int po_event_elapsed_ms(void* start, void* stop, float* ms) {
     g_err.clear();
-    HIPCHK(hipEventSynchronize((hipEvent_t)stop));
-    HIPCHK(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
+    PO_HIPCHK(hipEventSynchronize((hipEvent_t)stop));
+    PO_HIPCHK(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop));
     return PO_OK;
 }
 void po_event_destroy(void* ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }

@@ -30,8 +30,7 @@
 
 #include "../../include/poreover_hip.h"
 
-#include "po_host.h"
-#include "po_internal.h"
+#include "po_hostbuf.h"
 
 namespace {
 
@@ -400,18 +399,6 @@ __global__ __launch_bounds__(64) void label_trace_kernel(LBArgs a) {
 // ------------------------------------------------------------------------------------------------------------ host
 namespace {
 
-thread_local std::string g_lb_err;
-int lb_fail(int code, const std::string& msg) {
-    g_lb_err = msg;
-    po_set_error(g_lb_err.c_str());
-    return code;
-}
-#define LBCHK(x)                                                                                          \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) return lb_fail(PO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 inline bool lb_fast(int band) { return band >= 1 && band <= LB_FAST_MAX_B; }
 inline int lb_fast_ns(int band) { return (2 * band + 2 <= 64) ? 1 : 2; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -432,17 +419,6 @@ inline double lb_general_words_bound(int n, int64_t total_rows, int64_t max_rows
     return u;
 }
 
-struct LBDev {
-    void* p = nullptr;
-    ~LBDev() { if (p) (void)hipFree(p); }
-    hipError_t up(const void* src, size_t bytes) {
-        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 256));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        if (src && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    }
-};
-
 }  // namespace
 
 extern "C" {
@@ -457,14 +433,13 @@ size_t po_label_align_workspace_bytes(int n, int64_t total_rows, int64_t max_row
 int po_label_align_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int band_size,
                          const char* labels, const int64_t* label_off, const int32_t* guide, int32_t* map, double* score,
                          int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-    g_lb_err.clear();
     po_set_error("");
     if (n < 0 || !y_off || !label_off || (n > 0 && (!y || !labels || !map || !score || !status || !ws)))
-        return lb_fail(PO_E_ARG, "po_label_align_batch: null argument");
+        return po_fail(PO_E_ARG, "po_label_align_batch: null argument");
     const char* alpha = alphabet ? alphabet : "ACGT";
     const size_t A = std::strlen(alpha);
-    if (A < 1 || A > 4) return lb_fail(PO_E_ARG, "po_label_align_batch: alphabet must have 1..4 symbols");
-    if (C != (int)A + 1) return lb_fail(PO_E_ARG, "po_label_align_batch: C must be len(alphabet) + 1 (the plain ctc model)");
+    if (A < 1 || A > 4) return po_fail(PO_E_ARG, "po_label_align_batch: alphabet must have 1..4 symbols");
+    if (C != (int)A + 1) return po_fail(PO_E_ARG, "po_label_align_batch: C must be len(alphabet) + 1 (the plain ctc model)");
     if (n == 0) return PO_OK;
     hipStream_t s = (hipStream_t)stream;
     LBArgs a = {};
@@ -476,25 +451,23 @@ int po_label_align_batch(const double* y, const int64_t* y_off, int n, int C, co
         // count is read back (one blocking 8-byte copy per call, as the neighbours' batch_maxima) to refuse a workspace
         // that is too small; the offsets themselves are the caller's to keep non-decreasing, reads below 2^31 frames.
         int64_t rows = 0;
-        LBCHK(hipMemcpyAsync(&rows, y_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-        LBCHK(hipStreamSynchronize(s));
+        PO_HIPCHK(hipMemcpyAsync(&rows, y_off + n, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        PO_HIPCHK(hipStreamSynchronize(s));
         const int ns = lb_fast_ns(band_size);
-        if (ws_bytes < (size_t)rows * ns * 8) return lb_fail(PO_E_CAP, "po_label_align_batch: workspace too small");
+        if (ws_bytes < (size_t)rows * ns * 8) return po_fail(PO_E_CAP, "po_label_align_batch: workspace too small");
         a.bits = (unsigned long long*)ws;
         a.ns_fixed = ns;
         if (ns == 1) hipLaunchKernelGGL(label_forward_kernel<1>, dim3(n), dim3(64), 0, s, a);
         else hipLaunchKernelGGL(label_forward_kernel<2>, dim3(n), dim3(64), 0, s, a);
     } else {
         std::vector<int64_t> h(2 * (size_t)(n + 1));
-        LBCHK(hipMemcpyAsync(h.data(), y_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-        LBCHK(hipMemcpyAsync(h.data() + n + 1, label_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-        LBCHK(hipStreamSynchronize(s));
+        PO_HIPCHK(po_read_tables(y_off, label_off, n, s, h.data()));
         std::vector<LBDesc> desc((size_t)n);
         int64_t words = 0, nvals = 0;
         for (int i = 0; i < n; ++i) {
             const int64_t T = h[i + 1] - h[i], L = h[n + 1 + i + 1] - h[n + 1 + i];
             if (T < 0 || L < 0 || T >= ((int64_t)1 << 31) || L >= ((int64_t)1 << 30))
-                return lb_fail(PO_E_ARG, "po_label_align_batch: offsets must not decrease, reads must be shorter than 2^31 frames");
+                return po_fail(PO_E_ARG, "po_label_align_batch: offsets must not decrease, reads must be shorter than 2^31 frames");
             LBDesc& d = desc[i];
             lb_general_shape(L, band_size, &d.ns, &d.beff, &d.full);
             d.word_off = words;
@@ -505,56 +478,45 @@ int po_label_align_batch(const double* y, const int64_t* y_off, int n, int C, co
             d.pad = 0;
         }
         const size_t b_bits = al256((size_t)words * 8 + 8), b_vals = al256((size_t)nvals * 8), b_desc = al256(sizeof(LBDesc) * (size_t)n);
-        if (ws_bytes < b_bits + b_vals + b_desc) return lb_fail(PO_E_CAP, "po_label_align_batch: workspace too small");
+        if (ws_bytes < b_bits + b_vals + b_desc) return po_fail(PO_E_CAP, "po_label_align_batch: workspace too small");
         a.bits = (unsigned long long*)ws;
         a.vals = (double*)((char*)ws + b_bits);
         a.desc = (const LBDesc*)((char*)ws + b_bits + b_vals);
-        LBCHK(hipMemcpyAsync((void*)a.desc, desc.data(), sizeof(LBDesc) * (size_t)n, hipMemcpyHostToDevice, s));
-        LBCHK(hipStreamSynchronize(s));   // desc lives on this stack
+        PO_HIPCHK(hipMemcpyAsync((void*)a.desc, desc.data(), sizeof(LBDesc) * (size_t)n, hipMemcpyHostToDevice, s));
+        PO_HIPCHK(hipStreamSynchronize(s));   // desc lives on this stack
         a.ns_fixed = 0;
         hipLaunchKernelGGL(label_forward_general_kernel, dim3(n), dim3(64), 0, s, a);
     }
     hipLaunchKernelGGL(label_trace_kernel, dim3(n), dim3(64), 0, s, a);
-    LBCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
 int po_label_align_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, const char* alphabet, int band_size,
                            const char* labels_h, const int64_t* label_off_h, const int32_t* guide_h, int32_t* map_h,
                            double* score_h, int32_t* status_h) {
-    g_lb_err.clear();
     po_set_error("");
-    if (n <= 0) return n < 0 ? lb_fail(PO_E_ARG, "po_label_align_batch_h: negative n") : PO_OK;
-    if (!y_off_h || !label_off_h || !score_h || !status_h) return lb_fail(PO_E_ARG, "po_label_align_batch_h: null argument");
-    const int64_t rows = y_off_h[n] - y_off_h[0], nl = label_off_h[n] - label_off_h[0];
-    int64_t mx = 0;
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1), lof(label_off_h, label_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    for (auto& o : lof) o -= label_off_h[0];
-    for (int i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i] || lof[i + 1] < lof[i]) return lb_fail(PO_E_ARG, "po_label_align_batch_h: offsets must not decrease");
-        mx = std::max<int64_t>(mx, off[i + 1] - off[i]);
-    }
-    if ((rows > 0 && !y_h) || (nl > 0 && (!labels_h || !map_h))) return lb_fail(PO_E_ARG, "po_label_align_batch_h: null argument");
-    LBDev y, yo, lb, lo, gd, mp, sc, st, ws;
-    LBCHK(y.up(rows ? y_h + y_off_h[0] * C : nullptr, sizeof(double) * (size_t)rows * C));
-    LBCHK(yo.up(off.data(), sizeof(int64_t) * (n + 1)));
-    LBCHK(lb.up(nl ? labels_h + label_off_h[0] : nullptr, (size_t)nl));
-    LBCHK(lo.up(lof.data(), sizeof(int64_t) * (n + 1)));
-    if (guide_h) LBCHK(gd.up(rows ? guide_h + y_off_h[0] : nullptr, sizeof(int32_t) * (size_t)rows));
-    LBCHK(mp.up(nullptr, sizeof(int32_t) * (size_t)nl));
-    LBCHK(sc.up(nullptr, sizeof(double) * n));
-    LBCHK(st.up(nullptr, sizeof(int32_t) * n));
-    const size_t wsb = po_label_align_workspace_bytes(n, rows, mx, nl, band_size);
-    LBCHK(ws.up(nullptr, wsb));
-    const int rc = po_label_align_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, band_size, (const char*)lb.p,
-                                        (const int64_t*)lo.p, guide_h ? (const int32_t*)gd.p : nullptr, (int32_t*)mp.p,
-                                        (double*)sc.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    if (n <= 0) return n < 0 ? po_fail(PO_E_ARG, "po_label_align_batch_h: negative n") : PO_OK;
+    if (!y_off_h || !label_off_h || !score_h || !status_h) return po_fail(PO_E_ARG, "po_label_align_batch_h: null argument");
+    const PoRagged r(y_off_h, n, true), l(label_off_h, n, true);
+    if (!r.ordered || !l.ordered) return po_fail(PO_E_ARG, "po_label_align_batch_h: offsets must not decrease");
+    if ((r.total > 0 && !y_h) || (l.total > 0 && (!labels_h || !map_h))) return po_fail(PO_E_ARG, "po_label_align_batch_h: null argument");
+    PoRows y, lb;
+    PoDev gd, mp, sc, st, ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(lb.up(labels_h, l, 1));
+    if (guide_h) PO_HIPCHK(gd.up(guide_h + r.base, sizeof(int32_t) * r.total));   // one state per frame, at the read's rows
+    PO_HIPCHK(mp.up(nullptr, sizeof(int32_t) * l.total));
+    PO_HIPCHK(sc.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_label_align_workspace_bytes(n, r.total, r.max, l.total, band_size);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    const int rc = po_label_align_batch(y.data, y.off, n, C, alphabet, band_size, lb.data, lb.off, gd, mp, sc, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    LBCHK(hipDeviceSynchronize());
-    if (nl) LBCHK(hipMemcpy(map_h + label_off_h[0], mp.p, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost));
-    LBCHK(hipMemcpy(score_h, sc.p, sizeof(double) * n, hipMemcpyDeviceToHost));
-    LBCHK(hipMemcpy(status_h, st.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(mp.down(map_h + l.base, sizeof(int32_t) * l.total));   // one frame per base, at the label's place in the caller's table
+    PO_HIPCHK(sc.down(score_h, sizeof(double) * n));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 

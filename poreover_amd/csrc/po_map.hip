@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/poreover_hip.h"
-#include "po_host.h"
+#include "po_hostbuf.h"
 
 #include "po_internal.h"
 
@@ -733,19 +733,6 @@ __global__ __launch_bounds__(TPB) void pairs_anchor_write_kernel(const int64_t* 
 
 // ---------------------------------------------------------------------------------------------------- host
 
-thread_local std::string g_map_err;
-int map_fail(int code, const std::string& msg) {
-    g_map_err = msg;
-    po_set_error(msg.c_str());
-    return code;
-}
-int map_hip(hipError_t e, const char* what) { return map_fail(PO_E_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-#define MPCHK(x)                                      \
-    do {                                              \
-        hipError_t e_ = (x);                          \
-        if (e_ != hipSuccess) return map_hip(e_, #x); \
-    } while (0)
-
 // a grow-only device buffer
 struct DBuf {
     void* p = nullptr;
@@ -769,14 +756,14 @@ inline unsigned blocks(int64_t n, int per) { return (unsigned)std::max<int64_t>(
 // exclusive scan of in[0..n) into out[0..n] (out[n] = the total); tmp holds blocks(n, TILE) + 1 int64
 int scan_u32(const uint32_t* in, int64_t n, int64_t* out, int64_t* tmp) {
     if (n == 0) {
-        MPCHK(hipMemset(out, 0, sizeof(int64_t)));
+        PO_HIPCHK(hipMemset(out, 0, sizeof(int64_t)));
         return PO_OK;
     }
     const int64_t nt = (n + TILE - 1) / TILE;
     scan_tile_sum_kernel<<<(unsigned)nt, TPB>>>(in, n, tmp);
     scan_tiles_kernel<<<1, TPB>>>(tmp, nt);
     scan_tile_write_kernel<<<(unsigned)nt, TPB>>>(in, n, tmp, nt, out);
-    MPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -787,11 +774,11 @@ struct Sketch {  // device buffers of one sketch pass
 
 // sketch n sequences already in s.seq / s.off (P bases): minimizers into s.mh/mpos/mst/mseq, per-sequence offsets s.moff
 int run_sketch(Sketch& s, int n, int64_t P, bool with_seq) {
-    MPCHK(s.hs.need(P * 4)); MPCHK(s.ss.need(P)); MPCHK(s.flag.need(P * 4)); MPCHK(s.scan.need((P + 1) * 8));
-    MPCHK(s.tmp.need((blocks(P, TILE) + 1) * 8));
-    MPCHK(s.mh.need(P * 4)); MPCHK(s.mpos.need(P * 4)); MPCHK(s.mst.need(P));
-    if (with_seq) MPCHK(s.mseq.need(P * 4));
-    MPCHK(s.moff.need((n + 1) * 8));
+    PO_HIPCHK(s.hs.need(P * 4)); PO_HIPCHK(s.ss.need(P)); PO_HIPCHK(s.flag.need(P * 4)); PO_HIPCHK(s.scan.need((P + 1) * 8));
+    PO_HIPCHK(s.tmp.need((blocks(P, TILE) + 1) * 8));
+    PO_HIPCHK(s.mh.need(P * 4)); PO_HIPCHK(s.mpos.need(P * 4)); PO_HIPCHK(s.mst.need(P));
+    if (with_seq) PO_HIPCHK(s.mseq.need(P * 4));
+    PO_HIPCHK(s.moff.need((n + 1) * 8));
     if (P > 0) {
         map_hash_kernel<<<blocks(P, TPB), TPB>>>(s.seq.as<char>(), s.off.as<int64_t>(), n, P, s.hs.as<uint32_t>(),
                                                  s.ss.as<uint8_t>());
@@ -805,7 +792,7 @@ int run_sketch(Sketch& s, int n, int64_t P, bool with_seq) {
                                                  s.mpos.as<int32_t>(), s.mst.as<uint8_t>(),
                                                  with_seq ? s.mseq.as<int32_t>() : nullptr);
     map_gather_off_kernel<<<blocks(n + 1, TPB), TPB>>>(s.off.as<int64_t>(), n, s.scan.as<int64_t>(), s.moff.as<int64_t>());
-    MPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
@@ -830,27 +817,26 @@ size_t po_map_workspace_bytes(int64_t bases, int n_reads) {
 
 int po_map_sketch_h(const char* seq_h, const int64_t* off_h, int n, uint32_t* hash_h, int32_t* pos_h, uint8_t* strand_h,
                     int64_t* moff_h) {
-    g_map_err.clear();
     po_set_error("");
-    if (n < 0 || (n > 0 && (!off_h || !moff_h))) return map_fail(PO_E_ARG, "po_map_sketch_h: bad arguments");
+    if (n < 0 || (n > 0 && (!off_h || !moff_h))) return po_fail(PO_E_ARG, "po_map_sketch_h: bad arguments");
     if (n == 0) return PO_OK;
     const int64_t P = off_h[n];
-    if (off_h[0] != 0) return map_fail(PO_E_ARG, "po_map_sketch_h: offsets must start at 0");
+    if (off_h[0] != 0) return po_fail(PO_E_ARG, "po_map_sketch_h: offsets must start at 0");
     for (int i = 0; i < n; ++i)
-        if (off_h[i + 1] < off_h[i]) return map_fail(PO_E_ARG, "po_map_sketch_h: offsets must not decrease");
+        if (off_h[i + 1] < off_h[i]) return po_fail(PO_E_ARG, "po_map_sketch_h: offsets must not decrease");
     Sketch s;
     auto body = [&]() -> int {
-        MPCHK(s.seq.need(P + 1)); MPCHK(s.off.need((n + 1) * 8));
-        if (P) MPCHK(hipMemcpy(s.seq.p, seq_h, P, hipMemcpyHostToDevice));
-        MPCHK(hipMemcpy(s.off.p, off_h, (n + 1) * 8, hipMemcpyHostToDevice));
+        PO_HIPCHK(s.seq.need(P + 1)); PO_HIPCHK(s.off.need((n + 1) * 8));
+        if (P) PO_HIPCHK(hipMemcpy(s.seq.p, seq_h, P, hipMemcpyHostToDevice));
+        PO_HIPCHK(hipMemcpy(s.off.p, off_h, (n + 1) * 8, hipMemcpyHostToDevice));
         const int r = run_sketch(s, n, P, false);
         if (r) return r;
-        MPCHK(hipMemcpy(moff_h, s.moff.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+        PO_HIPCHK(hipMemcpy(moff_h, s.moff.p, (n + 1) * 8, hipMemcpyDeviceToHost));
         const int64_t M = moff_h[n];
         if (M) {
-            MPCHK(hipMemcpy(hash_h, s.mh.p, M * 4, hipMemcpyDeviceToHost));
-            MPCHK(hipMemcpy(pos_h, s.mpos.p, M * 4, hipMemcpyDeviceToHost));
-            MPCHK(hipMemcpy(strand_h, s.mst.p, M, hipMemcpyDeviceToHost));
+            PO_HIPCHK(hipMemcpy(hash_h, s.mh.p, M * 4, hipMemcpyDeviceToHost));
+            PO_HIPCHK(hipMemcpy(pos_h, s.mpos.p, M * 4, hipMemcpyDeviceToHost));
+            PO_HIPCHK(hipMemcpy(strand_h, s.mst.p, M, hipMemcpyDeviceToHost));
         }
         return PO_OK;
     };
@@ -861,15 +847,14 @@ int po_map_sketch_h(const char* seq_h, const int64_t* off_h, int n, uint32_t* ha
 
 po_map_index* po_map_index_create(const char* ctg_h, const int64_t* ctg_off_h, int n_ctg, const uint32_t* hash_h,
                                   const uint32_t* pos_h, const uint32_t* ctg_strand_h, int64_t n_entries) {
-    g_map_err.clear();
     po_set_error("");
     if (n_ctg < 1 || !ctg_off_h || n_entries < 0 || ctg_off_h[0] != 0) {
-        map_fail(PO_E_ARG, "po_map_index_create: bad arguments");
+        po_fail(PO_E_ARG, "po_map_index_create: bad arguments");
         return nullptr;
     }
     for (int i = 0; i < n_ctg; ++i)
         if (ctg_off_h[i + 1] < ctg_off_h[i] || ctg_off_h[i + 1] - ctg_off_h[i] >= ((int64_t)1 << 31)) {
-            map_fail(PO_E_ARG, "po_map_index_create: contig offsets must not decrease and contigs must be < 2^31 bases");
+            po_fail(PO_E_ARG, "po_map_index_create: contig offsets must not decrease and contigs must be < 2^31 bases");
             return nullptr;
         }
     po_map_index* ix = new po_map_index;
@@ -877,16 +862,16 @@ po_map_index* po_map_index_create(const char* ctg_h, const int64_t* ctg_off_h, i
     ix->n_entries = n_entries;
     const int64_t G = ctg_off_h[n_ctg];
     auto body = [&]() -> int {
-        MPCHK(ix->ctg.need(G + 1)); MPCHK(ix->ctg_off.need((n_ctg + 1) * 8));
-        MPCHK(ix->ih.need(n_entries * 4 + 4)); MPCHK(ix->ipos.need(n_entries * 4 + 4)); MPCHK(ix->ics.need(n_entries * 4 + 4));
-        if (G) MPCHK(hipMemcpy(ix->ctg.p, ctg_h, G, hipMemcpyHostToDevice));
-        MPCHK(hipMemcpy(ix->ctg_off.p, ctg_off_h, (n_ctg + 1) * 8, hipMemcpyHostToDevice));
+        PO_HIPCHK(ix->ctg.need(G + 1)); PO_HIPCHK(ix->ctg_off.need((n_ctg + 1) * 8));
+        PO_HIPCHK(ix->ih.need(n_entries * 4 + 4)); PO_HIPCHK(ix->ipos.need(n_entries * 4 + 4)); PO_HIPCHK(ix->ics.need(n_entries * 4 + 4));
+        if (G) PO_HIPCHK(hipMemcpy(ix->ctg.p, ctg_h, G, hipMemcpyHostToDevice));
+        PO_HIPCHK(hipMemcpy(ix->ctg_off.p, ctg_off_h, (n_ctg + 1) * 8, hipMemcpyHostToDevice));
         if (n_entries) {
-            MPCHK(hipMemcpy(ix->ih.p, hash_h, n_entries * 4, hipMemcpyHostToDevice));
-            MPCHK(hipMemcpy(ix->ipos.p, pos_h, n_entries * 4, hipMemcpyHostToDevice));
-            MPCHK(hipMemcpy(ix->ics.p, ctg_strand_h, n_entries * 4, hipMemcpyHostToDevice));
+            PO_HIPCHK(hipMemcpy(ix->ih.p, hash_h, n_entries * 4, hipMemcpyHostToDevice));
+            PO_HIPCHK(hipMemcpy(ix->ipos.p, pos_h, n_entries * 4, hipMemcpyHostToDevice));
+            PO_HIPCHK(hipMemcpy(ix->ics.p, ctg_strand_h, n_entries * 4, hipMemcpyHostToDevice));
         }
-        for (auto& e : ix->ev) MPCHK(hipEventCreate(&e));
+        for (auto& e : ix->ev) PO_HIPCHK(hipEventCreate(&e));
         return PO_OK;
     };
     if (body() != PO_OK) {
@@ -945,19 +930,19 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
     std::vector<char> hseq(P + 1, 0);
     for (int i = 0; i < nb; ++i) memcpy(hseq.data() + off[i], seq_h + off_h[src(i)], off[i + 1] - off[i]);
     Sketch& s = ix->sk;
-    MPCHK(s.seq.need(P + 1)); MPCHK(s.off.need((nb + 1) * 8));
-    MPCHK(hipMemcpy(s.seq.p, hseq.data(), P + 1, hipMemcpyHostToDevice));
-    MPCHK(hipMemcpy(s.off.p, off.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
-    MPCHK(hipEventRecord(ix->ev[0], 0));
+    PO_HIPCHK(s.seq.need(P + 1)); PO_HIPCHK(s.off.need((nb + 1) * 8));
+    PO_HIPCHK(hipMemcpy(s.seq.p, hseq.data(), P + 1, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipMemcpy(s.off.p, off.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipEventRecord(ix->ev[0], 0));
     int rc = run_sketch(s, nb, P, true);
     if (rc) return rc;
-    MPCHK(hipEventRecord(ix->ev[1], 0));
+    PO_HIPCHK(hipEventRecord(ix->ev[1], 0));
     // anchors: count, scan, per-read offsets
     std::vector<int64_t> mo(nb + 1);
-    MPCHK(hipMemcpy(mo.data(), s.moff.p, (nb + 1) * 8, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipMemcpy(mo.data(), s.moff.p, (nb + 1) * 8, hipMemcpyDeviceToHost));
     const int64_t M = mo[nb];
-    MPCHK(ix->cnt.need(M * 4 + 4)); MPCHK(ix->lbo.need(M * 8 + 8)); MPCHK(ix->aoff.need((M + 1) * 8));
-    MPCHK(ix->raoff.need((nb + 1) * 8));
+    PO_HIPCHK(ix->cnt.need(M * 4 + 4)); PO_HIPCHK(ix->lbo.need(M * 8 + 8)); PO_HIPCHK(ix->aoff.need((M + 1) * 8));
+    PO_HIPCHK(ix->raoff.need((nb + 1) * 8));
     if (M && pc)
         pairs_anchor_count_kernel<<<blocks(M, TPB), TPB>>>(s.mh.as<uint32_t>(), s.mseq.as<int32_t>(), M, pc->cand_tgt,
                                                            pc->key, pc->tmoff, pc->max_occ, ix->cnt.as<uint32_t>(),
@@ -965,14 +950,14 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
     else if (M)
         map_anchor_count_kernel<<<blocks(M, TPB), TPB>>>(s.mh.as<uint32_t>(), M, ix->ih.as<uint32_t>(), ix->n_entries,
                                                          ix->cnt.as<uint32_t>(), ix->lbo.as<int64_t>());
-    MPCHK(s.tmp.need((blocks(M, TILE) + 1) * 8));
+    PO_HIPCHK(s.tmp.need((blocks(M, TILE) + 1) * 8));
     rc = scan_u32(ix->cnt.as<uint32_t>(), M, ix->aoff.as<int64_t>(), s.tmp.as<int64_t>());
     if (rc) return rc;
     map_gather_off_kernel<<<blocks(nb + 1, TPB), TPB>>>(s.moff.as<int64_t>(), nb, ix->aoff.as<int64_t>(),
                                                         ix->raoff.as<int64_t>());
-    MPCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     std::vector<int64_t> raoff(nb + 1);
-    MPCHK(hipMemcpy(raoff.data(), ix->raoff.p, (nb + 1) * 8, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipMemcpy(raoff.data(), ix->raoff.p, (nb + 1) * 8, hipMemcpyDeviceToHost));
     const int64_t NA = raoff[nb];
     std::vector<int64_t> soff(nb + 1, 0);
     for (int i = 0; i < nb; ++i) {
@@ -980,9 +965,9 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
         while (np2 < n) np2 <<= 1;
         soff[i + 1] = soff[i] + (np2 > SORT_LDS ? np2 : 0);
     }
-    MPCHK(ix->A.need((NA + 1) * (int64_t)sizeof(Anc))); MPCHK(ix->scratch.need((soff[nb] + 1) * (int64_t)sizeof(Anc)));
-    MPCHK(ix->soff.need((nb + 1) * 8));
-    MPCHK(hipMemcpy(ix->soff.p, soff.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
+    PO_HIPCHK(ix->A.need((NA + 1) * (int64_t)sizeof(Anc))); PO_HIPCHK(ix->scratch.need((soff[nb] + 1) * (int64_t)sizeof(Anc)));
+    PO_HIPCHK(ix->soff.need((nb + 1) * 8));
+    PO_HIPCHK(hipMemcpy(ix->soff.p, soff.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
     if (M && pc)
         pairs_anchor_write_kernel<<<blocks(M, TPB), TPB>>>(s.off.as<int64_t>(), M, s.mpos.as<int32_t>(), s.mst.as<uint8_t>(),
                                                            s.mseq.as<int32_t>(), ix->cnt.as<uint32_t>(), ix->lbo.as<int64_t>(),
@@ -993,17 +978,17 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
                                                          ix->aoff.as<int64_t>(), ix->ipos.as<uint32_t>(),
                                                          ix->ics.as<uint32_t>(), ix->A.as<Anc>());
     map_sort_kernel<<<nb, TPB>>>(ix->A.as<Anc>(), ix->raoff.as<int64_t>(), ix->scratch.as<Anc>(), ix->soff.as<int64_t>());
-    MPCHK(hipGetLastError());
-    MPCHK(hipEventRecord(ix->ev[2], 0));
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipEventRecord(ix->ev[2], 0));
     // chain
-    MPCHK(ix->f.need(NA * 4 + 4)); MPCHK(ix->p.need(NA * 4 + 4)); MPCHK(ix->chain.need(NA * 4 + 4));
-    MPCHK(ix->co.need(nb * (int64_t)sizeof(ChainOut)));
+    PO_HIPCHK(ix->f.need(NA * 4 + 4)); PO_HIPCHK(ix->p.need(NA * 4 + 4)); PO_HIPCHK(ix->chain.need(NA * 4 + 4));
+    PO_HIPCHK(ix->co.need(nb * (int64_t)sizeof(ChainOut)));
     map_chain_kernel<<<nb, 64>>>(ix->A.as<Anc>(), ix->raoff.as<int64_t>(), ix->f.as<int32_t>(), ix->p.as<int32_t>(),
                                  ix->chain.as<int32_t>(), ix->co.as<ChainOut>());
-    MPCHK(hipGetLastError());
-    MPCHK(hipEventRecord(ix->ev[3], 0));
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipEventRecord(ix->ev[3], 0));
     std::vector<ChainOut> co(nb);
-    MPCHK(hipMemcpy(co.data(), ix->co.p, nb * sizeof(ChainOut), hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipMemcpy(co.data(), ix->co.p, nb * sizeof(ChainOut), hipMemcpyDeviceToHost));
     // align the reads whose chain passes; an op byte per alignment column: at most 2 len + (max D - min D) + 512
     std::vector<int32_t> list;
     std::vector<int64_t> opoff(nb + 1, 0);
@@ -1028,13 +1013,13 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
         hb[i] = h;
     }
     const int nl = (int)list.size();
-    MPCHK(ix->hits.need(nb * (int64_t)sizeof(po_map_hit)));
-    MPCHK(hipMemcpy(ix->hits.p, hb.data(), nb * sizeof(po_map_hit), hipMemcpyHostToDevice));
-    MPCHK(ix->band_lo.need(P * 4 + 4)); MPCHK(ix->tb.need(P * 256 + 256)); MPCHK(ix->best.need(nb * (int64_t)sizeof(BestOut)));
-    MPCHK(ix->opoff.need((nb + 1) * 8)); MPCHK(ix->ops.need(opoff[nb] + 1)); MPCHK(ix->list.need(nl * 4 + 4));
-    MPCHK(hipMemcpy(ix->opoff.p, opoff.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
-    if (nl) MPCHK(hipMemcpy(ix->list.p, list.data(), nl * 4, hipMemcpyHostToDevice));
-    MPCHK(hipEventRecord(ix->ev[4], 0));
+    PO_HIPCHK(ix->hits.need(nb * (int64_t)sizeof(po_map_hit)));
+    PO_HIPCHK(hipMemcpy(ix->hits.p, hb.data(), nb * sizeof(po_map_hit), hipMemcpyHostToDevice));
+    PO_HIPCHK(ix->band_lo.need(P * 4 + 4)); PO_HIPCHK(ix->tb.need(P * 256 + 256)); PO_HIPCHK(ix->best.need(nb * (int64_t)sizeof(BestOut)));
+    PO_HIPCHK(ix->opoff.need((nb + 1) * 8)); PO_HIPCHK(ix->ops.need(opoff[nb] + 1)); PO_HIPCHK(ix->list.need(nl * 4 + 4));
+    PO_HIPCHK(hipMemcpy(ix->opoff.p, opoff.data(), (nb + 1) * 8, hipMemcpyHostToDevice));
+    if (nl) PO_HIPCHK(hipMemcpy(ix->list.p, list.data(), nl * 4, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipEventRecord(ix->ev[4], 0));
     if (nl) {
         const char* ctg = pc ? pc->ctg : ix->ctg.as<char>();
         const int64_t* ctg_off = pc ? pc->ctg_off : ix->ctg_off.as<int64_t>();
@@ -1046,12 +1031,12 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
                     ctg, ctg_off, ix->band_lo.as<int32_t>(), ix->tb.as<uint32_t>(),
                     ix->best.as<BestOut>(), ix->opoff.as<int64_t>(), ix->ops.as<uint8_t>(), ix->hits.as<po_map_hit>()};
         map_trace_kernel<<<blocks(nl, 64), 64>>>(t);
-        MPCHK(hipGetLastError());
+        PO_HIPCHK(hipGetLastError());
     }
-    MPCHK(hipEventRecord(ix->ev[5], 0));
-    MPCHK(hipMemcpy(hb.data(), ix->hits.p, nb * sizeof(po_map_hit), hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipEventRecord(ix->ev[5], 0));
+    PO_HIPCHK(hipMemcpy(hb.data(), ix->hits.p, nb * sizeof(po_map_hit), hipMemcpyDeviceToHost));
     std::vector<uint8_t> ops(opoff[nb]);
-    if (opoff[nb]) MPCHK(hipMemcpy(ops.data(), ix->ops.p, opoff[nb], hipMemcpyDeviceToHost));
+    if (opoff[nb]) PO_HIPCHK(hipMemcpy(ops.data(), ix->ops.p, opoff[nb], hipMemcpyDeviceToHost));
     if (stats) {
         stats[0] += elapsed(ix->ev[0], ix->ev[1]);
         stats[1] += elapsed(ix->ev[1], ix->ev[2]);
@@ -1071,11 +1056,11 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
         std::vector<Anc> A(NA);
         std::vector<int32_t> ch(NA);
         if (NA) {
-            MPCHK(hipMemcpy(A.data(), ix->A.p, NA * sizeof(Anc), hipMemcpyDeviceToHost));
-            MPCHK(hipMemcpy(ch.data(), ix->chain.p, NA * 4, hipMemcpyDeviceToHost));
+            PO_HIPCHK(hipMemcpy(A.data(), ix->A.p, NA * sizeof(Anc), hipMemcpyDeviceToHost));
+            PO_HIPCHK(hipMemcpy(ch.data(), ix->chain.p, NA * 4, hipMemcpyDeviceToHost));
         }
         std::vector<int32_t> bl(P);
-        if (P) MPCHK(hipMemcpy(bl.data(), ix->band_lo.p, P * 4, hipMemcpyDeviceToHost));
+        if (P) PO_HIPCHK(hipMemcpy(bl.data(), ix->band_lo.p, P * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < nb; ++i) {
             const int r = ids[i];
             for (int64_t e = raoff[i]; e < raoff[i + 1]; ++e) {
@@ -1095,20 +1080,19 @@ int run_batch(po_map_index* ix, const char* seq_h, const int64_t* off_h, const s
 extern "C" int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t* off_h, int n, int64_t budget,
                               po_map_hit* hits_h, uint8_t* ops_h, int64_t ops_cap, int64_t* ops_len, po_map_debug* dbg,
                               double* stats_h) {
-    g_map_err.clear();
     po_set_error("");
     if (!ix || n < 0 || (n > 0 && (!off_h || !hits_h)) || ops_cap < 0)
-        return map_fail(PO_E_ARG, "po_map_batch_h: bad arguments");
+        return po_fail(PO_E_ARG, "po_map_batch_h: bad arguments");
     if (stats_h)
         for (int i = 0; i < 6; ++i) stats_h[i] = 0;
     if (n == 0) {
         if (ops_len) *ops_len = 0;
         return PO_OK;
     }
-    if (off_h[0] != 0) return map_fail(PO_E_ARG, "po_map_batch_h: offsets must start at 0");
+    if (off_h[0] != 0) return po_fail(PO_E_ARG, "po_map_batch_h: offsets must start at 0");
     for (int i = 0; i < n; ++i)
         if (off_h[i + 1] < off_h[i] || off_h[i + 1] - off_h[i] >= ((int64_t)1 << 31))
-            return map_fail(PO_E_ARG, "po_map_batch_h: offsets must not decrease and reads must be < 2^31 bases");
+            return po_fail(PO_E_ARG, "po_map_batch_h: offsets must not decrease and reads must be < 2^31 bases");
     if (budget <= 0) budget = (int64_t)std::min<size_t>((size_t)8 << 30, po_dev_info().mem / 16);
     // the debug arrays are laid out by the counts a previous call with the same reads left in hits_h
     std::vector<int64_t> aoff_h(n + 1, 0), choff_h(n + 1, 0);
@@ -1139,8 +1123,8 @@ extern "C" int po_map_batch_h(po_map_index* ix, const char* seq_h, const int64_t
     }
     if (ops_len) *ops_len = (int64_t)ops_all.size();
     if ((int64_t)ops_all.size() > ops_cap || (!ops_h && !ops_all.empty()))
-        return map_fail(PO_E_CAP, "po_map_batch_h: ops_cap " + std::to_string(ops_cap) + " < " +
-                                      std::to_string(ops_all.size()) + " alignment columns");
+        return po_fail(PO_E_CAP, "po_map_batch_h: ops_cap " + std::to_string(ops_cap) + " < " +
+                       std::to_string(ops_all.size()) + " alignment columns");
     if (!ops_all.empty()) memcpy(ops_h, ops_all.data(), ops_all.size());
     return PO_OK;
 }
@@ -1188,16 +1172,16 @@ int run_pairs_batch(po_map_index* ix, PairWork& w, const char* tgt_h, const int6
     std::vector<char> tseq(PT + 1, 0);
     for (int i = 0; i < nt; ++i) memcpy(tseq.data() + toff[i], tgt_h + tgt_off_h[tgts[i]], toff[i + 1] - toff[i]);
     Sketch& ts = w.ts;
-    MPCHK(ts.seq.need(PT + 1)); MPCHK(ts.off.need((nt + 1) * 8)); MPCHK(w.cand_tgt.need(nb * 4 + 4));
-    MPCHK(hipMemcpy(ts.seq.p, tseq.data(), PT + 1, hipMemcpyHostToDevice));
-    MPCHK(hipMemcpy(ts.off.p, toff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
-    MPCHK(hipMemcpy(w.cand_tgt.p, cand_tgt.data(), nb * 4, hipMemcpyHostToDevice));
-    MPCHK(hipEventRecord(w.ev[0], 0));
+    PO_HIPCHK(ts.seq.need(PT + 1)); PO_HIPCHK(ts.off.need((nt + 1) * 8)); PO_HIPCHK(w.cand_tgt.need(nb * 4 + 4));
+    PO_HIPCHK(hipMemcpy(ts.seq.p, tseq.data(), PT + 1, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipMemcpy(ts.off.p, toff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipMemcpy(w.cand_tgt.p, cand_tgt.data(), nb * 4, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipEventRecord(w.ev[0], 0));
     int rc = run_sketch(ts, nt, PT, false);
     if (rc) return rc;
-    MPCHK(hipEventRecord(w.ev[1], 0));
+    PO_HIPCHK(hipEventRecord(w.ev[1], 0));
     std::vector<int64_t> tmoff(nt + 1);
-    MPCHK(hipMemcpy(tmoff.data(), ts.moff.p, (nt + 1) * 8, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipMemcpy(tmoff.data(), ts.moff.p, (nt + 1) * 8, hipMemcpyDeviceToHost));
     const int64_t MT = tmoff[nt];
     std::vector<int64_t> soff(nt + 1, 0);
     for (int i = 0; i < nt; ++i) {
@@ -1205,16 +1189,16 @@ int run_pairs_batch(po_map_index* ix, PairWork& w, const char* tgt_h, const int6
         while (np2 < n) np2 <<= 1;
         soff[i + 1] = soff[i] + (np2 > SEG_LDS ? np2 : 0);
     }
-    MPCHK(w.key.need(MT * 8 + 8)); MPCHK(w.runc.need(MT * 4 + 4)); MPCHK(w.max_occ.need(nt * 4 + 4));
-    MPCHK(w.scratch.need(soff[nt] * 8 + 8)); MPCHK(w.soff.need((nt + 1) * 8));
-    MPCHK(hipMemcpy(w.soff.p, soff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
+    PO_HIPCHK(w.key.need(MT * 8 + 8)); PO_HIPCHK(w.runc.need(MT * 4 + 4)); PO_HIPCHK(w.max_occ.need(nt * 4 + 4));
+    PO_HIPCHK(w.scratch.need(soff[nt] * 8 + 8)); PO_HIPCHK(w.soff.need((nt + 1) * 8));
+    PO_HIPCHK(hipMemcpy(w.soff.p, soff.data(), (nt + 1) * 8, hipMemcpyHostToDevice));
     pairs_segsort_kernel<<<nt, TPB>>>(ts.mh.as<uint32_t>(), ts.mpos.as<int32_t>(), ts.mst.as<uint8_t>(),
                                       ts.moff.as<int64_t>(), w.key.as<uint64_t>(), w.scratch.as<uint64_t>(),
                                       w.soff.as<int64_t>());
     pairs_maxocc_kernel<<<nt, TPB>>>(w.key.as<uint64_t>(), ts.moff.as<int64_t>(), w.runc.as<uint32_t>(),
                                      w.max_occ.as<int32_t>());
-    MPCHK(hipGetLastError());
-    MPCHK(hipEventRecord(w.ev[2], 0));
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipEventRecord(w.ev[2], 0));
     // the batch's reads are its candidates' queries, numbered 0 .. nb - 1
     std::vector<int> local(nb);
     std::vector<int32_t> qry(nb);
@@ -1241,25 +1225,24 @@ int run_pairs_batch(po_map_index* ix, PairWork& w, const char* tgt_h, const int6
 extern "C" int po_map_pairs_h(const char* tgt_h, const int64_t* tgt_off_h, int n_tgt, const char* qry_h,
                               const int64_t* qry_off_h, int n_qry, const int32_t* cand_h, int n_cand, int64_t budget,
                               po_map_hit* hits_h, uint8_t* ops_h, int64_t ops_cap, int64_t* ops_len, double* stats_h) {
-    g_map_err.clear();
     po_set_error("");
     if (n_tgt < 0 || n_qry < 0 || n_cand < 0 || ops_cap < 0 || (n_tgt > 0 && !tgt_off_h) || (n_qry > 0 && !qry_off_h) ||
         (n_cand > 0 && (!cand_h || !hits_h)))
-        return map_fail(PO_E_ARG, "po_map_pairs_h: bad arguments");
+        return po_fail(PO_E_ARG, "po_map_pairs_h: bad arguments");
     if (stats_h)
         for (int i = 0; i < 8; ++i) stats_h[i] = 0;
     if (ops_len) *ops_len = 0;
     for (int s = 0; s < 2; ++s) {
         const int64_t* off = s ? qry_off_h : tgt_off_h;
         const int n = s ? n_qry : n_tgt;
-        if (n > 0 && off[0] != 0) return map_fail(PO_E_ARG, "po_map_pairs_h: offsets must start at 0");
+        if (n > 0 && off[0] != 0) return po_fail(PO_E_ARG, "po_map_pairs_h: offsets must start at 0");
         for (int i = 0; i < n; ++i)
             if (off[i + 1] < off[i] || off[i + 1] - off[i] >= ((int64_t)1 << 31))
-                return map_fail(PO_E_ARG, "po_map_pairs_h: offsets must not decrease and sequences must be < 2^31 bases");
+                return po_fail(PO_E_ARG, "po_map_pairs_h: offsets must not decrease and sequences must be < 2^31 bases");
     }
     for (int64_t c = 0; c < n_cand; ++c)
         if (cand_h[2 * c] < 0 || cand_h[2 * c] >= n_qry || cand_h[2 * c + 1] < 0 || cand_h[2 * c + 1] >= n_tgt)
-            return map_fail(PO_E_ARG, "po_map_pairs_h: candidate " + std::to_string(c) + " names a sequence out of range");
+            return po_fail(PO_E_ARG, "po_map_pairs_h: candidate " + std::to_string(c) + " names a sequence out of range");
     if (n_cand == 0) return PO_OK;
     if (budget <= 0) budget = (int64_t)std::min<size_t>((size_t)8 << 30, po_dev_info().mem / 16);
     auto qlen = [&](int c) { return qry_off_h[cand_h[2 * (int64_t)c] + 1] - qry_off_h[cand_h[2 * (int64_t)c]]; };
@@ -1273,8 +1256,8 @@ extern "C" int po_map_pairs_h(const char* tgt_h, const int64_t* tgt_off_h, int n
     std::vector<int32_t> slot_of(n_tgt, -1);
     std::vector<char> in_batch(n_tgt, 0);
     auto body = [&]() -> int {
-        for (auto& e : ix->ev) MPCHK(hipEventCreate(&e));
-        for (auto& e : w.ev) MPCHK(hipEventCreate(&e));
+        for (auto& e : ix->ev) PO_HIPCHK(hipEventCreate(&e));
+        for (auto& e : w.ev) PO_HIPCHK(hipEventCreate(&e));
         for (size_t i = 0; i < order.size();) {
             std::vector<int> ids;
             int64_t bytes = 0;
@@ -1302,8 +1285,8 @@ extern "C" int po_map_pairs_h(const char* tgt_h, const int64_t* tgt_off_h, int n
     if (rc) return rc;
     if (ops_len) *ops_len = (int64_t)ops_all.size();
     if ((int64_t)ops_all.size() > ops_cap || (!ops_h && !ops_all.empty()))
-        return map_fail(PO_E_CAP, "po_map_pairs_h: ops_cap " + std::to_string(ops_cap) + " < " +
-                                      std::to_string(ops_all.size()) + " alignment columns");
+        return po_fail(PO_E_CAP, "po_map_pairs_h: ops_cap " + std::to_string(ops_cap) + " < " +
+                       std::to_string(ops_all.size()) + " alignment columns");
     if (!ops_all.empty()) memcpy(ops_h, ops_all.data(), ops_all.size());
     return PO_OK;
 }

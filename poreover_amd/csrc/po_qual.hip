@@ -26,8 +26,7 @@
 
 #include "../../include/poreover_hip.h"
 
-#include "po_host.h"
-#include "po_internal.h"
+#include "po_hostbuf.h"
 
 namespace {
 
@@ -377,18 +376,6 @@ __global__ __launch_bounds__(64) void qual_kernel(QArgs a) {
 // ------------------------------------------------------------------------------------------------------------ host
 namespace {
 
-thread_local std::string g_q_err;
-int q_fail(int code, const std::string& msg) {
-    g_q_err = msg;
-    po_set_error(g_q_err.c_str());
-    return code;
-}
-#define QCHK(x)                                                                                          \
-    do {                                                                                                 \
-        hipError_t e_ = (x);                                                                             \
-        if (e_ != hipSuccess) return q_fail(PO_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 inline int q_per_state(int model) { return model == PO_MODEL_MERGE ? 14 : 8; }   // doubles of state per ring index (the last: two ints)
 inline int q_nb(int model) { return model == PO_MODEL_MERGE ? 2 : 1; }
 
@@ -399,17 +386,6 @@ inline int64_t q_ring(int64_t L, int band, int32_t* full) {
     *full = 0;
     return wb;
 }
-
-struct QDev {
-    void* p = nullptr;
-    ~QDev() { if (p) (void)hipFree(p); }
-    hipError_t up(const void* src, size_t bytes) {
-        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 256));
-        if (e != hipSuccess) { p = nullptr; return e; }
-        if (src && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-        return e;
-    }
-};
 
 }  // namespace
 
@@ -429,16 +405,15 @@ size_t po_qual_workspace_bytes(int n, int64_t total_rows, int64_t max_rows, int6
 int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
                   const int64_t* label_off, const int32_t* guide, int band_size, double* odds, double* logp,
                   int32_t* status, void* ws, size_t ws_bytes, void* stream) {
-    g_q_err.clear();
     po_set_error("");
-    if (model == PO_MODEL_FLIPFLOP) return q_fail(PO_E_UNSUPPORTED, "po_qual_batch: the flip-flop model has no quality lattice");
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return q_fail(PO_E_ARG, "po_qual_batch: unknown model");
+    if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, "po_qual_batch: the flip-flop model has no quality lattice");
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, "po_qual_batch: unknown model");
     if (n < 0 || !y_off || !label_off || (n > 0 && (!y || !labels || !odds || !logp || !status || !ws)))
-        return q_fail(PO_E_ARG, "po_qual_batch: null argument");
+        return po_fail(PO_E_ARG, "po_qual_batch: null argument");
     const char* alpha = alphabet ? alphabet : "ACGT";
     const size_t A = std::strlen(alpha);
-    if (A < 1 || A > 4) return q_fail(PO_E_ARG, "po_qual_batch: alphabet must have 1..4 symbols");
-    if (C != (int)A + 1) return q_fail(PO_E_ARG, "po_qual_batch: C must be len(alphabet) + 1");
+    if (A < 1 || A > 4) return po_fail(PO_E_ARG, "po_qual_batch: alphabet must have 1..4 symbols");
+    if (C != (int)A + 1) return po_fail(PO_E_ARG, "po_qual_batch: C must be len(alphabet) + 1");
     if (n == 0) return PO_OK;
     hipStream_t s = (hipStream_t)stream;
     QArgs a = {};
@@ -448,9 +423,7 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
     for (size_t i = 0; i < A; ++i) a.alphabet |= (uint32_t)(unsigned char)alpha[i] << (8 * i);
 
     std::vector<int64_t> h(2 * (size_t)(n + 1));
-    QCHK(hipMemcpyAsync(h.data(), y_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-    QCHK(hipMemcpyAsync(h.data() + n + 1, label_off, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost, s));
-    QCHK(hipStreamSynchronize(s));
+    PO_HIPCHK(po_read_tables(y_off, label_off, n, s, h.data()));
     std::vector<QDesc> desc((size_t)n);
     const int per = q_per_state(model), nb = q_nb(model);
     // launch classes: state in LDS of at most 4, 16, 48 KiB, state in the workspace — a read's dynamic LDS is its class's
@@ -462,7 +435,7 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
     for (int i = 0; i < n; ++i) {
         const int64_t T = h[i + 1] - h[i], L = h[n + 1 + i + 1] - h[n + 1 + i];
         if (T < 0 || L < 0 || T >= ((int64_t)1 << 31) - 1 || L >= ((int64_t)1 << 26))
-            return q_fail(PO_E_ARG, "po_qual_batch: offsets must not decrease, reads must be shorter than 2^31 - 1 frames and 2^26 bases");
+            return po_fail(PO_E_ARG, "po_qual_batch: offsets must not decrease, reads must be shorter than 2^31 - 1 frames and 2^26 bases");
         QDesc& d = desc[i];
         const int64_t w = q_ring(L, a.band, &d.full);
         d.wr = (int32_t)w;
@@ -491,59 +464,48 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
         first[c + 1] = (int)sorted.size();
     }
     const size_t b_beta = al256((size_t)nbeta * 8 + 8), b_st = al256((size_t)nst * 8 + 8), b_desc = al256(sizeof(QDesc) * (size_t)n);
-    if (ws_bytes < b_beta + b_st + b_desc) return q_fail(PO_E_CAP, "po_qual_batch: workspace too small");
+    if (ws_bytes < b_beta + b_st + b_desc) return po_fail(PO_E_CAP, "po_qual_batch: workspace too small");
     a.beta = (double*)ws;
     a.st = (double*)((char*)ws + b_beta);
     a.desc = (const QDesc*)((char*)ws + b_beta + b_st);
-    QCHK(hipMemcpyAsync((void*)a.desc, sorted.data(), sizeof(QDesc) * (size_t)n, hipMemcpyHostToDevice, s));
-    QCHK(hipStreamSynchronize(s));   // the table lives on this stack
+    PO_HIPCHK(hipMemcpyAsync((void*)a.desc, sorted.data(), sizeof(QDesc) * (size_t)n, hipMemcpyHostToDevice, s));
+    PO_HIPCHK(hipStreamSynchronize(s));   // the table lives on this stack
     for (int c = 0; c < NCLS; ++c) {
         if (first[c + 1] == first[c]) continue;
         a.first = first[c];
         hipLaunchKernelGGL(qual_kernel, dim3(first[c + 1] - first[c]), dim3(64), (size_t)lds[c] * 8, s, a);
     }
-    QCHK(hipGetLastError());
+    PO_HIPCHK(hipGetLastError());
     return PO_OK;
 }
 
 int po_qual_batch_h(const double* y_h, const int64_t* y_off_h, int n, int C, const char* alphabet, int model,
                     const char* labels_h, const int64_t* label_off_h, const int32_t* guide_h, int band_size, double* odds_h,
                     double* logp_h, int32_t* status_h) {
-    g_q_err.clear();
     po_set_error("");
-    if (model == PO_MODEL_FLIPFLOP) return q_fail(PO_E_UNSUPPORTED, "po_qual_batch_h: the flip-flop model has no quality lattice");
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return q_fail(PO_E_ARG, "po_qual_batch_h: unknown model");
-    if (n <= 0) return n < 0 ? q_fail(PO_E_ARG, "po_qual_batch_h: negative n") : PO_OK;
-    if (!y_off_h || !label_off_h || !logp_h || !status_h) return q_fail(PO_E_ARG, "po_qual_batch_h: null argument");
-    const int64_t rows = y_off_h[n] - y_off_h[0], nl = label_off_h[n] - label_off_h[0];
-    int64_t mx = 0;
-    std::vector<int64_t> off(y_off_h, y_off_h + n + 1), lof(label_off_h, label_off_h + n + 1);
-    for (auto& o : off) o -= y_off_h[0];
-    for (auto& o : lof) o -= label_off_h[0];
-    for (int i = 0; i < n; ++i) {
-        if (off[i + 1] < off[i] || lof[i + 1] < lof[i]) return q_fail(PO_E_ARG, "po_qual_batch_h: offsets must not decrease");
-        mx = std::max<int64_t>(mx, off[i + 1] - off[i]);
-    }
-    if ((rows > 0 && !y_h) || (nl > 0 && (!labels_h || !odds_h))) return q_fail(PO_E_ARG, "po_qual_batch_h: null argument");
-    QDev y, yo, lb, lo, gd, od, lp, st, ws;
-    QCHK(y.up(rows ? y_h + y_off_h[0] * C : nullptr, sizeof(double) * (size_t)rows * C));
-    QCHK(yo.up(off.data(), sizeof(int64_t) * (n + 1)));
-    QCHK(lb.up(nl ? labels_h + label_off_h[0] : nullptr, (size_t)nl));
-    QCHK(lo.up(lof.data(), sizeof(int64_t) * (n + 1)));
-    if (guide_h) QCHK(gd.up(rows ? guide_h + y_off_h[0] : nullptr, sizeof(int32_t) * (size_t)rows));
-    QCHK(od.up(nullptr, sizeof(double) * 5 * (size_t)nl));
-    QCHK(lp.up(nullptr, sizeof(double) * n));
-    QCHK(st.up(nullptr, sizeof(int32_t) * n));
-    const size_t wsb = po_qual_workspace_bytes(n, rows, mx, nl, band_size, model);
-    QCHK(ws.up(nullptr, wsb));
-    const int rc = po_qual_batch((const double*)y.p, (const int64_t*)yo.p, n, C, alphabet, model, (const char*)lb.p,
-                                 (const int64_t*)lo.p, guide_h ? (const int32_t*)gd.p : nullptr, band_size, (double*)od.p,
-                                 (double*)lp.p, (int32_t*)st.p, ws.p, wsb, nullptr);
+    if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, "po_qual_batch_h: the flip-flop model has no quality lattice");
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, "po_qual_batch_h: unknown model");
+    if (n <= 0) return n < 0 ? po_fail(PO_E_ARG, "po_qual_batch_h: negative n") : PO_OK;
+    if (!y_off_h || !label_off_h || !logp_h || !status_h) return po_fail(PO_E_ARG, "po_qual_batch_h: null argument");
+    const PoRagged r(y_off_h, n, true), l(label_off_h, n, true);
+    if (!r.ordered || !l.ordered) return po_fail(PO_E_ARG, "po_qual_batch_h: offsets must not decrease");
+    if ((r.total > 0 && !y_h) || (l.total > 0 && (!labels_h || !odds_h))) return po_fail(PO_E_ARG, "po_qual_batch_h: null argument");
+    PoRows y, lb;
+    PoDev gd, od, lp, st, ws;
+    PO_HIPCHK(y.up(y_h, r, sizeof(double) * C));
+    PO_HIPCHK(lb.up(labels_h, l, 1));
+    if (guide_h) PO_HIPCHK(gd.up(guide_h + r.base, sizeof(int32_t) * r.total));   // one state per frame, at the read's rows
+    PO_HIPCHK(od.up(nullptr, sizeof(double) * 5 * l.total));
+    PO_HIPCHK(lp.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
+    const size_t wsb = po_qual_workspace_bytes(n, r.total, r.max, l.total, band_size, model);
+    PO_HIPCHK(ws.up(nullptr, wsb));
+    const int rc = po_qual_batch(y.data, y.off, n, C, alphabet, model, lb.data, lb.off, gd, band_size, od, lp, st, ws, wsb, nullptr);
     if (rc != PO_OK) return rc;
-    QCHK(hipDeviceSynchronize());
-    if (nl) QCHK(hipMemcpy(odds_h + label_off_h[0] * 5, od.p, sizeof(double) * 5 * (size_t)nl, hipMemcpyDeviceToHost));
-    QCHK(hipMemcpy(logp_h, lp.p, sizeof(double) * n, hipMemcpyDeviceToHost));
-    QCHK(hipMemcpy(status_h, st.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(od.down(odds_h + l.base * 5, sizeof(double) * 5 * l.total));   // five odds per base, at the label's place in the caller's table
+    PO_HIPCHK(lp.down(logp_h, sizeof(double) * n));
+    PO_HIPCHK(st.down(status_h, sizeof(int32_t) * n));
     return PO_OK;
 }
 

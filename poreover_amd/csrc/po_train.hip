@@ -378,23 +378,6 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[e] = p[e] - lr_t * me / (sqrtf(ve) + eps);
 }
 
-thread_local std::string g_train_err;
-int train_fail(int code, const std::string& msg) {
-    g_train_err = msg;
-    po_set_error(msg.c_str());
-    return code;
-}
-int train_hip(hipError_t e, const char* what) {
-    return train_fail(PO_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define TRCHK(x)                                        \
-    do {                                                \
-        hipError_t e_ = (x);                            \
-        if (e_ != hipSuccess) return train_hip(e_, #x); \
-    } while (0)
-
-int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) { return check_model_for(L, nl, nweights, train_fail); }
-
 __global__ __launch_bounds__(RWAVES * 64) void gru_recur_save_kernel(RecurArgs a, float* save0, float* save1) {
     __shared__ float hs[2][RT][HS];
     gru_recur_body<true>(a, blockIdx.y ? save1 : save0, hs);
@@ -451,7 +434,7 @@ int wgrad(po_trainer* tr, const float* A, int64_t lda, const float* B, int64_t l
     const int64_t rows = split_rows(M);
     const int nz = (int)((M + rows - 1) / rows);
     const int64_t pstride = (int64_t)Ktot * N;
-    if ((int64_t)nz * pstride > tr->part_cap) return train_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
+    if ((int64_t)nz * pstride > tr->part_cap) return po_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
     hipLaunchKernelGGL(wgrad_kernel, dim3(blocks(K, 64), blocks(N, 64), nz), dim3(256), 0, tr->stream, A, lda, B, ldb, K, N,
                        M, tr->T, shift, rows, tr->part, N, p0, pstride);
     if (combine)
@@ -463,7 +446,7 @@ int wgrad(po_trainer* tr, const float* A, int64_t lda, const float* B, int64_t l
 int colsum(po_trainer* tr, const float* X, int64_t ldx, int N, int64_t M, float* out) {
     const int64_t rows = split_rows(M);
     const int nz = (int)((M + rows - 1) / rows);
-    if ((int64_t)nz * N > tr->part_cap) return train_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
+    if ((int64_t)nz * N > tr->part_cap) return po_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
     hipLaunchKernelGGL(colsum_kernel, dim3(blocks(N, 256), nz), dim3(256), 0, tr->stream, X, ldx, N, M, rows, tr->part,
                        (int64_t)N);
     hipLaunchKernelGGL(combine_kernel, dim3(blocks(N, 256)), dim3(256), 0, tr->stream, tr->part, nz, (int64_t)N, (int64_t)N,
@@ -480,16 +463,16 @@ struct Timer {
         if (!ms) return PO_OK;
         if (open >= 0) { int rc = end(); if (rc) return rc; }
         hipEvent_t a, b;
-        TRCHK(hipEventCreate(&a));
-        TRCHK(hipEventCreate(&b));
+        PO_HIPCHK(hipEventCreate(&a));
+        PO_HIPCHK(hipEventCreate(&b));
         ev.push_back({kind, {a, b}});
-        TRCHK(hipEventRecord(a, tr->stream));
+        PO_HIPCHK(hipEventRecord(a, tr->stream));
         open = kind;
         return PO_OK;
     }
     int end() {
         if (!ms || open < 0) return PO_OK;
-        TRCHK(hipEventRecord(ev.back().second.second, tr->stream));
+        PO_HIPCHK(hipEventRecord(ev.back().second.second, tr->stream));
         open = -1;
         return PO_OK;
     }
@@ -628,13 +611,12 @@ int train_backward(po_trainer* tr, int n, Timer& tm) {
 extern "C" {
 
 po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max_batch, int T) {
-    g_train_err.clear();
     po_set_error("");
     int64_t nw;
     const int64_t wmax = check_model(layers_h, n_layers, &nw);
     if (wmax < 0) return nullptr;
     if (max_batch < 1 || T < 1) {
-        train_fail(PO_E_ARG, "po_train_create: max_batch and T must be positive");
+        po_fail(PO_E_ARG, "po_train_create: max_batch and T must be positive");
         return nullptr;
     }
     po_trainer* tr = new po_trainer;
@@ -695,7 +677,7 @@ po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max
     if (ok && (e = hipMemset(tr->m, 0, nw * 4)) != hipSuccess) ok = false;
     if (ok && (e = hipMemset(tr->v, 0, nw * 4)) != hipSuccess) ok = false;
     if (!ok) {
-        train_hip(e, "po_train_create: device allocation");
+        po_fail_hip(e, "po_train_create: device allocation");
         trainer_free(tr);
         return nullptr;
     }
@@ -708,68 +690,67 @@ void po_train_destroy(po_trainer* tr) {
 
 int po_train_set_params(po_trainer* tr, const float* w_h, int64_t n) {
     po_set_error("");
-    if (!tr || !w_h) return train_fail(PO_E_ARG, "po_train_set_params: null argument");
-    if (n != tr->nw) return train_fail(PO_E_ARG, "po_train_set_params: the model has " + std::to_string(tr->nw) +
-                                                     " weights, " + std::to_string(n) + " given");
-    TRCHK(hipMemcpy(tr->p, w_h, n * 4, hipMemcpyHostToDevice));
-    TRCHK(hipMemset(tr->m, 0, n * 4));
-    TRCHK(hipMemset(tr->v, 0, n * 4));
+    if (!tr || !w_h) return po_fail(PO_E_ARG, "po_train_set_params: null argument");
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_set_params: the model has " + std::to_string(tr->nw) +
+                                    " weights, " + std::to_string(n) + " given");
+    PO_HIPCHK(hipMemcpy(tr->p, w_h, n * 4, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipMemset(tr->m, 0, n * 4));
+    PO_HIPCHK(hipMemset(tr->v, 0, n * 4));
     tr->step = 0;
     return PO_OK;
 }
 
 int po_train_get_params(po_trainer* tr, float* w_h, int64_t n) {
     po_set_error("");
-    if (!tr || !w_h) return train_fail(PO_E_ARG, "po_train_get_params: null argument");
-    if (n != tr->nw) return train_fail(PO_E_ARG, "po_train_get_params: the model has " + std::to_string(tr->nw) +
-                                                     " weights, " + std::to_string(n) + " asked for");
-    TRCHK(hipStreamSynchronize(tr->stream));
-    TRCHK(hipMemcpy(w_h, tr->p, n * 4, hipMemcpyDeviceToHost));
+    if (!tr || !w_h) return po_fail(PO_E_ARG, "po_train_get_params: null argument");
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_get_params: the model has " + std::to_string(tr->nw) +
+                                    " weights, " + std::to_string(n) + " asked for");
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    PO_HIPCHK(hipMemcpy(w_h, tr->p, n * 4, hipMemcpyDeviceToHost));
     return PO_OK;
 }
 
 int po_train_last(po_trainer* tr, int n, float* logits_h, float* dlogits_h) {
     po_set_error("");
-    if (!tr || n < 1 || n > tr->max_batch) return train_fail(PO_E_ARG, "po_train_last: null trainer or bad window count");
+    if (!tr || n < 1 || n > tr->max_batch) return po_fail(PO_E_ARG, "po_train_last: null trainer or bad window count");
     const size_t b = (size_t)n * tr->T * NOUT * 4;
-    TRCHK(hipStreamSynchronize(tr->stream));
-    if (logits_h) TRCHK(hipMemcpy(logits_h, tr->act.back(), b, hipMemcpyDeviceToHost));
-    if (dlogits_h) TRCHK(hipMemcpy(dlogits_h, tr->dlog, b, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    if (logits_h) PO_HIPCHK(hipMemcpy(logits_h, tr->act.back(), b, hipMemcpyDeviceToHost));
+    if (dlogits_h) PO_HIPCHK(hipMemcpy(dlogits_h, tr->dlog, b, hipMemcpyDeviceToHost));
     return PO_OK;
 }
 
 int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
                   int merge_repeated, float lr, float beta1, float beta2, float eps, int update, float* loss_h,
                   float* grad_h, float* stage_ms_h) {
-    g_train_err.clear();
     po_set_error("");
-    if (!tr || !signal_h || !label_len_h || !loss_h) return train_fail(PO_E_ARG, "po_train_step: null argument");
+    if (!tr || !signal_h || !label_len_h || !loss_h) return po_fail(PO_E_ARG, "po_train_step: null argument");
     if (n < 1 || n > tr->max_batch)
-        return train_fail(PO_E_ARG, "po_train_step: " + std::to_string(n) + " windows, the trainer holds 1 to " +
-                                        std::to_string(tr->max_batch));
+        return po_fail(PO_E_ARG, "po_train_step: " + std::to_string(n) + " windows, the trainer holds 1 to " +
+                       std::to_string(tr->max_batch));
     const int T = tr->T;
     std::vector<int64_t> loff(n + 1, 0);
     int64_t maxL = 0;
     for (int w = 0; w < n; ++w) {
         const int L = label_len_h[w];
-        if (L < 0) return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has a negative label length");
+        if (L < 0) return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has a negative label length");
         int rep = 0;
         for (int j = 0; j < L; ++j) {
             const int32_t c = labels_h[loff[w] + j];
             if (c < 0 || c > 3)
-                return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has label " + std::to_string(c) +
-                                                " at position " + std::to_string(j) + " (labels are 0..3 = A C G T)");
+                return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has label " + std::to_string(c) +
+                               " at position " + std::to_string(j) + " (labels are 0..3 = A C G T)");
             if (j > 0 && c == labels_h[loff[w] + j - 1]) ++rep;
         }
         const int need = L + (merge_repeated ? rep : 0);
         if (need > T)
-            return train_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + "'s " + std::to_string(L) +
-                                            " labels need " + std::to_string(need) + " frames, the window has " +
+            return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + "'s " + std::to_string(L) +
+                           " labels need " + std::to_string(need) + " frames, the window has " +
                                             std::to_string(T));
         loff[w + 1] = loff[w] + L;
         maxL = std::max<int64_t>(maxL, L);
     }
-    if (loff[n] > 0 && !labels_h) return train_fail(PO_E_ARG, "po_train_step: null labels");
+    if (loff[n] > 0 && !labels_h) return po_fail(PO_E_ARG, "po_train_step: null labels");
     const int64_t M = (int64_t)n * T;
     const int Smax = (int)(2 * maxL + 1);
     // α / β and the labels: sized by this batch's longest label, grown when a batch needs more
@@ -779,8 +760,8 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
         if (tr->beta) (void)hipFree(tr->beta);
         tr->alpha = tr->beta = nullptr;
         tr->ab_cap = 0;
-        TRCHK(hipMalloc(&tr->alpha, ab));
-        TRCHK(hipMalloc(&tr->beta, ab));
+        PO_HIPCHK(hipMalloc(&tr->alpha, ab));
+        PO_HIPCHK(hipMalloc(&tr->beta, ab));
         tr->ab_cap = ab;
     }
     const size_t lb = (size_t)std::max<int64_t>(1, loff[n]) * 4;
@@ -788,13 +769,13 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
         if (tr->lab) (void)hipFree(tr->lab);
         tr->lab = nullptr;
         tr->lab_cap = 0;
-        TRCHK(hipMalloc(&tr->lab, lb));
+        PO_HIPCHK(hipMalloc(&tr->lab, lb));
         tr->lab_cap = lb;
     }
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + NSTAGE, 0.f);
-    TRCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
-    if (loff[n] > 0) TRCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
-    TRCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
+    PO_HIPCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
+    if (loff[n] > 0) PO_HIPCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
+    PO_HIPCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
     Timer tm{tr, stage_ms_h};
     int rc = train_forward(tr, n, tm);
     if (rc == PO_OK) rc = tm.begin(1);
@@ -819,13 +800,13 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
     }
     if (rc == PO_OK) {
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = train_hip(e, "po_train_step: launch");
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_step: launch");
     }
     if (rc == PO_OK) {
         hipError_t e = hipMemcpyAsync(loss_h, tr->loss, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
         if (e == hipSuccess && grad_h) e = hipMemcpyAsync(grad_h, tr->g, (size_t)tr->nw * 4, hipMemcpyDeviceToHost, tr->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
-        if (e != hipSuccess) rc = train_hip(e, "po_train_step: results");
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_step: results");
     }
     tm.finish(rc == PO_OK);
     return rc;
