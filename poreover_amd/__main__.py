@@ -33,8 +33,8 @@ def build_parser():
     p.add_argument('--learning_rate', type=float, default=0.001, help='Learning rate for Adam optimizer')
     p.add_argument('--seed', type=int, default=None, help='Explicitly set random seed')
     p.add_argument('--num_neurons', type=int, default=128, help='Number of neurons in RNN layers')
-    p.add_argument('--kernel_size', type=int, default=9, help='Kernel size in Conv1D layer')
-    p.add_argument('--filters', type=int, default=256, help='Number of filters in Conv1D layer')
+    p.add_argument('--kernel_size', type=int, default=9, help='Kernel size in Conv1D layer (1 to 64)')
+    p.add_argument('--filters', type=int, default=256, help='Number of filters in Conv1D layer (at least 1)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="train")
 

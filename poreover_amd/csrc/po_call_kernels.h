@@ -212,7 +212,12 @@ int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
         if (l.cin != cin) return po_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " takes " + std::to_string(l.cin) +
                                          " channels, its input has " + std::to_string(cin));
         if (l.kind == PO_CALL_CONV) {
-            if (l.cout < 1 || l.kernel < 1 || l.kernel > 64) return po_fail(PO_E_ARG, "po_call: conv filters / kernel size");
+            if (l.kernel < 1 || l.kernel > 64)
+                return po_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " is a Conv1D of kernel size " +
+                               std::to_string(l.kernel) + " (supported: 1 to 64)");
+            if (l.cout < 1)
+                return po_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " is a Conv1D of " + std::to_string(l.cout) +
+                               " filters (at least 1)");
             nw += (int64_t)l.kernel * l.cin * l.cout + l.cout;
         } else if (l.kind == PO_CALL_BIGRU || l.kind == PO_CALL_GRU || l.kind == PO_CALL_GRU_BACK) {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;

@@ -27,6 +27,7 @@ __all__ = ["NetworkError", "Layer", "Network", "read_index", "read_checkpoint", 
 
 UNITS = 128          # the only GRU width the device kernel is built for (build_model's num_neurons default)
 NUM_LABELS = 5       # A, C, G, T, blank
+MAX_KERNEL = 64      # the longest Conv1D kernel the device takes (check_model in csrc/po_call_kernels.h); any filters >= 1
 
 
 class NetworkError(ValueError):

@@ -247,6 +247,9 @@ def train(args):
     for flag in ("batch_size", "epochs", "save_every", "loss_every", "kernel_size", "filters"):
         if getattr(args, flag) < 1:
             raise TrainError("train: --%s must be positive" % flag)
+    if args.kernel_size > ckpt.MAX_KERNEL:
+        raise TrainError("train: --kernel_size %d is not supported (the device kernels take Conv1D kernels of 1 to %d taps)" %
+                         (args.kernel_size, ckpt.MAX_KERNEL))
     if not 0.0 <= args.holdout < 1.0:
         raise TrainError("train: --holdout must be in [0, 1)")
     signal, labels, row_lengths = load_data(args.data)

@@ -117,6 +117,39 @@ def test_call_model(lib):
     _refused(lib, rc, L.E_UNSUPPORTED, "po_call: the model must end in Dense(5)")
 
 
+def _conv_dense(kernel, filters):
+    """Conv1D(filters, kernel) on the signal, then Dense(5)"""
+    return (L.CallLayer * 2)(L.CallLayer(L.CALL_KINDS["conv"], 1, filters, kernel),
+                             L.CallLayer(L.CALL_KINDS["dense"], filters, 5, 0))
+
+
+# the Conv1D range the kernels are written for (DESIGN.md §10): 1 <= kernel <= 64, filters >= 1
+CONV_REFUSED = [(65, 8, "po_call: layer 0 is a Conv1D of kernel size 65 (supported: 1 to 64)"),
+                (0, 8, "po_call: layer 0 is a Conv1D of kernel size 0 (supported: 1 to 64)"),
+                (9, 0, "po_call: layer 0 is a Conv1D of 0 filters (at least 1)")]
+
+
+@pytest.mark.parametrize("kernel,filters,text", CONV_REFUSED)
+def test_call_conv_shape(lib, kernel, filters, text):
+    nw = kernel * filters + filters + filters * 5 + 5
+    rc = lib.po_call_batch_h(_p(F32), 1, 2, _conv_dense(kernel, filters), 2, _p(np.zeros(max(nw, 1), dtype=np.float32)), nw,
+                             _p(F32), None, None)
+    _refused(lib, rc, L.E_ARG, text)
+
+
+@pytest.mark.parametrize("kernel,filters,text", CONV_REFUSED)
+def test_train_create_conv_shape(lib, kernel, filters, text):
+    assert lib.po_train_create(_conv_dense(kernel, filters), 2, 4, 4) is None
+    assert lib.po_last_error().decode() == text
+
+
+def test_conv_shape_at_the_limits_is_accepted(lib):
+    """kernel 64 and kernel 1 with one filter pass the model check: the call is refused later, for its weight count"""
+    for kernel in (1, 64):
+        rc = lib.po_call_batch_h(_p(F32), 1, 2, _conv_dense(kernel, 1), 2, _p(F32), 3, _p(F32), None, None)
+        _refused(lib, rc, L.E_ARG, "po_call_batch_h: the model has %d weights, 3 given" % (kernel + 1 + 5 + 5))
+
+
 def test_train_create_no_windows(lib):
     assert lib.po_train_create(DENSE, 1, 0, 4) is None
     assert lib.po_last_error().decode() == "po_train_create: max_batch and T must be positive"

@@ -19,10 +19,10 @@ ARCHS = ["bigru3", "conv1_bigru3", "conv2_bigru3", "conv1_gru5"]
 pytestmark = pytest.mark.gpu
 
 
-def _net(arch, seed=0, filters=256):
+def _net(arch, seed=0, filters=256, kernel_size=9):
     from poreover_amd.network import checkpoint as C
     from poreover_amd.network.train import init_weights
-    cfg = C.architecture(arch, filters=filters)
+    cfg = C.architecture(arch, kernel_size=kernel_size, filters=filters)
     return C.load_network(init_weights(cfg, seed), cfg)
 
 
@@ -86,10 +86,8 @@ def test_ctc_kernel_matches_oracle(merge, n):
         assert np.max(np.abs(loss[keep] + fb) / np.abs(fb)) <= 1e-5
 
 
-def _grad_parity(net, sig, labels, merge=False, tol=1e-3):
-    with _trainer(net, len(sig), sig.shape[1]) as tr:
-        loss, g = tr.step(sig, labels, merge_repeated=merge, update=False, grad=True)
-    want_loss, want_g, _, _ = O.loss_and_grad(net, sig, labels, merge)
+def _assert_grad(net, loss, g, want_loss, want_g, tol=1e-3):
+    """_grad_parity's bounds on a step's (loss, g) against the oracle's: the worst tensor's relative L2 error"""
     assert np.max(np.abs(loss - want_loss) / np.abs(want_loss)) <= 1e-4
     k = 0
     worst = 0.0
@@ -101,6 +99,14 @@ def _grad_parity(net, sig, labels, merge=False, tol=1e-3):
             assert rel <= tol, "%s tensor of shape %s: relative L2 error %.3g" % (l.kind, t.shape, rel)
             k += t.size
     return worst
+
+
+def _grad_parity(net, sig, labels, merge=False, tol=1e-3, oracle=None):
+    """oracle: O.loss_and_grad's result for these inputs, where the caller has it already"""
+    with _trainer(net, len(sig), sig.shape[1]) as tr:
+        loss, g = tr.step(sig, labels, merge_repeated=merge, update=False, grad=True)
+    want_loss, want_g, _, _ = oracle if oracle is not None else O.loss_and_grad(net, sig, labels, merge)
+    return _assert_grad(net, loss, g, want_loss, want_g, tol)
 
 
 @pytest.mark.parametrize("arch", ARCHS)

@@ -111,6 +111,27 @@ def test_oracle_gradient_matches_central_differences(arch, merge):
         assert abs(num - g[i]) <= 1e-6 * max(1.0, abs(num)), (i, num, g[i])
 
 
+@pytest.mark.filterwarnings("ignore:Using padding='same' with even kernel lengths")
+@pytest.mark.parametrize("K,cin,F,T", [(4, 1, 24, 7), (1, 3, 5, 9), (9, 24, 40, 20), (12, 5, 33, 6), (64, 2, 3, 10)])
+def test_oracles_conv1d_matches_torch_same_padding(K, cin, F, T):
+    """both oracles' Conv1D against torch's conv1d(padding='same') + ReLU in float64: torch, like TensorFlow, puts an
+    even kernel's extra tap on the right, which checks the oracles' (K - 1) // 2 independently of this project (even K,
+    K = 1, K > T).  Both sum K·cin <= 216 products of O(1) values in float64 in another order: 1e-12 absolute."""
+    import _call_oracle as OC
+    rng = np.random.default_rng(K * 1000 + F)
+    x = rng.standard_normal((3, T, cin))
+    W = rng.standard_normal((K, cin, F))
+    b = rng.standard_normal(F)
+    y = torch.nn.functional.conv1d(torch.as_tensor(x).permute(0, 2, 1), torch.as_tensor(W).permute(2, 1, 0),
+                                   torch.as_tensor(b), padding="same")
+    want = torch.relu(y).permute(0, 2, 1).numpy()
+    assert want.shape == (3, T, F) and (want > 0).mean() > 0.25
+    got_call = OC.conv1d_relu(x, W, b)
+    got_train = O.conv1d_relu(torch.as_tensor(x), torch.as_tensor(W), torch.as_tensor(b)).numpy()
+    assert np.abs(got_call - want).max() <= 1e-12
+    assert np.abs(got_train - want).max() <= 1e-12
+
+
 def test_adam_restatement_two_steps_by_hand():
     p = O.adam([1.0, -2.0], [[0.5, -1.0], [0.25, 2.0]], lr=0.1, beta1=0.9, beta2=0.999, eps=1e-7)
     # step 1: m = 0.1 g, v = 0.001 g², lr_t = 0.1·sqrt(0.001)/0.1 → p -= lr_t·m/(sqrt(v)+eps) ≈ 0.1·sign(g)
@@ -172,6 +193,11 @@ def test_refusals_before_device_use(tmp_path):
     from poreover_amd.synth import synth_training
     sig, lab, rl = synth_training(8, T=100, seed=1)
     assert "--num_neurons 64" in _refused(tmp_path, _npz(tmp_path), "--num_neurons", "64")
+    # the Conv1D range the device kernels take: 1 <= kernel_size <= 64, filters >= 1
+    assert "--kernel_size must be positive" in _refused(tmp_path, _npz(tmp_path), "--kernel_size", "0")
+    assert "--filters must be positive" in _refused(tmp_path, _npz(tmp_path), "--filters", "0")
+    e = _refused(tmp_path, _npz(tmp_path), "--kernel_size", "65")
+    assert "--kernel_size 65" in e and "1 to 64" in e
     bad = lab.copy()
     bad[rl[0] + 2] = 4
     e = _refused(tmp_path, _npz(tmp_path, labels=bad))
