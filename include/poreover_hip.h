@@ -461,6 +461,39 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
 int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* layers_h, int n_layers,
                     const float* weights_h, int64_t n_weights, float* probs_h, float* logits_h, float* stage_ms_h);
 
+/* ---- `basecall`: scaled signals to decoded strings in one device-resident pass --------
+ * The forward pass above, the log-softmax of po_ingest_batch (PO_INGEST_LOGITS_F32) and po_viterbi_batch / po_beam1d_batch
+ * in one synchronous call: each read's signal goes up once, the strings come down, and nothing per frame returns to the
+ * host in between (unless logits_h asks for it).  Windows may overlap.  For a read of L >= 1 samples, window W >= 1 and
+ * overlap O (even, 0 <= O < W), S = W - O:
+ *     the read has n = 1 window if L <= W, else n = 1 + ceil((L - W) / S);
+ *     window j covers samples [jS, jS + W), zeros at and past L (part of the last window's input, as in `call`), and
+ *              runs through the network from a zero state;
+ *     output frame t (0 <= t < L) is frame t - jS of window j = clamp(floor((t - O/2) / S), 0, n - 1).
+ * O = 0 is `call`'s windowing (n = ceil(L / W)) and gives po_call_batch_h's logits bit for bit; a window's bits do not
+ * depend on the pass it runs in, nor a read's on the reads it shares the call with.
+ *   - signal_h:  the scaled signals of n_reads reads back to back; sig_off_h int64[n_reads + 1] sample offsets,
+ *                sig_off_h[0] == 0; a read without samples is PO_E_ARG naming the read
+ *   - window, overlap: as above; window < 1 and an odd, negative or >= window overlap are PO_E_ARG naming the value
+ *   - layers_h, n_layers, weights_h, n_weights: the model, as for po_call_batch (its refusals and messages; a weight
+ *                count that is not the model's is PO_E_ARG naming both counts)
+ *   - alphabet:  4 symbols or NULL ("ACGT"); kind (PO_KIND_*), beam_width and model (PO_MODEL_*) as for
+ *                po_decode_1d_batch_h: beam_width <= 0 is Viterbi of `kind`, otherwise the 1-D beam search of `model`.
+ *                PO_KIND_FLIPFLOP and PO_MODEL_FLIPFLOP are PO_E_UNSUPPORTED (the network emits a CTC table, blank last)
+ *   - max_windows_per_pass: <= 0: as many windows per network pass as ~4 GiB of pass buffers hold (po_call_batch_h's
+ *                rule); > 0: at most that many (results do not depend on it)
+ *   - seq_h, seq_off_h (from 0), seq_len_h, status_h: the strings, as everywhere; a read's capacity must be at least
+ *                its number of samples (PO_E_CAP naming the read otherwise)
+ *   - logits_h (or NULL): the stitched Dense outputs, (sig_off_h[n_reads], 5) f32, read after read
+ *   - stage_ms_h (or NULL): float[6] device milliseconds, SET by the call: [0..3] po_call_batch's stages summed over the
+ *                passes, [4] window gather + stitch + ingest, [5] the decoder
+ * Every argument error is answered before the first device allocation. */
+int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                        const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                        const char* alphabet, int kind, int beam_width, int model, int max_windows_per_pass,
+                        char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                        float* logits_h, float* stage_ms_h);
+
 /* ---- CTC training of the basecalling network (`train`) -------------------------------------------
  * Replaces the reference's TensorFlow training step (train_ctc_model, network.py:78-131): the forward pass above,
  * tf.compat.v1.nn.ctc_loss (blank = class 4, softmax inside the loss) averaged over the batch, its gradient and Keras

@@ -1,6 +1,7 @@
 """`python -m poreover_amd train|call|decode|pair-decode|benchmark ...` — the five sub-commands of the reference CLI
-(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine — and `find-pairs`, which the
-reference lacks: the list of read pairs `pair-decode` starts from.  `train` runs CTC
+(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine — and two the reference lacks:
+`find-pairs`, the list of read pairs `pair-decode` starts from, and `basecall`, FAST5 to FASTA in one
+device-resident pass with overlapping windows.  `train` runs CTC
 training of the basecalling network in HIP and writes .npz checkpoints; `call` runs the network's forward pass and needs
 `--weights` (no weights ship with this package: a TF checkpoint prefix or directory, a `train` output directory, or an
 .npz from `python -m poreover_amd.network.convert`).  `benchmark` maps decoded reads to a reference genome with the
@@ -51,6 +52,22 @@ def build_parser():
     p.add_argument('--no_stack', default=False, action='store_true', help='Basecall [1xSIGNAL_LENGTH] tensor instead of splitting it into windows (slower)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="call")
+
+    p = subparsers.add_parser('basecall', help='Basecall FAST5 reads to a FASTA file: the network and the decoder in one pass on the GPU',
+                              formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('in', help='Single FAST5 file or directory of FAST5 files')
+    p.add_argument('--weights', default=None, help='Trained weights to load into model: a TF checkpoint prefix, a directory (loads latest from its checkpoint file) or an .npz (required: no weights ship with this package)')
+    p.add_argument('--model', help='Model config JSON file (default: conv1_bigru3)', default=None)
+    p.add_argument('--scaling', default='standard', choices=['standard', 'current', 'median', 'rescale'], help='Type of preprocessing (should be same as training)')
+    p.add_argument('--use_id', default=False, action='store_true', help='Name records by read ID instead of FAST5 filename')
+    p.add_argument('--window', type=int, default=1000, help='Call read using chunks of this size')
+    p.add_argument('--overlap', type=int, default=0, help='Samples that consecutive chunks share (even, smaller than --window); each chunk keeps its middle')
+    p.add_argument('--algorithm', default='viterbi', choices=['viterbi', 'beam'], help='Decoder')
+    p.add_argument('--beam_width', type=int, default=25, help='Width for beam search')
+    p.add_argument('--merge_repeats', default=False, action='store_true', help='Decode as CTC with merged repeats (for weights trained with --ctc_merge_repeated)')
+    p.add_argument('--out', default='out', help='Prefix for FASTA sequence output')
+    p.add_argument('-v', '--version', action='version', version=__version__)
+    p.set_defaults(func="basecall")
 
     p = subparsers.add_parser('decode', help='Decode basecaller probabilities to a FASTA file')
     p.add_argument('in', nargs='+', help='Probabilities to decode (.npy from PoreOver/Bonito, .csv, or HDF5/FAST5 from Flappie/Guppy)')
@@ -133,6 +150,11 @@ def main(argv=None):
         if args.window < 1:
             raise SystemExit("call: --window must be positive")
         _call(args)
+        print(args, file=sys.stderr)
+        return
+    if args.func == "basecall":
+        from .network import basecall as _basecall
+        _basecall.basecall(args)
         print(args, file=sys.stderr)
         return
     if args.func == "find-pairs":

@@ -47,6 +47,7 @@ class CallLayer(C.Structure):
 
 CALL_KINDS = {"conv": 0, "bigru": 1, "gru": 2, "gru_back": 3, "dense": 4}
 CALL_STAGES = ("conv", "gru_proj", "gru_recur", "dense_softmax")
+BASECALL_STAGES = CALL_STAGES + ("stitch_ingest", "decode")
 TRAIN_STAGES = ("forward", "ctc", "back_recur", "gemm", "adam")
 
 _vp, _i64p, _i32p, _dp, _cp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
@@ -155,6 +156,9 @@ PROTOTYPES = {
                                 C.c_size_t, _vp, C.POINTER(C.c_float)]),
     "po_call_batch_h": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64, _vp, _vp,
                                   C.POINTER(C.c_float)]),
+    "po_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
+                                      C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _vp,
+                                      C.POINTER(C.c_float)]),
     "po_train_create": (C.c_void_p, [C.POINTER(CallLayer), C.c_int, C.c_int, C.c_int]),
     "po_train_destroy": (None, [C.c_void_p]),
     "po_train_set_params": (C.c_int, [C.c_void_p, _vp, C.c_int64]),

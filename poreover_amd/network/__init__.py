@@ -1,2 +1,5 @@
-"""The basecalling network (`call`): FAST5 signal -> softmax probabilities, on the GPU (poreover_amd/csrc/po_call.hip)."""
+"""The basecalling network: `call` (FAST5 signal -> softmax probabilities, poreover_amd/csrc/po_call.hip) and `basecall`
+(FAST5 signal -> sequences in one device-resident pass, poreover_amd/csrc/po_basecall.hip; the module .basecall)."""
+from . import basecall  # noqa: F401
+from .basecall import basecall_signals, frame_window, window_plan  # noqa: F401
 from .network import batch_input, call, call_helper, parse_fast5  # noqa: F401

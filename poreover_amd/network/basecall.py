@@ -1,0 +1,181 @@
+"""`basecall`: FAST5 reads to a FASTA file in one device-resident pass, with windows that may overlap.
+
+What `call` followed by `decode` does, without the trip of every frame's probabilities to the host, to a file and back:
+po_basecall_batch_h (poreover_amd/csrc/po_basecall.hip) uploads each read's scaled signal once, cuts it into windows on
+the device, runs the network (po_call.hip), stitches the kept frames' logits, takes their log-softmax and decodes them
+(Viterbi or the 1-D beam search); the strings come back.
+
+Windows and stitching.  For a read of L >= 1 samples, window W >= 1 and overlap O (even, 0 <= O < W), S = W - O:
+  - the read has n = 1 window if L <= W, else n = 1 + ceil((L - W) / S);
+  - window j covers samples [jS, jS + W), zeros at and past L (as batch_input pads), and starts from a zero state;
+  - output frame t is frame t - jS of window j = clamp(floor((t - O/2) / S), 0, n - 1).
+Interior windows keep their middle [O/2, W - O/2): the frames whose forward and backward GRUs have both seen O/2 samples
+or more.  O = 0 is `call`'s windowing.  window_plan and frame_window state the rule in Python; the device follows
+csrc/po_basecall_plan.h."""
+import ctypes as C
+import glob
+import logging
+import os
+from pathlib import Path
+
+import numpy as np
+
+from .. import _lib
+from . import checkpoint as ckpt
+from .network import _layers_array, load_model, parse_fast5
+
+__all__ = ["window_plan", "frame_window", "check_time_order", "basecall_signals", "basecall", "check_window_args"]
+
+# Device memory that one engine call may hold for its per-sample state (the stitched logits, the log-probability table,
+# the decoder's workspace, the signal and the strings): 16 GiB, an eighteenth of an MI355X's 288 GB.  The network's pass
+# buffers (~4 GiB, po_basecall_batch_h's own bound) come on top.  A figure, not a tuned one.
+RESIDENT_BYTES = 16 << 30
+
+
+def check_window_args(window, overlap, what="basecall"):
+    """SystemExit naming the flag for a window / overlap pair the plan does not admit"""
+    if window < 1:
+        raise SystemExit("%s: --window %d must be at least 1" % (what, window))
+    if overlap < 0 or overlap % 2 or overlap >= window:
+        raise SystemExit("%s: --overlap %d must be even, at least 0 and smaller than --window %d" % (what, overlap, window))
+
+
+def window_plan(L, window, overlap):
+    """(n_windows, stride) of a read of L >= 1 samples"""
+    if L < 1 or window < 1 or overlap < 0 or overlap % 2 or overlap >= window:
+        raise ValueError("window_plan: L %d, window %d, overlap %d (L >= 1, window >= 1, overlap even and 0 <= overlap < window)"
+                         % (L, window, overlap))
+    S = window - overlap
+    return (1 if L <= window else 1 + -(-(L - window) // S)), S
+
+
+def frame_window(t, L, window, overlap):
+    """the window that supplies output frame t (0 <= t < L) of a read of L samples: its frame t - j * stride"""
+    n, S = window_plan(L, window, overlap)
+    if not 0 <= t < L:
+        raise ValueError("frame_window: frame %d of %d" % (t, L))
+    return min(max((t - overlap // 2) // S, 0), n - 1)
+
+
+def check_time_order(kinds):
+    """Stitching takes output frame k of a window for sample k.  A model with an odd number of bare go_backwards GRU
+    layers (outside Bidirectional) emits its windows in reversed time: refused by name (NetworkError)."""
+    back = [i for i, k in enumerate(kinds) if k == "gru_back"]
+    if len(back) % 2:
+        raise ckpt.NetworkError("basecall: the model has %d go_backwards GRU layer(s) outside Bidirectional (layer %s): its "
+                                "windows come out in reversed time, which the window stitching does not handle"
+                                % (len(back), ", ".join(map(str, back))))
+
+
+def _bytes_per_sample(lib, beam_width, model):
+    """resident device bytes per signal sample of one engine call: signal f32, logits 5 x f32, table 5 x f64, one
+    character, and the decoder's workspace per row (the beam search's node arena; Viterbi's is a constant)"""
+    b = 4 + ckpt.NUM_LABELS * 4 + ckpt.NUM_LABELS * 8 + 1
+    if beam_width > 0:
+        rows = 1 << 20
+        ws = lib.po_beam1d_workspace_bytes(1, rows, rows, ckpt.NUM_LABELS, beam_width, model)
+        b += -(-int(ws) // rows)
+    return b
+
+
+def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass):
+    n = len(sigs)
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(s) for s in sigs], out=off[1:])
+    rows = int(off[-1])
+    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
+    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+    layers = _layers_array(net)
+    seq = np.zeros(rows, dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int32)
+    st = np.zeros(n, dtype=np.int32)
+    lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
+    ms = (C.c_float * 6)() if stage_ms is not None else None
+    rc = lib.po_basecall_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
+                                 w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
+                                 seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
+                                 lg.ctypes.data if want_logits else None, ms)
+    _lib.check(rc, "po_basecall_batch_h")
+    for i in range(n):
+        if st[i] != 0:
+            raise _lib.EngineError(int(st[i]), "basecall of read %d" % i)
+    if stage_ms is not None:
+        for k, name in enumerate(_lib.BASECALL_STAGES):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+    raw = seq.tobytes()
+    strings = [raw[off[i]:off[i] + lens[i]].decode("ascii") for i in range(n)]
+    if want_logits:
+        return [(s, lg[off[i]:off[i + 1]]) for i, s in enumerate(strings)]
+    return strings
+
+
+def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
+                     logits=False, stage_ms=None, max_windows_per_pass=0):
+    """The decoded string of each scaled signal, in input order — or (string, (len(s), 5) float32 stitched logits) with
+    logits=True.  algorithm "viterbi" or "beam" (beam_width); merge_repeats: the decoder of a network trained with
+    ctc_merge_repeated (the ctc_merge_repeats tree / the bonito-kind Viterbi; the network's blank is already last, so no
+    column moves).  A read without samples gets "" and never reaches the device.  Reads go to the engine in groups, in
+    input order, of at most RESIDENT_BYTES // (resident bytes per sample) samples — a single longer read goes alone;
+    stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES)."""
+    if algorithm not in ("viterbi", "beam"):
+        raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
+    if algorithm == "beam" and not 1 <= beam_width <= 64:
+        raise ValueError("basecall_signals: beam_width %d (1 to 64)" % beam_width)
+    window_plan(1, window, overlap)
+    check_time_order(net.kinds)
+    sigs = [np.asarray(s, dtype=np.float32).ravel() for s in signals]
+    empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
+    out = [empty] * len(sigs)
+    todo = [i for i, s in enumerate(sigs) if len(s)]
+    if not todo:
+        return out
+    lib = _lib.load()
+    kind = _lib.KINDS["bonito" if merge_repeats else "poreover"]
+    model = _lib.MODELS["ctc_merge_repeats" if merge_repeats else "ctc"]
+    bw = int(beam_width) if algorithm == "beam" else 0
+    budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
+    group, held = [], 0
+    for i in todo + [None]:
+        if group and (i is None or held + len(sigs[i]) > budget):
+            res = _engine_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, logits, stage_ms,
+                               max_windows_per_pass)
+            for k, r in zip(group, res):
+                out[k] = r
+            group, held = [], 0
+        if i is not None:
+            group.append(i)
+            held += len(sigs[i])
+    return out
+
+
+def basecall(args):
+    """`poreover_amd basecall IN`: IN is a FAST5 file or a directory of *.fast5; writes {out}.fasta, one record per file
+    in sorted file order, named by the file's stem or (--use_id) by the read id"""
+    from ..decoding.decode import fasta_format
+    check_window_args(args.window, args.overlap)
+    if getattr(args, "weights", None) is None:
+        raise SystemExit("basecall: --weights is required (a TF checkpoint prefix, a directory with a `checkpoint` file, "
+                         "or an .npz); no weights ship with this package")
+    model = getattr(args, "model", None)
+    try:
+        check_time_order([k for k, _ in ckpt.parse_model_json(model if model is not None else ckpt.default_model_config())])
+    except ckpt.NetworkError as e:
+        raise SystemExit(str(e))
+    net = load_model(args)
+    src = getattr(args, "in")
+    files = sorted(glob.glob(os.path.join(src, "*.fast5"))) if os.path.isdir(src) else [src]
+    if not files:
+        raise SystemExit("basecall: no *.fast5 files in %s" % src)
+    parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
+    seqs = basecall_signals(net, [s for _, s in parsed], window=args.window, overlap=args.overlap, algorithm=args.algorithm,
+                            beam_width=args.beam_width, merge_repeats=args.merge_repeats)
+    out_path = args.out + ".fasta"
+    with open(out_path, "w") as f:
+        for path, (rid, _), s in zip(files, parsed, seqs):
+            if args.use_id:
+                name = rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid)
+            else:
+                name = Path(path).stem
+            print(fasta_format(name, s), file=f)
+    logging.info("basecall: %d read(s) -> %s", len(files), out_path)
+    return out_path
