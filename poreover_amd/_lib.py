@@ -17,6 +17,7 @@ SKIP_LENGTH, SKIP_IDENTITY = -10, -11
 MODELS = {"ctc": 0, "ctc_merge_repeats": 1, "ctc_flipflop": 2}
 METHODS = {"row": 0, "row_col": 1, "grid": 2}
 KINDS = {"poreover": 0, "bonito": 1, "flipflop": 2}
+MODEL_OF_KIND = {"poreover": "ctc", "bonito": "ctc_merge_repeats", "flipflop": "ctc_flipflop"}   # the tree model that decodes a basecaller kind
 K_VITERBI, K_BEAM1D, K_BEAM2D, K_ALIGN, K_ENVELOPE, K_BEAM2D_MAIN = range(6)
 _CODE_NAMES = {E_CAP: "PO_E_CAP (buffer too small)", E_ARG: "PO_E_ARG (bad argument)",
                E_ENVELOPE: "PO_E_ENVELOPE (envelope undefined for the reference)",
@@ -221,7 +222,7 @@ _CURRENT_DEVICE = [None]
 
 def set_device(device):
     """Bind this process (its calling thread, as HIP does) to `device` for every later engine call, and remember it:
-    the cached pipelines of batch.pair_decode_stream are per device and ask current_device()."""
+    the cached pipelines of stream.pair_decode_stream are per device and ask current_device()."""
     check(load().po_set_device(int(device)), "po_set_device(%d)" % int(device))
     _CURRENT_DEVICE[0] = int(device)
 

@@ -78,7 +78,7 @@ def _decode_pairs_skip_matches(in_paths, loaded, args, out):
     for i, (_, _, m1, _) in enumerate(loaded):
         by_kind.setdefault(m1.kind, []).append(i)
     for kind, idx in by_kind.items():
-        model = {"poreover": "ctc", "bonito": "ctc_merge_repeats", "flipflop": "ctc_flipflop"}[kind]
+        model = _lib.MODEL_OF_KIND[kind]
         ys1 = [loaded[i][2].log_prob for i in idx]
         ys2 = [loaded[i][3].log_prob for i in idx]
         seq1, map1, st1 = _batch.viterbi_batch(ys1, kind, return_map=True)
@@ -163,7 +163,7 @@ def _decode_pairs_split(in_paths, loaded, args, out):
     for i, (_, _, m1, _) in enumerate(loaded):
         by_kind.setdefault(m1.kind, []).append(i)
     for kind, idx in by_kind.items():
-        model = {"poreover": "ctc", "bonito": "ctc_merge_repeats", "flipflop": "ctc_flipflop"}[kind]
+        model = _lib.MODEL_OF_KIND[kind]
         b1, b2, owner, pieces = [], [], [], {}
         for i in idx:
             y1, y2 = loaded[i][2].log_prob, loaded[i][3].log_prob

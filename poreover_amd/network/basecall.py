@@ -20,7 +20,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .. import _lib
+from .. import _lib, _marshal
 from . import checkpoint as ckpt
 from .network import _layers_array, load_model, parse_fast5
 
@@ -80,8 +80,7 @@ def _bytes_per_sample(lib, beam_width, model):
 
 def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass):
     n = len(sigs)
-    off = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum([len(s) for s in sigs], out=off[1:])
+    off = _marshal.offsets([len(s) for s in sigs])
     rows = int(off[-1])
     signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
     w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
@@ -96,14 +95,11 @@ def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_
                                  seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
                                  lg.ctypes.data if want_logits else None, ms)
     _lib.check(rc, "po_basecall_batch_h")
-    for i in range(n):
-        if st[i] != 0:
-            raise _lib.EngineError(int(st[i]), "basecall of read %d" % i)
+    _marshal.raise_on_status(st, n, "basecall of read")
     if stage_ms is not None:
         for k, name in enumerate(_lib.BASECALL_STAGES):
             stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
-    raw = seq.tobytes()
-    strings = [raw[off[i]:off[i] + lens[i]].decode("ascii") for i in range(n)]
+    strings = _marshal.strings(seq, off, lens)
     if want_logits:
         return [(s, lg[off[i]:off[i + 1]]) for i, s in enumerate(strings)]
     return strings

@@ -16,7 +16,7 @@ from . import batch as _batch
 __all__ = ["DEFAULT_BAND", "MODEL_OF_KIND", "phred", "combine", "fastq_format", "qual_string", "call_qualities", "refuse_flipflop"]
 
 DEFAULT_BAND = _batch.QUAL_DEFAULT_BAND   # the one default of the knob (batch.qual_batch, --qual_band)
-MODEL_OF_KIND = {"poreover": "ctc", "bonito": "ctc_merge_repeats"}
+MODEL_OF_KIND = {k: m for k, m in _lib.MODEL_OF_KIND.items() if m != "ctc_flipflop"}   # (no quality lattice for flip-flop)
 Q_MAX = 60
 
 
