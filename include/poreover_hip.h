@@ -268,7 +268,8 @@ typedef struct {
     int model;             /* PO_MODEL_*                         */
     int method;            /* --beam_search_method row_col       */
     int padding;           /* --padding 5                        */
-    int full_alignment;    /* --alignment full (0 = banded, 500) */
+    int full_alignment;    /* --alignment full (0 = banded, 500): read 2's basecall of at most 2048 bases,
+                              a longer one gives that pair PO_E_UNSUPPORTED (read 1's is not limited) */
     int diagonal_envelope; /* --diagonal_envelope                */
     int diagonal_width;    /* --diagonal_width 50                */
 } po_pair_options;

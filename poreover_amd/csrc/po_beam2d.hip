@@ -1226,6 +1226,8 @@ B2Geom b2_geometry(int n, int64_t mr1, int64_t mr2, int W, int model, int method
     // the small passes (pairs handed back by beam2d_reg_kernel, retries after PO_E_NOMEM) run the W <= 6 class on the
     // W <= 12 kernel (256 instead of 112 row groups) and the W <= 12 class on the W <= 25 kernel (768)
     if (max_blocks > 0 && g.wclass < 25) g.wclass = (g.wclass == 6) ? 12 : 25;
+    const bool wide = (max_blocks == REG_WIDE_BLOCKS);   // the last pass: every class on the W <= 25 kernel
+    if (wide) g.wclass = 25;
     g.threads = g.wclass == 6 ? 64 : (g.wclass == 12 ? 128 : 256);
     const int per_cu = b2_blocks_per_cu(model, g.wclass);
     g.blocks = po_dev_info().cus * per_cu;
@@ -1239,6 +1241,14 @@ B2Geom b2_geometry(int n, int64_t mr1, int64_t mr2, int W, int model, int method
     // (the W <= 6 class, with 16 workgroups per CU, gets half of that on its direct path: its 112 row groups fit
     // windows up to 126 frames in it, and a pair that runs out is decoded again by the retry pass below)
     g.pool_bytes = al256((K == 1 ? (size_t)4 : (size_t)8) << ((g.wclass == 25 || max_blocks > 0) ? 22 : (g.wclass == 6 ? 19 : 20)));
+    if (wide) {
+        // all row groups of that class (768) at the ring length of the widest window these reads can have (a whole row or column), within
+        // 128 / 256 MB per workgroup: with an envelope of whole rows no group is given back before the pair ends
+        size_t R = 32;
+        while ((int64_t)R < std::max(mr1, mr2) + 2) R <<= 1;
+        const size_t want = (size_t)B2Smem<PO_MODEL_CTC, 25>::NGL * PO_A * 2 * R * (K == 1 ? sizeof(Entry<1>) : sizeof(Entry<3>));
+        g.pool_bytes = al256(std::min<size_t>(want, (K == 1 ? (size_t)128 : (size_t)256) << 20));
+    }
     const int64_t WM = W > PO_A ? W : PO_A;
     const int64_t steps = (method == PO_METHOD_ROW) ? mr1 : std::min(mr1, mr2);
     g.arena_cap = ((size_t)(1 + PO_A + (int64_t)PO_A * WM * (steps + 1)) + 1) & ~size_t(1);  // even: a double array follows
@@ -1342,7 +1352,9 @@ extern "C" int po_launch_lae_peak(int iters, double* lae_per_s, hipStream_t stre
 }
 
 size_t po_b2_legacy_ws_bytes(int n, int64_t mr1, int64_t mr2, int W, int model, int method, int max_blocks) {
-    return b2_geometry(n, mr1, mr2, W, model, method, max_blocks).total;
+    // (the pass over deferred / refused pairs is followed by the wide pass: po_b2_launch_legacy)
+    return b2_geometry(n, mr1, mr2, W, model, method, max_blocks).total +
+           (max_blocks == REG_FB_BLOCKS ? b2_geometry(n, mr1, mr2, W, model, method, REG_WIDE_BLOCKS).total : 0);
 }
 
 int po_b2_launch_legacy(const PoB2Call& c, void* ws, size_t ws_bytes, int max_blocks, const int2* only_meta, int retry, const int* retry_flag) {
@@ -1351,9 +1363,10 @@ int po_b2_launch_legacy(const PoB2Call& c, void* ws, size_t ws_bytes, int max_bl
     // direct path: a second, small pass (64 workgroups, four times the store) decodes the pairs whose live rows did
     // not fit the first one's store — windows hundreds of frames wide; an empty pass costs its 1 GB memset
     if (max_blocks == 0 && !retry) {
-        const size_t rb = b2_geometry(c.n, c.mr1, c.mr2, c.W, c.model, c.method, REG_FB_BLOCKS).total;
+        const size_t rb = po_b2_legacy_ws_bytes(c.n, c.mr1, c.mr2, c.W, c.model, c.method, REG_FB_BLOCKS);
         if (ws_bytes < g.total + rb) return PO_E_CAP;
     }
+    if (max_blocks == REG_FB_BLOCKS && ws_bytes < po_b2_legacy_ws_bytes(c.n, c.mr1, c.mr2, c.W, c.model, c.method, REG_FB_BLOCKS)) return PO_E_CAP;
     hipStream_t stream = c.stream;
     char* w = (char*)ws;
     B2Args a = {};
@@ -1407,5 +1420,9 @@ int po_b2_launch_legacy(const PoB2Call& c, void* ws, size_t ws_bytes, int max_bl
 #endif
     if (max_blocks == 0 && !retry)
         return po_b2_launch_legacy(c, (char*)ws + g.total, ws_bytes - g.total, REG_FB_BLOCKS, nullptr, 1, a.queue + 8);
+    // what this small pass refused in its turn (PO_E_NOMEM: no free row group — windows hundreds of frames wide that never
+    // retire a time): once more on the wide pass's store; a no-op launch otherwise
+    if (max_blocks == REG_FB_BLOCKS)
+        return po_b2_launch_legacy(c, (char*)ws + g.total, ws_bytes - g.total, REG_WIDE_BLOCKS, nullptr, 1, a.queue + 8);
     return PO_OK;
 }

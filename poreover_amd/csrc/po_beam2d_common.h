@@ -75,6 +75,9 @@ constexpr int PS_FROZEN = -1, PS_ROOT = -2;
 // geometry, or its row-group table ran out)
 constexpr int REG_DEFERRED = -2;
 constexpr int REG_FB_BLOCKS = 64;   // workgroups of the beam2d_kernel pass over deferred pairs (16 / 32 MB of store each)
+// workgroups of the last pass, over the pairs that one refused with PO_E_NOMEM: the widest kernel class (768 row groups) on a
+// store sized for them (b2_geometry) — envelopes whose rows never retire a time (`--padding` beyond the reads' length)
+constexpr int REG_WIDE_BLOCKS = 2;
 
 // LDS hand-over between iterations.  One wave per workgroup: a wave's LDS operations execute in order,
 // only the compiler needs fencing.  More waves: LDS-only barrier (outstanding stores are not waited for).

@@ -6,6 +6,8 @@ unequal lengths, non-default scores (the trace-back keeps the defaults), degener
 import numpy as np
 import pytest
 
+from _align_cases import mutated as _mutated
+
 pytestmark = pytest.mark.gpu
 
 
@@ -14,20 +16,6 @@ def eng():
     from poreover_amd import _lib
     _lib.load()
     return _lib
-
-
-def _mutated(rng, ref, p=0.08):
-    out = []
-    for b in ref:
-        r = rng.random()
-        if r < p / 3:
-            continue
-        if r < 2 * p / 3:
-            b = "ACGT"[rng.integers(4)]
-        out.append(b)
-        if rng.random() < p / 3:
-            out.append("ACGT"[rng.integers(4)])
-    return "".join(out)
 
 
 def _cases(seed):
@@ -64,6 +52,28 @@ def test_skew_vs_oracle_and_legacy(eng, oracle, band):
         if len(p[0]) * min(len(p[1]), 2 * band + 1) <= 700 * 1001:     # the oracle is a per-cell loop
             w1, w2 = oracle.global_pair_banded(p[0], p[1], band)
             assert (n[0], n[1]) == ("".join(w1), "".join(w2)), ("oracle", band, k, len(p[0]), len(p[1]))
+
+
+@pytest.mark.parametrize("band", [501, 512, 513, 600, 5000])
+def test_skew_wide_bands(eng, oracle, band):
+    """bands beyond the default 500: the skewed wavefront takes any band; a row of the row-at-a-time kernel holds 64 x 16
+    cells, so it answers bands up to 512 and refuses the call (a pair whose row is wider: PO_E_UNSUPPORTED) above that"""
+    pairs = _cases(100 + band)
+    new = _run(pairs, band, (2, -1, -1), legacy=False)
+    try:
+        old = _run(pairs, band, (2, -1, -1), legacy=True)
+    except eng.EngineError as e:
+        assert e.code == eng.E_UNSUPPORTED and band > 512, (band, str(e))
+        old = None
+    checked = 0
+    for k, (p, n) in enumerate(zip(pairs, new)):
+        if old is not None:
+            assert n == old[k], ("legacy", band, k, len(p[0]), len(p[1]))
+        if len(p[0]) * min(len(p[1]), 2 * band + 1) <= 700 * 1001:     # the oracle is a per-cell loop
+            w1, w2 = oracle.global_pair_banded(p[0], p[1], band)
+            assert (n[0], n[1]) == ("".join(w1), "".join(w2)), ("oracle", band, k, len(p[0]), len(p[1]))
+            checked += 1
+    assert checked >= 20
 
 
 @pytest.mark.parametrize("scores", [(3, -2, -2), (1, -3, -1), (2, -1, -3), (5, 0, -1), (2, 2, -1)])

@@ -56,3 +56,22 @@ def test_gamma_dense_golden(eng, golden, golden_inputs):
             g00 = decoding_cy.pair_gamma_log(np.log(np.array(pm[a])), np.log(np.array(pm[b])))[0, 0]
             assert np.isclose(g00, hexf(rec["gamma00_cy"]), rtol=1e-12)
     assert decoding_cy.diagonal_band_envelope(10, 20, 3)[1].tolist()[:3] == [[0, 3], [0, 5], [1, 7]]
+
+
+def test_gamma_envelope_backward_boundary_sums(eng, oracle):
+    """pairs beyond U^2 + V^2 = 2^22, where the kernel takes the boundary sums of the blank columns from the backward
+    recurrence (two threads, s += y[k] from the end) instead of one forward sum per entry, and one pair just below, in one
+    call.  Inside a band of half-width w the boundary cells that are stored hold suffix sums of at most w + 1 terms, on which
+    the two summation orders differ by about an ulp (1.6e-16 relative, measured on the CPU); the rest is the arithmetic the
+    tests above bound, hence their RTOL."""
+    y1s, y2s, envs, want = [], [], [], []
+    for i, T in enumerate((1400, 1500, 1600, 2200)):
+        y1, y2 = synth_pair(9800 + i, T=T)
+        e = _inclusive_band(len(y1), len(y2), 10)
+        y1s.append(y1); y2s.append(y2); envs.append(e)
+        want.append(oracle.pair_gamma_log_envelope(y1, y2, e))
+    size = [len(a) ** 2 + len(b) ** 2 for a, b in zip(y1s, y2s)]
+    assert size[0] <= 2 ** 22 < min(size[1:])
+    got = eng.pair_gamma_batch(y1s, y2s, envs)
+    print("gamma, relative differences:", [abs(g - w) / abs(w) for g, w in zip(got, want)])
+    assert np.all(np.isfinite(want)) and np.allclose(got, want, rtol=RTOL, atol=0)
