@@ -495,6 +495,52 @@ int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_r
                         char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
                         float* logits_h, float* stage_ms_h);
 
+/* ---- `basecall --fastq`: the same pass, with per-base qualities -----------------------
+ * po_basecall_batch_h's arguments, refusals and strings (bit for bit), then, behind the decoder on the same stream and on
+ * the table and strings that are on the device already: the Viterbi call of `kind` with its frame map (Viterbi of
+ * PO_KIND_POREOVER: the decode itself; otherwise a second, cheap call, so that a PO_KIND_BONITO map whose count differs from
+ * the string's - PO_E_ARG in po_viterbi_batch's status, the diagonal here - leaves status_h what po_basecall_batch_h gives), the band guide of every read (quality.call_guides' rule: the map where the scored string is the Viterbi
+ * call; otherwise the two are aligned by po_align_batch, band_width = 500 + the largest length difference among the
+ * call's pairs, and the map is counted in the scored string's bases; the diagonal for an empty string, a failed Viterbi
+ * call or a failed alignment), po_qual_batch of the tree model of `kind` (PO_KIND_POREOVER: PO_MODEL_CTC, PO_KIND_BONITO:
+ * PO_MODEL_MERGE) and the Phred characters.  Between the upload of the signals and the download of the results only
+ * per-read words (lengths, statuses, offsets) cross to the host.
+ *   - band_size:     po_qual_batch's; <= 0: no band, no guide
+ *   - qual_h:        the FASTQ characters 33 + Q, seq_len_h[i] of them at seq_off_h[i]
+ *                    (Q = clip(floor(-10 log10(e) + 0.5), 0, 60), e = the alternatives' share of the odds, float64)
+ *   - qual_status_h: int32[n_reads], po_qual_batch's status per read.  PO_E_ENVELOPE (the band admits no path) is reported,
+ *                    not retried; a read with a non-zero status gets '!' (Q 0) for every base
+ *   - odds_h (or NULL): the log-odds, five float64 per base at seq_off_h[i] * 5
+ *   - guide_h (or NULL): the guide, int32 per frame at sig_off_h[i]; untouched for band_size <= 0
+ *   - stage_ms_h (or NULL): float[8]: po_basecall_batch_h's six, [6] Viterbi map (beam) + alignment + guides,
+ *                    [7] label compaction + lattice + Phred
+ * A null qual_h or qual_status_h is PO_E_ARG naming it; every argument error is answered before the first allocation. */
+int po_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                              const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                              const char* alphabet, int kind, int beam_width, int model, int max_windows_per_pass,
+                              char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                              float* logits_h, int band_size, char* qual_h, int32_t* qual_status_h, double* odds_h,
+                              int32_t* guide_h, float* stage_ms_h);
+
+/* The three device stages of the above alone, on host buffers (tables from 0, non-decreasing; PO_E_ARG otherwise).  The
+ * per-element rules are poreover_amd/csrc/po_fastq_rules.h.  mode (one int32 per read): 0 the scored string is the Viterbi
+ * call (consumed[j] = j + 1), 1 consumed[] is given, 2 the diagonal floor((t + 1) * L / T).
+ *   po_fastq_guide_h:    make_labeled_data.guide_from_alignment.  Read i has y_off_h[i+1] - y_off_h[i] frames; its map
+ *                        (called_len_h[i] increasing frames), its consumed[] (mode 1) and its guide are at y_off_h[i];
+ *                        label_len_h[i] = L.  consumed_h may be NULL when no read has mode 1.
+ *   po_fastq_consumed_h: consumed_from_columns + the clip at L.  Pair i has ncol_h[i] columns at aln_off_h[i] of both rows
+ *                        ('-' = gap); consumed of its called_len_h[i] bases goes to out_off_h[i]; mode_h[i] = 1, or 2 where
+ *                        row 1 does not hold exactly called_len_h[i] bases.
+ *   po_fastq_phred_h:    quality.phred + qual_string.  odds five float64 per base, labels and qual at label_off_h[i];
+ *                        a read with qual_status_h[i] != 0 gets '!' throughout. */
+int po_fastq_guide_h(const int32_t* map_h, const int32_t* consumed_h, const int64_t* y_off_h, int n, const int32_t* called_len_h,
+                     const int32_t* label_len_h, const int32_t* mode_h, int32_t* guide_h);
+int po_fastq_consumed_h(const char* aln1_h, const char* aln2_h, const int64_t* aln_off_h, const int32_t* ncol_h, int n,
+                        const int32_t* called_len_h, const int32_t* label_len_h, const int64_t* out_off_h, int32_t* consumed_h,
+                        int32_t* mode_h);
+int po_fastq_phred_h(const double* odds_h, const char* labels_h, const int64_t* label_off_h, int n, const char* alphabet,
+                     const int32_t* qual_status_h, char* qual_h);
+
 /* ---- CTC training of the basecalling network (`train`) -------------------------------------------
  * Replaces the reference's TensorFlow training step (train_ctc_model, network.py:78-131): the forward pass above,
  * tf.compat.v1.nn.ctc_loss (blank = class 4, softmax inside the loss) averaged over the batch, its gradient and Keras

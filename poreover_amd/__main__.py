@@ -66,6 +66,8 @@ def build_parser():
     p.add_argument('--beam_width', type=int, default=25, help='Width for beam search')
     p.add_argument('--merge_repeats', default=False, action='store_true', help='Decode as CTC with merged repeats (for weights trained with --ctc_merge_repeated)')
     p.add_argument('--out', default='out', help='Prefix for FASTA sequence output')
+    p.add_argument('--fastq', action='store_true', default=False, help='Also write {out}.fastq with a Phred quality per base')
+    p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="basecall")
 

@@ -11,12 +11,17 @@
 //
 // Both are streaming copies, one lane per f32 value of the pass, consecutive lanes on consecutive addresses on the pass's
 // side and on runs of consecutive addresses on the reads' side; every output value has one writer.
+//
+// po_basecall_fastq_batch_h (`basecall --fastq`) is the same body followed by the quality stages on the
+// same stream: FastqStages below enqueues them (kernels: po_fastq.hip, the lattice: po_qual.hip) on the table and the
+// strings the decoder left on the device.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "po_basecall_plan.h"
+#include "po_fastq_rules.h"
 #include "po_hostbuf.h"
 
 namespace {
@@ -86,38 +91,194 @@ struct Spans {
     }
 };
 
-}  // namespace
+// what po_basecall_fastq_batch_h adds to po_basecall_batch_h's arguments
+struct FastqOut {
+    int band_size;
+    char* qual_h; int32_t* qual_status_h; double* odds_h; int32_t* guide_h;
+};
 
-extern "C" int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
-                                   const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
-                                   const char* alphabet, int kind, int beam_width, int model, int max_windows_per_pass,
-                                   char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
-                                   float* logits_h, float* stage_ms_h) {
+// The quality stages, enqueued behind the decoder on its stream: the table dy, the strings of `out` and
+// (Viterbi) the frame map stay where they are; lengths, statuses, modes and offsets are the only words that cross.
+struct FastqStages {
+    PoDev map, vseq, vlen, vst, mode, consumed, guide, labels, label_off, odds, logp, qst, qual, wsv, wsq;
+    PoDev pair_read, pair_seq, pair_off, aln1, aln2, aln_off, ncol, ast, wsa;
+    std::vector<int64_t> label_off_h;
+    int32_t* called_len = nullptr;   // device: the Viterbi call's lengths
+    // The Viterbi call with its frame map is the decode itself only for Viterbi of PO_KIND_POREOVER.  For PO_KIND_BONITO the
+    // map follows the reference's get_sequence_mapping, whose count can differ from the string's; po_viterbi_batch reports
+    // that as PO_E_ARG in the read's status (such a read gets the diagonal, as in quality.call_guides), and the decode's
+    // own status has to stay what po_basecall_batch_h gives: the map then comes from a second Viterbi call, as for the beam.
+    bool second = false;
+
+    // before the decoder: the buffers whose size is known from the signals
+    int prepare(int n, int64_t rows, int kind, int beam_width, size_t cap) {
+        second = beam_width > 0 || kind != PO_KIND_POREOVER;
+        PO_HIPCHK(map.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        PO_HIPCHK(mode.up(nullptr, sizeof(int32_t) * n));
+        PO_HIPCHK(guide.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        PO_HIPCHK(qst.up(nullptr, sizeof(int32_t) * n));
+        PO_HIPCHK(logp.up(nullptr, sizeof(double) * n));
+        PO_HIPCHK(qual.up(nullptr, cap));
+        if (second) {
+            PO_HIPCHK(vseq.up(nullptr, cap));
+            PO_HIPCHK(vlen.up(nullptr, sizeof(int32_t) * n));
+            PO_HIPCHK(vst.up(nullptr, sizeof(int32_t) * n));
+            PO_HIPCHK(wsv.up(nullptr, po_viterbi_workspace_bytes(n, rows, NOUT, kind)));
+        }
+        if (beam_width > 0) PO_HIPCHK(consumed.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        return PO_OK;
+    }
+
+    // steps 1 to 3: the Viterbi call with its map, the pairs that need an alignment, the guide
+    int guides(const char* me, const FastqOut& fq, const double* dy, const int64_t* dsoff, int n, int64_t rows, const char* alphabet,
+               int kind, int beam_width, const PoSeqOut& out, hipStream_t stream) {
+        int rc;
+        const char* called = out.seq.as<char>();
+        const int32_t* called_st = out.status.as<int32_t>();
+        called_len = out.len.as<int32_t>();
+        if (second) {
+            rc = po_viterbi_batch(dy, dsoff, n, NOUT, alphabet, kind, nullptr, vseq, out.off, vlen, map, vst, wsv,
+                                  po_viterbi_workspace_bytes(n, rows, NOUT, kind), stream);
+            if (rc != PO_OK) return rc;
+            called = vseq.as<char>();
+            called_st = vst.as<int32_t>();
+            called_len = vlen.as<int32_t>();
+        }
+        po_launch_fastq_mode(out.seq, out.len, called, called_len, called_st, out.off, n, mode, stream);
+        PO_HIPCHK(hipGetLastError());
+        if (beam_width > 0) {
+            std::vector<int32_t> h(3 * (size_t)n);   // mode | scored lengths | called lengths
+            PO_HIPCHK(hipMemcpyAsync(h.data(), mode.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+            PO_HIPCHK(hipMemcpyAsync(h.data() + n, out.len.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+            PO_HIPCHK(hipMemcpyAsync(h.data() + 2 * n, vlen.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+            PO_HIPCHK(hipStreamSynchronize(stream));
+            std::vector<int32_t> reads;
+            std::vector<int64_t> so(1, 0), ao(1, 0);
+            int64_t slack = 0, m1 = 0, m2 = 0;
+            for (int i = 0; i < n; ++i) {
+                if (h[i] != PO_FQ_ALIGN) continue;
+                const int64_t Lc = h[2 * (size_t)n + i], L = h[(size_t)n + i];
+                reads.push_back(i);
+                so.push_back(so.back() + Lc);       // pair = (called, scored), as quality.call_guides aligns them
+                so.push_back(so.back() + L);
+                ao.push_back(ao.back() + Lc + L + 8);
+                slack = std::max(slack, Lc > L ? Lc - L : L - Lc);
+                m1 = std::max(m1, Lc);
+                m2 = std::max(m2, L);
+            }
+            const int m = (int)reads.size();
+            if (m > 0) {
+                if (500 + slack > INT32_MAX) return po_fail(PO_E_ARG, std::string(me) + ": alignment band beyond 2^31 - 1");
+                const int band = (int)(500 + slack);   // call_guides' rule: one band for the call's pairs
+                // the aligner's workspace is per workgroup in flight: as many pairs a launch as ~4 GiB of it hold
+                const size_t per_pair = po_align_workspace_bytes(1, m1, m2, band);
+                const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, ((size_t)4 << 30) / per_pair));
+                const size_t wab = po_align_workspace_bytes(step, m1, m2, band);
+                PO_HIPCHK(pair_read.up(reads.data(), sizeof(int32_t) * m));
+                PO_HIPCHK(pair_off.up(so.data(), sizeof(int64_t) * so.size()));
+                PO_HIPCHK(aln_off.up(ao.data(), sizeof(int64_t) * ao.size()));
+                PO_HIPCHK(pair_seq.up(nullptr, (size_t)so.back()));
+                PO_HIPCHK(aln1.up(nullptr, (size_t)ao.back()));
+                PO_HIPCHK(aln2.up(nullptr, (size_t)ao.back()));
+                PO_HIPCHK(ncol.up(nullptr, sizeof(int32_t) * m));
+                PO_HIPCHK(ast.up(nullptr, sizeof(int32_t) * m));
+                PO_HIPCHK(wsa.up(nullptr, wab));
+                po_launch_fastq_gather(called, out.seq, out.off, pair_read, 2, pair_off, 2 * m, so.back(), pair_seq, stream);
+                PO_HIPCHK(hipGetLastError());
+                for (int p0 = 0; p0 < m; p0 += step) {
+                    rc = po_align_batch(pair_seq, pair_off.as<int64_t>() + 2 * p0, std::min(step, m - p0), band, aln1, aln2,
+                                        aln_off.as<int64_t>() + p0, ncol.as<int32_t>() + p0, ast.as<int32_t>() + p0, wsa, wab, stream);
+                    if (rc != PO_OK) return rc;
+                }
+                po_launch_fastq_consumed(aln1, aln2, aln_off, ncol, ast, m, pair_read, dsoff, called_len, out.len, consumed, mode, stream);
+                PO_HIPCHK(hipGetLastError());
+            }
+        }
+        if (fq.band_size > 0) {
+            po_launch_fastq_guide(map, beam_width > 0 ? consumed.as<int32_t>() : nullptr, dsoff, n, rows, called_len, out.len, mode,
+                                  guide, stream);
+            PO_HIPCHK(hipGetLastError());
+        }
+        return PO_OK;
+    }
+
+    // steps 4 to 6: dense labels, the lattice on the resident table, Phred characters at the strings' offsets
+    int lattice(const FastqOut& fq, const double* dy, const int64_t* dsoff, int n, int64_t rows, int64_t max_rows,
+                const char* alphabet, int kind, const PoSeqOut& out, hipStream_t stream) {
+        std::vector<int32_t> len((size_t)n);
+        PO_HIPCHK(hipMemcpyAsync(len.data(), out.len.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipStreamSynchronize(stream));
+        label_off_h.assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) label_off_h[(size_t)i + 1] = label_off_h[i] + std::max(len[i], 0);
+        const int64_t total = label_off_h[n];
+        const int model = kind == PO_KIND_BONITO ? PO_MODEL_MERGE : PO_MODEL_CTC;   // the tree model of the decoder's kind
+        const size_t wqb = po_qual_workspace_bytes(n, rows, max_rows, total, fq.band_size, model);
+        PO_HIPCHK(label_off.up(label_off_h.data(), sizeof(int64_t) * label_off_h.size()));
+        PO_HIPCHK(labels.up(nullptr, (size_t)total));
+        PO_HIPCHK(odds.up(nullptr, sizeof(double) * 5 * (size_t)total));
+        PO_HIPCHK(wsq.up(nullptr, wqb));
+        po_launch_fastq_gather(out.seq, out.seq, out.off, nullptr, 1, label_off, n, total, labels, stream);
+        PO_HIPCHK(hipGetLastError());
+        const int rc = po_qual_batch(dy, dsoff, n, NOUT, alphabet, model, labels, label_off, fq.band_size > 0 ? guide.as<int32_t>() : nullptr,
+                                     fq.band_size, odds, logp, qst, wsq, wqb, stream);
+        if (rc != PO_OK) return rc;
+        po_launch_fastq_phred(odds, labels, label_off, qst, out.off, n, total, alphabet, qual, stream);
+        PO_HIPCHK(hipGetLastError());
+        return PO_OK;
+    }
+
+    // after the synchronise: the characters, the statuses and (where asked for) the odds and the guide
+    int down(const FastqOut& fq, const int64_t* seq_off_h, int n, int64_t rows, size_t cap) {
+        PO_HIPCHK(qual.down(fq.qual_h, cap));
+        PO_HIPCHK(qst.down(fq.qual_status_h, sizeof(int32_t) * n));
+        if (fq.guide_h && fq.band_size > 0) PO_HIPCHK(guide.down(fq.guide_h, sizeof(int32_t) * (size_t)rows));
+        if (fq.odds_h) {   // dense on the device, at the strings' offsets in the caller's table
+            const int64_t total = label_off_h[n];
+            std::vector<double> dense((size_t)total * 5);
+            PO_HIPCHK(odds.down(dense.data(), sizeof(double) * dense.size()));
+            for (int i = 0; i < n; ++i) {
+                const int64_t L = label_off_h[(size_t)i + 1] - label_off_h[i];
+                if (L > 0) std::memcpy(fq.odds_h + seq_off_h[i] * 5, dense.data() + label_off_h[i] * 5, sizeof(double) * 5 * (size_t)L);
+            }
+        }
+        return PO_OK;
+    }
+};
+
+// po_basecall_batch_h (fq == NULL) and po_basecall_fastq_batch_h under their own names
+int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                  const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights, const char* alphabet,
+                  int kind, int beam_width, int model, int max_windows_per_pass, char* seq_h, const int64_t* seq_off_h,
+                  int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h, const FastqOut* fq) {
+    const std::string me = std::string(name) + ": ";
+    const int n_stages = fq ? 8 : 6;
     po_set_error("");
     // ---- every argument error, before the first allocation
-    if (n_reads < 0) return po_fail(PO_E_ARG, "po_basecall_batch_h: n_reads " + std::to_string(n_reads));
+    if (n_reads < 0) return po_fail(PO_E_ARG, me + "n_reads " + std::to_string(n_reads));
     if (!signal_h || !sig_off_h || !layers_h || !weights_h || !seq_h || !seq_off_h || !seq_len_h || !status_h)
-        return po_fail(PO_E_ARG, std::string("po_basecall_batch_h: null argument ") +
+        return po_fail(PO_E_ARG, me + "null argument " +
                        (!signal_h ? "signal_h" : !sig_off_h ? "sig_off_h" : !layers_h ? "layers_h" : !weights_h ? "weights_h" :
                         !seq_h ? "seq_h" : !seq_off_h ? "seq_off_h" : !seq_len_h ? "seq_len_h" : "status_h"));
+    if (fq && (!fq->qual_h || !fq->qual_status_h))
+        return po_fail(PO_E_ARG, me + "null argument " + (!fq->qual_h ? "qual_h" : "qual_status_h"));
     PoBasecallPlan plan;
     std::string err;
-    int rc = po_basecall_make_plan(sig_off_h, n_reads, window, overlap, seq_off_h, &plan, &err);
+    int rc = po_basecall_make_plan(sig_off_h, n_reads, window, overlap, seq_off_h, &plan, &err, name);
     if (rc != PO_OK) return po_fail(rc, err);
     if (kind == PO_KIND_FLIPFLOP || model == PO_MODEL_FLIPFLOP)
-        return po_fail(PO_E_UNSUPPORTED, "po_basecall_batch_h: flip-flop decoding (kind " + std::to_string(kind) + ", model " +
+        return po_fail(PO_E_UNSUPPORTED, me + "flip-flop decoding (kind " + std::to_string(kind) + ", model " +
                        std::to_string(model) + "): the network's output is a CTC table");
-    if (kind != PO_KIND_POREOVER && kind != PO_KIND_BONITO) return po_fail(PO_E_ARG, "po_basecall_batch_h: kind " + std::to_string(kind));
-    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, "po_basecall_batch_h: model " + std::to_string(model));
-    if (beam_width > 64) return po_fail(PO_E_ARG, "po_basecall_batch_h: beam_width " + std::to_string(beam_width) + " (at most 64)");
+    if (kind != PO_KIND_POREOVER && kind != PO_KIND_BONITO) return po_fail(PO_E_ARG, me + "kind " + std::to_string(kind));
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, me + "model " + std::to_string(model));
+    if (beam_width > 64) return po_fail(PO_E_ARG, me + "beam_width " + std::to_string(beam_width) + " (at most 64)");
     if (alphabet && std::strlen(alphabet) != NOUT - 1)
-        return po_fail(PO_E_ARG, std::string("po_basecall_batch_h: alphabet \"") + alphabet + "\" (4 symbols: the network has 5 outputs)");
+        return po_fail(PO_E_ARG, me + "alphabet \"" + alphabet + "\" (4 symbols: the network has 5 outputs)");
     // the model and the weights' length: po_call_batch's own checks, which come before it looks at a buffer (no windows:
     // the pointers are not followed)
     rc = po_call_batch(weights_h, 0, window, layers_h, n_layers, weights_h, n_weights, (float*)weights_h, nullptr, nullptr, 0,
                        nullptr, nullptr);
     if (rc != PO_OK) return rc;
-    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + 6, 0.f);
+    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + n_stages, 0.f);
     if (n_reads == 0) return PO_OK;
 
     // ---- windows per pass: as many as ~4 GiB of pass buffers hold (po_call_batch_h's rule), whole recurrence tiles
@@ -148,8 +309,13 @@ extern "C" int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off
     const size_t wsb2 = beam_width <= 0 ? po_viterbi_workspace_bytes(n_reads, rows, NOUT, kind)
                                         : po_beam1d_workspace_bytes(n_reads, rows, plan.max_rows, NOUT, beam_width, model);
     PO_HIPCHK(dws2.up(nullptr, wsb2));
+    FastqStages fs;
+    if (fq) {
+        rc = fs.prepare(n_reads, rows, kind, beam_width, out.cap);
+        if (rc != PO_OK) return rc;
+    }
 
-    Spans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr);
+    Spans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr), guides(stage_ms_h != nullptr), lattice(stage_ms_h != nullptr);
     WinArgs a;
     a.sig_off = dsoff; a.win_off = dwoff; a.win_read = dwread;
     a.W = window; a.S = plan.stride; a.O = overlap;
@@ -172,22 +338,64 @@ extern "C" int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off
     // the reference's f32 log-softmax of the logits, widened (decode.py:34-39), then the decoder over all reads at once
     PO_HIPCHK(stitch.mark(stream));
     rc = po_launch_ingest(dlog, dsoff, n_reads, NOUT, PO_INGEST_LOGITS_F32, nullptr, 0, rows, dy, stream);
-    if (rc != PO_OK) return po_fail(rc, "po_basecall_batch_h: ingest");
+    if (rc != PO_OK) return po_fail(rc, me + "ingest");
     PO_HIPCHK(stitch.mark(stream));
     PO_HIPCHK(hipGetLastError());
     PO_HIPCHK(decode.mark(stream));
-    rc = beam_width <= 0 ? po_viterbi_batch(dy, dsoff, n_reads, NOUT, alphabet, kind, nullptr, out.seq, out.off, out.len, nullptr,
-                                            out.status, dws2, wsb2, stream)
+    rc = beam_width <= 0 ? po_viterbi_batch(dy, dsoff, n_reads, NOUT, alphabet, kind, nullptr, out.seq, out.off, out.len,
+                                            fq && !fs.second ? fs.map.as<int32_t>() : nullptr, out.status, dws2, wsb2, stream)
                          : po_beam1d_batch(dy, dsoff, n_reads, NOUT, alphabet, beam_width, model, out.seq, out.off, out.len,
                                            out.status, dws2, wsb2, stream);
     if (rc != PO_OK) return rc;
     PO_HIPCHK(decode.mark(stream));
+    if (fq) {   // the quality stages, on the table, the strings and (Viterbi) the frame map the decoder left on the device
+        PO_HIPCHK(guides.mark(stream));
+        rc = fs.guides(name, *fq, dy, dsoff, n_reads, rows, alphabet, kind, beam_width, out, stream);
+        if (rc != PO_OK) return rc;
+        PO_HIPCHK(guides.mark(stream));
+        PO_HIPCHK(lattice.mark(stream));
+        rc = fs.lattice(*fq, dy, dsoff, n_reads, rows, plan.max_rows, alphabet, kind, out, stream);
+        if (rc != PO_OK) return rc;
+        PO_HIPCHK(lattice.mark(stream));
+    }
     PO_HIPCHK(hipStreamSynchronize(stream));
     if (stage_ms_h) {
         stage_ms_h[4] = stitch.total();
         stage_ms_h[5] = decode.total();
+        if (fq) {
+            stage_ms_h[6] = guides.total();
+            stage_ms_h[7] = lattice.total();
+        }
     }
     PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
     PO_HIPCHK(dlog.down(logits_h, (size_t)rows * NOUT * 4));
+    if (fq) {
+        rc = fs.down(*fq, seq_off_h, n_reads, rows, out.cap);
+        if (rc != PO_OK) return rc;
+    }
     return PO_OK;
+}
+
+}  // namespace
+
+extern "C" int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                   const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                   const char* alphabet, int kind, int beam_width, int model, int max_windows_per_pass,
+                                   char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                                   float* logits_h, float* stage_ms_h) {
+    return basecall_impl("po_basecall_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
+                         n_weights, alphabet, kind, beam_width, model, max_windows_per_pass, seq_h, seq_off_h, seq_len_h, status_h,
+                         logits_h, stage_ms_h, nullptr);
+}
+
+extern "C" int po_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                         const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                         const char* alphabet, int kind, int beam_width, int model, int max_windows_per_pass,
+                                         char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                                         float* logits_h, int band_size, char* qual_h, int32_t* qual_status_h, double* odds_h,
+                                         int32_t* guide_h, float* stage_ms_h) {
+    const FastqOut fq = {band_size, qual_h, qual_status_h, odds_h, guide_h};
+    return basecall_impl("po_basecall_fastq_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
+                         n_weights, alphabet, kind, beam_width, model, max_windows_per_pass, seq_h, seq_off_h, seq_len_h, status_h,
+                         logits_h, stage_ms_h, &fq);
 }

@@ -35,10 +35,10 @@ struct PoBasecallPlan {
 };
 
 // Checks window, overlap, the signal offsets and (where given) the sequence capacities, then fills *p.  Returns PO_OK, or
-// PO_E_ARG / PO_E_CAP with *err naming the value.  Touches no device.
+// PO_E_ARG / PO_E_CAP with *err naming the value under the name of the entry that asks.  Touches no device.
 inline int po_basecall_make_plan(const int64_t* sig_off_h, int n_reads, int window, int overlap, const int64_t* seq_off_h,
-                                 PoBasecallPlan* p, std::string* err) {
-    const std::string me = "po_basecall_batch_h: ";
+                                 PoBasecallPlan* p, std::string* err, const char* entry = "po_basecall_batch_h") {
+    const std::string me = std::string(entry) + ": ";
     if (window < 1) { *err = me + "window " + std::to_string(window) + " (at least 1)"; return PO_E_ARG; }
     if (overlap < 0 || overlap >= window || (overlap & 1)) {
         *err = me + "overlap " + std::to_string(overlap) + " (even, 0 <= overlap < window " + std::to_string(window) + ")";

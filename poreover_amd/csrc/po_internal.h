@@ -109,6 +109,21 @@ int po_launch_gamma(const double* y1, const int64_t* y1_off, const double* y2, c
 // po_ingest.hip
 int po_launch_ingest(const void* src, const int64_t* row_off, int n, int C, int mode, const int* perm, int reverse,
                      int64_t total_rows, double* out, hipStream_t stream);
+
+// po_fastq.hip (enqueue only; the rules are po_fastq_rules.h's)
+int po_launch_fastq_mode(const char* seq, const int32_t* len, const char* vseq, const int32_t* vlen, const int32_t* vstatus,
+                         const int64_t* seq_off, int n, int32_t* mode, hipStream_t stream);
+int po_launch_fastq_gather(const char* src0, const char* src1, const int64_t* src_off, const int32_t* item, int per,
+                           const int64_t* dst_off, int n_strings, int64_t total, char* dst, hipStream_t stream);
+int po_launch_fastq_consumed(const char* aln1, const char* aln2, const int64_t* aln_off, const int32_t* ncol,
+                             const int32_t* aln_status, int n_pairs, const int32_t* pair_read, const int64_t* out_off,
+                             const int32_t* called_len, const int32_t* label_len, int32_t* consumed, int32_t* mode,
+                             hipStream_t stream);
+int po_launch_fastq_guide(const int32_t* map, const int32_t* consumed, const int64_t* y_off, int n, int64_t rows,
+                          const int32_t* called_len, const int32_t* label_len, const int32_t* mode, int32_t* guide,
+                          hipStream_t stream);
+int po_launch_fastq_phred(const double* odds, const char* labels, const int64_t* label_off, const int32_t* qstatus,
+                          const int64_t* out_off, int n, int64_t total, const char* alphabet, char* qual, hipStream_t stream);
 }  // extern "C"
 
 // ---- The pair-beam launch layer: po_beam2d_route.hip owns every process-wide setting and chooses the kernel family; po_beam2d.hip and

@@ -3,7 +3,9 @@
 What `call` followed by `decode` does, without the trip of every frame's probabilities to the host, to a file and back:
 po_basecall_batch_h (poreover_amd/csrc/po_basecall.hip) uploads each read's scaled signal once, cuts it into windows on
 the device, runs the network (po_call.hip), stitches the kept frames' logits, takes their log-softmax and decodes them
-(Viterbi or the 1-D beam search); the strings come back.
+(Viterbi or the 1-D beam search); the strings come back.  With qualities (`--fastq`)
+po_basecall_fastq_batch_h goes on from there on the device: the Viterbi frame map, the band guides, the quality lattice
+of po_qual.hip on the table that is already resident, and the Phred characters.
 
 Windows and stitching.  For a read of L >= 1 samples, window W >= 1 and overlap O (even, 0 <= O < W), S = W - O:
   - the read has n = 1 window if L <= W, else n = 1 + ceil((L - W) / S);
@@ -67,15 +69,69 @@ def check_time_order(kinds):
                                 % (len(back), ", ".join(map(str, back))))
 
 
-def _bytes_per_sample(lib, beam_width, model):
+def _bytes_per_sample(lib, beam_width, model, qual_band=None):
     """resident device bytes per signal sample of one engine call: signal f32, logits 5 x f32, table 5 x f64, one
-    character, and the decoder's workspace per row (the beam search's node arena; Viterbi's is a constant)"""
+    character, and the decoder's workspace per row (the beam search's node arena; Viterbi's is a constant).  With
+    qualities (qual_band not None): the frame map and the guide (int32 each), the quality characters, the dense labels
+    and their odds (5 x f64 per base, a base per sample at most), the Viterbi call where it is not the decode itself, for
+    the beam search its consumed counts, and for a band the lattice's stored rows as po_qual_workspace_bytes counts them
+    (without a band they are not per sample: _qual_rows_bytes).  The aligner's workspace (~4 GiB at most, the entry's own bound) comes on top."""
     b = 4 + ckpt.NUM_LABELS * 4 + ckpt.NUM_LABELS * 8 + 1
+    rows = 1 << 20
     if beam_width > 0:
-        rows = 1 << 20
         ws = lib.po_beam1d_workspace_bytes(1, rows, rows, ckpt.NUM_LABELS, beam_width, model)
         b += -(-int(ws) // rows)
+    if qual_band is not None:
+        b += 4 + 4 + 1 + 1 + ckpt.NUM_LABELS * 8 + 1 + (4 if beam_width > 0 else 0)
+        if qual_band > 0:
+            b += -(-int(lib.po_qual_workspace_bytes(1, rows, rows, rows, int(qual_band), model)) // rows)
     return b
+
+
+def _qual_rows_bytes(lib, n, total, longest, model):
+    """the unbanded lattice's workspace for n reads of `total` samples, the longest of `longest`, in one call: a base per
+    sample at most"""
+    return int(lib.po_qual_workspace_bytes(n, total, longest, total, 0, model))
+
+
+def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, want_logits=False, want_odds=False,
+                want_guides=False, stage_ms=None, max_windows_per_pass=0):
+    """One po_basecall_fastq_batch_h call.  Returns a dict: strings, quals (uint8 Phred arrays), qual_status int32 (n,),
+    and where asked for logits, odds (float64 (L, 5) per read) and guides (int32 (T,) per read; None for band <= 0)."""
+    n = len(sigs)
+    off = _marshal.offsets([len(s) for s in sigs])
+    rows = int(off[-1])
+    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
+    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+    layers = _layers_array(net)
+    seq = np.zeros(rows, dtype=np.uint8)
+    qual = np.zeros(rows, dtype=np.uint8)
+    lens = np.zeros(n, dtype=np.int32)
+    st = np.zeros(n, dtype=np.int32)
+    qst = np.zeros(n, dtype=np.int32)
+    lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
+    od = np.zeros((rows, 5), dtype=np.float64) if want_odds else None
+    gd = np.zeros(rows, dtype=np.int32) if want_guides and band > 0 else None
+    ms = (C.c_float * 8)() if stage_ms is not None else None
+    rc = lib.po_basecall_fastq_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
+                                       w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
+                                       seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
+                                       lg.ctypes.data if want_logits else None, int(band), qual.ctypes.data, qst.ctypes.data,
+                                       od.ctypes.data if od is not None else None, gd.ctypes.data if gd is not None else None, ms)
+    _lib.check(rc, "po_basecall_fastq_batch_h")
+    _marshal.raise_on_status(st, n, "basecall of read")
+    if stage_ms is not None:
+        for k, name in enumerate(_lib.BASECALL_FASTQ_STAGES):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+    res = {"strings": _marshal.strings(seq, off, lens), "qual_status": qst,
+           "quals": [qual[off[i]:off[i] + lens[i]] - 33 for i in range(n)]}
+    if want_logits:
+        res["logits"] = [lg[off[i]:off[i + 1]] for i in range(n)]
+    if want_odds:
+        res["odds"] = [od[off[i]:off[i] + lens[i]].copy() for i in range(n)]
+    if want_guides:
+        res["guides"] = [gd[off[i]:off[i + 1]] for i in range(n)] if gd is not None else None
+    return res
 
 
 def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass):
@@ -105,14 +161,36 @@ def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_
     return strings
 
 
+def _groups(todo, lens, fits):
+    """todo in input order, cut into runs: a read joins the run while fits(reads, samples, longest read) holds for the run
+    with it; a read that does not fit alone goes alone"""
+    out, group, total, longest = [], [], 0, 0
+    for i in todo:
+        if group and not fits(len(group) + 1, total + lens[i], max(longest, lens[i])):
+            out.append(group)
+            group, total, longest = [], 0, 0
+        group.append(i)
+        total += lens[i]
+        longest = max(longest, lens[i])
+    if group:
+        out.append(group)
+    return out
+
+
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
-                     logits=False, stage_ms=None, max_windows_per_pass=0):
+                     logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None):
     """The decoded string of each scaled signal, in input order — or (string, (len(s), 5) float32 stitched logits) with
-    logits=True.  algorithm "viterbi" or "beam" (beam_width); merge_repeats: the decoder of a network trained with
+    logits=True.  qualities=True adds a uint8 (len(string),) array of Phred values as the last item: (string, q) or
+    (string, logits, q), from the quality lattice (poreover_amd.quality) within qual_band label positions of the call's
+    frames (None: quality.DEFAULT_BAND; <= 0: no band).  A read whose banded lattice is lost (E_ENVELOPE) goes through a
+    second engine call without a band (a window's bits do not depend on its call: the string is the same); one that is
+    still unscored gets Q 0 and a line in the log (quality.warn_unscored).  algorithm "viterbi" or "beam" (beam_width);
+    merge_repeats: the decoder of a network trained with
     ctc_merge_repeated (the ctc_merge_repeats tree / the bonito-kind Viterbi; the network's blank is already last, so no
     column moves).  A read without samples gets "" and never reaches the device.  Reads go to the engine in groups, in
     input order, of at most RESIDENT_BYTES // (resident bytes per sample) samples — a single longer read goes alone;
-    stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES)."""
+    stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES; with qualities
+    _lib.BASECALL_FASTQ_STAGES)."""
     if algorithm not in ("viterbi", "beam"):
         raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
     if algorithm == "beam" and not 1 <= beam_width <= 64:
@@ -121,6 +199,8 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     check_time_order(net.kinds)
     sigs = [np.asarray(s, dtype=np.float32).ravel() for s in signals]
     empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
+    if qualities:
+        empty = (empty if logits else (empty,)) + (np.zeros(0, dtype=np.uint8),)
     out = [empty] * len(sigs)
     todo = [i for i, s in enumerate(sigs) if len(s)]
     if not todo:
@@ -129,24 +209,55 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     kind = _lib.KINDS["bonito" if merge_repeats else "poreover"]
     model = _lib.MODELS["ctc_merge_repeats" if merge_repeats else "ctc"]
     bw = int(beam_width) if algorithm == "beam" else 0
-    budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
-    group, held = [], 0
-    for i in todo + [None]:
-        if group and (i is None or held + len(sigs[i]) > budget):
+    lens = [len(s) for s in sigs]
+    if not qualities:
+        budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
+        for group in _groups(todo, lens, lambda n, total, longest: total <= budget):
             res = _engine_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, logits, stage_ms,
                                max_windows_per_pass)
             for k, r in zip(group, res):
                 out[k] = r
-            group, held = [], 0
-        if i is not None:
-            group.append(i)
-            held += len(sigs[i])
+        return out
+
+    from .. import quality
+    band = quality.DEFAULT_BAND if qual_band is None else int(qual_band)
+
+    def fits(band_):
+        per = _bytes_per_sample(lib, bw, model, band_)
+        if band_ > 0:
+            return lambda n, total, longest: total * per <= RESIDENT_BYTES
+        return lambda n, total, longest: total * per + _qual_rows_bytes(lib, n, total, longest, model) <= RESIDENT_BYTES
+
+    def run(reads, band_, want_logits):
+        for group in _groups(reads, lens, fits(band_)):
+            r = _fastq_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, band_, want_logits=want_logits,
+                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass)
+            for j, k in enumerate(group):
+                yield k, r, j
+
+    strings, quals, status, lgs = {}, {}, {}, {}
+    for k, r, j in run(todo, band, logits):
+        strings[k], quals[k], status[k] = r["strings"][j], r["quals"][j], int(r["qual_status"][j])
+        if logits:
+            lgs[k] = r["logits"][j]
+    retry = [k for k in todo if status[k] == _lib.E_ENVELOPE] if band > 0 else []
+    for k, r, j in run(retry, 0, False):
+        if r["strings"][j] != strings[k]:
+            raise RuntimeError("basecall_signals: read %d decodes differently in the unbanded retry" % k)
+        quals[k], status[k] = r["quals"][j], int(r["qual_status"][j])
+    bad = [k for k in todo if status[k] != 0]
+    if bad:
+        quality.warn_unscored(["read %d (%s)" % (k, _lib._CODE_NAMES.get(status[k], status[k])) for k in bad])
+    for k in todo:
+        q = quals[k] if status[k] == 0 else np.zeros(len(strings[k]), dtype=np.uint8)
+        out[k] = (strings[k], lgs[k], q) if logits else (strings[k], q)
     return out
 
 
 def basecall(args):
     """`poreover_amd basecall IN`: IN is a FAST5 file or a directory of *.fast5; writes {out}.fasta, one record per file
-    in sorted file order, named by the file's stem or (--use_id) by the read id"""
+    in sorted file order, named by the file's stem or (--use_id) by the read id; with --fastq also {out}.fastq, the same
+    records with a Phred quality per base"""
     from ..decoding.decode import fasta_format
     check_window_args(args.window, args.overlap)
     if getattr(args, "weights", None) is None:
@@ -163,15 +274,27 @@ def basecall(args):
     if not files:
         raise SystemExit("basecall: no *.fast5 files in %s" % src)
     parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
+    fastq = bool(getattr(args, "fastq", False))
     seqs = basecall_signals(net, [s for _, s in parsed], window=args.window, overlap=args.overlap, algorithm=args.algorithm,
-                            beam_width=args.beam_width, merge_repeats=args.merge_repeats)
+                            beam_width=args.beam_width, merge_repeats=args.merge_repeats, qualities=fastq,
+                            qual_band=getattr(args, "qual_band", None))
+    quals = [q for _, q in seqs] if fastq else None
+    seqs = [s for s, _ in seqs] if fastq else seqs
+    names = []
+    for path, (rid, _) in zip(files, parsed):
+        if args.use_id:
+            names.append(rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid))
+        else:
+            names.append(Path(path).stem)
     out_path = args.out + ".fasta"
     with open(out_path, "w") as f:
-        for path, (rid, _), s in zip(files, parsed, seqs):
-            if args.use_id:
-                name = rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid)
-            else:
-                name = Path(path).stem
+        for name, s in zip(names, seqs):
             print(fasta_format(name, s), file=f)
     logging.info("basecall: %d read(s) -> %s", len(files), out_path)
+    if fastq:
+        from ..quality import fastq_format
+        with open(args.out + ".fastq", "w") as f:
+            for name, s, q in zip(names, seqs, quals):
+                f.write(fastq_format(name, s, q))
+        logging.info("basecall: %d read(s) -> %s", len(files), args.out + ".fastq")
     return out_path
