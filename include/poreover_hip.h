@@ -541,6 +541,44 @@ int po_fastq_consumed_h(const char* aln1_h, const char* aln2_h, const int64_t* a
 int po_fastq_phred_h(const double* odds_h, const char* labels_h, const int64_t* label_off_h, int n, const char* alphabet,
                      const int32_t* qual_status_h, char* qual_h);
 
+/* ---- `pair-basecall`: scaled signals and a list of read pairs to 1D2 consensus strings in one device-resident pass
+ *  -----------------------------------------------------------------------------------------------
+ * po_basecall_batch_h's network part (the same windows, passes and stitched logits, bit for bit), then, on the same stream
+ * and on the logits that are on the device already: the two pair-major float64 tables of po_pair_decode_batch (the
+ * log-softmax of po_ingest_batch, PO_INGEST_LOGITS_F32; read 2 time-reversed with columns [3,2,1,0,4] where
+ * reverse_complement is set) and po_pair_decode_batch itself.  Each read's signal goes up once, however many pairs name
+ * it and on whichever side; the strings come down; nothing per frame returns to the host in between (unless logits_h asks).
+ *   - signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass:
+ *                as for po_basecall_batch_h, with its refusals and messages (every read needs a sample, named or not)
+ *   - pair_idx_h: int32[2 * n_pairs]; pair i = reads pair_idx_h[2i] (read 1) and pair_idx_h[2i + 1] (read 2).  An index
+ *                outside [0, n_reads) is PO_E_ARG naming the pair; n_pairs < 0 is PO_E_ARG; n_pairs == 0 is PO_OK and
+ *                writes no output
+ *   - reverse_complement: 0 or 1 (transducer.reverse_complement of read 2, pair_decode.py:323-329)
+ *   - opt:       as for po_pair_decode_batch; model PO_MODEL_CTC or PO_MODEL_MERGE.  PO_MODEL_FLIPFLOP is PO_E_UNSUPPORTED
+ *                (the network emits a CTC table, blank last); beam_width outside 1..25 and an unknown method are PO_E_ARG
+ *   - seq1d_h, seq1d_off_h (2 n_pairs + 1 entries, from 0), len1_h, len2_h, identity_h, seq_h, seq_off_h (from 0),
+ *                seq_len_h, status_h: as po_pair_decode_batch_h writes them, PO_SKIP_LENGTH / PO_SKIP_IDENTITY included.
+ *                A read's room in seq1d must be at least its number of samples, and seq_off_h must not decrease
+ *                (PO_E_CAP naming the pair otherwise); a consensus longer than its room is that pair's PO_E_CAP status
+ *   - logits_h (or NULL): the stitched Dense outputs, (sig_off_h[n_reads], 5) f32, read after read
+ *   - stage_ms_h (or NULL): float[6] device milliseconds, SET by the call: [0..3] po_call_batch's stages summed over the
+ *                passes, [4] window gather + stitch + pair tables, [5] po_pair_decode_batch as a whole
+ * Every argument error is answered before the first device allocation.  One device, one stream, synchronous. */
+int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                             const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                             int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                             const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                             int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
+                             int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h);
+
+/* The table stage of the above alone, on host buffers.  logits_h: (row_off_h[n_reads], 5) f32, read-major; row_off_h from
+ * 0, non-decreasing; a read that a pair names needs a row (PO_E_ARG naming the pair).  y1_h / y2_h get, pair after pair, the
+ * rows of each pair's first / second read: x - logsumexp(x) per row in float32, widened (po_ingest_batch's bits); table 2
+ * time-reversed inside each pair where reverse2 is set, its columns through perm2_h (5 ints or NULL: out[:, c] =
+ * value[:, perm2_h[c]]).  The caller sizes y1_h / y2_h: 5 float64 per row of the pairs' first / second reads. */
+int po_pair_tables_h(const float* logits_h, const int64_t* row_off_h, int n_reads, const int32_t* pair_idx_h, int n_pairs,
+                     int reverse2, const int* perm2_h, double* y1_h, double* y2_h);
+
 /* ---- CTC training of the basecalling network (`train`) -------------------------------------------
  * Replaces the reference's TensorFlow training step (train_ctc_model, network.py:78-131): the forward pass above,
  * tf.compat.v1.nn.ctc_loss (blank = class 4, softmax inside the loss) averaged over the batch, its gradient and Keras

@@ -1,7 +1,8 @@
 """`python -m poreover_amd train|call|decode|pair-decode|benchmark ...` — the five sub-commands of the reference CLI
-(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine — and two the reference lacks:
-`find-pairs`, the list of read pairs `pair-decode` starts from, and `basecall`, FAST5 to FASTA in one
-device-resident pass with overlapping windows.  `train` runs CTC
+(reference __main__.py:19-99) with the same flags and defaults, on the GPU engine — and three the reference lacks:
+`find-pairs`, the list of read pairs `pair-decode` starts from, `basecall`, FAST5 to FASTA in one
+device-resident pass with overlapping windows, and `pair-basecall`, FAST5 pairs to their 1D² consensus in
+one such pass.  `train` runs CTC
 training of the basecalling network in HIP and writes .npz checkpoints; `call` runs the network's forward pass and needs
 `--weights` (no weights ship with this package: a TF checkpoint prefix or directory, a `train` output directory, or an
 .npz from `python -m poreover_amd.network.convert`).  `benchmark` maps decoded reads to a reference genome with the
@@ -70,6 +71,33 @@ def build_parser():
     p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="basecall")
+
+    p = subparsers.add_parser('pair-basecall', help='1D2 consensus of FAST5 read pairs: the network and the pair decoder in one pass on the GPU',
+                              formatter_class=argparse.ArgumentDefaultsHelpFormatter)
+    p.add_argument('in', help='List of read pairs: two read names per line, as find-pairs writes them')
+    p.add_argument('--dir', default='.', help='Directory of the FAST5 files the pairs name (a .npy or .fast5 suffix, or none, is replaced by .fast5)')
+    p.add_argument('--weights', default=None, help='Trained weights to load into model: a TF checkpoint prefix, a directory (loads latest from its checkpoint file) or an .npz (required: no weights ship with this package)')
+    p.add_argument('--model', help='Model config JSON file (default: conv1_bigru3)', default=None)
+    p.add_argument('--scaling', default='standard', choices=['standard', 'current', 'median', 'rescale'], help='Type of preprocessing (should be same as training)')
+    p.add_argument('--window', type=int, default=1000, help='Call read using chunks of this size')
+    p.add_argument('--overlap', type=int, default=0, help='Samples that consecutive chunks share (even, smaller than --window); each chunk keeps its middle')
+    p.add_argument('--reverse_complement', default=False, action='store_true', help='Whether to reverse complement the second sequence')
+    p.add_argument('--merge_repeats', default=False, action='store_true', help='Decode as CTC with merged repeats (for weights trained with --ctc_merge_repeated)')
+    p.add_argument('--beam_width', type=int, default=5, help='Width for beam search')
+    p.add_argument('--padding', type=int, default=5, help='Padding for building alignment envelope')
+    p.add_argument('--alignment', default='banded', choices=['banded', 'full'], help='Do full Needleman-Wunsch alignment between 1D basecalls to build envelope')
+    p.add_argument('--diagonal_envelope', action='store_true', help='Use a simple diagonal band for the signal alignment envelope')
+    p.add_argument('--diagonal_width', type=int, default=50, help='Width of diagonal band envelope')
+    p.add_argument('--beam_search_method', choices=['row', 'row_col', 'grid'], default="row_col", help=argparse.SUPPRESS)
+    p.add_argument('--out', default='out', help='Prefix for FASTA sequence output')
+    # what pair-decode offers and this route does not: parsed so that each is refused by name (pair_basecall.check_args)
+    p.add_argument('--fastq', action='store_true', default=False, help=argparse.SUPPRESS)
+    p.add_argument('--single', default='viterbi', help=argparse.SUPPRESS)
+    p.add_argument('--skip_matches', action='store_true', default=False, help=argparse.SUPPRESS)
+    p.add_argument('--method', default='envelope', help=argparse.SUPPRESS)
+    p.add_argument('--threads', type=int, default=1, help=argparse.SUPPRESS)
+    p.add_argument('-v', '--version', action='version', version=__version__)
+    p.set_defaults(func="pair-basecall")
 
     p = subparsers.add_parser('decode', help='Decode basecaller probabilities to a FASTA file')
     p.add_argument('in', nargs='+', help='Probabilities to decode (.npy from PoreOver/Bonito, .csv, or HDF5/FAST5 from Flappie/Guppy)')
@@ -157,6 +185,11 @@ def main(argv=None):
     if args.func == "basecall":
         from .network import basecall as _basecall
         _basecall.basecall(args)
+        print(args, file=sys.stderr)
+        return
+    if args.func == "pair-basecall":
+        from .network import pair_basecall as _pair_basecall
+        _pair_basecall.pair_basecall(args)
         print(args, file=sys.stderr)
         return
     if args.func == "find-pairs":

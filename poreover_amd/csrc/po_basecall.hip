@@ -12,6 +12,9 @@
 // Both are streaming copies, one lane per f32 value of the pass, consecutive lanes on consecutive addresses on the pass's
 // side and on runs of consecutive addresses on the reads' side; every output value has one writer.
 //
+// The buffers of the network part and its pass loop (gather -> po_call_batch -> stitch) are PoBasecallPasses
+// (po_basecall_pass.h), defined here and run by po_pair_basecall.hip too: one loop, the same logits bits in both.
+//
 // po_basecall_fastq_batch_h (`basecall --fastq`) is the same body followed by the quality stages on the
 // same stream: FastqStages below enqueues them (kernels: po_fastq.hip, the lattice: po_qual.hip) on the table and the
 // strings the decoder left on the device.
@@ -20,9 +23,8 @@
 #include <string>
 #include <vector>
 
-#include "po_basecall_plan.h"
+#include "po_basecall_pass.h"
 #include "po_fastq_rules.h"
-#include "po_hostbuf.h"
 
 namespace {
 
@@ -69,27 +71,57 @@ __global__ __launch_bounds__(256) void window_stitch_kernel(WinArgs a, const flo
 
 unsigned grid_for(int64_t count) { return (unsigned)std::min<int64_t>((count + 255) / 256, 256 * 64); }
 
-// event pairs on the call's stream, summed into one figure at the end (only where stage times are asked for)
-struct Spans {
-    std::vector<hipEvent_t> ev;
-    bool on;
-    explicit Spans(bool on_) : on(on_) {}
-    ~Spans() { for (auto e : ev) (void)hipEventDestroy(e); }
-    hipError_t mark(hipStream_t s) {
-        if (!on) return hipSuccess;
-        hipEvent_t e = nullptr;
-        hipError_t rc = hipEventCreate(&e);
-        if (rc != hipSuccess) return rc;
-        ev.push_back(e);
-        return hipEventRecord(e, s);
+}  // namespace
+
+int PoBasecallPasses::up(const PoBasecallPlan& plan, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window,
+                         const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                         int max_windows_per_pass) {
+    // ---- windows per pass: as many as ~4 GiB of pass buffers hold (po_call_batch_h's rule), whole recurrence tiles
+    const size_t per_window = po_call_workspace_bytes(1, window, layers_h, n_layers) + (size_t)window * NOUT * 4 * 2 + (size_t)window * 4;
+    chunk = (int64_t)std::max<size_t>(1, ((size_t)4 << 30) / per_window);
+    if (chunk >= TILE) chunk = chunk / TILE * TILE;
+    if (max_windows_per_pass > 0) chunk = std::min<int64_t>(chunk, max_windows_per_pass);   // (a smaller bound: the tests')
+    chunk = std::min<int64_t>(chunk, plan.windows);
+    const int64_t Mc = chunk * window;
+    ws_bytes = po_call_workspace_bytes((int)chunk, window, layers_h, n_layers);
+    PO_HIPCHK(w.up(weights_h, (size_t)n_weights * 4));
+    PO_HIPCHK(sig.up(signal_h, (size_t)plan.rows * 4));             // each read's signal once, whatever the overlap
+    PO_HIPCHK(sig_off.up(sig_off_h, sizeof(int64_t) * ((size_t)n_reads + 1)));
+    PO_HIPCHK(win_off.up(plan.win_off.data(), sizeof(int64_t) * plan.win_off.size()));
+    PO_HIPCHK(win_read.up(plan.win_read.data(), sizeof(int32_t) * plan.win_read.size()));
+    PO_HIPCHK(win.up(nullptr, (size_t)Mc * 4));
+    PO_HIPCHK(prob.up(nullptr, (size_t)Mc * NOUT * 4));
+    PO_HIPCHK(plog.up(nullptr, (size_t)Mc * NOUT * 4));
+    PO_HIPCHK(ws.up(nullptr, ws_bytes));
+    PO_HIPCHK(logits.up(nullptr, (size_t)plan.rows * NOUT * 4));
+    return PO_OK;
+}
+
+int PoBasecallPasses::run(const PoBasecallPlan& plan, int window, int overlap, const po_call_layer* layers_h, int n_layers,
+                          int64_t n_weights, hipStream_t stream, float* stage_ms_h, PoSpans& stitch) {
+    WinArgs a;
+    a.sig_off = sig_off; a.win_off = win_off; a.win_read = win_read;
+    a.W = window; a.S = plan.stride; a.O = overlap;
+    for (int64_t w0 = 0; w0 < plan.windows; w0 += chunk) {
+        const int nc = (int)std::min<int64_t>(chunk, plan.windows - w0);
+        a.w0 = w0;
+        a.count = (int64_t)nc * window;
+        PO_HIPCHK(stitch.mark(stream));
+        hipLaunchKernelGGL(window_gather_kernel, dim3(grid_for(a.count)), dim3(256), 0, stream, a, sig.as<float>(), win.as<float>());
+        PO_HIPCHK(stitch.mark(stream));
+        PO_HIPCHK(hipGetLastError());
+        const int rc = po_call_batch(win, nc, window, layers_h, n_layers, w, n_weights, prob, plog, ws, ws_bytes, stream, stage_ms_h);
+        if (rc != PO_OK) return rc;
+        a.count = (int64_t)nc * window * NOUT;
+        PO_HIPCHK(stitch.mark(stream));
+        hipLaunchKernelGGL(window_stitch_kernel, dim3(grid_for(a.count)), dim3(256), 0, stream, a, plog.as<float>(), logits.as<float>());
+        PO_HIPCHK(stitch.mark(stream));
+        PO_HIPCHK(hipGetLastError());
     }
-    float total() const {   // after a synchronise
-        float sum = 0.f, ms = 0.f;
-        for (size_t i = 0; i + 1 < ev.size(); i += 2)
-            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) sum += ms;
-        return sum;
-    }
-};
+    return PO_OK;
+}
+
+namespace {
 
 // what po_basecall_fastq_batch_h adds to po_basecall_batch_h's arguments
 struct FastqOut {
@@ -281,30 +313,15 @@ int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_of
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + n_stages, 0.f);
     if (n_reads == 0) return PO_OK;
 
-    // ---- windows per pass: as many as ~4 GiB of pass buffers hold (po_call_batch_h's rule), whole recurrence tiles
-    const size_t per_window = po_call_workspace_bytes(1, window, layers_h, n_layers) + (size_t)window * NOUT * 4 * 2 + (size_t)window * 4;
-    int64_t chunk = (int64_t)std::max<size_t>(1, ((size_t)4 << 30) / per_window);
-    if (chunk >= TILE) chunk = chunk / TILE * TILE;
-    if (max_windows_per_pass > 0) chunk = std::min<int64_t>(chunk, max_windows_per_pass);   // (a smaller bound: the tests')
-    chunk = std::min<int64_t>(chunk, plan.windows);
-    const int64_t Mc = chunk * window;
-    const size_t wsb = po_call_workspace_bytes((int)chunk, window, layers_h, n_layers);
-
     hipStream_t stream = nullptr;
     const int64_t rows = plan.rows;
-    PoDev dw, dsig, dsoff, dwoff, dwread, dwin, dprob, dplog, dws, dlog, dy, dws2;
+    PoBasecallPasses net;
+    PoDev dy, dws2;
     PoSeqOut out;
-    PO_HIPCHK(dw.up(weights_h, (size_t)n_weights * 4));
-    PO_HIPCHK(dsig.up(signal_h, (size_t)rows * 4));             // each read's signal once, whatever the overlap
-    PO_HIPCHK(dsoff.up(sig_off_h, sizeof(int64_t) * ((size_t)n_reads + 1)));
-    PO_HIPCHK(dwoff.up(plan.win_off.data(), sizeof(int64_t) * plan.win_off.size()));
-    PO_HIPCHK(dwread.up(plan.win_read.data(), sizeof(int32_t) * plan.win_read.size()));
-    PO_HIPCHK(dwin.up(nullptr, (size_t)Mc * 4));
-    PO_HIPCHK(dprob.up(nullptr, (size_t)Mc * NOUT * 4));
-    PO_HIPCHK(dplog.up(nullptr, (size_t)Mc * NOUT * 4));
-    PO_HIPCHK(dws.up(nullptr, wsb));
-    PO_HIPCHK(dlog.up(nullptr, (size_t)rows * NOUT * 4));       // resident: the stitched logits ...
-    PO_HIPCHK(dy.up(nullptr, (size_t)rows * NOUT * 8));         // ... and the f64 log-probability table
+    rc = net.up(plan, signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
+    if (rc != PO_OK) return rc;
+    const PoDev &dsoff = net.sig_off, &dlog = net.logits;   // resident: the stitched logits ...
+    PO_HIPCHK(dy.up(nullptr, (size_t)rows * NOUT * 8));     // ... and the f64 log-probability table
     PO_HIPCHK(out.up(seq_off_h, n_reads));
     const size_t wsb2 = beam_width <= 0 ? po_viterbi_workspace_bytes(n_reads, rows, NOUT, kind)
                                         : po_beam1d_workspace_bytes(n_reads, rows, plan.max_rows, NOUT, beam_width, model);
@@ -315,26 +332,9 @@ int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_of
         if (rc != PO_OK) return rc;
     }
 
-    Spans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr), guides(stage_ms_h != nullptr), lattice(stage_ms_h != nullptr);
-    WinArgs a;
-    a.sig_off = dsoff; a.win_off = dwoff; a.win_read = dwread;
-    a.W = window; a.S = plan.stride; a.O = overlap;
-    for (int64_t w0 = 0; w0 < plan.windows; w0 += chunk) {
-        const int nc = (int)std::min<int64_t>(chunk, plan.windows - w0);
-        a.w0 = w0;
-        a.count = (int64_t)nc * window;
-        PO_HIPCHK(stitch.mark(stream));
-        hipLaunchKernelGGL(window_gather_kernel, dim3(grid_for(a.count)), dim3(256), 0, stream, a, dsig.as<float>(), dwin.as<float>());
-        PO_HIPCHK(stitch.mark(stream));
-        PO_HIPCHK(hipGetLastError());
-        rc = po_call_batch(dwin, nc, window, layers_h, n_layers, dw, n_weights, dprob, dplog, dws, wsb, stream, stage_ms_h);
-        if (rc != PO_OK) return rc;
-        a.count = (int64_t)nc * window * NOUT;
-        PO_HIPCHK(stitch.mark(stream));
-        hipLaunchKernelGGL(window_stitch_kernel, dim3(grid_for(a.count)), dim3(256), 0, stream, a, dplog.as<float>(), dlog.as<float>());
-        PO_HIPCHK(stitch.mark(stream));
-        PO_HIPCHK(hipGetLastError());
-    }
+    PoSpans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr), guides(stage_ms_h != nullptr), lattice(stage_ms_h != nullptr);
+    rc = net.run(plan, window, overlap, layers_h, n_layers, n_weights, stream, stage_ms_h, stitch);
+    if (rc != PO_OK) return rc;
     // the reference's f32 log-softmax of the logits, widened (decode.py:34-39), then the decoder over all reads at once
     PO_HIPCHK(stitch.mark(stream));
     rc = po_launch_ingest(dlog, dsoff, n_reads, NOUT, PO_INGEST_LOGITS_F32, nullptr, 0, rows, dy, stream);

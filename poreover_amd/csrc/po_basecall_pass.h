@@ -1,0 +1,52 @@
+// The network part of `basecall`, once: the buffers and the pass loop window_gather_kernel -> po_call_batch ->
+// window_stitch_kernel that leave the stitched logits of every read on the device (po_basecall.hip defines it).
+// po_basecall_batch_h, po_basecall_fastq_batch_h and po_pair_basecall_batch_h (po_pair_basecall.hip) all run this loop, so
+// a window's logits are the same bits in each.  Host only, hidden: nothing here is part of the library's symbol table.
+#pragma once
+#include <vector>
+
+#include "po_basecall_plan.h"
+#include "po_hostbuf.h"
+
+#pragma GCC visibility push(hidden)
+
+// event pairs on the call's stream, summed into one figure at the end (only where stage times are asked for)
+struct PoSpans {
+    std::vector<hipEvent_t> ev;
+    bool on;
+    explicit PoSpans(bool on_) : on(on_) {}
+    PoSpans(const PoSpans&) = delete;
+    PoSpans& operator=(const PoSpans&) = delete;
+    ~PoSpans() { for (auto e : ev) (void)hipEventDestroy(e); }
+    hipError_t mark(hipStream_t s) {
+        if (!on) return hipSuccess;
+        hipEvent_t e = nullptr;
+        hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+        ev.push_back(e);
+        return hipEventRecord(e, s);
+    }
+    float total() const {   // after a synchronise
+        float sum = 0.f, ms = 0.f;
+        for (size_t i = 0; i + 1 < ev.size(); i += 2)
+            if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) sum += ms;
+        return sum;
+    }
+};
+
+struct PoBasecallPasses {
+    PoDev w, sig, sig_off, win_off, win_read, win, prob, plog, ws, logits;   // logits: [rows][5] f32, read-major, resident
+    int64_t chunk = 0;      // windows per pass
+    size_t ws_bytes = 0;    // po_call_batch's workspace for a pass
+    // the weights, each read's signal (once, whatever the overlap), the plan's tables; the pass buffers and the logits.
+    // Windows per pass: as many as ~4 GiB of pass buffers hold (po_call_batch_h's rule), whole recurrence tiles;
+    // max_windows_per_pass > 0: at most that many.  plan.windows >= 1.
+    int up(const PoBasecallPlan& plan, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window,
+           const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights, int max_windows_per_pass);
+    // enqueues every pass on `stream`; stage_ms_h (or NULL): po_call_batch's four stages, added; the gather and stitch
+    // kernels are bracketed in `stitch`
+    int run(const PoBasecallPlan& plan, int window, int overlap, const po_call_layer* layers_h, int n_layers, int64_t n_weights,
+            hipStream_t stream, float* stage_ms_h, PoSpans& stitch);
+};
+
+#pragma GCC visibility pop

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "po_device.h"
+#include "po_ingest_rules.h"
 #include "po_internal.h"
 
 namespace {
@@ -38,21 +39,7 @@ __global__ __launch_bounds__(64) void ingest_kernel(IGArgs a) {
         }
         double v[8];
         if (a.mode == 0) {
-            const float* x = (const float*)a.src + srow * C;
-            // scipy.special.logsumexp as shipped in this image (1.15.3, _logsumexp.py): the maximal elements leave
-            // the sum (cnt of them), s = sum of exp(x - max) over the others in index order (numpy adds fewer than
-            // 8 elements sequentially; the maximal ones contribute exp(-inf) = +0), lse = log1p(s / cnt) + log(cnt) + max
-            float xv[8], m = x[0];
-            for (int c = 0; c < C; ++c) { xv[c] = x[c]; m = fmaxf(m, xv[c]); }
-            const float shift = isfinite(m) ? m : 0.f;
-            float sum = 0.f, cnt = 0.f;
-            for (int c = 0; c < C; ++c) {
-                if (xv[c] == m) cnt += 1.f;
-                else sum += expf(xv[c] - shift);
-            }
-            if (sum != 0.f) sum = sum / cnt;
-            const float lse = (log1pf(sum) + logf(cnt)) + m;
-            for (int c = 0; c < C; ++c) v[c] = (double)(xv[c] - lse);
+            po_ingest_log_softmax_f32((const float*)a.src + srow * C, C, v);   // (po_ingest_rules.h)
         } else if (a.mode == 1) {
             const unsigned char* x = (const unsigned char*)a.src + srow * C;
             const double eps = 0.0000001;

@@ -314,6 +314,54 @@ def _attach_fastq(loaded, out, args):
     return out
 
 
+def pair_record(in_path, stem1, stem2, r, args):
+    """The reference's return tuple (pair_decode.py:375,398,526-529) of one pair from the engine's record r (the dicts of
+    batch.pair_decode_batch): (1-D FASTA text, consensus FASTA text, summary), (consensus text, summary) with
+    --diagonal_envelope, or [summary] for a skipped pair."""
+    if r["status"] not in (0, _lib.SKIP_LENGTH, _lib.SKIP_IDENTITY):
+        # a per-pair engine refusal (capacity, an envelope the reference itself is undefined on): the pair is
+        # reported and skipped, the other pairs of the batch are unaffected — whatever the output route
+        logging.getLogger("poreover_amd").warning("pair %s %s not decoded: %s", in_path[0], in_path[1],
+                                                  _lib._CODE_NAMES.get(r["status"], r["status"]))
+        return [{'read1': in_path[0], 'read2': in_path[1], 'length1': r["length1"], 'length2': r["length2"],
+                 'skipped': 1, 'error': _lib._CODE_NAMES.get(r["status"], str(r["status"]))}]
+    if args.diagonal_envelope:
+        # no 1-D decoding to return; the header quirk of pair_decode.py:527 is kept
+        return (fasta_format('consensus;{};{}'.format(args.method, stem1, stem2), r["consensus"]),
+                {'read1': in_path[0], 'read2': in_path[1]})
+    summary = {'read1': in_path[0], 'read2': in_path[1], 'length1': r["length1"], 'length2': r["length2"]}
+    if r["status"] == _lib.SKIP_LENGTH:
+        summary['skipped'] = 1
+        return [summary]
+    summary['sequence_identity'] = r["sequence_identity"]
+    if r["status"] == _lib.SKIP_IDENTITY:
+        summary['skipped'] = 1
+        return [summary]
+    summary['skipped'] = 0
+    return (fasta_format(in_path[0], r["seq1"]) + fasta_format(in_path[1], r["seq2"]),
+            fasta_format('consensus;{};{}'.format(stem1, stem2), r["consensus"]), summary)
+
+
+def write_pair_files(results, args):
+    """{out}.1d.fasta, {out}.2d.fasta and {out}.log of a list of pair_record's tuples (pair_decode.py:277-300)"""
+    keys = ["read1", "read2", "length1", "length2", "sequence_identity", "skipped"]
+    with open(args.out + '.1d.fasta', 'w') as out_1d_f, open(args.out + '.2d.fasta', 'w') as out_2d_f, \
+            open(args.out + '.log', 'w', 1) as log_f:
+        print('# PoreOver pair-decode', file=log_f)
+        print('# ' + str(vars(args)), file=log_f)
+        print('# ' + '\t'.join(keys), file=log_f)
+        for x in results:   # input order (the reference: process-completion order)
+            if len(x) == 3:
+                print(x[0], file=out_1d_f)
+                print(x[1], file=out_2d_f)
+                print('\t'.join(map(str, [x[2].get(k, "") for k in keys])), file=log_f)
+            elif len(x) == 2:
+                print(x[0], file=out_2d_f)
+                print('\t'.join(map(str, [x[1].get(k, "") for k in ["read1", "read2"]])), file=log_f)
+            elif len(x) == 1:
+                print('\t'.join(map(str, [x[0].get(k, "") for k in keys])), file=log_f)
+
+
 def decode_pairs_local(in_paths, args, devices=None):
     """pair_decode_helper for a list of pairs in THIS process — on its device, or on every device of `devices` through
     the multi-device pipeline: returns a list of the reference's return tuples (1-, 2- or 3-tuples,
@@ -372,14 +420,6 @@ def _decode_pairs_local(in_paths, loaded, args, devices=None):
         for i, r in zip(idx, res):
             in_path = in_paths[i]
             path1, path2 = loaded[i][0], loaded[i][1]
-            if r["status"] not in (0, _lib.SKIP_LENGTH, _lib.SKIP_IDENTITY):
-                # a per-pair engine refusal (capacity, an envelope the reference itself is undefined on): the pair is
-                # reported and skipped, the other pairs of the batch are unaffected — whatever the output route
-                logging.getLogger("poreover_amd").warning("pair %s %s not decoded: %s", in_path[0], in_path[1],
-                                                          _lib._CODE_NAMES.get(r["status"], r["status"]))
-                out[i] = [{'read1': in_path[0], 'read2': in_path[1], 'length1': r["length1"], 'length2': r["length2"],
-                           'skipped': 1, 'error': _lib._CODE_NAMES.get(r["status"], str(r["status"]))}]
-                continue
             if getattr(args, 'debug_envelope', False) and r["status"] == 0:
                 # pair_decode.py:503-507: band statistics of the envelope instead of a consensus
                 import numpy as np
@@ -390,24 +430,7 @@ def _decode_pairs_local(in_paths, loaded, args, devices=None):
                       np.min(size), np.max(size))
                 out[i] = [{"skipped": 1}]
                 continue
-            if args.diagonal_envelope:
-                # no 1-D decoding to return; the header quirk of pair_decode.py:527 is kept
-                out[i] = (fasta_format('consensus;{};{}'.format(args.method, path1.stem, path2.stem), r["consensus"]),
-                          {'read1': in_path[0], 'read2': in_path[1]})
-                continue
-            summary = {'read1': in_path[0], 'read2': in_path[1], 'length1': r["length1"], 'length2': r["length2"]}
-            if r["status"] == _lib.SKIP_LENGTH:
-                summary['skipped'] = 1
-                out[i] = [summary]
-                continue
-            summary['sequence_identity'] = r["sequence_identity"]
-            if r["status"] == _lib.SKIP_IDENTITY:
-                summary['skipped'] = 1
-                out[i] = [summary]
-                continue
-            summary['skipped'] = 0
-            out[i] = (fasta_format(in_path[0], r["seq1"]) + fasta_format(in_path[1], r["seq2"]),
-                      fasta_format('consensus;{};{}'.format(path1.stem, path2.stem), r["consensus"]), summary)
+            out[i] = pair_record(in_path, path1.stem, path2.stem, r, args)
     return out
 
 
@@ -442,22 +465,7 @@ def pair_decode(args):
                     if t is not None:
                         q1.write(t[0] or '')
                         q2.write(t[1])
-        keys = ["read1", "read2", "length1", "length2", "sequence_identity", "skipped"]
-        with open(args.out + '.1d.fasta', 'w') as out_1d_f, open(args.out + '.2d.fasta', 'w') as out_2d_f, \
-                open(args.out + '.log', 'w', 1) as log_f:
-            print('# PoreOver pair-decode', file=log_f)
-            print('# ' + str(vars(args)), file=log_f)
-            print('# ' + '\t'.join(keys), file=log_f)
-            for x in results:   # input order (the reference: process-completion order)
-                if len(x) == 3:
-                    print(x[0], file=out_1d_f)
-                    print(x[1], file=out_2d_f)
-                    print('\t'.join(map(str, [x[2].get(k, "") for k in keys])), file=log_f)
-                elif len(x) == 2:
-                    print(x[0], file=out_2d_f)
-                    print('\t'.join(map(str, [x[1].get(k, "") for k in ["read1", "read2"]])), file=log_f)
-                elif len(x) == 1:
-                    print('\t'.join(map(str, [x[0].get(k, "") for k in keys])), file=log_f)
+        write_pair_files(results, args)
     else:
         res = pair_decode_helper(args)
         if len(res) == 3:

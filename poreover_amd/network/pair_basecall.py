@@ -1,0 +1,227 @@
+"""`pair-basecall`: FAST5 read pairs to 1D² consensus sequences in one device-resident pass.
+
+What `call` followed by `pair-decode` does, without the trip of every frame's probabilities to the host, to a file per
+read and back, and with `basecall`'s overlapping windows: po_pair_basecall_batch_h (poreover_amd/csrc/po_pair_basecall.hip)
+uploads each read's scaled signal once, runs `basecall`'s network passes (the same windows and stitching: window_plan,
+frame_window), builds the two pair-major log-probability tables on the device (read 2 reverse-complemented where asked)
+and runs the pair chain of `pair-decode` on them: Viterbi of both reads, length skip, alignment, identity skip, envelope,
+pair beam search.  The strings come back."""
+import ctypes as C
+import logging
+import os
+from pathlib import Path
+
+import numpy as np
+
+from .. import _lib, _marshal
+from . import basecall as _basecall
+from . import checkpoint as ckpt
+from .network import _layers_array, load_model, parse_fast5
+
+__all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read"]
+
+RC_PERM = [3, 2, 1, 0, 4]   # the complement's column order: A <-> T, C <-> G, blank stays
+
+
+def pair_groups(pairs, lens, ws_bytes, budget=None):
+    """The pairs (index pairs into lens, the reads' sample counts) in input order, cut into runs that one engine call
+    holds: a pair joins the run while the run's resident bytes with it stay within budget (basecall.RESIDENT_BYTES) — 4 + 20
+    per sample of the run's distinct reads (signal, stitched logits), 40 per frame of every pair side (the two float64
+    tables) and ws_bytes(n_pairs, rows1, rows2, longest1, longest2), the pair chain's workspace.  Not in the sum, as in
+    basecall's: the network's pass buffers (windows, probabilities, logits and po_call_batch's workspace of a pass: ~4 GiB
+    at most, the entry's own bound) and the output strings (2 B per frame of a pair side: the 1-D calls and the
+    consensus), so a run sized to the budget holds that much more on the device.  A pair that does not fit alone goes alone.  Returns a list of lists of positions in `pairs`; a read that two runs name is run in each."""
+    budget = _basecall.RESIDENT_BYTES if budget is None else budget
+    out = []
+    group, reads, samples, tr, mr = [], set(), 0, [0, 0], [0, 0]
+    for k, (a, b) in enumerate(pairs):
+        new = {a, b} - reads
+        s = samples + sum(lens[r] for r in new)
+        t = [tr[0] + lens[a], tr[1] + lens[b]]
+        m = [max(mr[0], lens[a]), max(mr[1], lens[b])]
+        if group and s * 24 + (t[0] + t[1]) * 40 + ws_bytes(len(group) + 1, t[0], t[1], m[0], m[1]) > budget:
+            out.append(group)
+            group, reads = [], set()
+            s, t, m = sum(lens[r] for r in {a, b}), [lens[a], lens[b]], [lens[a], lens[b]]
+        group.append(k)
+        reads |= {a, b}
+        samples, tr, mr = s, t, m
+    if group:
+        out.append(group)
+    return out
+
+
+def pair_tables(logits, pairs, reverse2=False, perm2=None):
+    """The table stage alone (po_pair_tables_h): per-read (T, 5) float32 logits and index pairs into them -> (y1, y2), two
+    lists of (T, 5) float64 log-probability tables, one per pair: batch.ingest_batch of each pair's first read, and of its
+    second read with perm=perm2, reverse=reverse2."""
+    lib = _lib.load()
+    lgs = [np.ascontiguousarray(a, dtype=np.float32) for a in logits]
+    if any(a.ndim != 2 or a.shape[1] != ckpt.NUM_LABELS for a in lgs):
+        raise ValueError("pair_tables takes (T, %d) float32 logits" % ckpt.NUM_LABELS)
+    P = len(pairs)
+    off = _marshal.offsets([len(a) for a in lgs])
+    src = np.ascontiguousarray(np.concatenate(lgs + [np.zeros((1, ckpt.NUM_LABELS), dtype=np.float32)]))
+    idx = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1)) if P else np.zeros(2, dtype=np.int32)
+    o1 = _marshal.offsets([len(lgs[a]) if 0 <= a < len(lgs) else 0 for a, _ in pairs], P)
+    o2 = _marshal.offsets([len(lgs[b]) if 0 <= b < len(lgs) else 0 for _, b in pairs], P)
+    y1, y2 = _marshal.out(o1[-1], np.float64, ckpt.NUM_LABELS), _marshal.out(o2[-1], np.float64, ckpt.NUM_LABELS)
+    ptr = _marshal.ptr
+    _lib.check(lib.po_pair_tables_h(ptr(src), ptr(off), len(lgs), ptr(idx), P, 1 if reverse2 else 0,
+                                    _marshal.perm_array(perm2, ckpt.NUM_LABELS), ptr(y1), ptr(y2)), "po_pair_tables_h")
+    return [y1[o1[i]:o1[i + 1]] for i in range(P)], [y2[o2[i]:o2[i + 1]] for i in range(P)]
+
+
+def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass):
+    """One po_pair_basecall_batch_h call on the reads sigs and the index pairs `pairs` into them.  Returns (records as
+    batch.pair_decode_batch's, per-read logits or None)."""
+    n, P = len(sigs), len(pairs)
+    off = _marshal.offsets([len(s) for s in sigs])
+    rows = int(off[-1])
+    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
+    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+    layers = _layers_array(net)
+    idx = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
+    s1o = _marshal.offsets([len(sigs[r]) for ab in pairs for r in ab], 2 * P)
+    so = _marshal.offsets([len(sigs[a]) + len(sigs[b]) for a, b in pairs], P)
+    o1 = _marshal.offsets([len(sigs[a]) for a, _ in pairs], P)
+    seq1d, seq = _marshal.out(s1o[-1], np.uint8), _marshal.out(so[-1], np.uint8)
+    l1, l2, lens, st = (_marshal.out(P) for _ in range(4))
+    ident = _marshal.out(P, np.float64)
+    lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
+    ms = (C.c_float * 6)() if stage_ms is not None else None
+    ptr = _marshal.ptr
+    rc = lib.po_pair_basecall_batch_h(ptr(signal), ptr(off), n, window, overlap, layers, len(net.layers), ptr(w), w.size,
+                                      int(max_windows_per_pass), ptr(idx), P, 1 if reverse_complement else 0, C.byref(opt),
+                                      ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2), ptr(ident), ptr(seq), ptr(so), ptr(lens), ptr(st),
+                                      ptr(lg), ms)
+    _lib.check(rc, "po_pair_basecall_batch_h")
+    if stage_ms is not None:
+        for k, name in enumerate(_lib.PAIR_BASECALL_STAGES):
+            stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+    recs = []
+    _marshal.pair_records(recs, seq1d, s1o, seq, so, l1, l2, lens, st, ident, None, o1, strict=False)(0, P)
+    return recs, ([lg[off[i]:off[i + 1]] for i in range(n)] if want_logits else None)
+
+
+def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
+                          beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
+                          diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0):
+    """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
+    batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
+    consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
+    logits=True: (results, [per-read (len(s), 5) float32 stitched logits, None for a read no pair names]).
+    reverse_complement: read 2 of every pair is time-reversed and complemented, as pair-decode --reverse_complement does;
+    merge_repeats: the decoders of a network trained with ctc_merge_repeated.  window / overlap as basecall_signals;
+    method "row_col", "row" or "grid" is the pair beam search's.  Pairs go to the engine in groups (pair_groups), in input
+    order; stage_ms (a dict) gets the device milliseconds per stage added (_lib.PAIR_BASECALL_STAGES)."""
+    if method not in _lib.METHODS:
+        raise ValueError("pair_basecall_signals: method %r (row_col, row or grid; the split method is not built here)" % (method,))
+    if alignment not in ("banded", "full"):
+        raise ValueError("pair_basecall_signals: alignment %r (banded or full)" % (alignment,))
+    if not 1 <= int(beam_width) <= 25:
+        raise ValueError("pair_basecall_signals: beam_width %d (1 to 25)" % beam_width)
+    _basecall.window_plan(1, window, overlap)
+    _basecall.check_time_order(net.kinds)
+    sigs = [np.asarray(s, dtype=np.float32).ravel() for s in signals]
+    pairs = [tuple(p) for p in pairs]
+    for k, p in enumerate(pairs):
+        if len(p) != 2:
+            raise ValueError("pair_basecall_signals: pair %d has %d entries (two read indices)" % (k, len(p)))
+        for r in p:
+            if not (isinstance(r, (int, np.integer)) and 0 <= r < len(sigs)):
+                raise ValueError("pair_basecall_signals: pair %d names read %r (reads 0 to %d)" % (k, r, len(sigs) - 1))
+            if not len(sigs[r]):
+                raise ValueError("pair_basecall_signals: pair %d: read %d has no samples" % (k, r))
+    pairs = [(int(a), int(b)) for a, b in pairs]
+    results, read_logits = [None] * len(pairs), [None] * len(sigs)
+    if pairs:
+        lib = _lib.load()
+        kind = "bonito" if merge_repeats else "poreover"
+        opt = _marshal.pair_options(kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width)
+        lens = [len(s) for s in sigs]
+
+        def ws_bytes(n, t1, t2, m1, m2):
+            return int(lib.po_pair_decode_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt)))
+        for group in pair_groups(pairs, lens, ws_bytes):
+            reads = sorted({r for k in group for r in pairs[k]})
+            local = {r: j for j, r in enumerate(reads)}
+            recs, lgs = _engine_call(lib, net, [sigs[r] for r in reads], [(local[pairs[k][0]], local[pairs[k][1]]) for k in group],
+                                     window, overlap, reverse_complement, opt, logits, stage_ms, max_windows_per_pass)
+            for k, rec in zip(group, recs):
+                results[k] = rec
+            if logits:
+                for r, lg in zip(reads, lgs):
+                    read_logits[r] = lg
+    return (results, read_logits) if logits else results
+
+
+def resolve_read(name, reads_dir):
+    """READS_DIR/<name> with a .npy or .fast5 suffix, or none, replaced by .fast5: a pairs file may list the reads by the
+    names of their FAST5 files, of `call`'s .npy outputs (as `pair-decode` reads them) or by their stems"""
+    p = Path(name)
+    p = p.with_suffix(".fast5") if p.suffix in (".npy", ".fast5") else Path(str(p) + ".fast5")
+    return os.path.join(reads_dir, str(p))
+
+
+def check_args(args):
+    """SystemExit naming the flag for what pair-decode offers and this route does not"""
+    _basecall.check_window_args(args.window, args.overlap, "pair-basecall")
+    if getattr(args, "fastq", False):
+        raise SystemExit("pair-basecall: --fastq is not built for this route (qualities: `call`, then `pair-decode --fastq`)")
+    if getattr(args, "single", "viterbi") != "viterbi":
+        raise SystemExit("pair-basecall: --single %s is not built for this route (the 1-D basecalls are Viterbi's; `call`, then "
+                         "`pair-decode --single beam`)" % args.single)
+    if getattr(args, "skip_matches", False):
+        raise SystemExit("pair-basecall: --skip_matches is not built for this route (`call`, then `pair-decode --skip_matches`)")
+    if getattr(args, "method", "envelope") != "envelope":
+        raise SystemExit("pair-basecall: --method %s is not built for this route (only the envelope method; `call`, then "
+                         "`pair-decode --method %s`)" % (args.method, args.method))
+    if getattr(args, "threads", 1) not in (None, 0, 1):
+        raise SystemExit("pair-basecall: --threads %d: one device per call (several devices: `call`, then `pair-decode --threads`)"
+                         % args.threads)
+    if getattr(args, "weights", None) is None:
+        raise SystemExit("pair-basecall: --weights is required (a TF checkpoint prefix, a directory with a `checkpoint` file, "
+                         "or an .npz); no weights ship with this package")
+    model = getattr(args, "model", None)
+    try:
+        _basecall.check_time_order([k for k, _ in ckpt.parse_model_json(model if model is not None else ckpt.default_model_config())])
+    except ckpt.NetworkError as e:
+        raise SystemExit(str(e).replace("basecall:", "pair-basecall:", 1))
+
+
+def pair_basecall(args):
+    """`poreover_amd pair-basecall PAIRS --dir READS_DIR`: PAIRS holds two read names per line (find-pairs' output);
+    writes {out}.1d.fasta, {out}.2d.fasta and {out}.log as `pair-decode` does for a list of pairs"""
+    from ..decoding import pair_decode as _pd
+    check_args(args)
+    with open(getattr(args, "in"), "r") as f:
+        names = [line.split() for line in f if line.split()]
+    for k, p in enumerate(names):
+        if len(p) != 2:
+            raise SystemExit("pair-basecall: line %d of %s has %d names (two per line)" % (k + 1, getattr(args, "in"), len(p)))
+    files, order = {}, []
+    for p in names:
+        for name in p:
+            path = resolve_read(name, args.dir)
+            if path not in files:
+                if not os.path.isfile(path):
+                    raise SystemExit("pair-basecall: %s: no such file (read %s of %s)" % (path, name, getattr(args, "in")))
+                files[path] = len(order)
+                order.append(path)
+    logging.getLogger("poreover_amd").info("found {} read pairs in {}".format(len(names), getattr(args, "in")))
+    net = load_model(args)
+    signals = [parse_fast5(path, scaling=args.scaling)[1] for path in order]   # each distinct file once
+    pairs = [(files[resolve_read(a, args.dir)], files[resolve_read(b, args.dir)]) for a, b in names]
+    for k, (a, b) in enumerate(pairs):
+        for r in (a, b):
+            if not len(signals[r]):
+                raise SystemExit("pair-basecall: %s has no samples (line %d of %s)" % (order[r], k + 1, getattr(args, "in")))
+    res = pair_basecall_signals(net, signals, pairs, window=args.window, overlap=args.overlap,
+                                reverse_complement=args.reverse_complement, merge_repeats=args.merge_repeats,
+                                beam_width=args.beam_width, method=args.beam_search_method, padding=args.padding,
+                                alignment=args.alignment, diagonal_envelope=args.diagonal_envelope,
+                                diagonal_width=args.diagonal_width)
+    records = [_pd.pair_record(p, Path(order[a]).stem, Path(order[b]).stem, r, args) for p, (a, b), r in zip(names, pairs, res)]
+    _pd.write_pair_files(records, args)
+    return records
