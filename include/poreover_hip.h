@@ -462,6 +462,27 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
 int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* layers_h, int n_layers,
                     const float* weights_h, int64_t n_weights, float* probs_h, float* logits_h, float* stage_ms_h);
 
+/* The precision of the GRU input projections x·W + b_in, process-wide like po_set_chain_mode and read once per
+ * po_call_batch call — so by everything that runs the network through it: po_call_batch_h, po_basecall_batch_h,
+ * po_basecall_fastq_batch_h, po_pair_basecall_batch_h (po_train_* is not affected):
+ *   PO_CALL_F32   (default) f32 operands on v_mfma_f32_16x16x4_f32
+ *   PO_CALL_BF16  x and W rounded to bf16 (round to nearest even, csrc/po_bf16_rules.h), products and sums in f32 on
+ *                 v_mfma_f32_16x16x32_bf16, the bias added in f32; P, the recurrence, Conv1D, Dense and the softmax stay f32.
+ *                 About one called base in a thousand differs from f32.  po_call_workspace_bytes then includes room for
+ *                 the bf16 copy of a layer's W (a constant: what the query answers for n = 0), made anew in every call
+ *                 (its time counts in stage 1); a workspace sized
+ *                 under PO_CALL_F32 and used under PO_CALL_BF16 is PO_E_CAP.
+ * Any other value is PO_E_ARG and leaves the mode as it was. */
+#define PO_CALL_F32 0
+#define PO_CALL_BF16 1
+int po_set_call_precision(int precision);
+int po_get_call_precision(void);
+/* The projection stage alone, on host buffers: P_h[ndir][M][384] = x_h[M][cin] · w_h[ndir][cin][384] + bin_h[ndir][384] by the
+ * kernel(s) of `precision` (explicit: the selector above is not read).  M >= 0 (0: PO_OK, nothing written), cin >= 1, ndir 1
+ * or 2; a null pointer, another value or another precision is PO_E_ARG naming the argument, before any allocation. */
+int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w_h, const float* bin_h, int precision,
+                  float* P_h);
+
 /* ---- `basecall`: scaled signals to decoded strings in one device-resident pass --------
  * The forward pass above, the log-softmax of po_ingest_batch (PO_INGEST_LOGITS_F32) and po_viterbi_batch / po_beam1d_batch
  * in one synchronous call: each read's signal goes up once, the strings come down, and nothing per frame returns to the

@@ -15,6 +15,10 @@ from . import __version__
 from .quality import DEFAULT_BAND
 
 
+PRECISION_HELP = ('bf16: GRU input projections with bf16 operands, f32 accumulation; about one base in a thousand differs '
+                  'from f32')
+
+
 def build_parser():
     parser = argparse.ArgumentParser(prog="poreover_amd",
                                      description='PoreOver decoding on MI355X: consensus basecalling for nanopore sequencing')
@@ -51,6 +55,7 @@ def build_parser():
     p.add_argument('--window', type=int, default=1000, help='Call read using chunks of this size')
     p.add_argument('--format', choices=['csv', 'npy'], default='npy', help='Save softmax probabilities to CSV file or logits to binarized NumPy format')
     p.add_argument('--no_stack', default=False, action='store_true', help='Basecall [1xSIGNAL_LENGTH] tensor instead of splitting it into windows (slower)')
+    p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="call")
 
@@ -69,6 +74,7 @@ def build_parser():
     p.add_argument('--out', default='out', help='Prefix for FASTA sequence output')
     p.add_argument('--fastq', action='store_true', default=False, help='Also write {out}.fastq with a Phred quality per base')
     p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
+    p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="basecall")
 
@@ -96,6 +102,7 @@ def build_parser():
     p.add_argument('--skip_matches', action='store_true', default=False, help=argparse.SUPPRESS)
     p.add_argument('--method', default='envelope', help=argparse.SUPPRESS)
     p.add_argument('--threads', type=int, default=1, help=argparse.SUPPRESS)
+    p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="pair-basecall")
 

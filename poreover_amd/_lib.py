@@ -4,6 +4,7 @@ The product path has NO CPU fallback: if the HIP library is missing or no GPU is
 calls raise EngineUnavailable.  (The CPU restatement under oracle/ is test infrastructure and
 is never imported from here.)
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -159,6 +160,9 @@ PROTOTYPES = {
                                 C.c_size_t, _vp, C.POINTER(C.c_float)]),
     "po_call_batch_h": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64, _vp, _vp,
                                   C.POINTER(C.c_float)]),
+    "po_set_call_precision": (C.c_int, [C.c_int]),
+    "po_get_call_precision": (C.c_int, []),
+    "po_gru_proj_h": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
     "po_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                       C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _vp,
                                       C.POINTER(C.c_float)]),
@@ -268,6 +272,40 @@ def set_chain_mode(mode="serial"):
 
 def get_chain_mode():
     return {v: k for k, v in CHAIN_MODES.items()}[int(load(False).po_get_chain_mode())]
+
+
+CALL_PRECISIONS = {"f32": 0, "bf16": 1}
+
+
+def _precision_code(name):
+    if name not in CALL_PRECISIONS:
+        raise ValueError("call precision %r (one of %s)" % (name, ", ".join(CALL_PRECISIONS)))
+    return CALL_PRECISIONS[name]
+
+
+def set_call_precision(name="f32"):
+    """po_set_call_precision: the operands of the network's GRU input projections — "f32" (default) or "bf16" (rounded to
+    bf16, products and sums in f32; about one called base in a thousand differs).  Process-wide: prefer
+    call_precision() or the precision= keyword of forward / basecall_signals / pair_basecall_signals, which restore it."""
+    code = _precision_code(name)
+    check(load(False).po_set_call_precision(code), "po_set_call_precision")
+
+
+def get_call_precision():
+    return {v: k for k, v in CALL_PRECISIONS.items()}[int(load(False).po_get_call_precision())]
+
+
+@contextlib.contextmanager
+def call_precision(name):
+    """the engine calls of the block run under call precision `name`; the previous one is back afterwards, whatever happens"""
+    code = _precision_code(name)
+    lib = load(False)
+    before = int(lib.po_get_call_precision())
+    check(lib.po_set_call_precision(code), "po_set_call_precision")
+    try:
+        yield
+    finally:
+        lib.po_set_call_precision(before)
 
 
 def set_reg_fixed_shape(on=True):

@@ -77,7 +77,11 @@ int PoBasecallPasses::up(const PoBasecallPlan& plan, const float* signal_h, cons
                          const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
                          int max_windows_per_pass) {
     // ---- windows per pass: as many as ~4 GiB of pass buffers hold (po_call_batch_h's rule), whole recurrence tiles
-    const size_t per_window = po_call_workspace_bytes(1, window, layers_h, n_layers) + (size_t)window * NOUT * 4 * 2 + (size_t)window * 4;
+    // (the part of the workspace that grows with the windows: under PO_CALL_BF16 the size of no windows is the bf16 copy of W,
+    // which a pass holds once; 0 under PO_CALL_F32)
+    const size_t ws_const = po_call_workspace_bytes(0, window, layers_h, n_layers);
+    const size_t per_window = po_call_workspace_bytes(1, window, layers_h, n_layers) - ws_const + (size_t)window * NOUT * 4 * 2 +
+                              (size_t)window * 4;
     chunk = (int64_t)std::max<size_t>(1, ((size_t)4 << 30) / per_window);
     if (chunk >= TILE) chunk = chunk / TILE * TILE;
     if (max_windows_per_pass > 0) chunk = std::min<int64_t>(chunk, max_windows_per_pass);   // (a smaller bound: the tests')

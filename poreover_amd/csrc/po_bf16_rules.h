@@ -1,0 +1,38 @@
+// The rounding of `--precision bf16`, once: f32 -> bf16 by round-to-nearest-even on the upper 16 bits.
+// The weight conversion kernel of po_call_bf16.h and the host use this function; the projection kernel rounds x with the
+// hardware's packed conversion, which the device test holds against this rule at exact ties.  No HIP in this file:
+// tools/bf16_check.cpp compiles it alone under sanitizers and holds it against a brute-force statement of the rule.
+//   NaN stays a NaN (quiet, sign kept); +-inf and +-0 are kept; a finite value whose rounding overflows becomes +-inf
+#pragma once
+#include <cstdint>
+#include <cstring>
+
+#ifdef __HIPCC__
+#define PO_BF_HD __host__ __device__
+#else
+#define PO_BF_HD
+#endif
+
+// the bf16 bit pattern nearest the f32 bit pattern u, ties to the even pattern
+PO_BF_HD inline uint16_t po_bf16_bits_from_f32_bits(uint32_t u) {
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);   // NaN: keep the top payload, set quiet
+    // add half an ulp of the kept part, less one where the kept part is even: a tie goes to the even neighbour.  The carry
+    // runs into the exponent, so 0x7f7f.... with its upper discarded half rounds to 0x7f80 = inf, and inf itself stays.
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+PO_BF_HD inline uint16_t po_bf16_from_f32(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return po_bf16_bits_from_f32_bits(u);
+}
+
+PO_BF_HD inline float po_f32_from_bf16(uint16_t b) {
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// f rounded to bf16, as an f32
+PO_BF_HD inline float po_round_bf16(float f) { return po_f32_from_bf16(po_bf16_from_f32(f)); }

@@ -1,4 +1,6 @@
-// The basecalling network's forward pass (`poreover call`) on the device, in f32 throughout.
+// The basecalling network's forward pass (`poreover call`) on the device, in f32 throughout by default; under
+// po_set_call_precision(PO_CALL_BF16) the GRU input projections alone take bf16 operands (f32 products and sums): the two
+// kernels of po_call_bf16.h in place of gru_proj_kernel.  No fp16, no bf16 anywhere else.
 //
 // Replaces, from network/network.py of the reference: the Keras models of build_model (network.py:15-55: bigru3,
 // conv1_bigru3, conv2_bigru3, conv1_gru5) run by call_helper (network.py:253-282) on windows of the scaled signal, and
@@ -20,19 +22,41 @@
 // Windows are independent (h_0 = 0 each) and every element's arithmetic depends only on its own window, so a window's
 // output is the same bits whichever batch, tile or chunk it runs in.
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "po_call_kernels.h"
+#include "po_call_bf16.h"
 
 #include "po_host.h"
 #include "po_internal.h"
 
 namespace {
 
+std::atomic<int> g_precision{PO_CALL_F32};   // po_set_call_precision: process-wide, read once per po_call_batch call
+
+// room for the bf16 copy of a GRU layer's input kernels: the largest layer's (a layer's copy is made in its own stage)
+size_t wb_bytes_for(const po_call_layer* L, int nl) {
+    size_t b = 0;
+    for (int k = 0; k < nl; ++k)
+        if (L[k].kind == PO_CALL_BIGRU || L[k].kind == PO_CALL_GRU || L[k].kind == PO_CALL_GRU_BACK)
+            b = std::max(b, al256(bf_w_elems(L[k].cin, L[k].kind == PO_CALL_BIGRU ? 2 : 1) * 2));
+    return b;
+}
+
 size_t ws_bytes_for(int64_t M, int64_t wmax) {
     return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G * 4);
+}
+
+// workgroups of gru_proj_bf16_kernel: one per compute unit (each holds ~100 KB of LDS); any count gives the same bits
+int bf_blocks_cap() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 1)
+        cus = 256;
+    return cus;
 }
 
 struct Stage {
@@ -48,8 +72,17 @@ size_t po_call_workspace_bytes(int n, int T, const po_call_layer* layers_h, int 
     int64_t nw;
     const int64_t wmax = check_model(layers_h, n_layers, &nw);
     if (wmax < 0 || n < 0 || T < 1) return 0;
-    return ws_bytes_for((int64_t)n * T, wmax);
+    return ws_bytes_for((int64_t)n * T, wmax) + (g_precision.load() == PO_CALL_BF16 ? wb_bytes_for(layers_h, n_layers) : 0);
 }
+
+int po_set_call_precision(int precision) {
+    if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
+        return po_fail(PO_E_ARG, "po_set_call_precision: precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
+    g_precision.store(precision);
+    return PO_OK;
+}
+
+int po_get_call_precision(void) { return g_precision.load(); }
 
 int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers_h, int n_layers, const float* weights,
                   int64_t n_weights, float* probs, float* logits, void* ws, size_t ws_bytes, void* stream_,
@@ -63,11 +96,15 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
                                         std::to_string(n_weights) + " given");
     if (n == 0) return PO_OK;
     const int64_t M = (int64_t)n * T;
-    if (!ws || ws_bytes < ws_bytes_for(M, wmax)) return po_fail(PO_E_CAP, "po_call_batch: workspace too small");
+    const bool bf16 = g_precision.load() == PO_CALL_BF16;   // (a mode set after the size query finds the workspace too small)
+    if (!ws || ws_bytes < ws_bytes_for(M, wmax) + (bf16 ? wb_bytes_for(layers_h, n_layers) : 0))
+        return po_fail(PO_E_CAP, "po_call_batch: workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
     char* p = (char*)ws;
     float* act[2] = {(float*)p, (float*)(p + al256((size_t)M * wmax * 4))};
     float* P = (float*)(p + 2 * al256((size_t)M * wmax * 4));
+    uint16_t* Wb = (uint16_t*)(p + ws_bytes_for(M, wmax));
+    const int bf_cap = bf16 ? bf_blocks_cap() : 0;
     std::vector<Stage> st;
     auto begin = [&](int kind) -> int {
         if (!stage_ms_h) return PO_OK;
@@ -107,8 +144,12 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
             const int64_t per_dir = (int64_t)l.cin * G + (int64_t)H * G + 2 * G;   // W, U, bias (2, 384)
             if ((rc = begin(1)) != PO_OK) break;
-            hipLaunchKernelGGL(gru_proj_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(nd * (G / 64))), dim3(256), 0,
-                               stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, P, M);
+            if (bf16)
+                launch_gru_proj_bf16(stream, x, l.cin, nd, w, per_dir, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, Wb, P, M,
+                                     bf_cap);
+            else
+                hipLaunchKernelGGL(gru_proj_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(nd * (G / 64))), dim3(256), 0,
+                                   stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, P, M);
             if ((rc = end()) != PO_OK) break;
             RecurArgs ra;
             std::memset(&ra, 0, sizeof(ra));
@@ -171,7 +212,9 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
     if (chunk >= RT) chunk = chunk / RT * RT;
     chunk = std::min(chunk, n);
     const int64_t Mc = (int64_t)chunk * T;
-    const size_t wsb = ws_bytes_for(Mc, wmax);
+    // (the bf16 copies are a few hundred KB and do not grow with the pass; a mode set by another thread in between is
+    // answered by po_call_batch's own check)
+    const size_t wsb = ws_bytes_for(Mc, wmax) + (g_precision.load() == PO_CALL_BF16 ? wb_bytes_for(layers_h, n_layers) : 0);
     PoDev dw, dsig, dprob, dlog, dws;   // (dlog stays NULL without a logits output)
     PO_HIPCHK(dw.up(weights_h, (size_t)n_weights * 4));
     PO_HIPCHK(dsig.up(nullptr, (size_t)Mc * 4));
@@ -187,6 +230,37 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
         PO_HIPCHK(dprob.down(probs_h + (int64_t)w0 * T * NOUT, M * NOUT * 4));
         if (logits_h) PO_HIPCHK(dlog.down(logits_h + (int64_t)w0 * T * NOUT, M * NOUT * 4));
     }
+    return PO_OK;
+}
+
+int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w_h, const float* bin_h, int precision,
+                  float* P_h) {
+    const std::string me = "po_gru_proj_h: ";
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (!x_h || !w_h || !bin_h || !P_h)
+        return po_fail(PO_E_ARG, me + "null argument " + (!x_h ? "x_h" : !w_h ? "w_h" : !bin_h ? "bin_h" : "P_h"));
+    if (M < 0) return po_fail(PO_E_ARG, me + "M " + std::to_string(M));
+    if (cin < 1) return po_fail(PO_E_ARG, me + "cin " + std::to_string(cin) + " (at least 1)");
+    if (ndir < 1 || ndir > 2) return po_fail(PO_E_ARG, me + "ndir " + std::to_string(ndir) + " (1 or 2)");
+    if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
+        return po_fail(PO_E_ARG, me + "precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
+    if (M == 0) return PO_OK;
+    PoDev dx, dw, db, dP, dwb;
+    PO_HIPCHK(dx.up(x_h, (size_t)M * cin * 4));
+    PO_HIPCHK(dw.up(w_h, (size_t)ndir * cin * G * 4));
+    PO_HIPCHK(db.up(bin_h, (size_t)ndir * G * 4));
+    PO_HIPCHK(dP.up(nullptr, (size_t)ndir * M * G * 4));
+    if (precision == PO_CALL_BF16) {
+        PO_HIPCHK(dwb.up(nullptr, bf_w_elems(cin, ndir) * 2));
+        launch_gru_proj_bf16(nullptr, dx, cin, ndir, dw, (int64_t)cin * G, db, G, dwb, dP, M, bf_blocks_cap());
+    } else {
+        hipLaunchKernelGGL(gru_proj_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(ndir * (G / 64))), dim3(256), 0, nullptr,
+                           dx.as<float>(), cin, dw.as<float>(), db.as<float>(), (int64_t)cin * G, (int64_t)G, dP.as<float>(), M);
+    }
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(dP.down(P_h, (size_t)ndir * M * G * 4));
     return PO_OK;
 }
 

@@ -95,7 +95,7 @@ def _qual_rows_bytes(lib, n, total, longest, model):
 
 
 def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, want_logits=False, want_odds=False,
-                want_guides=False, stage_ms=None, max_windows_per_pass=0):
+                want_guides=False, stage_ms=None, max_windows_per_pass=0, precision="f32"):
     """One po_basecall_fastq_batch_h call.  Returns a dict: strings, quals (uint8 Phred arrays), qual_status int32 (n,),
     and where asked for logits, odds (float64 (L, 5) per read) and guides (int32 (T,) per read; None for band <= 0)."""
     n = len(sigs)
@@ -113,11 +113,13 @@ def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, 
     od = np.zeros((rows, 5), dtype=np.float64) if want_odds else None
     gd = np.zeros(rows, dtype=np.int32) if want_guides and band > 0 else None
     ms = (C.c_float * 8)() if stage_ms is not None else None
-    rc = lib.po_basecall_fastq_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
-                                       w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
-                                       seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
-                                       lg.ctypes.data if want_logits else None, int(band), qual.ctypes.data, qst.ctypes.data,
-                                       od.ctypes.data if od is not None else None, gd.ctypes.data if gd is not None else None, ms)
+    with _lib.call_precision(precision):
+        rc = lib.po_basecall_fastq_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
+                                           w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
+                                           seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
+                                           lg.ctypes.data if want_logits else None, int(band), qual.ctypes.data, qst.ctypes.data,
+                                           od.ctypes.data if od is not None else None, gd.ctypes.data if gd is not None else None,
+                                           ms)
     _lib.check(rc, "po_basecall_fastq_batch_h")
     _marshal.raise_on_status(st, n, "basecall of read")
     if stage_ms is not None:
@@ -134,7 +136,8 @@ def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, 
     return res
 
 
-def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass):
+def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass,
+                 precision="f32"):
     n = len(sigs)
     off = _marshal.offsets([len(s) for s in sigs])
     rows = int(off[-1])
@@ -146,10 +149,11 @@ def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_
     st = np.zeros(n, dtype=np.int32)
     lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
     ms = (C.c_float * 6)() if stage_ms is not None else None
-    rc = lib.po_basecall_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
-                                 w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
-                                 seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
-                                 lg.ctypes.data if want_logits else None, ms)
+    with _lib.call_precision(precision):
+        rc = lib.po_basecall_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
+                                     w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
+                                     seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
+                                     lg.ctypes.data if want_logits else None, ms)
     _lib.check(rc, "po_basecall_batch_h")
     _marshal.raise_on_status(st, n, "basecall of read")
     if stage_ms is not None:
@@ -178,7 +182,7 @@ def _groups(todo, lens, fits):
 
 
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
-                     logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None):
+                     logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None, precision="f32"):
     """The decoded string of each scaled signal, in input order — or (string, (len(s), 5) float32 stitched logits) with
     logits=True.  qualities=True adds a uint8 (len(string),) array of Phred values as the last item: (string, q) or
     (string, logits, q), from the quality lattice (poreover_amd.quality) within qual_band label positions of the call's
@@ -190,7 +194,9 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     column moves).  A read without samples gets "" and never reaches the device.  Reads go to the engine in groups, in
     input order, of at most RESIDENT_BYTES // (resident bytes per sample) samples — a single longer read goes alone;
     stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES; with qualities
-    _lib.BASECALL_FASTQ_STAGES)."""
+    _lib.BASECALL_FASTQ_STAGES).  precision "f32" or "bf16": the GRU input projections' operands
+    (_lib.set_call_precision), set around each engine call made here and restored after it."""
+    _lib._precision_code(precision)
     if algorithm not in ("viterbi", "beam"):
         raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
     if algorithm == "beam" and not 1 <= beam_width <= 64:
@@ -214,7 +220,7 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
         budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
         for group in _groups(todo, lens, lambda n, total, longest: total <= budget):
             res = _engine_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, logits, stage_ms,
-                               max_windows_per_pass)
+                               max_windows_per_pass, precision=precision)
             for k, r in zip(group, res):
                 out[k] = r
         return out
@@ -231,7 +237,7 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     def run(reads, band_, want_logits):
         for group in _groups(reads, lens, fits(band_)):
             r = _fastq_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, band_, want_logits=want_logits,
-                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass)
+                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass, precision=precision)
             for j, k in enumerate(group):
                 yield k, r, j
 
@@ -277,7 +283,7 @@ def basecall(args):
     fastq = bool(getattr(args, "fastq", False))
     seqs = basecall_signals(net, [s for _, s in parsed], window=args.window, overlap=args.overlap, algorithm=args.algorithm,
                             beam_width=args.beam_width, merge_repeats=args.merge_repeats, qualities=fastq,
-                            qual_band=getattr(args, "qual_band", None))
+                            qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"))
     quals = [q for _, q in seqs] if fastq else None
     seqs = [s for s, _ in seqs] if fastq else seqs
     names = []

@@ -17,7 +17,8 @@ from .. import _lib
 from ..decoding import hdf5_lite
 from . import checkpoint as ckpt
 
-__all__ = ["parse_fast5", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model"]
+__all__ = ["parse_fast5", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model", "round_bf16",
+           "gru_proj"]
 
 SCALINGS = ("standard", "current", "median", "rescale", "raw")
 
@@ -69,9 +70,37 @@ def _layers_array(net):
     return arr
 
 
-def forward(net, windows, logits=False, stage_ms=None):
+def round_bf16(a):
+    """`a` as float32 with every value rounded to bfloat16, the rule of csrc/po_bf16_rules.h: round to nearest, ties to
+    even, on the upper 16 bits; NaN stays NaN (quiet), +-inf and +-0 are kept, a finite value whose rounding overflows
+    becomes +-inf.  What `--precision bf16` does to the operands of the GRU input projections."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7fffffff)) > np.uint32(0x7f800000)
+    r = (u + np.uint32(0x7fff) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xffff0000)
+    r = np.where(nan, (u & np.uint32(0xffff0000)) | np.uint32(0x00400000), r).astype(np.uint32)
+    return r.view(np.float32).reshape(np.shape(a))
+
+
+def gru_proj(x, W, b_in, precision="f32"):
+    """The GRU input projection stage alone on the device (po_gru_proj_h): x (M, cin), W (ndir, cin, 384), b_in (ndir, 384)
+    -> P (ndir, M, 384) float32 = x @ W[d] + b_in[d], by the kernels of `precision`"""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    b = np.ascontiguousarray(b_in, dtype=np.float32)
+    if x.ndim != 2 or W.ndim != 3 or W.shape[1:] != (x.shape[1], 384) or b.shape != (W.shape[0], 384):
+        raise ValueError("gru_proj: x (M, cin), W (ndir, cin, 384), b_in (ndir, 384); got %s, %s, %s" % (x.shape, W.shape, b.shape))
+    P = np.empty((W.shape[0], x.shape[0], 384), dtype=np.float32)
+    _lib.check(lib.po_gru_proj_h(x.ctypes.data, x.shape[0], x.shape[1], W.shape[0], W.ctypes.data, b.ctypes.data,
+                                 _lib._precision_code(precision), P.ctypes.data), "po_gru_proj_h")
+    return P
+
+
+def forward(net, windows, logits=False, stage_ms=None, precision="f32"):
     """softmax probabilities (n, T, 5) float32 of `windows` (n, T) through `net` on the device; with logits=True also the
-    Dense outputs; stage_ms (a dict) gets the device milliseconds per stage added (_lib.CALL_STAGES)"""
+    Dense outputs; stage_ms (a dict) gets the device milliseconds per stage added (_lib.CALL_STAGES); precision "f32" or
+    "bf16" (_lib.set_call_precision; set for this call alone)"""
+    _lib._precision_code(precision)
     lib = _lib.load()
     x = np.ascontiguousarray(windows, dtype=np.float32)
     n, T = x.shape
@@ -79,18 +108,20 @@ def forward(net, windows, logits=False, stage_ms=None):
     probs = np.empty((n, T, ckpt.NUM_LABELS), dtype=np.float32)
     lg = np.empty_like(probs) if logits else None
     ms = (C.c_float * 4)() if stage_ms is not None else None
-    rc = lib.po_call_batch_h(x.ctypes.data, n, T, _layers_array(net), len(net.layers), w.ctypes.data, w.size,
-                             probs.ctypes.data, lg.ctypes.data if logits else None, ms)
-    _lib.check(rc, "po_call_batch_h")
+    with _lib.call_precision(precision):
+        rc = lib.po_call_batch_h(x.ctypes.data, n, T, _layers_array(net), len(net.layers), w.ctypes.data, w.size,
+                                 probs.ctypes.data, lg.ctypes.data if logits else None, ms)
+        _lib.check(rc, "po_call_batch_h")
     if stage_ms is not None:
         for k, name in enumerate(_lib.CALL_STAGES):
             stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
     return (probs, lg) if logits else probs
 
 
-def basecall_signals(net, signals, window=1000, no_stack=False, logits=False):
+def basecall_signals(net, signals, window=1000, no_stack=False, logits=False, precision="f32"):
     """[(len(s), 5) float32 probabilities] for each scaled signal: all reads' windows in shared device passes (windows
-    of one length go together; --no_stack: each read is one window of its own length, reads of equal length together)"""
+    of one length go together; --no_stack: each read is one window of its own length, reads of equal length together);
+    precision as forward's"""
     groups = {}
     for i, s in enumerate(signals):
         T = max(1, len(s)) if no_stack else window
@@ -98,7 +129,7 @@ def basecall_signals(net, signals, window=1000, no_stack=False, logits=False):
     out = [None] * len(signals)
     for T, idx in groups.items():
         parts = [batch_input(signals[i], T) for i in idx]
-        res = forward(net, np.concatenate([p[0] for p in parts]), logits=logits)
+        res = forward(net, np.concatenate([p[0] for p in parts]), logits=logits, precision=precision)
         pr, lg = res if logits else (res, None)
         k = 0
         for i, (wins, frames) in zip(idx, parts):
@@ -135,7 +166,8 @@ def call_helper(args, model, files=None):
     """basecall getattr(args, 'in') (or `files`) with `model` and write one output per read; returns the paths"""
     files = [getattr(args, "in")] if files is None else files
     parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
-    probs = basecall_signals(model, [s for _, s in parsed], window=args.window, no_stack=getattr(args, "no_stack", False))
+    probs = basecall_signals(model, [s for _, s in parsed], window=args.window, no_stack=getattr(args, "no_stack", False),
+                             precision=getattr(args, "precision", "f32"))
     return [_write(args, f, rid, p) for f, (rid, _), p in zip(files, parsed, probs)]
 
 

@@ -106,7 +106,7 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
 
 def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
                           beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
-                          diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0):
+                          diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32"):
     """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
     batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
     consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
@@ -114,7 +114,9 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     reverse_complement: read 2 of every pair is time-reversed and complemented, as pair-decode --reverse_complement does;
     merge_repeats: the decoders of a network trained with ctc_merge_repeated.  window / overlap as basecall_signals;
     method "row_col", "row" or "grid" is the pair beam search's.  Pairs go to the engine in groups (pair_groups), in input
-    order; stage_ms (a dict) gets the device milliseconds per stage added (_lib.PAIR_BASECALL_STAGES)."""
+    order; stage_ms (a dict) gets the device milliseconds per stage added (_lib.PAIR_BASECALL_STAGES).  precision "f32" or
+    "bf16": the GRU input projections' operands (_lib.set_call_precision), set for the engine calls made here alone."""
+    _lib._precision_code(precision)
     if method not in _lib.METHODS:
         raise ValueError("pair_basecall_signals: method %r (row_col, row or grid; the split method is not built here)" % (method,))
     if alignment not in ("banded", "full"):
@@ -146,8 +148,10 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
         for group in pair_groups(pairs, lens, ws_bytes):
             reads = sorted({r for k in group for r in pairs[k]})
             local = {r: j for j, r in enumerate(reads)}
-            recs, lgs = _engine_call(lib, net, [sigs[r] for r in reads], [(local[pairs[k][0]], local[pairs[k][1]]) for k in group],
-                                     window, overlap, reverse_complement, opt, logits, stage_ms, max_windows_per_pass)
+            with _lib.call_precision(precision):
+                recs, lgs = _engine_call(lib, net, [sigs[r] for r in reads],
+                                         [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
+                                         reverse_complement, opt, logits, stage_ms, max_windows_per_pass)
             for k, rec in zip(group, recs):
                 results[k] = rec
             if logits:
@@ -221,7 +225,7 @@ def pair_basecall(args):
                                 reverse_complement=args.reverse_complement, merge_repeats=args.merge_repeats,
                                 beam_width=args.beam_width, method=args.beam_search_method, padding=args.padding,
                                 alignment=args.alignment, diagonal_envelope=args.diagonal_envelope,
-                                diagonal_width=args.diagonal_width)
+                                diagonal_width=args.diagonal_width, precision=getattr(args, "precision", "f32"))
     records = [_pd.pair_record(p, Path(order[a]).stem, Path(order[b]).stem, r, args) for p, (a, b), r in zip(names, pairs, res)]
     _pd.write_pair_files(records, args)
     return records

@@ -8,7 +8,10 @@ around synchronous calls, the routes alternating; device milliseconds per stage 
 one JSON line.
 
     python scripts/bench_pair_basecall.py [--arch conv1_bigru3] [--pairs 256] [--samples 4000] [--window 1000]
-                                          [--overlap 200] [--beam_width 5] [--steps 5] [--warmup 2]
+                                          [--overlap 200] [--beam_width 5] [--steps 5] [--warmup 2] [--precision f32]
+
+--precision bf16 runs every route with bf16 GRU input projections and adds the share of pairs whose status, 1-D calls and
+consensus are the f32 run's.
 """
 import argparse
 import json
@@ -36,6 +39,7 @@ def main():
     p.add_argument("--beam_width", type=int, default=5)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--precision", default="f32", choices=["f32", "bf16"])
     a = p.parse_args()
     _lib.load()   # no device: fail here, not after the set-up
     cfg = C.ARCHITECTURES[a.arch]()
@@ -50,10 +54,11 @@ def main():
     pairs = [(2 * i, 2 * i + 1) for i in range(a.pairs)]
 
     def fused(overlap, ms=None):
-        return PB.pair_basecall_signals(net, sigs, pairs, window=a.window, overlap=overlap, beam_width=a.beam_width, stage_ms=ms)
+        return PB.pair_basecall_signals(net, sigs, pairs, window=a.window, overlap=overlap, beam_width=a.beam_width, stage_ms=ms,
+                                        precision=a.precision)
 
     def composed(overlap):
-        lg = [x for _, x in B.basecall_signals(net, sigs, window=a.window, overlap=overlap, logits=True)]
+        lg = [x for _, x in B.basecall_signals(net, sigs, window=a.window, overlap=overlap, logits=True, precision=a.precision)]
         return batch.pair_decode_stream([lg[i] for i, _ in pairs], [lg[j] for _, j in pairs], beam_width=a.beam_width, strict=False)
 
     routes = [("fused_overlap_0", lambda ms=None: fused(0, ms)), ("composed_overlap_0", lambda ms=None: composed(0)),
@@ -77,6 +82,10 @@ def main():
            "pairs_decoded_overlap": sum(r["status"] == 0 for r in out["fused_overlap"]),
            "records_differ_overlap_0": differ("fused_overlap_0", "composed_overlap_0"),
            "records_differ_overlap": differ("fused_overlap", "composed_overlap")}
+    if a.precision != "f32":      # (the default output keeps its keys)
+        res["precision"] = a.precision
+        f32 = PB.pair_basecall_signals(net, sigs, pairs, window=a.window, overlap=0, beam_width=a.beam_width)
+        res["records_identical_to_f32_share"] = sum(all(r[k] == s[k] for k in keys) for r, s in zip(out["fused_overlap_0"], f32)) / len(f32)
     for name, _ in routes:
         w = np.array(wall[name])
         res[name] = {"pairs_per_s": a.pairs / float(np.median(w)), "wall_ms_median": float(np.median(w)) * 1e3,
