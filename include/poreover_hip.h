@@ -600,6 +600,66 @@ int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, in
 int po_pair_tables_h(const float* logits_h, const int64_t* row_off_h, int n_reads, const int32_t* pair_idx_h, int n_pairs,
                      int reverse2, const int* perm2_h, double* y1_h, double* y2_h);
 
+/* ---- the pair pass with per-base qualities ----------------------------------------------------
+ * po_pair_basecall_batch_h's arguments, refusals, strings, lengths, identities and statuses (bit for bit), then, behind the
+ * pair chain on the same stream and on the tables and strings that are on the device already, what `pair-decode --fastq`
+ * computes (pair_decode._attach_fastq).  Every pair whose status is 0 has four scored items, k = 0 .. 3: seq1 on table 1,
+ * seq2 on table 2 (as the pair decoder saw it: time-reversed and complemented where reverse_complement is set), the
+ * consensus on table 1, the consensus on table 2; the items of any other pair are empty (with opt->diagonal_envelope a
+ * pair has no 1-D calls: items 0 and 1 are empty).  Per item: the Viterbi call of its table with its frame map (a second,
+ * cheap po_viterbi_batch per side), the band guide by quality.call_guides' rule (the map where the scored string is that
+ * call; otherwise the two are aligned by po_align_batch, band_width = 500 + the largest length difference among ALL
+ * aligned items of the call, both sides together, and the map is counted in the scored string's bases; the diagonal for
+ * an empty string, a failed Viterbi call or a failed alignment), po_qual_batch of opt->model (four calls of n_pairs reads,
+ * one workspace) and the Phred characters: a 1-D item's own; the consensus from the element-wise sum of its two tables'
+ * odds (quality.combine), or from one table's odds alone where the other item's status is not 0.
+ *   - band_size:     po_qual_batch's; <= 0: no band, no guides
+ *   - unbanded_h (or NULL): int32[4 n_pairs], item k of pair i at 4 i + k; a non-zero entry scores that item without a
+ *                    band while the others keep theirs (the retry of a lost lattice; the consensus then mixes a banded
+ *                    and an unbanded table)
+ *   - qual1d_h:      the 1-D FASTQ characters 33 + Q, len1_h[i] / len2_h[i] of them at seq1d_off_h[2i] / [2i + 1]
+ *   - qual_h:        the consensus characters, seq_len_h[i] of them at seq_off_h[i]; a pair that is not decoded gets none
+ *                    (the rest of both buffers is zero)
+ *   - qual_status_h: int32[4 n_pairs], po_qual_batch's status of item k of pair i at 4 i + k, 0 for an empty item.
+ *                    PO_E_ENVELOPE (the band admits no path) is reported, not retried; an item with a non-zero status is '!'
+ *                    (Q 0) throughout, and the consensus is '!' throughout where both of its items have one
+ *   - odds1d_h (or NULL): the 1-D items' log-odds, five float64 per base at seq1d_off_h[2i + side] * 5
+ *   - odds_cons_h (or NULL): the consensus items' log-odds, [2][5 * seq_off_h[n_pairs]]: table 1's at seq_off_h[i] * 5,
+ *                    table 2's 5 * seq_off_h[n_pairs] values further on
+ *   - guide_h (or NULL): the guides, int32[2 * (rows1 + rows2)] (rows = a table's frames): the four item types one behind
+ *                    the other (rows1, rows2, rows1, rows2 values), pair i of a type at its table's row offset; untouched
+ *                    for band_size <= 0
+ *   - stage_ms_h (or NULL): float[8]: po_pair_basecall_batch_h's six, [6] second Viterbi + alignment + guides,
+ *                    [7] label compaction + lattices + Phred
+ * A null qual1d_h, qual_h or qual_status_h is PO_E_ARG naming it; every argument error is answered before the first
+ * allocation. */
+int po_pair_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                   const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                   int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                                   const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                                   int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
+                                   int32_t* seq_len_h, int32_t* status_h, float* logits_h, int band_size,
+                                   const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h,
+                                   double* odds1d_h, double* odds_cons_h, int32_t* guide_h, float* stage_ms_h);
+
+/* The quality stages of the above alone, on host buffers: what the fused entry runs behind the pair chain.  y1_h / y2_h
+ * with y1_off_h / y2_off_h: the two pair-major float64 tables (po_pair_tables_h's, 5 columns); model PO_MODEL_CTC or
+ * PO_MODEL_MERGE (PO_MODEL_FLIPFLOP: PO_E_UNSUPPORTED); seq1d_h .. status_h: a pair decode's outputs, read (every table
+ * from 0, non-decreasing: PO_E_ARG; a decoded pair's string longer than its room: PO_E_CAP naming the pair).  The outputs
+ * as above. */
+int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n, int model,
+                   const char* seq1d_h, const int64_t* seq1d_off_h, const int32_t* len1_h, const int32_t* len2_h,
+                   const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h,
+                   int band_size, const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h,
+                   double* odds1d_h, double* odds_cons_h, int32_t* guide_h);
+
+/* The consensus Phred kernel alone (poreover_amd/csrc/po_fastq_rules.h: po_fq_pair_phred).  odds1_h / odds2_h: five
+ * float64 per base, labels and qual at label_off_h[i] (from 0, non-decreasing); item i gets quality.phred of
+ * quality.combine(odds1, odds2) where st1_h[i] and st2_h[i] are 0, of one table alone where only its status is 0, '!'
+ * throughout where neither is. */
+int po_fastq_pair_phred_h(const double* odds1_h, const double* odds2_h, const char* labels_h, const int64_t* label_off_h, int n,
+                          const char* alphabet, const int32_t* st1_h, const int32_t* st2_h, char* qual_h);
+
 /* ---- CTC training of the basecalling network (`train`) -------------------------------------------
  * Replaces the reference's TensorFlow training step (train_ctc_model, network.py:78-131): the forward pass above,
  * tf.compat.v1.nn.ctc_loss (blank = class 4, softmax inside the loss) averaged over the batch, its gradient and Keras

@@ -52,6 +52,7 @@ CALL_STAGES = ("conv", "gru_proj", "gru_recur", "dense_softmax")
 BASECALL_STAGES = CALL_STAGES + ("stitch_ingest", "decode")
 BASECALL_FASTQ_STAGES = BASECALL_STAGES + ("guides", "lattice_phred")
 PAIR_BASECALL_STAGES = CALL_STAGES + ("stitch_tables", "pair_decode")
+PAIR_BASECALL_FASTQ_STAGES = PAIR_BASECALL_STAGES + ("guides", "lattice_phred")
 TRAIN_STAGES = ("forward", "ctc", "back_recur", "gemm", "adam")
 
 _vp, _i64p, _i32p, _dp, _cp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
@@ -175,6 +176,13 @@ PROTOTYPES = {
     "po_pair_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                            C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp, _i64p, _i32p, _i32p, _dp,
                                            _cp, _i64p, _i32p, _i32p, _vp, C.POINTER(C.c_float)]),
+    "po_pair_basecall_fastq_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
+                                                 C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp, _i64p, _i32p, _i32p,
+                                                 _dp, _cp, _i64p, _i32p, _i32p, _vp, C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p,
+                                                 C.POINTER(C.c_float)]),
+    "po_pair_qual_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _cp, _i64p, _i32p, _i32p,
+                                 C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p]),
+    "po_fastq_pair_phred_h": (C.c_int, [_dp, _dp, _cp, _i64p, C.c_int, C.c_char_p, _i32p, _i32p, _cp]),
     "po_pair_tables_h": (C.c_int, [_vp, _i64p, C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "po_train_create": (C.c_void_p, [C.POINTER(CallLayer), C.c_int, C.c_int, C.c_int]),
     "po_train_destroy": (None, [C.c_void_p]),

@@ -25,6 +25,7 @@
 
 #include "po_basecall_pass.h"
 #include "po_fastq_rules.h"
+#include "po_fastq_stages.h"
 
 namespace {
 
@@ -137,7 +138,7 @@ struct FastqOut {
 // (Viterbi) the frame map stay where they are; lengths, statuses, modes and offsets are the only words that cross.
 struct FastqStages {
     PoDev map, vseq, vlen, vst, mode, consumed, guide, labels, label_off, odds, logp, qst, qual, wsv, wsq;
-    PoDev pair_read, pair_seq, pair_off, aln1, aln2, aln_off, ncol, ast, wsa;
+    PoFqAligner al;   // the pairs that need an alignment (po_fastq_stages.h)
     std::vector<int64_t> label_off_h;
     int32_t* called_len = nullptr;   // device: the Viterbi call's lengths
     // The Viterbi call with its frame map is the decode itself only for Viterbi of PO_KIND_POREOVER.  For PO_KIND_BONITO the
@@ -188,45 +189,17 @@ struct FastqStages {
             PO_HIPCHK(hipMemcpyAsync(h.data() + n, out.len.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             PO_HIPCHK(hipMemcpyAsync(h.data() + 2 * n, vlen.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             PO_HIPCHK(hipStreamSynchronize(stream));
-            std::vector<int32_t> reads;
-            std::vector<int64_t> so(1, 0), ao(1, 0);
-            int64_t slack = 0, m1 = 0, m2 = 0;
-            for (int i = 0; i < n; ++i) {
-                if (h[i] != PO_FQ_ALIGN) continue;
-                const int64_t Lc = h[2 * (size_t)n + i], L = h[(size_t)n + i];
-                reads.push_back(i);
-                so.push_back(so.back() + Lc);       // pair = (called, scored), as quality.call_guides aligns them
-                so.push_back(so.back() + L);
-                ao.push_back(ao.back() + Lc + L + 8);
-                slack = std::max(slack, Lc > L ? Lc - L : L - Lc);
-                m1 = std::max(m1, Lc);
-                m2 = std::max(m2, L);
-            }
-            const int m = (int)reads.size();
+            for (int i = 0; i < n; ++i)
+                if (h[i] == PO_FQ_ALIGN) al.add(i, h[2 * (size_t)n + i], h[(size_t)n + i]);
+            const int m = al.m();
             if (m > 0) {
-                if (500 + slack > INT32_MAX) return po_fail(PO_E_ARG, std::string(me) + ": alignment band beyond 2^31 - 1");
-                const int band = (int)(500 + slack);   // call_guides' rule: one band for the call's pairs
-                // the aligner's workspace is per workgroup in flight: as many pairs a launch as ~4 GiB of it hold
-                const size_t per_pair = po_align_workspace_bytes(1, m1, m2, band);
-                const int step = (int)std::max<size_t>(1, std::min<size_t>((size_t)m, ((size_t)4 << 30) / per_pair));
-                const size_t wab = po_align_workspace_bytes(step, m1, m2, band);
-                PO_HIPCHK(pair_read.up(reads.data(), sizeof(int32_t) * m));
-                PO_HIPCHK(pair_off.up(so.data(), sizeof(int64_t) * so.size()));
-                PO_HIPCHK(aln_off.up(ao.data(), sizeof(int64_t) * ao.size()));
-                PO_HIPCHK(pair_seq.up(nullptr, (size_t)so.back()));
-                PO_HIPCHK(aln1.up(nullptr, (size_t)ao.back()));
-                PO_HIPCHK(aln2.up(nullptr, (size_t)ao.back()));
-                PO_HIPCHK(ncol.up(nullptr, sizeof(int32_t) * m));
-                PO_HIPCHK(ast.up(nullptr, sizeof(int32_t) * m));
-                PO_HIPCHK(wsa.up(nullptr, wab));
-                po_launch_fastq_gather(called, out.seq, out.off, pair_read, 2, pair_off, 2 * m, so.back(), pair_seq, stream);
+                rc = al.up(me);
+                if (rc != PO_OK) return rc;
+                po_launch_fastq_gather(called, out.seq, out.off, al.pair_read, 2, al.pair_off, 2 * m, al.so.back(), al.pair_seq, stream);
                 PO_HIPCHK(hipGetLastError());
-                for (int p0 = 0; p0 < m; p0 += step) {
-                    rc = po_align_batch(pair_seq, pair_off.as<int64_t>() + 2 * p0, std::min(step, m - p0), band, aln1, aln2,
-                                        aln_off.as<int64_t>() + p0, ncol.as<int32_t>() + p0, ast.as<int32_t>() + p0, wsa, wab, stream);
-                    if (rc != PO_OK) return rc;
-                }
-                po_launch_fastq_consumed(aln1, aln2, aln_off, ncol, ast, m, pair_read, dsoff, called_len, out.len, consumed, mode, stream);
+                rc = al.run(stream);
+                if (rc != PO_OK) return rc;
+                po_launch_fastq_consumed(al.aln1, al.aln2, al.aln_off, al.ncol, al.ast, m, al.pair_read, dsoff, called_len, out.len, consumed, mode, stream);
                 PO_HIPCHK(hipGetLastError());
             }
         }

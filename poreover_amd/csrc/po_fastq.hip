@@ -10,6 +10,13 @@
 //   fastq_guide_kernel     one lane per frame: a binary search in the read's frame map
 //   fastq_phred_kernel     one lane per base: five float64 log-odds to one character
 //
+// and of the pair pass, where the scored string, the Viterbi call and the consensus live at offsets of
+// their own:
+//
+//   fastq_mode2_kernel       fastq_mode_kernel with a table for the scored and one for the called string
+//   fastq_gather2_kernel     the (called, scored) pairs for po_align_batch, each source at its own table
+//   fastq_pair_phred_kernel  one lane per consensus base: the two reads' log-odds, summed where both stand, to one character
+//
 // No atomics, one writer per value, nothing depends on the launch geometry.
 #include <cstring>
 #include <string>
@@ -131,6 +138,66 @@ __global__ __launch_bounds__(256) void fastq_phred_kernel(FqPhredArgs a) {
     }
 }
 
+// fastq_mode_kernel for strings that live in two buffers: the scored string of item i at seq + seq_off[i], the Viterbi call
+// at vseq + vseq_off[i]
+__global__ __launch_bounds__(64) void fastq_mode2_kernel(const char* __restrict__ seq, const int64_t* __restrict__ seq_off,
+                                                         const int32_t* __restrict__ len, const char* __restrict__ vseq,
+                                                         const int64_t* __restrict__ vseq_off, const int32_t* __restrict__ vlen,
+                                                         const int32_t* __restrict__ vstatus, int32_t* __restrict__ mode) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int L = len[i], Lc = vlen[i];
+    int m = PO_FQ_IDENTITY;
+    if (vstatus[i] != PO_OK || L <= 0 || Lc <= 0) m = PO_FQ_DIAGONAL;
+    else if (L != Lc) m = PO_FQ_ALIGN;
+    else {
+        const int64_t o = seq_off[i], vo = vseq_off[i];
+        int differ = 0;
+        for (int k = lane; k < L; k += 64) differ |= seq[o + k] != vseq[vo + k];
+        if (__ballot(differ) != 0ull) m = PO_FQ_ALIGN;
+    }
+    if (lane == 0) mode[i] = m;
+}
+
+// dst[k], dst_off[s] <= k < dst_off[s + 1], for the `total` characters from dst_off[0] on: character k - dst_off[s] of
+// string s, which is the called (s even: src0 at off0[r]) or the scored (s odd: src1 at off1[r]) string of item r = item[s / 2]
+__global__ __launch_bounds__(256) void fastq_gather2_kernel(const char* __restrict__ src0, const int64_t* __restrict__ off0,
+                                                            const char* __restrict__ src1, const int64_t* __restrict__ off1,
+                                                            const int32_t* __restrict__ item, const int64_t* __restrict__ dst_off,
+                                                            int n_strings, int64_t base, int64_t total, char* __restrict__ dst) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t k = base + j;
+        const int s = fq_find(dst_off, n_strings, k);
+        const int r = item[s / 2];
+        const int64_t c = k - dst_off[s];
+        dst[k] = (s & 1) ? src1[off1[r] + c] : src0[off0[r] + c];
+    }
+}
+
+struct FqPairPhredArgs {
+    const double* odds1; const double* odds2;     // five float64 per base
+    const int64_t* pos1; const int64_t* pos2;     // the first odds row of pair i's consensus on either side
+    const int32_t* sel1; const int32_t* sel2;     // the entry of qst1 / qst2 that holds the pair's status, or NULL: i
+    const int32_t* qst1; const int32_t* qst2;
+    const char* seq; const int64_t* seq_off;      // the consensus strings; the characters go to qual at the same offsets
+    const int64_t* dense_off;                     // [n + 1] the consensus lengths, summed: one lane per base
+    int n; int64_t total; char alphabet[4]; char* qual;
+};
+
+__global__ __launch_bounds__(256) void fastq_pair_phred_kernel(FqPairPhredArgs a) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k < a.total; k += (int64_t)gridDim.x * blockDim.x) {
+        const int i = fq_find(a.dense_off, a.n, k);
+        const int64_t j = k - a.dense_off[i];
+        const bool ok1 = a.qst1[a.sel1 ? a.sel1[i] : i] == PO_OK, ok2 = a.qst2[a.sel2 ? a.sel2[i] : i] == PO_OK;
+        const double* p1 = a.odds1 + (a.pos1[i] + j) * 5;
+        const double* p2 = a.odds2 + (a.pos2[i] + j) * 5;
+        double o1[5], o2[5];
+#pragma unroll
+        for (int b = 0; b < 5; ++b) { o1[b] = p1[b]; o2[b] = p2[b]; }
+        const int64_t at = a.seq_off[i] + j;
+        a.qual[at] = (char)(33 + po_fq_pair_phred(o1, o2, ok1, ok2, po_fq_code(a.alphabet, a.seq[at])));
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------ launches
 extern "C" {
 
@@ -174,6 +241,32 @@ int po_launch_fastq_phred(const double* odds, const char* labels, const int64_t*
     FqPhredArgs a = {odds, labels, label_off, qstatus, out_off, n, total, {0, 0, 0, 0}, qual};
     std::memcpy(a.alphabet, alphabet ? alphabet : "ACGT", 4);
     hipLaunchKernelGGL(fastq_phred_kernel, dim3(fq_grid(total)), dim3(256), 0, stream, a);
+    return PO_OK;
+}
+
+int po_launch_fastq_mode2(const char* seq, const int64_t* seq_off, const int32_t* len, const char* vseq, const int64_t* vseq_off,
+                          const int32_t* vlen, const int32_t* vstatus, int n, int32_t* mode, hipStream_t stream) {
+    if (n <= 0) return PO_OK;
+    hipLaunchKernelGGL(fastq_mode2_kernel, dim3(n), dim3(64), 0, stream, seq, seq_off, len, vseq, vseq_off, vlen, vstatus, mode);
+    return PO_OK;
+}
+
+int po_launch_fastq_gather2(const char* src0, const int64_t* off0, const char* src1, const int64_t* off1, const int32_t* item,
+                            const int64_t* dst_off, int n_strings, int64_t base, int64_t total, char* dst, hipStream_t stream) {
+    if (n_strings <= 0 || total <= 0) return PO_OK;
+    hipLaunchKernelGGL(fastq_gather2_kernel, dim3(fq_grid(total)), dim3(256), 0, stream, src0, off0, src1, off1, item, dst_off,
+                       n_strings, base, total, dst);
+    return PO_OK;
+}
+
+int po_launch_fastq_pair_phred(const double* odds1, const int64_t* pos1, const int32_t* sel1, const int32_t* qst1,
+                               const double* odds2, const int64_t* pos2, const int32_t* sel2, const int32_t* qst2, const char* seq,
+                               const int64_t* seq_off, const int64_t* dense_off, int n, int64_t total, const char* alphabet,
+                               char* qual, hipStream_t stream) {
+    if (n <= 0 || total <= 0) return PO_OK;
+    FqPairPhredArgs a = {odds1, odds2, pos1, pos2, sel1, sel2, qst1, qst2, seq, seq_off, dense_off, n, total, {0, 0, 0, 0}, qual};
+    std::memcpy(a.alphabet, alphabet ? alphabet : "ACGT", 4);
+    hipLaunchKernelGGL(fastq_pair_phred_kernel, dim3(fq_grid(total)), dim3(256), 0, stream, a);
     return PO_OK;
 }
 
@@ -279,6 +372,36 @@ int po_fastq_phred_h(const double* odds_h, const char* labels_h, const int64_t* 
     PO_HIPCHK(qs.up(qual_status_h, sizeof(int32_t) * n));
     PO_HIPCHK(ql.up(nullptr, (size_t)total));
     po_launch_fastq_phred(od, lb, lo, qs, lo, n, total, alphabet, ql, nullptr);
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(ql.down(qual_h, (size_t)total));
+    return PO_OK;
+}
+
+int po_fastq_pair_phred_h(const double* odds1_h, const double* odds2_h, const char* labels_h, const int64_t* label_off_h, int n,
+                          const char* alphabet, const int32_t* st1_h, const int32_t* st2_h, char* qual_h) {
+    const char* me = "po_fastq_pair_phred_h";
+    po_set_error("");
+    if (n < 0) return po_fail(PO_E_ARG, std::string(me) + ": n " + std::to_string(n));
+    if (n == 0) return PO_OK;
+    if (!label_off_h || !st1_h || !st2_h)
+        return po_fail(PO_E_ARG, std::string(me) + ": null argument " + (!label_off_h ? "label_off_h" : !st1_h ? "st1_h" : "st2_h"));
+    if (alphabet && std::strlen(alphabet) != 4) return po_fail(PO_E_ARG, std::string(me) + ": alphabet \"" + alphabet + "\" (4 symbols)");
+    const int rc = fq_check_table(me, "label_off", label_off_h, n);
+    if (rc != PO_OK) return rc;
+    const int64_t total = label_off_h[n];
+    if (total > 0 && (!odds1_h || !odds2_h || !labels_h || !qual_h))
+        return po_fail(PO_E_ARG, std::string(me) + ": null argument " +
+                       (!odds1_h ? "odds1_h" : !odds2_h ? "odds2_h" : !labels_h ? "labels_h" : "qual_h"));
+    PoDev o1, o2, lb, lo, s1, s2, ql;
+    PO_HIPCHK(o1.up(odds1_h, sizeof(double) * 5 * (size_t)total));
+    PO_HIPCHK(o2.up(odds2_h, sizeof(double) * 5 * (size_t)total));
+    PO_HIPCHK(lb.up(labels_h, (size_t)total));
+    PO_HIPCHK(lo.up(label_off_h, sizeof(int64_t) * ((size_t)n + 1)));
+    PO_HIPCHK(s1.up(st1_h, sizeof(int32_t) * n));
+    PO_HIPCHK(s2.up(st2_h, sizeof(int32_t) * n));
+    PO_HIPCHK(ql.up(nullptr, (size_t)total));
+    po_launch_fastq_pair_phred(o1, lo, nullptr, s1, o2, lo, nullptr, s2, lb, lo, lo, n, total, alphabet, ql, nullptr);
     PO_HIPCHK(hipGetLastError());
     PO_HIPCHK(hipDeviceSynchronize());
     PO_HIPCHK(ql.down(qual_h, (size_t)total));

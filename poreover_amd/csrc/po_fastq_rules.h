@@ -7,6 +7,8 @@
 //   consumed  make_labeled_data.consumed_from_columns + the clip of quality.call_guides: per called base, the scored
 //             string's bases up to and including its column, at most L
 //   phred     quality.phred: the alternatives' share of the odds, in log space, float64
+//   pair      quality.combine and pair_decode._attach_fastq's rule for a consensus scored on two reads' tables: the
+//             element-wise sum where both lattices stand, one read's odds alone where the other's is lost, Q 0 for neither
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -82,6 +84,15 @@ PO_FQ_HD inline int po_fq_phred(const double* odds, int own) {
     const double q = -10.0 * log_e / 2.302585092994046;                   // ln 10
     const double r = floor(q + 0.5);
     return r < 0.0 ? 0 : r > (double)PO_FQ_QMAX ? PO_FQ_QMAX : (int)r;
+}
+
+// Q of one consensus base from the five log-odds it has on each read's table; ok1 / ok2: that table's lattice stands
+// (quality status 0).  The sum is a float64 add per value: there is no product next to it to contract with.
+PO_FQ_HD inline int po_fq_pair_phred(const double* odds1, const double* odds2, bool ok1, bool ok2, int own) {
+    if (!ok1 && !ok2) return 0;
+    double o[5];
+    for (int b = 0; b < 5; ++b) o[b] = (ok1 && ok2) ? odds1[b] + odds2[b] : ok1 ? odds1[b] : odds2[b];
+    return po_fq_phred(o, own);
 }
 
 // the alphabet index of a base (4 symbols), or -1

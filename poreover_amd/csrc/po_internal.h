@@ -124,6 +124,14 @@ int po_launch_fastq_guide(const int32_t* map, const int32_t* consumed, const int
                           hipStream_t stream);
 int po_launch_fastq_phred(const double* odds, const char* labels, const int64_t* label_off, const int32_t* qstatus,
                           const int64_t* out_off, int n, int64_t total, const char* alphabet, char* qual, hipStream_t stream);
+int po_launch_fastq_mode2(const char* seq, const int64_t* seq_off, const int32_t* len, const char* vseq, const int64_t* vseq_off,
+                          const int32_t* vlen, const int32_t* vstatus, int n, int32_t* mode, hipStream_t stream);
+int po_launch_fastq_gather2(const char* src0, const int64_t* off0, const char* src1, const int64_t* off1, const int32_t* item,
+                            const int64_t* dst_off, int n_strings, int64_t base, int64_t total, char* dst, hipStream_t stream);
+int po_launch_fastq_pair_phred(const double* odds1, const int64_t* pos1, const int32_t* sel1, const int32_t* qst1,
+                               const double* odds2, const int64_t* pos2, const int32_t* sel2, const int32_t* qst2, const char* seq,
+                               const int64_t* seq_off, const int64_t* dense_off, int n, int64_t total, const char* alphabet,
+                               char* qual, hipStream_t stream);
 }  // extern "C"
 
 // ---- The pair-beam launch layer: po_beam2d_route.hip owns every process-wide setting and chooses the kernel family; po_beam2d.hip and

@@ -12,12 +12,20 @@
 //
 // A streaming copy like ingest_kernel: one lane per output frame, 20 bytes in, 40 bytes out, a frame's five values
 // contiguous on both sides; every output value has one writer, so two runs give the same bits.
+//
+// po_pair_basecall_fastq_batch_h is the same body followed by the quality stages on the same stream:
+// PairFastqStages below enqueues them (kernels: po_fastq.hip, the lattice: po_qual.hip) on the two tables, the 1-D strings
+// and the consensus the pair chain left on the device.  po_pair_qual_h runs those stages alone on host buffers.
 #include <algorithm>
+#include <cstring>
 #include <string>
 
 #include "po_basecall_pass.h"
+#include "po_fastq_rules.h"
+#include "po_fastq_stages.h"
 #include "po_ingest_rules.h"
 #include "po_pair_basecall_plan.h"
+#include "po_pair_fastq_plan.h"
 
 namespace {
 
@@ -79,6 +87,217 @@ struct PairTables {
     }
 };
 
+// what po_pair_basecall_fastq_batch_h adds to po_pair_basecall_batch_h's arguments
+struct PairFastqOut {
+    int band_size; const int32_t* unbanded_h;
+    char* qual1d_h; char* qual_h; int32_t* qual_status_h; double* odds1d_h; double* odds_cons_h; int32_t* guide_h;
+};
+
+// what the quality stages read: the two tables and the strings on the device, the strings' offset tables on both sides
+struct PairQualIn {
+    const double* y[2]; const int64_t* y_off[2];   // device
+    int64_t rows[2], max_rows[2];
+    int n, model;
+    const char* seq1d; const int64_t* seq1d_off_h;                      // device; host, 2 n + 1 entries
+    const char* seq; const int64_t* seq_off; const int64_t* seq_off_h;  // device; device; host, n + 1 entries
+};
+
+int null_quality_pointer(const std::string& me, const PairFastqOut& fq) {
+    if (fq.qual1d_h && fq.qual_h && fq.qual_status_h) return PO_OK;
+    return po_fail(PO_E_ARG, me + "null argument " + (!fq.qual1d_h ? "qual1d_h" : !fq.qual_h ? "qual_h" : "qual_status_h"));
+}
+
+// The quality stages of a pair call, enqueued behind the pair chain on its stream.  The tables, the 1-D
+// strings and the consensus stay where they are; lengths, statuses, modes and offsets are the only words that cross.
+// Item k of a pair (po_pair_fastq_plan.h) is scored on the table of side s = k & 1; per side there is one Viterbi call
+// with its map and one consumed table, which the side's two items use one after the other.
+struct PairFastqStages {
+    PoDev vseq[2], vlen[2], vst[2], map[2], consumed[2], wsv, mode, guide[PO_PQ_ITEMS];
+    PoDev off1d[2], elen[PO_PQ_ITEMS], lob[PO_PQ_ITEMS], lou[PO_PQ_ITEMS], pos[2], sel[2], coff;
+    PoDev labels[PO_PQ_ITEMS], odds[PO_PQ_ITEMS], qst[PO_PQ_ITEMS], logp, wsq, qual1d, qual;
+    PoFqAligner al;
+    PoPairFastqPlan plan;
+    size_t s1b = 0, cap = 0, wvb = 0;
+    bool banded = false;
+    int kind = PO_KIND_POREOVER;
+
+    // before the decoder: the buffers whose size is known from the tables
+    int prepare(const PairQualIn& in, const PairFastqOut& fq) {
+        const int n = in.n;
+        banded = fq.band_size > 0;
+        kind = in.model == PO_MODEL_MERGE ? PO_KIND_BONITO : PO_KIND_POREOVER;
+        s1b = (size_t)in.seq1d_off_h[2 * (size_t)n];
+        cap = (size_t)in.seq_off_h[n];
+        PO_HIPCHK(qual1d.up(nullptr, s1b));
+        PO_HIPCHK(qual.up(nullptr, cap));
+        PO_HIPCHK(logp.up(nullptr, sizeof(double) * n));
+        if (!banded) return PO_OK;
+        PO_HIPCHK(mode.up(nullptr, sizeof(int32_t) * PO_PQ_ITEMS * (size_t)n));
+        for (int s = 0; s < 2; ++s) {
+            PO_HIPCHK(vseq[s].up(nullptr, (size_t)in.rows[s]));
+            PO_HIPCHK(vlen[s].up(nullptr, sizeof(int32_t) * n));
+            PO_HIPCHK(vst[s].up(nullptr, sizeof(int32_t) * n));
+            PO_HIPCHK(map[s].up(nullptr, sizeof(int32_t) * (size_t)in.rows[s]));
+            PO_HIPCHK(consumed[s].up(nullptr, sizeof(int32_t) * (size_t)in.rows[s]));
+            wvb = std::max(wvb, po_viterbi_workspace_bytes(n, in.rows[s], NOUT, kind));
+        }
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) PO_HIPCHK(guide[k].up(nullptr, sizeof(int32_t) * (size_t)in.rows[po_pq_side(k)]));
+        PO_HIPCHK(wsv.up(nullptr, wvb));
+        return PO_OK;
+    }
+
+    // step 1: the Viterbi call of either table with its frame map (the pair chain does not expose its own); a call's string
+    // has its table's row offsets: a base per frame at most
+    int viterbi(const PairQualIn& in, hipStream_t stream) {
+        PO_HIPCHK(hipMemsetAsync(qual1d.p, 0, std::max<size_t>(s1b, 1), stream));
+        PO_HIPCHK(hipMemsetAsync(qual.p, 0, std::max<size_t>(cap, 1), stream));
+        for (int s = 0; banded && s < 2; ++s) {
+            const int rc = po_viterbi_batch(in.y[s], in.y_off[s], in.n, NOUT, "ACGT", kind, nullptr, vseq[s], in.y_off[s], vlen[s], map[s],
+                                            vst[s], wsv, wvb, stream);
+            if (rc != PO_OK) return rc;
+        }
+        return PO_OK;
+    }
+
+    const char* scored(const PairQualIn& in, int k) const { return k < 2 ? in.seq1d : in.seq; }
+    const int64_t* scored_off(const PairQualIn& in, int k) const { return k < 2 ? off1d[k].as<int64_t>() : in.seq_off; }
+
+    // steps 2 and 3, after the pair chain's lengths and statuses have come down: the plan of the four items, the items that
+    // need an alignment (one band for all of them, both sides together), the guides
+    int guides(const char* me, const PairQualIn& in, const PairFastqOut& fq, const int32_t* st_h, const int32_t* l1_h,
+               const int32_t* l2_h, const int32_t* ln_h, hipStream_t stream) {
+        const int n = in.n;
+        po_pair_fastq_make_plan(in.seq1d_off_h, n, st_h, l1_h, l2_h, ln_h, fq.band_size, fq.unbanded_h, &plan);
+        for (int s = 0; s < 2; ++s) {
+            PO_HIPCHK(off1d[s].up(plan.off1d[s].data(), sizeof(int64_t) * ((size_t)n + 1)));
+            PO_HIPCHK(pos[s].up(plan.pos[2 + s].data(), sizeof(int64_t) * n));
+            PO_HIPCHK(sel[s].up(plan.sel[2 + s].data(), sizeof(int32_t) * n));
+        }
+        PO_HIPCHK(coff.up(plan.cons_off.data(), sizeof(int64_t) * ((size_t)n + 1)));
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            PO_HIPCHK(elen[k].up(plan.len_b[k].data(), sizeof(int32_t) * n));
+            PO_HIPCHK(lob[k].up(plan.off_b[k].data(), sizeof(int64_t) * ((size_t)n + 1)));
+            PO_HIPCHK(lou[k].up(plan.off_u[k].data(), sizeof(int64_t) * ((size_t)n + 1)));
+        }
+        if (!banded) return PO_OK;
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            const int s = po_pq_side(k);
+            po_launch_fastq_mode2(scored(in, k), scored_off(in, k), elen[k], vseq[s], in.y_off[s], vlen[s], vst[s], n,
+                                  mode.as<int32_t>() + (size_t)k * n, stream);
+            PO_HIPCHK(hipGetLastError());
+        }
+        std::vector<int32_t> h((PO_PQ_ITEMS + 2) * (size_t)n);   // modes of the four item types | called lengths of the two sides
+        PO_HIPCHK(hipMemcpyAsync(h.data(), mode.p, sizeof(int32_t) * PO_PQ_ITEMS * n, hipMemcpyDeviceToHost, stream));
+        for (int s = 0; s < 2; ++s)
+            PO_HIPCHK(hipMemcpyAsync(h.data() + (PO_PQ_ITEMS + s) * (size_t)n, vlen[s].p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipStreamSynchronize(stream));
+        int first[PO_PQ_ITEMS + 1] = {0, 0, 0, 0, 0};   // the aligned pairs of item type k: first[k] .. first[k + 1]
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            for (int i = 0; i < n; ++i)
+                if (h[(size_t)k * n + i] == PO_FQ_ALIGN) al.add(i, h[(PO_PQ_ITEMS + po_pq_side(k)) * (size_t)n + i], plan.len_b[k][i]);
+            first[k + 1] = al.m();
+        }
+        int rc;
+        if (al.m() > 0) {
+            rc = al.up(me);
+            if (rc != PO_OK) return rc;
+            for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+                const int s = po_pq_side(k), a0 = first[k], mk = first[k + 1] - a0;
+                if (mk == 0) continue;
+                const int64_t base = al.so[2 * (size_t)a0];
+                po_launch_fastq_gather2(vseq[s], in.y_off[s], scored(in, k), scored_off(in, k), al.pair_read.as<int32_t>() + a0,
+                                        al.pair_off.as<int64_t>() + 2 * a0, 2 * mk, base, al.so[2 * (size_t)first[k + 1]] - base,
+                                        al.pair_seq, stream);
+                PO_HIPCHK(hipGetLastError());
+            }
+            rc = al.run(stream);
+            if (rc != PO_OK) return rc;
+        }
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {   // (a side's two items use its consumed table one after the other)
+            const int s = po_pq_side(k), a0 = first[k], mk = first[k + 1] - a0;
+            int32_t* md = mode.as<int32_t>() + (size_t)k * n;
+            if (mk > 0) {
+                po_launch_fastq_consumed(al.aln1, al.aln2, al.aln_off.as<int64_t>() + a0, al.ncol.as<int32_t>() + a0,
+                                         al.ast.as<int32_t>() + a0, mk, al.pair_read.as<int32_t>() + a0, in.y_off[s], vlen[s], elen[k],
+                                         consumed[s], md, stream);
+                PO_HIPCHK(hipGetLastError());
+            }
+            po_launch_fastq_guide(map[s], consumed[s], in.y_off[s], n, in.rows[s], vlen[s], elen[k], md, guide[k], stream);
+            PO_HIPCHK(hipGetLastError());
+        }
+        return PO_OK;
+    }
+
+    // steps 4 to 6: dense labels, the four items' lattices on the resident tables (an item in the banded call or in the
+    // one without a band, L = 0 in the other), Phred characters at the strings' offsets
+    int lattice(const PairQualIn& in, const PairFastqOut& fq, hipStream_t stream) {
+        const int n = in.n;
+        size_t wqb = 0;
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            const int s = po_pq_side(k);
+            const size_t tot = (size_t)plan.total(k);
+            PO_HIPCHK(labels[k].up(nullptr, tot));
+            PO_HIPCHK(odds[k].up(nullptr, sizeof(double) * 5 * tot));
+            PO_HIPCHK(qst[k].up(nullptr, sizeof(int32_t) * 2 * (size_t)n));
+            PO_HIPCHK(hipMemsetAsync(qst[k].p, 0, sizeof(int32_t) * 2 * (size_t)n, stream));
+            if (plan.total_b[k] > 0) wqb = std::max(wqb, po_qual_workspace_bytes(n, in.rows[s], in.max_rows[s], plan.total_b[k], fq.band_size, in.model));
+            if (plan.total_u[k] > 0) wqb = std::max(wqb, po_qual_workspace_bytes(n, in.rows[s], in.max_rows[s], plan.total_u[k], 0, in.model));
+        }
+        PO_HIPCHK(wsq.up(nullptr, wqb));
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            const int s = po_pq_side(k);
+            const int64_t tb = plan.total_b[k], tu = plan.total_u[k];
+            for (int u = 0; u < 2; ++u) {   // the banded call, then the one without a band, each with its own dense layout
+                const int64_t tot = u ? tu : tb, at = u ? tb : 0;
+                if (tot == 0) continue;
+                const int64_t* lo = u ? lou[k].as<int64_t>() : lob[k].as<int64_t>();
+                char* lab = labels[k].as<char>() + at;
+                double* od = odds[k].as<double>() + at * 5;
+                int32_t* q = qst[k].as<int32_t>() + (u ? n : 0);
+                po_launch_fastq_gather(scored(in, k), scored(in, k), scored_off(in, k), nullptr, 1, lo, n, tot, lab, stream);
+                PO_HIPCHK(hipGetLastError());
+                const int rc = po_qual_batch(in.y[s], in.y_off[s], n, NOUT, "ACGT", in.model, lab, lo, u ? nullptr : guide[k].as<int32_t>(),
+                                             u ? 0 : fq.band_size, od, logp, q, wsq, wqb, stream);
+                if (rc != PO_OK) return rc;
+                if (k < 2) {
+                    po_launch_fastq_phred(od, lab, lo, q, off1d[s], n, tot, "ACGT", qual1d, stream);
+                    PO_HIPCHK(hipGetLastError());
+                }
+            }
+        }
+        po_launch_fastq_pair_phred(odds[2], pos[0], sel[0], qst[2], odds[3], pos[1], sel[1], qst[3], in.seq, in.seq_off, coff, n,
+                                   plan.cons_off[n], "ACGT", qual, stream);
+        PO_HIPCHK(hipGetLastError());
+        return PO_OK;
+    }
+
+    // after the synchronise: the characters, the statuses and (where asked for) the odds and the guides
+    int down(const PairQualIn& in, const PairFastqOut& fq) {
+        const int n = in.n;
+        PO_HIPCHK(qual1d.down(fq.qual1d_h, s1b));
+        PO_HIPCHK(qual.down(fq.qual_h, cap));
+        std::vector<int32_t> st(2 * (size_t)n);
+        std::vector<double> dense;
+        for (int k = 0; k < PO_PQ_ITEMS; ++k) {
+            const int s = po_pq_side(k);
+            PO_HIPCHK(qst[k].down(st.data(), sizeof(int32_t) * st.size()));
+            for (int i = 0; i < n; ++i) fq.qual_status_h[PO_PQ_ITEMS * (size_t)i + k] = po_pair_fastq_status(plan, k, i, st.data());
+            double* dst = k < 2 ? fq.odds1d_h : fq.odds_cons_h ? fq.odds_cons_h + (size_t)(k - 2) * 5 * cap : nullptr;
+            if (dst && plan.total(k) > 0) {   // dense on the device, at the strings' offsets in the caller's tables
+                dense.resize((size_t)plan.total(k) * 5);
+                PO_HIPCHK(odds[k].down(dense.data(), sizeof(double) * dense.size()));
+                for (int i = 0; i < n; ++i) {
+                    const int64_t L = plan.len[k][i], at = k < 2 ? plan.off1d[s][i] : in.seq_off_h[i];
+                    if (L > 0) std::memcpy(dst + at * 5, dense.data() + plan.pos[k][i] * 5, sizeof(double) * 5 * (size_t)L);
+                }
+            }
+            if (fq.guide_h && banded)
+                PO_HIPCHK(guide[k].down(fq.guide_h + po_pair_fastq_guide_base(k, in.rows[0], in.rows[1]), sizeof(int32_t) * (size_t)in.rows[s]));
+        }
+        return PO_OK;
+    }
+};
+
 int check_perm(const std::string& me, const int* perm2_h) {
     for (int c = 0; perm2_h && c < NOUT; ++c)
         if (perm2_h[c] < 0 || perm2_h[c] >= NOUT)
@@ -120,13 +339,16 @@ extern "C" int po_pair_tables_h(const float* logits_h, const int64_t* row_off_h,
     return PO_OK;
 }
 
-extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
-                                        const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
-                                        int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
-                                        const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
-                                        int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
-                                        int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h) {
-    const char* name = "po_pair_basecall_batch_h";
+namespace {
+
+// po_pair_basecall_batch_h (fq == NULL) and po_pair_basecall_fastq_batch_h under their own names
+int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                       const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                       int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                       const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
+                       double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                       float* logits_h, float* stage_ms_h, const PairFastqOut* fq) {
+    const int n_stages = fq ? 8 : 6;
     const std::string me = std::string(name) + ": ";
     po_set_error("");
     // ---- every argument error, before the first allocation
@@ -138,6 +360,7 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
         {identity_h, "identity_h"}, {seq_h, "seq_h"}, {seq_off_h, "seq_off_h"}, {seq_len_h, "seq_len_h"}, {status_h, "status_h"}};
     for (const auto& a : ptrs)
         if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
+    if (fq && null_quality_pointer(me, *fq) != PO_OK) return PO_E_ARG;
     PoBasecallPlan plan;
     PoPairBasecallPlan pp;
     std::string err;
@@ -160,7 +383,7 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
     rc = po_call_batch(weights_h, 0, window, layers_h, n_layers, weights_h, n_weights, (float*)weights_h, nullptr, nullptr, 0,
                        nullptr, nullptr);
     if (rc != PO_OK) return rc;
-    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + 6, 0.f);
+    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + n_stages, 0.f);
     if (n_pairs == 0 || n_reads == 0) return PO_OK;
 
     hipStream_t stream = nullptr;
@@ -182,8 +405,18 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
     PO_HIPCHK(idn.up(nullptr, sizeof(double) * (size_t)n_pairs));
     const size_t wsb = po_pair_decode_workspace_bytes(n_pairs, pp.rows[0], pp.rows[1], pp.max_rows[0], pp.max_rows[1], NOUT, opt);
     PO_HIPCHK(ws.up(nullptr, wsb));
+    PairFastqStages fs;
+    PairQualIn qin;
+    if (fq) {
+        for (int s = 0; s < 2; ++s) { qin.y[s] = t.y[s]; qin.y_off[s] = t.off[s]; qin.rows[s] = pp.rows[s]; qin.max_rows[s] = pp.max_rows[s]; }
+        qin.n = n_pairs; qin.model = opt->model;
+        qin.seq1d = s1; qin.seq1d_off_h = seq1d_off_h;
+        qin.seq = out.seq; qin.seq_off = out.off; qin.seq_off_h = seq_off_h;
+        rc = fs.prepare(qin, *fq);
+        if (rc != PO_OK) return rc;
+    }
 
-    PoSpans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr);
+    PoSpans stitch(stage_ms_h != nullptr), decode(stage_ms_h != nullptr), guides(stage_ms_h != nullptr), lattice(stage_ms_h != nullptr);
     rc = net.run(plan, window, overlap, layers_h, n_layers, n_weights, stream, stage_ms_h, stitch);
     if (rc != PO_OK) return rc;
     PO_HIPCHK(stitch.mark(stream));
@@ -195,10 +428,32 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
                               out.len, out.status, ws, wsb, stream);
     if (rc != PO_OK) return rc;
     PO_HIPCHK(decode.mark(stream));
+    if (fq) {   // the quality stages, on the tables and the strings the pair chain left on the device
+        PO_HIPCHK(guides.mark(stream));
+        rc = fs.viterbi(qin, stream);
+        if (rc != PO_OK) return rc;
+        std::vector<int32_t> h(4 * (size_t)n_pairs);   // statuses | 1-D lengths of side 0 | of side 1 | consensus lengths
+        PO_HIPCHK(hipMemcpyAsync(h.data(), out.status.p, per, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipMemcpyAsync(h.data() + n_pairs, l1.p, per, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipMemcpyAsync(h.data() + 2 * (size_t)n_pairs, l2.p, per, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipMemcpyAsync(h.data() + 3 * (size_t)n_pairs, out.len.p, per, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipStreamSynchronize(stream));
+        rc = fs.guides(name, qin, *fq, h.data(), h.data() + n_pairs, h.data() + 2 * (size_t)n_pairs, h.data() + 3 * (size_t)n_pairs, stream);
+        if (rc != PO_OK) return rc;
+        PO_HIPCHK(guides.mark(stream));
+        PO_HIPCHK(lattice.mark(stream));
+        rc = fs.lattice(qin, *fq, stream);
+        if (rc != PO_OK) return rc;
+        PO_HIPCHK(lattice.mark(stream));
+    }
     PO_HIPCHK(hipStreamSynchronize(stream));
     if (stage_ms_h) {
         stage_ms_h[4] = stitch.total();
         stage_ms_h[5] = decode.total();
+        if (fq) {
+            stage_ms_h[6] = guides.total();
+            stage_ms_h[7] = lattice.total();
+        }
     }
     PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
     PO_HIPCHK(s1.down(seq1d_h, s1b));
@@ -206,5 +461,104 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
     PO_HIPCHK(l2.down(len2_h, per));
     PO_HIPCHK(idn.down(identity_h, sizeof(double) * (size_t)n_pairs));
     PO_HIPCHK(net.logits.down(logits_h, (size_t)plan.rows * NOUT * 4));
+    if (fq) {
+        rc = fs.down(qin, *fq);
+        if (rc != PO_OK) return rc;
+    }
     return PO_OK;
+}
+
+}  // namespace
+
+extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                        const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                        int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                                        const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                                        int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
+                                        int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h) {
+    return pair_basecall_impl("po_pair_basecall_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
+                              n_weights, max_windows_per_pass, pair_idx_h, n_pairs, reverse_complement, opt, seq1d_h, seq1d_off_h,
+                              len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h, nullptr);
+}
+
+extern "C" int po_pair_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                              const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                              int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs,
+                                              int reverse_complement, const po_pair_options* opt, char* seq1d_h,
+                                              const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h,
+                                              char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                                              float* logits_h, int band_size, const int32_t* unbanded_h, char* qual1d_h, char* qual_h,
+                                              int32_t* qual_status_h, double* odds1d_h, double* odds_cons_h, int32_t* guide_h,
+                                              float* stage_ms_h) {
+    const PairFastqOut fq = {band_size, unbanded_h, qual1d_h, qual_h, qual_status_h, odds1d_h, odds_cons_h, guide_h};
+    return pair_basecall_impl("po_pair_basecall_fastq_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers,
+                              weights_h, n_weights, max_windows_per_pass, pair_idx_h, n_pairs, reverse_complement, opt, seq1d_h,
+                              seq1d_off_h, len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h, &fq);
+}
+
+extern "C" int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n, int model,
+                              const char* seq1d_h, const int64_t* seq1d_off_h, const int32_t* len1_h, const int32_t* len2_h,
+                              const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h,
+                              int band_size, const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h,
+                              double* odds1d_h, double* odds_cons_h, int32_t* guide_h) {
+    const char* name = "po_pair_qual_h";
+    const std::string me = std::string(name) + ": ";
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (n < 0) return po_fail(PO_E_ARG, me + "n " + std::to_string(n));
+    const struct { const void* p; const char* name; } ptrs[] = {
+        {y1_h, "y1_h"}, {y1_off_h, "y1_off_h"}, {y2_h, "y2_h"}, {y2_off_h, "y2_off_h"}, {seq1d_h, "seq1d_h"}, {seq1d_off_h, "seq1d_off_h"},
+        {len1_h, "len1_h"}, {len2_h, "len2_h"}, {seq_h, "seq_h"}, {seq_off_h, "seq_off_h"}, {seq_len_h, "seq_len_h"}, {status_h, "status_h"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
+    const PairFastqOut fq = {band_size, unbanded_h, qual1d_h, qual_h, qual_status_h, odds1d_h, odds_cons_h, guide_h};
+    if (null_quality_pointer(me, fq) != PO_OK) return PO_E_ARG;
+    if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, me + "the flip-flop model has no quality lattice");
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, me + "model " + std::to_string(model));
+    const struct { const int64_t* off; int count; const char* name; } tables[] = {
+        {y1_off_h, n, "y1_off"}, {y2_off_h, n, "y2_off"}, {seq1d_off_h, 2 * n, "seq1d_off"}, {seq_off_h, n, "seq_off"}};
+    for (const auto& tb : tables) {
+        if (tb.off[0] != 0) return po_fail(PO_E_ARG, me + tb.name + "[0] is " + std::to_string(tb.off[0]) + " (must be 0)");
+        for (int i = 0; i < tb.count; ++i)
+            if (tb.off[i + 1] < tb.off[i]) return po_fail(PO_E_ARG, me + tb.name + " decreases at item " + std::to_string(i));
+    }
+    for (int i = 0; i < n; ++i) {
+        if (status_h[i] != 0) continue;   // (what a pair that is not decoded holds is not read)
+        const int64_t room[3] = {seq1d_off_h[2 * (size_t)i + 1] - seq1d_off_h[2 * (size_t)i],
+                                 seq1d_off_h[2 * (size_t)i + 2] - seq1d_off_h[2 * (size_t)i + 1], seq_off_h[i + 1] - seq_off_h[i]};
+        const int32_t len[3] = {len1_h[i], len2_h[i], seq_len_h[i]};
+        for (int k = 0; k < 3; ++k)
+            if (len[k] < 0 || len[k] > room[k])
+                return po_fail(PO_E_CAP, me + "pair " + std::to_string(i) + ": " + (k == 0 ? "seq1" : k == 1 ? "seq2" : "the consensus") +
+                               " has " + std::to_string(len[k]) + " characters in room for " + std::to_string(room[k]));
+    }
+    if (n == 0) return PO_OK;
+
+    hipStream_t stream = nullptr;
+    PoDev y[2], yo[2], s1, sq, so;
+    PairQualIn in;
+    const double* y_h[2] = {y1_h, y2_h};
+    const int64_t* yo_h[2] = {y1_off_h, y2_off_h};
+    for (int s = 0; s < 2; ++s) {
+        in.rows[s] = yo_h[s][n];
+        in.max_rows[s] = 0;
+        for (int i = 0; i < n; ++i) in.max_rows[s] = std::max(in.max_rows[s], yo_h[s][i + 1] - yo_h[s][i]);
+        PO_HIPCHK(y[s].up(y_h[s], sizeof(double) * NOUT * (size_t)in.rows[s]));
+        PO_HIPCHK(yo[s].up(yo_h[s], sizeof(int64_t) * ((size_t)n + 1)));
+        in.y[s] = y[s]; in.y_off[s] = yo[s];
+    }
+    PO_HIPCHK(s1.up(seq1d_h, (size_t)seq1d_off_h[2 * (size_t)n]));
+    PO_HIPCHK(sq.up(seq_h, (size_t)seq_off_h[n]));
+    PO_HIPCHK(so.up(seq_off_h, sizeof(int64_t) * ((size_t)n + 1)));
+    in.n = n; in.model = model;
+    in.seq1d = s1; in.seq1d_off_h = seq1d_off_h;
+    in.seq = sq; in.seq_off = so; in.seq_off_h = seq_off_h;
+    PairFastqStages fs;
+    int rc = fs.prepare(in, fq);
+    if (rc == PO_OK) rc = fs.viterbi(in, stream);
+    if (rc == PO_OK) rc = fs.guides(name, in, fq, status_h, len1_h, len2_h, seq_len_h, stream);
+    if (rc == PO_OK) rc = fs.lattice(in, fq, stream);
+    if (rc != PO_OK) return rc;
+    PO_HIPCHK(hipStreamSynchronize(stream));
+    return fs.down(in, fq);
 }

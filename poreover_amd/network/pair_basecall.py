@@ -5,7 +5,9 @@ read and back, and with `basecall`'s overlapping windows: po_pair_basecall_batch
 uploads each read's scaled signal once, runs `basecall`'s network passes (the same windows and stitching: window_plan,
 frame_window), builds the two pair-major log-probability tables on the device (read 2 reverse-complemented where asked)
 and runs the pair chain of `pair-decode` on them: Viterbi of both reads, length skip, alignment, identity skip, envelope,
-pair beam search.  The strings come back."""
+pair beam search.  The strings come back.  With qualities po_pair_basecall_fastq_batch_h goes on from
+there on the device — what `pair-decode --fastq` computes from the files: the band guides, the quality lattice of
+po_qual.hip for the two 1-D calls and for the consensus on both resident tables, and the Phred characters."""
 import ctypes as C
 import logging
 import os
@@ -18,20 +20,44 @@ from . import basecall as _basecall
 from . import checkpoint as ckpt
 from .network import _layers_array, load_model, parse_fast5
 
-__all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read"]
+__all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read", "qual_bytes_query",
+           "write_pair_fastq"]
 
 RC_PERM = [3, 2, 1, 0, 4]   # the complement's column order: A <-> T, C <-> G, blank stays
 
 
-def pair_groups(pairs, lens, ws_bytes, budget=None):
+def qual_bytes_query(lib, band, model):
+    """The quality stages' resident bytes of an engine call, as a function (n_pairs, rows1, rows2, longest1, longest2) for
+    pair_groups: per frame of a side one map, one consumed table and two guides (int32 each; a band only) and the side's
+    Viterbi call (1 B); the quality characters (the 1-D strings' and the consensus' room: 2 B per frame of a side); the
+    dense labels and odds of the four items, 41 B per base with a base per frame at most (the consensus: a base per frame
+    of both sides); and the largest of the four po_qual_workspace_bytes, which the four lattice calls share.  band <= 0:
+    the lattice without a band, whose workspace grows with rows x bases."""
+    band = int(band)
+
+    def query(n, t1, t2, m1, m2):
+        ws = max(int(lib.po_qual_workspace_bytes(n, t, m, L, band, model))
+                 for t, m in ((t1, m1), (t2, m2)) for L in (t, t1 + t2))
+        return (t1 + t2) * ((17 if band > 0 else 0) + 2 + 41 * 3) + ws
+    return query
+
+
+def pair_groups(pairs, lens, ws_bytes, budget=None, qual_bytes=None):
     """The pairs (index pairs into lens, the reads' sample counts) in input order, cut into runs that one engine call
     holds: a pair joins the run while the run's resident bytes with it stay within budget (basecall.RESIDENT_BYTES) — 4 + 20
     per sample of the run's distinct reads (signal, stitched logits), 40 per frame of every pair side (the two float64
     tables) and ws_bytes(n_pairs, rows1, rows2, longest1, longest2), the pair chain's workspace.  Not in the sum, as in
     basecall's: the network's pass buffers (windows, probabilities, logits and po_call_batch's workspace of a pass: ~4 GiB
     at most, the entry's own bound) and the output strings (2 B per frame of a pair side: the 1-D calls and the
-    consensus), so a run sized to the budget holds that much more on the device.  A pair that does not fit alone goes alone.  Returns a list of lists of positions in `pairs`; a read that two runs name is run in each."""
+    consensus), so a run sized to the budget holds that much more on the device.  A pair that does not fit alone goes alone.  Returns a list of lists of positions in `pairs`; a read that two runs name is run in each.
+    qual_bytes (the same arguments as ws_bytes; qual_bytes_query): the quality stages' bytes, which then count toward the
+    budget as well; without it the runs are those of a call without qualities."""
     budget = _basecall.RESIDENT_BYTES if budget is None else budget
+    if qual_bytes is not None:
+        chain = ws_bytes
+
+        def ws_bytes(n, t1, t2, m1, m2):
+            return chain(n, t1, t2, m1, m2) + qual_bytes(n, t1, t2, m1, m2)
     out = []
     group, reads, samples, tr, mr = [], set(), 0, [0, 0], [0, 0]
     for k, (a, b) in enumerate(pairs):
@@ -72,9 +98,11 @@ def pair_tables(logits, pairs, reverse2=False, perm2=None):
     return [y1[o1[i]:o1[i + 1]] for i in range(P)], [y2[o2[i]:o2[i + 1]] for i in range(P)]
 
 
-def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass):
+def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass,
+                 fastq=None):
     """One po_pair_basecall_batch_h call on the reads sigs and the index pairs `pairs` into them.  Returns (records as
-    batch.pair_decode_batch's, per-read logits or None)."""
+    batch.pair_decode_batch's, per-read logits or None).  fastq (a dict: band, flags — per pair the four items' "no band"
+    flags, or None — and odds): po_pair_basecall_fastq_batch_h instead, and a third item, quality.pair_fields' dicts."""
     n, P = len(sigs), len(pairs)
     off = _marshal.offsets([len(s) for s in sigs])
     rows = int(off[-1])
@@ -89,24 +117,38 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
     l1, l2, lens, st = (_marshal.out(P) for _ in range(4))
     ident = _marshal.out(P, np.float64)
     lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
-    ms = (C.c_float * 6)() if stage_ms is not None else None
     ptr = _marshal.ptr
-    rc = lib.po_pair_basecall_batch_h(ptr(signal), ptr(off), n, window, overlap, layers, len(net.layers), ptr(w), w.size,
-                                      int(max_windows_per_pass), ptr(idx), P, 1 if reverse_complement else 0, C.byref(opt),
-                                      ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2), ptr(ident), ptr(seq), ptr(so), ptr(lens), ptr(st),
-                                      ptr(lg), ms)
-    _lib.check(rc, "po_pair_basecall_batch_h")
+    stages = _lib.PAIR_BASECALL_STAGES if fastq is None else _lib.PAIR_BASECALL_FASTQ_STAGES
+    ms = (C.c_float * len(stages))() if stage_ms is not None else None
+    common = (ptr(signal), ptr(off), n, window, overlap, layers, len(net.layers), ptr(w), w.size, int(max_windows_per_pass),
+              ptr(idx), P, 1 if reverse_complement else 0, C.byref(opt), ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2), ptr(ident),
+              ptr(seq), ptr(so), ptr(lens), ptr(st), ptr(lg))
+    if fastq is None:
+        _lib.check(lib.po_pair_basecall_batch_h(*common, ms), "po_pair_basecall_batch_h")
+    else:
+        flags = fastq.get("flags")
+        ub = np.ascontiguousarray(np.asarray(flags, dtype=np.int32).reshape(-1)) if flags is not None else None
+        qual1d, qual, qst = _marshal.out(s1o[-1], np.uint8), _marshal.out(so[-1], np.uint8), _marshal.out(4 * P)
+        od1 = _marshal.out(s1o[-1], np.float64, 5) if fastq.get("odds") else None
+        odc = np.zeros((2, int(so[-1]), 5), dtype=np.float64) if fastq.get("odds") else None   # [2][5 * seq_off[n_pairs]]
+        _lib.check(lib.po_pair_basecall_fastq_batch_h(*common, int(fastq["band"]), ptr(ub), ptr(qual1d), ptr(qual), ptr(qst),
+                                                      ptr(od1), ptr(odc), None, ms), "po_pair_basecall_fastq_batch_h")
     if stage_ms is not None:
-        for k, name in enumerate(_lib.PAIR_BASECALL_STAGES):
+        for k, name in enumerate(stages):
             stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
     recs = []
     _marshal.pair_records(recs, seq1d, s1o, seq, so, l1, l2, lens, st, ident, None, o1, strict=False)(0, P)
-    return recs, ([lg[off[i]:off[i + 1]] for i in range(n)] if want_logits else None)
+    read_logits = [lg[off[i]:off[i + 1]] for i in range(n)] if want_logits else None
+    if fastq is None:
+        return recs, read_logits
+    from .. import quality
+    return recs, read_logits, quality.pair_fields(recs, s1o, so, qual1d, qual, qst, od1, odc)
 
 
 def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
                           beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
-                          diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32"):
+                          diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32",
+                          qualities=False, qual_band=None, odds=False):
     """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
     batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
     consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
@@ -115,8 +157,22 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     merge_repeats: the decoders of a network trained with ctc_merge_repeated.  window / overlap as basecall_signals;
     method "row_col", "row" or "grid" is the pair beam search's.  Pairs go to the engine in groups (pair_groups), in input
     order; stage_ms (a dict) gets the device milliseconds per stage added (_lib.PAIR_BASECALL_STAGES).  precision "f32" or
-    "bf16": the GRU input projections' operands (_lib.set_call_precision), set for the engine calls made here alone."""
+    "bf16": the GRU input projections' operands (_lib.set_call_precision), set for the engine calls made here alone.
+    qualities=True (po_pair_basecall_fastq_batch_h instead of po_pair_basecall_batch_h): the record of a
+    decoded pair gains qual1, qual2 (FASTQ quality strings of seq1 and seq2, None where the record has no 1-D call: the
+    diagonal envelope), qual (the consensus') and qual_status (four ints: seq1, seq2, the consensus on read 1's table and
+    on read 2's), by `pair-decode --fastq`'s rule, within qual_band label positions of the call's frames (None:
+    quality.DEFAULT_BAND; <= 0: no band); odds=True adds odds1, odds2, odds_cons1, odds_cons2, float64 (L, 5).  An item
+    whose banded lattice is lost (E_ENVELOPE) is scored again without a band, that item alone, in a second engine call for
+    its pair (a window's bits do not depend on its call: the strings are the same, and are checked); an item still
+    unscored gets Q 0 (the consensus: the other table's evidence alone) and a line in the log (quality.warn_unscored).
+    The records of pairs that are not decoded are unchanged; stage_ms then has _lib.PAIR_BASECALL_FASTQ_STAGES."""
     _lib._precision_code(precision)
+    if not qualities and (qual_band is not None or odds):
+        raise ValueError("pair_basecall_signals: qual_band and odds are options of qualities=True")
+    if qualities:
+        from .. import quality
+        band = quality.check_band("pair_basecall_signals", qual_band)
     if method not in _lib.METHODS:
         raise ValueError("pair_basecall_signals: method %r (row_col, row or grid; the split method is not built here)" % (method,))
     if alignment not in ("banded", "full"):
@@ -145,18 +201,41 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
 
         def ws_bytes(n, t1, t2, m1, m2):
             return int(lib.po_pair_decode_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt)))
-        for group in pair_groups(pairs, lens, ws_bytes):
-            reads = sorted({r for k in group for r in pairs[k]})
-            local = {r: j for j, r in enumerate(reads)}
-            with _lib.call_precision(precision):
-                recs, lgs = _engine_call(lib, net, [sigs[r] for r in reads],
-                                         [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
-                                         reverse_complement, opt, logits, stage_ms, max_windows_per_pass)
-            for k, rec in zip(group, recs):
-                results[k] = rec
-            if logits:
-                for r, lg in zip(reads, lgs):
-                    read_logits[r] = lg
+
+        def run(which, want_logits, band_=None, flags=None):
+            """the engine calls of the pairs `which` (positions in pairs), group by group: (position, record, fields or None)"""
+            model = _lib.MODELS[_lib.MODEL_OF_KIND[kind]]
+            sub = [pairs[k] for k in which]
+            # (a retry call scores its flagged items without a band: its groups are sized for that workspace)
+            query = qual_bytes_query(lib, 0 if flags else band_, model) if band_ is not None else None
+            for group in pair_groups(sub, lens, ws_bytes, qual_bytes=query):
+                group = [which[g] for g in group]
+                reads = sorted({r for k in group for r in pairs[k]})
+                local = {r: j for j, r in enumerate(reads)}
+                fastq = None if band_ is None else {"band": band_, "odds": odds, "flags": [flags[k] for k in group] if flags else None}
+                with _lib.call_precision(precision):
+                    res = _engine_call(lib, net, [sigs[r] for r in reads],
+                                       [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
+                                       reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass, fastq=fastq)
+                if want_logits:
+                    for r, lg in zip(reads, res[1]):
+                        read_logits[r] = lg
+                for j, k in enumerate(group):
+                    yield k, res[0][j], (res[2][j] if fastq else None)
+
+        fields = [None] * len(pairs)
+        for k, rec, f in run(list(range(len(pairs))), logits, band if qualities else None):
+            results[k], fields[k] = rec, f
+        if qualities:
+            retry = quality.pair_retry_flags(fields, band)
+            for k, rec, g in run(sorted(retry), False, band, retry):
+                if any(rec[key] != results[k][key] for key in ("status", "seq1", "seq2", "consensus")):
+                    raise RuntimeError("pair_basecall_signals: pair %d decodes differently in the unbanded retry" % k)
+                quality.pair_retry_merge(fields[k], g, retry[k])
+            quality.pair_warn_unscored(fields)
+            for rec, f in zip(results, fields):
+                if f is not None:
+                    rec.update(f)
     return (results, read_logits) if logits else results
 
 
@@ -166,6 +245,25 @@ def resolve_read(name, reads_dir):
     p = Path(name)
     p = p.with_suffix(".fast5") if p.suffix in (".npy", ".fast5") else Path(str(p) + ".fast5")
     return os.path.join(reads_dir, str(p))
+
+
+def write_pair_fastq(records, names, pairs, prefix):
+    """{prefix}.1d.fastq and {prefix}.2d.fastq of pair_basecall_signals(qualities=True)'s records, as `pair-decode --fastq`
+    writes them for a list of pairs: names[r] is read r's name as the pairs file has it, pairs the index pairs.  A decoded
+    pair's two 1-D records carry the names of the pairs file, its consensus is consensus;stem1;stem2; a record without 1-D
+    calls (the diagonal envelope) has the consensus alone, under the name `pair-decode` gives it there
+    (consensus;envelope;stem1: pair_decode.pair_record's note); a pair that is not decoded has no record."""
+    from ..quality import fastq_format
+    with open(prefix + ".1d.fastq", "w") as q1, open(prefix + ".2d.fastq", "w") as q2:
+        for r, (a, b) in zip(records, pairs):
+            if r["status"] != 0:
+                continue
+            stem1, stem2 = (Path(resolve_read(names[x], "")).stem for x in (a, b))
+            if r.get("qual1") is not None:
+                q1.write(fastq_format(names[a], r["seq1"], r["qual1"]) + fastq_format(names[b], r["seq2"], r["qual2"]))
+                q2.write(fastq_format("consensus;{};{}".format(stem1, stem2), r["consensus"], r["qual"]))
+            else:
+                q2.write(fastq_format("consensus;{};{}".format("envelope", stem1, stem2), r["consensus"], r["qual"]))
 
 
 def check_args(args):

@@ -13,7 +13,8 @@ import numpy as np
 from . import _lib
 from . import batch as _batch
 
-__all__ = ["DEFAULT_BAND", "MODEL_OF_KIND", "phred", "combine", "fastq_format", "qual_string", "call_qualities", "refuse_flipflop"]
+__all__ = ["DEFAULT_BAND", "MODEL_OF_KIND", "phred", "combine", "fastq_format", "qual_string", "call_qualities", "refuse_flipflop",
+           "pair_qualities"]
 
 DEFAULT_BAND = _batch.QUAL_DEFAULT_BAND   # the one default of the knob (batch.qual_batch, --qual_band)
 MODEL_OF_KIND = {k: m for k, m in _lib.MODEL_OF_KIND.items() if m != "ctc_flipflop"}   # (no quality lattice for flip-flop)
@@ -149,3 +150,135 @@ def qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND):
     if bad:
         warn_unscored(["read %d (%s)" % (i, _lib._CODE_NAMES.get(int(status[i]), int(status[i]))) for i in bad])
     return [phred(o, s) if st == 0 else np.zeros(len(s), dtype=np.uint8) for o, s, st in zip(odds, seqs, status)]
+
+
+# ---- the pair pass's quality stages: po_pair_basecall_fastq_batch_h and po_pair_qual_h give, per pair,
+# four scored items — seq1 on table 1, seq2 on table 2, the consensus on table 1 and on table 2 — at the strings' offsets
+PAIR_ITEMS = ("seq1", "seq2", "consensus on read 1", "consensus on read 2")
+PAIR_ODDS_KEYS = ("odds1", "odds2", "odds_cons1", "odds_cons2")
+
+
+def check_band(who, band):
+    """the band of a quality call as an int (None: DEFAULT_BAND; <= 0: no band); ValueError for anything but an integer"""
+    if band is None:
+        return DEFAULT_BAND
+    if isinstance(band, bool) or not isinstance(band, (int, np.integer)):
+        raise ValueError("%s: qual_band %r (an integer; <= 0: no band)" % (who, band))
+    return int(band)
+
+
+def pair_fields(recs, s1o, so, qual1d, qual, qst, odds1d=None, odds_cons=None):
+    """One dict per record of a pair quality call's outputs, None for a pair that is not decoded: qual1, qual2 (None where
+    the record has no 1-D call), qual, qual_status (four ints) and, where the odds came down, PAIR_ODDS_KEYS."""
+    raw1, raw = qual1d.tobytes(), qual.tobytes()
+    out = []
+    for i, r in enumerate(recs):
+        if r["status"] != 0:
+            out.append(None)
+            continue
+        b1, b2, b = int(s1o[2 * i]), int(s1o[2 * i + 1]), int(so[i])
+        l1, l2, ln = len(r["seq1"]), len(r["seq2"]), len(r["consensus"])
+        has_1d = bool(l1 or l2)
+        f = {"qual1": raw1[b1:b1 + l1].decode("ascii") if has_1d else None,
+             "qual2": raw1[b2:b2 + l2].decode("ascii") if has_1d else None,
+             "qual": raw[b:b + ln].decode("ascii"), "qual_status": [int(x) for x in qst[4 * i:4 * i + 4]]}
+        if odds1d is not None:
+            f["odds1"], f["odds2"] = odds1d[b1:b1 + l1].copy(), odds1d[b2:b2 + l2].copy()
+            f["odds_cons1"], f["odds_cons2"] = odds_cons[0, b:b + ln].copy(), odds_cons[1, b:b + ln].copy()
+        out.append(f)
+    return out
+
+
+def pair_retry_flags(fields, band):
+    """{position: [flag of each of the four items]} of the pairs with an item whose banded lattice is lost"""
+    if band <= 0:
+        return {}
+    return {i: [1 if st == _lib.E_ENVELOPE else 0 for st in f["qual_status"]]
+            for i, f in enumerate(fields) if f is not None and _lib.E_ENVELOPE in f["qual_status"]}
+
+
+def pair_retry_merge(f, g, flags):
+    """call_qualities' retry for one pair: f the banded call's fields, g those of the call that scored the flagged items
+    without a band.  Only a flagged item takes the second call's status, odds and characters; the consensus characters
+    come from the second call when one of its two items was flagged (its other item has its banded table there)."""
+    for k, key in enumerate(("qual1", "qual2")):
+        if flags[k]:
+            f[key] = g[key]
+    if flags[2] or flags[3]:
+        f["qual"] = g["qual"]
+    for k in range(4):
+        if flags[k]:
+            f["qual_status"][k] = g["qual_status"][k]
+            if PAIR_ODDS_KEYS[k] in f:
+                f[PAIR_ODDS_KEYS[k]] = g[PAIR_ODDS_KEYS[k]]
+    return f
+
+
+def pair_warn_unscored(fields, what="pair"):
+    bad = ["%s of %s %d (%s)" % (PAIR_ITEMS[k], what, i, _lib._CODE_NAMES.get(st, st))
+           for i, f in enumerate(fields) if f is not None for k, st in enumerate(f["qual_status"]) if st != 0]
+    if bad:
+        warn_unscored(bad)
+
+
+def _pair_qual_call(lib, tables1, tables2, records, model, band, flags=None, odds=False, guides=False):
+    """one po_pair_qual_h call on the records' strings; flags: per record the four items' "no band" flags, or None"""
+    from . import _marshal
+    n = len(records)
+    y1, o1, _ = _marshal.pack_rows(tables1, 5)
+    y2, o2, _ = _marshal.pack_rows(tables2, 5)
+    s1 = [(r.get("seq1") or "", r.get("seq2") or "") for r in records]
+    cons = [r.get("consensus") or "" for r in records]
+    seq1d, s1o = _marshal.pack_string_pairs(s1)
+    seq, so = _marshal.pack_text(cons)
+    l1 = np.array([len(a) for a, _ in s1] + [0], dtype=np.int32)
+    l2 = np.array([len(b) for _, b in s1] + [0], dtype=np.int32)
+    ln = np.array([len(c) for c in cons] + [0], dtype=np.int32)
+    st = np.array([r["status"] for r in records] + [0], dtype=np.int32)
+    ub = np.ascontiguousarray(np.asarray(flags, dtype=np.int32).reshape(-1)) if flags is not None else None
+    qual1d, qual, qst = _marshal.out(s1o[-1], np.uint8), _marshal.out(so[-1], np.uint8), _marshal.out(4 * n)
+    od1 = _marshal.out(s1o[-1], np.float64, 5) if odds else None
+    odc = np.zeros((2, int(so[-1]), 5), dtype=np.float64) if odds else None   # [2][5 * seq_off[n]]
+    gd = np.zeros(max(2 * int(o1[-1] + o2[-1]), 1), dtype=np.int32) if guides and band > 0 else None
+    ptr = _marshal.ptr
+    rc = lib.po_pair_qual_h(ptr(y1), ptr(o1), ptr(y2), ptr(o2), n, _lib.MODELS[model], ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2),
+                            ptr(seq), ptr(so), ptr(ln), ptr(st), int(band), ptr(ub), ptr(qual1d), ptr(qual), ptr(qst), ptr(od1),
+                            ptr(odc), ptr(gd))
+    _lib.check(rc, "po_pair_qual_h")
+    fields = pair_fields(records, s1o, so, qual1d, qual, qst, od1, odc)
+    if guides:
+        r1, r2 = int(o1[-1]), int(o2[-1])
+        base = [0, r1, r1 + r2, 2 * r1 + r2]
+        for i, f in enumerate(fields):
+            if f is not None:
+                f["guides"] = None if gd is None else [gd[base[k] + (o1, o2)[k & 1][i]:base[k] + (o1, o2)[k & 1][i + 1]].copy()
+                                                        for k in range(4)]
+    return fields
+
+
+def pair_qualities(tables1, tables2, records, kind, band=DEFAULT_BAND, odds=False, guides=False):
+    """The qualities of decoded pairs for a caller who holds the tables (po_pair_qual_h: the quality stages of the pair
+    pass alone).  tables1[i] / tables2[i]: the (T, 5) float64 tables of pair i as the pair decoder saw them; records: the
+    dicts of batch.pair_decode_batch.  Returns one dict per record — qual1, qual2 (None where the record has no 1-D call),
+    qual, qual_status (four ints, after the retry) and with odds=True odds1, odds2, odds_cons1, odds_cons2 — or None for a
+    pair that is not decoded.  An item whose banded lattice is lost is scored once more without a band, that item alone
+    (call_qualities' rule); guides=True adds "guides": the four items' int32 band guides of the first call."""
+    if kind not in MODEL_OF_KIND:
+        raise _lib.EngineError(_lib.E_UNSUPPORTED, "pair_qualities", "no quality lattice for %r inputs" % (kind,))
+    band = check_band("pair_qualities", band)
+    if not (len(tables1) == len(tables2) == len(records)):
+        raise ValueError("pair_qualities: one table per side and one record per pair")
+    if not records:
+        return []
+    lib = _lib.load()
+    model = MODEL_OF_KIND[kind]
+    fields = _pair_qual_call(lib, tables1, tables2, records, model, band, None, odds, guides)
+    retry = pair_retry_flags(fields, band)
+    if retry:
+        idx = sorted(retry)
+        second = _pair_qual_call(lib, [tables1[i] for i in idx], [tables2[i] for i in idx], [records[i] for i in idx], model, band,
+                                 [retry[i] for i in idx], odds)
+        for i, g in zip(idx, second):
+            pair_retry_merge(fields[i], g, retry[i])
+    pair_warn_unscored(fields)
+    return fields
