@@ -691,6 +691,32 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
                   float* grad_h, float* stage_ms_h);
 int po_train_last(po_trainer* tr, int n, float* logits_h, float* dlogits_h);
 
+/* Held-out validation on the trainer's resident parameters (train.validation_error's argmax path and edit distance,
+ * DESIGN.md §11.1; the rules are poreover_amd/csrc/po_eval_rules.h).
+ *   - po_train_eval takes n (1 .. max_batch) windows and their labels as po_train_step does, with the same checks,
+ *     answered before any launch (PO_E_ARG naming the window).  On the trainer's stream it runs the forward pass; with
+ *     loss_h given, the CTC lattice of merge_repeated, loss_h[n] = -log P(label | window), bit for bit what
+ *     po_train_step(update = 0) writes; the path of every window (per frame np.argmax's class over the 5 probabilities:
+ *     the first NaN, else the first maximum; classes 0..3 kept in frame order, class 4 dropped, repeats kept, whatever
+ *     merge_repeated is); and the unit-cost edit distance of each path to its labels.  Writes edit_h[n], pred_len_h[n]
+ *     (the paths' lengths), status_h[n] (0, or PO_E_CAP with edit -1 where both the path and the label are longer than
+ *     PO_EDIT_MAX_SHORT = 4095: the other windows are still answered), pred_h (or NULL: n * T codes 0..3, window w's
+ *     path at w * T, the rest of its T bytes unspecified).  No gradient, no Adam: parameters, m, v and the step count
+ *     are untouched.  po_train_last afterwards describes this call's logits (its dlogits are an earlier step's).
+ *   - stage_ms_h (or NULL): HOST float[3] set to device milliseconds by events: 0 forward, 1 CTC loss (0 without
+ *     loss_h), 2 path and edit distance
+ *   - po_eval_path_h: the path stage alone on host buffers: probs_h n * T * 5 f32, pred_h n * T codes, pred_len_h[n]
+ *   - po_edit_distance_batch_h: the edit distance stage alone: pair i is a_h[a_off_h[i] .. a_off_h[i+1]) against
+ *     b_h[b_off_h[i] .. b_off_h[i+1]) (bytes compared for equality; tables non-decreasing, their first entry need not
+ *     be 0).  dist_h[n], status_h[n]: 0, or PO_E_CAP with dist -1 where min(la, lb) > 4095; the batch goes on.
+ * All three are synchronous; the same inputs give the same bits at every batch position and on every run. */
+int po_edit_distance_batch_h(const uint8_t* a_h, const int64_t* a_off_h, const uint8_t* b_h, const int64_t* b_off_h,
+                             int n, int32_t* dist_h, int32_t* status_h);
+int po_eval_path_h(const float* probs_h, int n, int T, uint8_t* pred_h, int32_t* pred_len_h);
+int po_train_eval(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                  int merge_repeated, float* loss_h, int32_t* edit_h, int32_t* pred_len_h, int32_t* status_h,
+                  uint8_t* pred_h, float* stage_ms_h);
+
 /* ---- read-to-genome mapping for `benchmark` (replaces mappy.Aligner as benchmark.py:16-20 uses it) ----
  * minimap2's map-ont seeds (k = 15, w = 10, its hash64) and scores reduced to a fixed integer specification: one
  * primary hit per read, a local affine alignment in a 512-column band around the best chain.  Sequences are upper-case

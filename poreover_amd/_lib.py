@@ -54,6 +54,8 @@ BASECALL_FASTQ_STAGES = BASECALL_STAGES + ("guides", "lattice_phred")
 PAIR_BASECALL_STAGES = CALL_STAGES + ("stitch_tables", "pair_decode")
 PAIR_BASECALL_FASTQ_STAGES = PAIR_BASECALL_STAGES + ("guides", "lattice_phred")
 TRAIN_STAGES = ("forward", "ctc", "back_recur", "gemm", "adam")
+EVAL_STAGES = ("forward", "ctc", "path_edit")
+EDIT_MAX_SHORT = 4095    # po_edit_distance_batch_h / po_train_eval: the shorter string of a pair (beyond it: E_CAP, distance -1)
 
 _vp, _i64p, _i32p, _dp, _cp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
 # every symbol include/poreover_hip.h declares: (restype, argtypes)
@@ -191,6 +193,10 @@ PROTOTYPES = {
     "po_train_step": (C.c_int, [C.c_void_p, _vp, C.c_int, _i32p, _i32p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int, _vp, _vp, C.POINTER(C.c_float)]),
     "po_train_last": (C.c_int, [C.c_void_p, C.c_int, _vp, _vp]),
+    "po_train_eval": (C.c_int, [C.c_void_p, _vp, C.c_int, _i32p, _i32p, C.c_int, _vp, _i32p, _i32p, _i32p, _cp,
+                                C.POINTER(C.c_float)]),
+    "po_eval_path_h": (C.c_int, [_vp, C.c_int, C.c_int, _cp, _i32p]),
+    "po_edit_distance_batch_h": (C.c_int, [_cp, _i64p, _cp, _i64p, C.c_int, _i32p, _i32p]),
     "po_map_sketch_h": (C.c_int, [_cp, _i64p, C.c_int, _vp, _vp, _vp, _i64p]),
     "po_map_index_create": (C.c_void_p, [_cp, _i64p, C.c_int, _vp, _vp, _vp, C.c_int64]),
     "po_map_index_destroy": (None, [C.c_void_p]),

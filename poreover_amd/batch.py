@@ -377,3 +377,30 @@ def pair_gamma_batch(arrays1, arrays2, envelopes=None, flavor="cpp", return_matr
     if return_matrix:
         return [dn[dof[i]:dof[i + 1]].reshape(len(arrays1[i]) + 1, len(arrays2[i]) + 1) for i in range(n)]
     return g0[:n].copy()
+
+
+def edit_distance_batch(a_list, b_list, return_status=False):
+    """Unit-cost edit distance (Levenshtein: accuracy.alignment_summary's edit_distance, an empty side giving the other
+    side's length) of every pair (a_list[i], b_list[i]) in one call (po_edit_distance_batch_h).  An item is a str or
+    bytes, or a sequence of ints 0..255; symbols are compared for equality.  Returns int32 (n,); a pair whose SHORTER
+    side is longer than _lib.EDIT_MAX_SHORT raises EngineError(E_CAP), or with return_status=True gets distance -1 and
+    status E_CAP in the returned (distances, status) while the other pairs are answered."""
+    if len(a_list) != len(b_list):
+        raise ValueError("edit_distance_batch: %d and %d items" % (len(a_list), len(b_list)))
+    n = len(a_list)
+    if n == 0:
+        return (np.zeros(0, np.int32), np.zeros(0, np.int32)) if return_status else np.zeros(0, np.int32)
+
+    def pack(items):
+        rows = [np.frombuffer(x.encode("latin-1") if isinstance(x, str) else bytes(x), dtype=np.uint8)
+                if isinstance(x, (str, bytes, bytearray)) else np.asarray(x).astype(np.uint8, casting="unsafe").ravel() for x in items]
+        return M.concat_spare(rows, np.uint8), M.offsets([len(r) for r in rows], n)
+
+    lib = L.load()
+    (a, ao), (b, bo) = pack(a_list), pack(b_list)
+    dist, st = M.out(n), M.out(n)
+    L.check(lib.po_edit_distance_batch_h(_ptr(a), _ptr(ao), _ptr(b), _ptr(bo), n, _ptr(dist), _ptr(st)), "po_edit_distance_batch_h")
+    if return_status:
+        return dist[:n].copy(), st[:n].copy()
+    M.raise_on_status(st, n, "edit distance of pair")
+    return dist[:n].copy()

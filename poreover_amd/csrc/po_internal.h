@@ -132,6 +132,12 @@ int po_launch_fastq_pair_phred(const double* odds1, const int64_t* pos1, const i
                                const double* odds2, const int64_t* pos2, const int32_t* sel2, const int32_t* qst2, const char* seq,
                                const int64_t* seq_off, const int64_t* dense_off, int n, int64_t total, const char* alphabet,
                                char* qual, hipStream_t stream);
+
+// po_eval.hip (enqueue only; the rules are po_eval_rules.h's).  Pair i of po_launch_edit_distance is a[a_off[i] ..] of
+// a_len[i] symbols (a_len NULL: a_off[i + 1] - a_off[i]) against b[b_off[i] .. b_off[i + 1])
+int po_launch_eval_path(const float* probs, int n, int T, uint8_t* pred, int32_t* pred_len, hipStream_t stream);
+int po_launch_edit_distance(const uint8_t* a, const int64_t* a_off, const int32_t* a_len, const uint8_t* b,
+                            const int64_t* b_off, int n, int32_t* dist, int32_t* status, hipStream_t stream);
 }  // extern "C"
 
 // ---- The pair-beam launch layer: po_beam2d_route.hip owns every process-wide setting and chooses the kernel family; po_beam2d.hip and

@@ -24,6 +24,10 @@
 //   adam_kernel        Keras Adam on the flat parameter vector
 // No float atomics and no hand-off between workgroups within a launch: a step's gradient is the same bits every run.
 //
+// po_train_eval (held-out validation) is the forward pass above, ctc_lsm_kernel + ctc_alpha_beta_kernel (α
+// only) + ctc_loss_kernel where the losses are asked for, then po_eval.hip's eval_path_kernel and edit_distance_kernel on the
+// trainer's probabilities and labels: no gradient, no Adam.
+//
 // BPTT of one direction, walk step s (input time t, output position to), dh = dout[to] + the carried dh:
 //   dz = dh·(h_prev − h~);  dah = dh·(1 − z)·(1 − h~²);  dr = dah·u_h;  daz = dz·z(1 − z);  dar = dr·r(1 − r)
 //   dA = (daz, dar, dah) → input projection and b_in;  dR = (daz, dar, dah·r) → U and b_rec;  dh_prev = dh·z + dR·Uᵀ
@@ -69,10 +73,11 @@ __device__ __forceinline__ bool skip_ok(const int32_t* lab, int s, int merge) {
 }
 
 // One workgroup per window.  A[t][s] = log P(frames 0..t, state s at t), B[t][s] = log P(frames t+1..T-1 | state s at
-// t) (exclusive of frame t), rows of S = 2L+1 states at stride Smax; logz[w] = log P(label | window)
+// t) (exclusive of frame t), rows of S = 2L+1 states at stride Smax; logz[w] = log P(label | window), which is α's alone:
+// with_beta = 0 (po_train_eval, which runs no gradient) leaves B as it is
 __global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const double* __restrict__ lsm, const int32_t* __restrict__ labels,
                                                              const int64_t* __restrict__ loff, int T, int Smax, int merge,
-                                                             double* __restrict__ A, double* __restrict__ B,
+                                                             int with_beta, double* __restrict__ A, double* __restrict__ B,
                                                              double* __restrict__ logz) {
     const int w = blockIdx.x;
     const int32_t* lab = labels + loff[w];
@@ -96,10 +101,10 @@ __global__ __launch_bounds__(256) void ctc_alpha_beta_kernel(const double* __res
         }
         __syncthreads();
     }
-    for (int s = threadIdx.x; s < S; s += blockDim.x)
+    for (int s = threadIdx.x; with_beta && s < S; s += blockDim.x)
         Bw[(int64_t)(T - 1) * Smax + s] = (s == S - 1 || s == S - 2) ? 0.0 : -INFINITY;
     __syncthreads();
-    for (int t = T - 2; t >= 0; --t) {
+    for (int t = T - 2; with_beta && t >= 0; --t) {
         const double* nx = Bw + (int64_t)(t + 1) * Smax;
         const double* lpn = lp + (int64_t)(t + 1) * NOUT;
         double* row = Bw + (int64_t)t * Smax;
@@ -136,6 +141,12 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(const double* __restrict_
     for (int s = 0; s < S; ++s) occ[state_label(lab, s)] += exp(a[s] + b[s] - lz);
     for (int c = 0; c < NOUT; ++c) dlogits[m * NOUT + c] = (float)(exp(lsm[m * NOUT + c]) - occ[c]) * inv_n;
     if (t == 0) loss[w] = (float)(-lz);
+}
+
+// loss[w] = -log Z, as ctc_grad_kernel writes it (po_train_eval runs no gradient)
+__global__ __launch_bounds__(256) void ctc_loss_kernel(const double* __restrict__ logz, int n, float* __restrict__ loss) {
+    const int w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < n) loss[w] = (float)(-logz[w]);
 }
 
 // dX[m][c] = sum_k dY[m][k] * Wd[c][k]  (Dense: k < 5)
@@ -404,6 +415,11 @@ struct po_trainer {
     int32_t* lab = nullptr;
     int64_t* loff = nullptr;
     int64_t part_cap = 0;
+    // po_train_eval: the windows' paths (T codes of room each, at poff), their lengths, distances and statuses, the labels as bytes
+    uint8_t *pred = nullptr, *lab8 = nullptr;
+    int64_t* poff = nullptr;
+    int32_t *pred_len = nullptr, *edit = nullptr, *estatus = nullptr;
+    size_t lab8_cap = 0;
     hipStream_t stream = nullptr;
 };
 
@@ -414,7 +430,8 @@ void trainer_free(po_trainer* tr) {
     for (void* q : {(void*)tr->p, (void*)tr->g, (void*)tr->m, (void*)tr->v, (void*)tr->sig, (void*)tr->P, (void*)tr->probs,
                     (void*)tr->dlog, (void*)tr->loss, (void*)tr->dact[0], (void*)tr->dact[1], (void*)tr->dA, (void*)tr->dR,
                     (void*)tr->part, (void*)tr->lsm, (void*)tr->logz, (void*)tr->alpha, (void*)tr->beta, (void*)tr->lab,
-                    (void*)tr->loff})
+                    (void*)tr->loff, (void*)tr->pred, (void*)tr->lab8, (void*)tr->poff, (void*)tr->pred_len, (void*)tr->edit,
+                    (void*)tr->estatus})
         f(q);
     for (float* q : tr->act) f(q);
     for (float* q : tr->save) f(q);
@@ -606,6 +623,62 @@ int train_backward(po_trainer* tr, int n, Timer& tm) {
     return tm.end();
 }
 
+// the argument and label checks of a step, for `me` (po_train_step / po_train_eval): loff[0..n] = the windows' label
+// offsets, *maxL = the longest label
+int check_batch(const po_trainer* tr, const std::string& me, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                int merge_repeated, std::vector<int64_t>& loff, int64_t* maxL) {
+    if (n < 1 || n > tr->max_batch)
+        return po_fail(PO_E_ARG, me + ": " + std::to_string(n) + " windows, the trainer holds 1 to " +
+                       std::to_string(tr->max_batch));
+    const int T = tr->T;
+    loff.assign(n + 1, 0);
+    *maxL = 0;
+    for (int w = 0; w < n; ++w) {
+        const int L = label_len_h[w];
+        if (L < 0) return po_fail(PO_E_ARG, me + ": window " + std::to_string(w) + " has a negative label length");
+        if (L > 0 && !labels_h) return po_fail(PO_E_ARG, me + ": null labels");
+        int rep = 0;
+        for (int j = 0; j < L; ++j) {
+            const int32_t c = labels_h[loff[w] + j];
+            if (c < 0 || c > 3)
+                return po_fail(PO_E_ARG, me + ": window " + std::to_string(w) + " has label " + std::to_string(c) +
+                               " at position " + std::to_string(j) + " (labels are 0..3 = A C G T)");
+            if (j > 0 && c == labels_h[loff[w] + j - 1]) ++rep;
+        }
+        const int need = L + (merge_repeated ? rep : 0);
+        if (need > T)
+            return po_fail(PO_E_ARG, me + ": window " + std::to_string(w) + "'s " + std::to_string(L) +
+                           " labels need " + std::to_string(need) + " frames, the window has " +
+                                            std::to_string(T));
+        loff[w + 1] = loff[w] + L;
+        *maxL = std::max<int64_t>(*maxL, L);
+    }
+    return PO_OK;
+}
+
+// α / β (with_ab) and the labels: sized by this batch's longest label and label count, grown when a batch needs more
+int grow_batch_buffers(po_trainer* tr, int64_t M, int Smax, int64_t n_labels, bool with_ab) {
+    const size_t ab = (size_t)M * Smax * 8;
+    if (with_ab && ab > tr->ab_cap) {
+        if (tr->alpha) (void)hipFree(tr->alpha);
+        if (tr->beta) (void)hipFree(tr->beta);
+        tr->alpha = tr->beta = nullptr;
+        tr->ab_cap = 0;
+        PO_HIPCHK(hipMalloc(&tr->alpha, ab));
+        PO_HIPCHK(hipMalloc(&tr->beta, ab));
+        tr->ab_cap = ab;
+    }
+    const size_t lb = (size_t)std::max<int64_t>(1, n_labels) * 4;
+    if (lb > tr->lab_cap) {
+        if (tr->lab) (void)hipFree(tr->lab);
+        tr->lab = nullptr;
+        tr->lab_cap = 0;
+        PO_HIPCHK(hipMalloc(&tr->lab, lb));
+        tr->lab_cap = lb;
+    }
+    return PO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -672,6 +745,11 @@ po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max
     alloc((void**)&tr->lsm, (size_t)M * NOUT * 8);
     alloc((void**)&tr->logz, (size_t)max_batch * 8);
     alloc((void**)&tr->loff, (size_t)(max_batch + 1) * 8);
+    alloc((void**)&tr->pred, (size_t)M);
+    alloc((void**)&tr->poff, (size_t)(max_batch + 1) * 8);
+    alloc((void**)&tr->pred_len, (size_t)max_batch * 4);
+    alloc((void**)&tr->edit, (size_t)max_batch * 4);
+    alloc((void**)&tr->estatus, (size_t)max_batch * 4);
     if (ok && (e = hipStreamCreateWithFlags(&tr->stream, hipStreamNonBlocking)) != hipSuccess) ok = false;
     if (ok && (e = hipMemset(tr->p, 0, nw * 4)) != hipSuccess) ok = false;
     if (ok && (e = hipMemset(tr->m, 0, nw * 4)) != hipSuccess) ok = false;
@@ -725,65 +803,26 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
                   float* grad_h, float* stage_ms_h) {
     po_set_error("");
     if (!tr || !signal_h || !label_len_h || !loss_h) return po_fail(PO_E_ARG, "po_train_step: null argument");
-    if (n < 1 || n > tr->max_batch)
-        return po_fail(PO_E_ARG, "po_train_step: " + std::to_string(n) + " windows, the trainer holds 1 to " +
-                       std::to_string(tr->max_batch));
-    const int T = tr->T;
-    std::vector<int64_t> loff(n + 1, 0);
+    std::vector<int64_t> loff;
     int64_t maxL = 0;
-    for (int w = 0; w < n; ++w) {
-        const int L = label_len_h[w];
-        if (L < 0) return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has a negative label length");
-        int rep = 0;
-        for (int j = 0; j < L; ++j) {
-            const int32_t c = labels_h[loff[w] + j];
-            if (c < 0 || c > 3)
-                return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + " has label " + std::to_string(c) +
-                               " at position " + std::to_string(j) + " (labels are 0..3 = A C G T)");
-            if (j > 0 && c == labels_h[loff[w] + j - 1]) ++rep;
-        }
-        const int need = L + (merge_repeated ? rep : 0);
-        if (need > T)
-            return po_fail(PO_E_ARG, "po_train_step: window " + std::to_string(w) + "'s " + std::to_string(L) +
-                           " labels need " + std::to_string(need) + " frames, the window has " +
-                                            std::to_string(T));
-        loff[w + 1] = loff[w] + L;
-        maxL = std::max<int64_t>(maxL, L);
-    }
-    if (loff[n] > 0 && !labels_h) return po_fail(PO_E_ARG, "po_train_step: null labels");
+    int rc = check_batch(tr, "po_train_step", n, labels_h, label_len_h, merge_repeated, loff, &maxL);
+    if (rc != PO_OK) return rc;
+    const int T = tr->T;
     const int64_t M = (int64_t)n * T;
     const int Smax = (int)(2 * maxL + 1);
-    // α / β and the labels: sized by this batch's longest label, grown when a batch needs more
-    const size_t ab = (size_t)M * Smax * 8;
-    if (ab > tr->ab_cap) {
-        if (tr->alpha) (void)hipFree(tr->alpha);
-        if (tr->beta) (void)hipFree(tr->beta);
-        tr->alpha = tr->beta = nullptr;
-        tr->ab_cap = 0;
-        PO_HIPCHK(hipMalloc(&tr->alpha, ab));
-        PO_HIPCHK(hipMalloc(&tr->beta, ab));
-        tr->ab_cap = ab;
-    }
-    const size_t lb = (size_t)std::max<int64_t>(1, loff[n]) * 4;
-    if (lb > tr->lab_cap) {
-        if (tr->lab) (void)hipFree(tr->lab);
-        tr->lab = nullptr;
-        tr->lab_cap = 0;
-        PO_HIPCHK(hipMalloc(&tr->lab, lb));
-        tr->lab_cap = lb;
-    }
+    if ((rc = grow_batch_buffers(tr, M, Smax, loff[n], true)) != PO_OK) return rc;
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + NSTAGE, 0.f);
     PO_HIPCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
     if (loff[n] > 0) PO_HIPCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
     PO_HIPCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
     Timer tm{tr, stage_ms_h};
-    int rc = train_forward(tr, n, tm);
+    rc = train_forward(tr, n, tm);
     if (rc == PO_OK) rc = tm.begin(1);
     if (rc == PO_OK) {
         const float* logits = tr->act.back();
         hipLaunchKernelGGL(ctc_lsm_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, logits, tr->lsm, M);
         hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)n), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, T,
-                           Smax, merge_repeated ? 1 : 0, tr->alpha, tr->beta, tr->logz);
+                           Smax, merge_repeated ? 1 : 0, 1, tr->alpha, tr->beta, tr->logz);
         hipLaunchKernelGGL(ctc_grad_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, n, T,
                            Smax, tr->alpha, tr->beta, tr->logz, 1.f / (float)n, tr->dlog, tr->loss);
         rc = tm.end();
@@ -807,6 +846,76 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
         if (e == hipSuccess && grad_h) e = hipMemcpyAsync(grad_h, tr->g, (size_t)tr->nw * 4, hipMemcpyDeviceToHost, tr->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
         if (e != hipSuccess) rc = po_fail_hip(e, "po_train_step: results");
+    }
+    tm.finish(rc == PO_OK);
+    return rc;
+}
+
+int po_train_eval(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                  int merge_repeated, float* loss_h, int32_t* edit_h, int32_t* pred_len_h, int32_t* status_h,
+                  uint8_t* pred_h, float* stage_ms_h) {
+    po_set_error("");
+    if (!tr || !signal_h || !label_len_h || !edit_h || !pred_len_h || !status_h)
+        return po_fail(PO_E_ARG, "po_train_eval: null argument");
+    std::vector<int64_t> loff;
+    int64_t maxL = 0;
+    int rc = check_batch(tr, "po_train_eval", n, labels_h, label_len_h, merge_repeated, loff, &maxL);
+    if (rc != PO_OK) return rc;
+    const int T = tr->T;
+    const int64_t M = (int64_t)n * T;
+    const int Smax = (int)(2 * maxL + 1);
+    if ((rc = grow_batch_buffers(tr, M, Smax, loff[n], loss_h != nullptr)) != PO_OK) return rc;
+    const size_t nl = (size_t)loff[n];
+    if (std::max<size_t>(nl, 1) > tr->lab8_cap) {
+        if (tr->lab8) (void)hipFree(tr->lab8);
+        tr->lab8 = nullptr;
+        tr->lab8_cap = 0;
+        PO_HIPCHK(hipMalloc(&tr->lab8, std::max<size_t>(nl, 1)));
+        tr->lab8_cap = std::max<size_t>(nl, 1);
+    }
+    // (pageable host memory: each copy below has left these vectors when its call returns)
+    std::vector<uint8_t> lab8(nl);
+    for (size_t j = 0; j < nl; ++j) lab8[j] = (uint8_t)labels_h[j];
+    std::vector<int64_t> poff(n + 1);
+    for (int w = 0; w <= n; ++w) poff[w] = (int64_t)w * T;
+    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + 3, 0.f);
+    PO_HIPCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
+    if (nl > 0) {
+        PO_HIPCHK(hipMemcpyAsync(tr->lab8, lab8.data(), nl, hipMemcpyHostToDevice, tr->stream));
+        if (loss_h) PO_HIPCHK(hipMemcpyAsync(tr->lab, labels_h, nl * 4, hipMemcpyHostToDevice, tr->stream));
+    }
+    PO_HIPCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
+    PO_HIPCHK(hipMemcpyAsync(tr->poff, poff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
+    Timer tm{tr, stage_ms_h};
+    rc = train_forward(tr, n, tm);
+    if (rc == PO_OK && loss_h) {
+        rc = tm.begin(1);
+        if (rc == PO_OK) {
+            hipLaunchKernelGGL(ctc_lsm_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, tr->act.back(), tr->lsm, M);
+            hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)n), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff,
+                               T, Smax, merge_repeated ? 1 : 0, 0, tr->alpha, tr->beta, tr->logz);
+            hipLaunchKernelGGL(ctc_loss_kernel, dim3(blocks(n, 256)), dim3(256), 0, tr->stream, tr->logz, n, tr->loss);
+            rc = tm.end();
+        }
+    }
+    if (rc == PO_OK) rc = tm.begin(2);
+    if (rc == PO_OK) {
+        po_launch_eval_path(tr->probs, n, T, tr->pred, tr->pred_len, tr->stream);
+        po_launch_edit_distance(tr->pred, tr->poff, tr->pred_len, tr->lab8, tr->loff, n, tr->edit, tr->estatus, tr->stream);
+        rc = tm.end();
+    }
+    if (rc == PO_OK) {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_eval: launch");
+    }
+    if (rc == PO_OK) {
+        hipError_t e = hipMemcpyAsync(edit_h, tr->edit, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(pred_len_h, tr->pred_len, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(status_h, tr->estatus, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess && loss_h) e = hipMemcpyAsync(loss_h, tr->loss, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess && pred_h) e = hipMemcpyAsync(pred_h, tr->pred, (size_t)M, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_eval: results");
     }
     tm.finish(rc == PO_OK);
     return rc;

@@ -1,7 +1,8 @@
 """`train`: CTC training of the basecalling network (the reference's network.py:66-179), on the GPU.
 
 The step (forward pass, tf.compat.v1.nn.ctc_loss averaged over the batch, its gradient, Keras Adam) runs in HIP
-(poreover_amd/csrc/po_train.hip through a po_trainer handle); this module does what the reference's host loop does:
+(poreover_amd/csrc/po_train.hip through a po_trainer handle), and so does the held-out validation (po_train_eval: the
+argmax path and its edit distance to the labels); this module does what the reference's host loop does:
 loads the .npz, draws the holdout and the batches, runs the schedule, prints the same stderr lines, writes train.log,
 model.json and the checkpoints.  Where the reference differs from its own flags, this honours them:
 --learning_rate and --ctc_merge_repeated take effect, T is the data's window length, the holdout is fixed for the run,
@@ -18,7 +19,7 @@ from .. import _lib
 from . import checkpoint as ckpt
 
 __all__ = ["TrainError", "Trainer", "load_data", "check_labels", "plan_batches", "init_weights", "validation_error",
-           "train"]
+           "validation_error_device", "train"]
 
 ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7)     # Keras Adam()'s defaults
 
@@ -198,6 +199,34 @@ class Trainer:
                 stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
         return (loss, g) if grad else loss
 
+    def evaluate(self, windows, labels, merge_repeated=False, loss=True, predictions=False, stage_ms=None):
+        """held-out validation of windows (n, T) with labels (a list of n int sequences) on the resident parameters
+        (po_train_eval; no gradient, no update): a dict of edit (n,) int32, the edit distance of each window's argmax path
+        (classes 0..3 in frame order, repeats kept) to its labels; pred_len (n,) int32, the paths' lengths; status (n,)
+        int32, 0 or E_CAP (edit -1) where path and label are both longer than EDIT_MAX_SHORT; with loss=True loss (n,)
+        float32, step(update=False)'s bits; with predictions=True pred, a list of n uint8 arrays of codes 0..3"""
+        x = np.ascontiguousarray(windows, dtype=np.float32)
+        n = x.shape[0]
+        lens = np.asarray([len(l) for l in labels], dtype=np.int32)
+        lab = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).ravel() for l in labels])
+                                   if lens.sum() else np.zeros(1, dtype=np.int32), dtype=np.int32)
+        edit, plen, st = (np.empty(n, dtype=np.int32) for _ in range(3))
+        ls = np.empty(n, dtype=np.float32) if loss else None
+        pred = np.empty((n, self.T), dtype=np.uint8) if predictions else None
+        ms = (C.c_float * len(_lib.EVAL_STAGES))() if stage_ms is not None else None
+        rc = self.lib.po_train_eval(self.h, x.ctypes.data, n, lab.ctypes.data, lens.ctypes.data, 1 if merge_repeated else 0,
+                                    ls.ctypes.data if loss else None, edit.ctypes.data, plen.ctypes.data, st.ctypes.data,
+                                    pred.ctypes.data if predictions else None, ms)
+        _lib.check(rc, "po_train_eval")
+        if stage_ms is not None:
+            for k, name in enumerate(_lib.EVAL_STAGES):
+                stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+        out = {"edit": edit, "pred_len": plen, "status": st}
+        if loss:
+            out["loss"] = ls
+        if predictions:
+            out["pred"] = [pred[w, :plen[w]].copy() for w in range(n)]
+        return out
 
     def last(self, n):
         """(logits, dlogits), each (n, T, 5) float32, of the last step's first n windows"""
@@ -227,6 +256,26 @@ def validation_error(net, batches, signal, labels):
         probs = forward(net, signal[b])
         best = np.argmax(probs, axis=2)
         d = [_edit(p[p < 4], labels[w]) / len(labels[w]) for p, w in zip(best, b) if len(labels[w])]
+        if d:
+            per_batch.append(np.mean(d))
+    return float(np.mean(per_batch)) if per_batch else float("nan")
+
+
+def validation_error_device(trainer, batches, signal, labels, stage_ms=None):
+    """validation_error on the trainer's resident parameters (Trainer.evaluate: the forward pass, the argmax path and the
+    edit distance stay on the device; no parameter leaves it): the same arithmetic in the same order and dtype, so the
+    same float.  A window the device declines (status E_CAP) gets its distance on the host, from the downloaded path."""
+    per_batch = []
+    for b in batches:
+        lab = [labels[w] for w in b]
+        r = trainer.evaluate(signal[b], lab, loss=False, stage_ms=stage_ms)
+        edit = [int(e) for e in r["edit"]]
+        capped = [k for k in range(len(b)) if r["status"][k] != _lib.OK and len(lab[k])]
+        if capped:
+            pred = trainer.evaluate(signal[b], lab, loss=False, predictions=True)["pred"]
+            for k in capped:
+                edit[k] = _edit(pred[k], lab[k])
+        d = [edit[k] / len(lab[k]) for k in range(len(b)) if len(lab[k])]
         if d:
             per_batch.append(np.mean(d))
     return float(np.mean(per_batch)) if per_batch else float("nan")
@@ -291,7 +340,7 @@ def train(args):
             if t % args.loss_every == 0:
                 print("Iteration:{}\tLoss:{}".format(t, mean), file=sys.stderr)
             if t % args.save_every == 0 and len(held) > 0:
-                d = validation_error(tr.network(), held, signal, lab_list)
+                d = validation_error_device(tr, held, signal, lab_list)
                 print("Iteration:{}\tEdit distance (test):{}".format(t, d), file=sys.stderr)
         ckpt.write_weights(os.path.join(out_dir, "final.npz"), tr.network())
     saved.append("final")
