@@ -435,13 +435,17 @@ int po_wave_plan(const int64_t* rows1, const int64_t* rows2, int n, int wave_pai
  *              k-1's cout (1 for the first); the last layer is PO_CALL_DENSE with cout 5
  *   - weights: every layer's f32 tensors back to back, in Keras' layouts, layer by layer:
  *              PO_CALL_CONV   kernel (kernel, cin, cout), bias (cout)          Conv1D, padding "same", stride 1, ReLU
- *              PO_CALL_BIGRU  forward then backward GRU(128), each: kernel (cin, 384), recurrent kernel (128, 384),
- *                             bias (2, 384) (input bias, recurrent bias; reset_after); gates z, r, h; cout = 256,
+ *              PO_CALL_BIGRU  forward then backward GRU(H), each: kernel (cin, 3H), recurrent kernel (H, 3H),
+ *                             bias (2, 3H) (input bias, recurrent bias; reset_after); gates z, r, h; cout = 2H,
  *                             [forward, backward] with the backward output in forward time order (Bidirectional)
- *              PO_CALL_GRU    one forward GRU(128), tensors as above; cout = 128
- *              PO_CALL_GRU_BACK  GRU(128, go_backwards = True): walks the window from its end and writes its outputs in
- *                             that reversed order (the next layer consumes them so); cout = 128
+ *              PO_CALL_GRU    one forward GRU(H), tensors as above; cout = H
+ *              PO_CALL_GRU_BACK  GRU(H, go_backwards = True): walks the window from its end and writes its outputs in
+ *                             that reversed order (the next layer consumes them so); cout = H
  *              PO_CALL_DENSE  kernel (cin, 5), bias (5)
+ *              H, the units per direction, is read from cout: 16, 32, 48, 64, 80, 96, 112 or 128 (one wave of the
+ *              recurrence per 16 units, at most 8), the same in every GRU layer of a model; a GRU direction holds
+ *              cin * 3H + H * 3H + 2 * 3H weights.  Any other width, or layers of different widths, is
+ *              PO_E_UNSUPPORTED with the width in the message, from every entry that takes a model (po_train_create too).
  *   - probs:   n * T * 5 softmax probabilities; logits (or NULL): the Dense outputs before the softmax
  *   - stage_ms_h (or NULL): HOST float[4] to which device milliseconds are ADDED per stage — 0 Conv1D, 1 GRU input
  *              projection, 2 GRU recurrence, 3 Dense + softmax — measured with events (the call then synchronises)
@@ -471,13 +475,14 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
  *                 About one called base in a thousand differs from f32.  po_call_workspace_bytes then includes room for
  *                 the bf16 copy of a layer's W (a constant: what the query answers for n = 0), made anew in every call
  *                 (its time counts in stage 1); a workspace sized
- *                 under PO_CALL_F32 and used under PO_CALL_BF16 is PO_E_CAP.
+ *                 under PO_CALL_F32 and used under PO_CALL_BF16 is PO_E_CAP.  Built for GRU layers of 128 units alone: a
+ *                 model of another width run under PO_CALL_BF16 is PO_E_UNSUPPORTED, naming the precision and the width.
  * Any other value is PO_E_ARG and leaves the mode as it was. */
 #define PO_CALL_F32 0
 #define PO_CALL_BF16 1
 int po_set_call_precision(int precision);
 int po_get_call_precision(void);
-/* The projection stage alone, on host buffers: P_h[ndir][M][384] = x_h[M][cin] · w_h[ndir][cin][384] + bin_h[ndir][384] by the
+/* The projection stage alone of a 128-unit layer, on host buffers: P_h[ndir][M][384] = x_h[M][cin] · w_h[ndir][cin][384] + bin_h[ndir][384] by the
  * kernel(s) of `precision` (explicit: the selector above is not read).  M >= 0 (0: PO_OK, nothing written), cin >= 1, ndir 1
  * or 2; a null pointer, another value or another precision is PO_E_ARG naming the argument, before any allocation. */
 int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w_h, const float* bin_h, int precision,

@@ -11,9 +11,10 @@
 //   gru_proj_kernel    a GRU layer's input projection x·W + b_in for all timesteps of all windows and both directions:
 //                      a time-parallel GEMM on v_mfma_f32_16x16x4_f32 (a k-ordered fma chain per element)
 //   gru_recur_kernel   the recurrence, ONE persistent launch per layer covering both directions: a workgroup owns 16
-//                      windows in one direction and walks their T steps; its 8 waves own 16 hidden units each and keep
-//                      their 48 columns of U (128 x 48 f32 = 96 VGPRs per lane) in registers for the whole walk; h_t
-//                      goes through LDS (double buffered: one barrier per step)
+//                      windows in one direction and walks their T steps; its H / 16 waves (H units per direction: 16 to
+//                      128 in steps of 16, one instantiation each) own 16 hidden units each and keep their 48 columns
+//                      of U (H x 48 f32 = 3H/4 VGPRs per lane, 96 at H = 128) in registers for the whole walk; h_t goes
+//                      through LDS (double buffered: one barrier per step)
 //   dense_softmax_kernel  Dense(5) + softmax, one lane per frame
 //
 // Keras' GRU (reset_after = True), gates in the order z, r, h:
@@ -46,8 +47,9 @@ size_t wb_bytes_for(const po_call_layer* L, int nl) {
     return b;
 }
 
+// (P is sized for the widest GRU, whatever the model's)
 size_t ws_bytes_for(int64_t M, int64_t wmax) {
-    return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G * 4);
+    return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G_MAX * 4);
 }
 
 // workgroups of gru_proj_bf16_kernel: one per compute unit (each holds ~100 KB of LDS); any count gives the same bits
@@ -57,6 +59,14 @@ int bf_blocks_cap() {
         cus < 1)
         cus = 256;
     return cus;
+}
+
+// the bf16 projection kernels own G / 2 = 192 columns per workgroup: 128 units alone
+int check_bf16_units(int units, const char* me) {
+    if (units && units != H_MAX)
+        return po_fail(PO_E_UNSUPPORTED, std::string(me) + ": bf16 precision (PO_CALL_BF16) is built for GRU layers of " +
+                       std::to_string(H_MAX) + " units, the model has " + std::to_string(units) + " (use PO_CALL_F32)");
+    return PO_OK;
 }
 
 struct Stage {
@@ -90,13 +100,15 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
     po_set_error("");
     if (n < 0 || T < 1 || !signal || !weights || !probs) return po_fail(PO_E_ARG, "po_call_batch: null argument or T < 1");
     int64_t nw;
-    const int64_t wmax = check_model(layers_h, n_layers, &nw);
+    int units = 0, rc0;
+    const int64_t wmax = check_model(layers_h, n_layers, &nw, &units);
     if (wmax < 0) return (int)wmax;
     if (nw != n_weights) return po_fail(PO_E_ARG, "po_call_batch: the model has " + std::to_string(nw) + " weights, " +
                                         std::to_string(n_weights) + " given");
+    const bool bf16 = g_precision.load() == PO_CALL_BF16;   // (a mode set after the size query finds the workspace too small)
+    if (bf16 && (rc0 = check_bf16_units(units, "po_call_batch")) != PO_OK) return rc0;
     if (n == 0) return PO_OK;
     const int64_t M = (int64_t)n * T;
-    const bool bf16 = g_precision.load() == PO_CALL_BF16;   // (a mode set after the size query finds the workspace too small)
     if (!ws || ws_bytes < ws_bytes_for(M, wmax) + (bf16 ? wb_bytes_for(layers_h, n_layers) : 0))
         return po_fail(PO_E_CAP, "po_call_batch: workspace too small");
     hipStream_t stream = (hipStream_t)stream_;
@@ -142,14 +154,14 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
             break;
         } else {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
-            const int64_t per_dir = (int64_t)l.cin * G + (int64_t)H * G + 2 * G;   // W, U, bias (2, 384)
+            const int H = gru_units(l), G = 3 * H;
+            const int64_t per_dir = (int64_t)l.cin * G + (int64_t)H * G + 2 * G;   // W, U, bias (2, G)
             if ((rc = begin(1)) != PO_OK) break;
             if (bf16)
                 launch_gru_proj_bf16(stream, x, l.cin, nd, w, per_dir, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, Wb, P, M,
                                      bf_cap);
             else
-                hipLaunchKernelGGL(gru_proj_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(nd * (G / 64))), dim3(256), 0,
-                                   stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, P, M);
+                launch_gru_proj(stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, P, M, G, nd);
             if ((rc = end()) != PO_OK) break;
             RecurArgs ra;
             std::memset(&ra, 0, sizeof(ra));
@@ -167,8 +179,8 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
             ra.n = n;
             ra.T = T;
             if ((rc = begin(2)) != PO_OK) break;
-            hipLaunchKernelGGL(gru_recur_kernel, dim3((unsigned)((n + RT - 1) / RT), (unsigned)nd), dim3(RWAVES * 64), 0,
-                               stream, ra);
+            PO_FOR_UNITS(H, hipLaunchKernelGGL(gru_recur_kernel<HH>, dim3((unsigned)((n + RT - 1) / RT), (unsigned)nd),
+                                               dim3(HH * 4), 0, stream, ra));
             rc = end();
             w += nd * per_dir;
         }
@@ -199,10 +211,12 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
     po_set_error("");
     if (n < 0 || T < 1 || !signal_h || !weights_h || !probs_h) return po_fail(PO_E_ARG, "po_call_batch_h: null argument or T < 1");
     int64_t nw;
-    const int64_t wmax = check_model(layers_h, n_layers, &nw);
+    int units = 0, rc0;
+    const int64_t wmax = check_model(layers_h, n_layers, &nw, &units);
     if (wmax < 0) return (int)wmax;
     if (nw != n_weights) return po_fail(PO_E_ARG, "po_call_batch_h: the model has " + std::to_string(nw) + " weights, " +
                                         std::to_string(n_weights) + " given");
+    if (g_precision.load() == PO_CALL_BF16 && (rc0 = check_bf16_units(units, "po_call_batch_h")) != PO_OK) return rc0;
     if (n == 0) return PO_OK;
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + 4, 0.f);
     // windows per pass: as many as ~4 GiB of workspace holds, a whole number of recurrence tiles (a window's bits do
@@ -246,6 +260,7 @@ int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w
     if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
         return po_fail(PO_E_ARG, me + "precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
     if (M == 0) return PO_OK;
+    constexpr int G = G_MAX;   // (this entry is the 128-unit projection alone)
     PoDev dx, dw, db, dP, dwb;
     PO_HIPCHK(dx.up(x_h, (size_t)M * cin * 4));
     PO_HIPCHK(dw.up(w_h, (size_t)ndir * cin * G * 4));
@@ -255,8 +270,8 @@ int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w
         PO_HIPCHK(dwb.up(nullptr, bf_w_elems(cin, ndir) * 2));
         launch_gru_proj_bf16(nullptr, dx, cin, ndir, dw, (int64_t)cin * G, db, G, dwb, dP, M, bf_blocks_cap());
     } else {
-        hipLaunchKernelGGL(gru_proj_kernel, dim3((unsigned)((M + 63) / 64), (unsigned)(ndir * (G / 64))), dim3(256), 0, nullptr,
-                           dx.as<float>(), cin, dw.as<float>(), db.as<float>(), (int64_t)cin * G, (int64_t)G, dP.as<float>(), M);
+        launch_gru_proj(nullptr, dx.as<float>(), cin, dw.as<float>(), db.as<float>(), (int64_t)cin * G, (int64_t)G, dP.as<float>(),
+                        M, G, ndir);
     }
     PO_HIPCHK(hipGetLastError());
     PO_HIPCHK(hipDeviceSynchronize());

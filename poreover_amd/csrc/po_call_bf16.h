@@ -36,6 +36,7 @@ namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+constexpr int G = G_MAX;            // these kernels are built for 128 units alone (po_call_batch refuses the others)
 constexpr int BF_CH = G / 2;        // columns a workgroup owns (one half of a direction)
 constexpr int BF_CT = BF_CH / 16;   // 12 column tiles per wave
 constexpr int BF_PK = 256;          // k per LDS panel

@@ -7,12 +7,13 @@
 namespace {
 
 
-constexpr int H = 128;          // GRU units
-constexpr int G = 3 * H;        // gate columns per direction
+// GRU units per direction, H: a multiple of 16 from 16 to H_MAX, one width for the whole model (check_model).  The
+// recurrence kernels are templates on H (H / 16 waves of 16 units, G = 3 H gate columns per direction); everything else
+// takes a layer's H and G as arguments.
+constexpr int H_MAX = 128;
+constexpr int G_MAX = 3 * H_MAX;
 constexpr int NOUT = 5;         // Dense outputs (A, C, G, T, blank)
 constexpr int RT = 16;          // windows per recurrence workgroup (the MFMA's M)
-constexpr int RWAVES = H / 16;  // 8 waves, 16 units each
-constexpr int HS = H + 1;       // LDS row stride of h (one pad word: the 16 rows of an MFMA operand hit distinct banks)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -41,16 +42,22 @@ __global__ __launch_bounds__(256) void conv_relu_kernel(const float* __restrict_
     }
 }
 
-// P[d][m][c] = sum_k x[m][k] * W[d][k][c] + b_in[d][c] for m < M, c < 384, d < ndir.  One wave per 16 rows x 64 columns
+// P[d][m][c] = sum_k x[m][k] * W[d][k][c] + b_in[d][c] for m < M, c < G, d < ndir.  One wave per 16 rows x 64 columns
 // (four 16 x 16 accumulators), four waves per workgroup along the rows; K is walked 4 at a time, zero-filled past cin.
+// G is a multiple of 16: the last of a direction's (G + 63) / 64 column tiles may hold fewer than four live 16-column
+// sub-tiles, and a dead one neither loads nor stores (the gates' boundaries mean nothing here).  WHOLE: G is a multiple of
+// 64 (H = 64 and 128) and every sub-tile is live, known at compile time.
+template <bool WHOLE>
 __global__ __launch_bounds__(256) void gru_proj_kernel(const float* __restrict__ x, int cin, const float* __restrict__ W,
                                                        const float* __restrict__ bin, int64_t wstride, int64_t bstride,
-                                                       float* __restrict__ P, int64_t M) {
+                                                       float* __restrict__ P, int64_t M, int G) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
     if (m0 >= M) return;
-    const int d = blockIdx.y / (G / 64);
-    const int c0 = (blockIdx.y % (G / 64)) * 64;
+    const int ntile = (G + 63) / 64;
+    const int d = blockIdx.y / ntile;
+    const int c0 = (blockIdx.y % ntile) * 64;
+    const int nq = WHOLE ? 4 : min(4, (G - c0) / 16);   // live sub-tiles (wave-uniform)
     const float* Wd = W + d * wstride;
     const int i = lane & 15, kq = lane >> 4;
     const int64_t arow = m0 + i;
@@ -63,12 +70,13 @@ __global__ __launch_bounds__(256) void gru_proj_kernel(const float* __restrict__
         const float a = (arow_ok && kok) ? x[arow * cin + k] : 0.f;
         const float* wr = Wd + (int64_t)k * G + c0 + i;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = mfma4(a, kok ? wr[q * 16] : 0.f, acc[q]);
+        for (int q = 0; q < 4; ++q) acc[q] = mfma4(a, (kok && q < nq) ? wr[q * 16] : 0.f, acc[q]);
     }
     float* Pd = P + (int64_t)d * M * G;
     const float* bd = bin + d * bstride;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
+        if (q >= nq) break;
         const int col = c0 + q * 16 + i;
         const float b = bd[col];
 #pragma unroll
@@ -79,10 +87,20 @@ __global__ __launch_bounds__(256) void gru_proj_kernel(const float* __restrict__
     }
 }
 
+// gru_proj_kernel for nd directions on `stream`
+inline void launch_gru_proj(hipStream_t stream, const float* x, int cin, const float* W, const float* bin, int64_t wstride,
+                            int64_t bstride, float* P, int64_t M, int G, int nd) {
+    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)(nd * ((G + 63) / 64)));
+    if (G % 64 == 0)
+        hipLaunchKernelGGL(gru_proj_kernel<true>, grid, dim3(256), 0, stream, x, cin, W, bin, wstride, bstride, P, M, G);
+    else
+        hipLaunchKernelGGL(gru_proj_kernel<false>, grid, dim3(256), 0, stream, x, cin, W, bin, wstride, bstride, P, M, G);
+}
+
 struct RecurDir {
-    const float* P;     // [n * T][384] input projections of this direction
-    const float* U;     // [128][384] recurrent kernel
-    const float* brec;  // [384] recurrent bias
+    const float* P;     // [n * T][G] input projections of this direction
+    const float* U;     // [H][G] recurrent kernel
+    const float* brec;  // [G] recurrent bias
     int backward;       // walk t = T-1 .. 0
     int rev_out;        // write step s at position s (go_backwards without Bidirectional) instead of at t
     int col;            // first output channel
@@ -97,18 +115,20 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-
 
 // SAVE (training): also write, per walk step s of window w, what backpropagation through time needs to `save` (this
 // workgroup's direction) at row
-// w * T + s: z, r, h~, u_h = h_prev·U_h + b_rec,h and h_prev (SV_* below), 128 values each
-constexpr int SV = 5 * H;
-enum { SV_Z = 0, SV_R = H, SV_HH = 2 * H, SV_UH = 3 * H, SV_HP = 4 * H };
-template <bool SAVE>
-__device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (&hs)[2][RT][HS]) {
+// w * T + s: z, r, h~, u_h = h_prev·U_h + b_rec,h and h_prev, H values each, in this order (rows of SV = 5 H)
+enum { SV_Z = 0, SV_R = 1, SV_HH = 2, SV_UH = 3, SV_HP = 4, SV_N = 5 };
+// A workgroup of H / 16 waves, 16 units each; hs: h_t in LDS at a row stride of H + 1 (one pad word: the 16 rows of an
+// MFMA operand hit distinct banks)
+template <int H, bool SAVE>
+__device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (&hs)[2][RT][H + 1]) {
+    constexpr int G = 3 * H, HS = H + 1, SV = SV_N * H;
     const RecurDir D = a.dir[blockIdx.y];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, kq = lane >> 4;
     const int unit = wave * 16 + i;
     const int w0 = blockIdx.x * RT;
     const int T = a.T;
-    // this lane's B operands for every k-step and gate: U[4 kk + kq][g * 128 + unit]
+    // this lane's B operands for every k-step and gate: U[4 kk + kq][g * H + unit]
     float u[3][H / 4];
 #pragma unroll
     for (int kk = 0; kk < H / 4; ++kk)
@@ -157,11 +177,11 @@ __device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (
             const float hn = z * h[r] + (1.f - z) * hh;
             if (SAVE && live[r]) {
                 float* sv = save + ((int64_t)(w0 + kq * 4 + r) * T + s) * SV + unit;
-                sv[SV_Z] = z;
-                sv[SV_R] = rg;
-                sv[SV_HH] = hh;
-                sv[SV_UH] = acc[2][r] + br[2];
-                sv[SV_HP] = h[r];
+                sv[SV_Z * H] = z;
+                sv[SV_R * H] = rg;
+                sv[SV_HH * H] = hh;
+                sv[SV_UH * H] = acc[2][r] + br[2];
+                sv[SV_HP * H] = h[r];
             }
             if (live[r]) {
                 h[r] = hn;
@@ -173,10 +193,25 @@ __device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (
     }
 }
 
-__global__ __launch_bounds__(RWAVES * 64) void gru_recur_kernel(RecurArgs a) {
-    __shared__ float hs[2][RT][HS];
-    gru_recur_body<false>(a, nullptr, hs);
+template <int H>
+__global__ __launch_bounds__(H * 4) void gru_recur_kernel(RecurArgs a) {
+    __shared__ float hs[2][RT][H + 1];
+    gru_recur_body<H, false>(a, nullptr, hs);
 }
+
+// STMT with `HH` the compile-time constant equal to H_, one of the supported widths (check_model has refused the others)
+#define PO_FOR_UNITS(H_, STMT)                                                             \
+    switch (H_) {                                                                          \
+        case 16: { constexpr int HH = 16; STMT; } break;                                   \
+        case 32: { constexpr int HH = 32; STMT; } break;                                   \
+        case 48: { constexpr int HH = 48; STMT; } break;                                   \
+        case 64: { constexpr int HH = 64; STMT; } break;                                   \
+        case 80: { constexpr int HH = 80; STMT; } break;                                   \
+        case 96: { constexpr int HH = 96; STMT; } break;                                   \
+        case 112: { constexpr int HH = 112; STMT; } break;                                 \
+        case 128: { constexpr int HH = 128; STMT; } break;                                 \
+        default: break;                                                                    \
+    }
 
 // probs[m][c] = softmax(x[m]·Wd + bd)[c]; logits too when asked
 __global__ __launch_bounds__(256) void dense_softmax_kernel(const float* __restrict__ x, int cin, const float* __restrict__ Wd,
@@ -202,11 +237,18 @@ __global__ __launch_bounds__(256) void dense_softmax_kernel(const float* __restr
     }
 }
 
-// the model checked against the weights' length; returns the widest activation (channels) or po_fail(PO_E_*, message)'s code
-int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
+// units per direction of a GRU layer, or 0 where cout is not a whole number of directions
+inline int gru_units(const po_call_layer& l) {
+    const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
+    return l.cout > 0 && l.cout % nd == 0 ? l.cout / nd : 0;
+}
+
+// the model checked against the weights' length; returns the widest activation (channels) or po_fail(PO_E_*, message)'s code.
+// *units: the GRU layers' units per direction (0 for a model without one)
+int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights, int* units = nullptr) {
     if (!L || nl < 1) return po_fail(PO_E_ARG, "po_call: empty model");
     int64_t wmax = 1, nw = 0;
-    int cin = 1;
+    int cin = 1, H = 0;
     for (int k = 0; k < nl; ++k) {
         const po_call_layer& l = L[k];
         if (l.cin != cin) return po_fail(PO_E_ARG, "po_call: layer " + std::to_string(k) + " takes " + std::to_string(l.cin) +
@@ -221,7 +263,18 @@ int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
             nw += (int64_t)l.kernel * l.cin * l.cout + l.cout;
         } else if (l.kind == PO_CALL_BIGRU || l.kind == PO_CALL_GRU || l.kind == PO_CALL_GRU_BACK) {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
-            if (l.cout != nd * H) return po_fail(PO_E_UNSUPPORTED, "po_call: GRU layers have 128 units per direction");
+            const int h = gru_units(l);
+            const std::string accepted = " (accepted: 16, 32, 48, 64, 80, 96, 112 or 128 units per direction, one width for "
+                                         "every GRU layer)";
+            if (h < 16 || h > H_MAX || h % 16 != 0)
+                return po_fail(PO_E_UNSUPPORTED, "po_call: layer " + std::to_string(k) + " is a GRU of " + std::to_string(l.cout) +
+                               " outputs in " + std::to_string(nd) + " direction" + (nd == 2 ? "s" : "") + ", " +
+                               (h ? std::to_string(h) : std::string("not a whole number of")) + " units each" + accepted);
+            if (H && h != H)
+                return po_fail(PO_E_UNSUPPORTED, "po_call: layer " + std::to_string(k) + " is a GRU of " + std::to_string(h) +
+                               " units, an earlier one has " + std::to_string(H) + accepted);
+            H = h;
+            const int64_t G = 3 * (int64_t)H;
             nw += nd * ((int64_t)l.cin * G + (int64_t)H * G + 2 * G);
         } else if (l.kind == PO_CALL_DENSE) {
             if (k != nl - 1 || l.cout != NOUT) return po_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
@@ -234,6 +287,7 @@ int64_t check_model(const po_call_layer* L, int nl, int64_t* nweights) {
     }
     if (L[nl - 1].kind != PO_CALL_DENSE) return po_fail(PO_E_UNSUPPORTED, "po_call: the model must end in Dense(5)");
     *nweights = nw;
+    if (units) *units = H;
     return wmax;
 }
 

@@ -14,9 +14,10 @@
 //   ctc_grad_kernel    one lane per frame: dlogits = (softmax - posterior occupancy) / n, summed over states in order
 //   dense backward     dW = Xᵀ·dlogits (wgrad), db = column sums, dX = dlogits·Wᵀ (dense_dx_kernel)
 //   gru_back_recur_kernel  BPTT, one persistent launch per GRU layer covering both directions, the mirror of the forward
-//                      recurrence: 16 windows x one direction per workgroup, 8 waves x 16 units; each lane keeps its unit's
-//                      row of U (384 f32 = 96 VGPRs) as the B operand of dh_prev = dh⊙z + dR·Uᵀ (96 MFMA per step); dR
-//                      passes through LDS, double buffered (one barrier per step)
+//                      recurrence: 16 windows x one direction per workgroup, H / 16 waves x 16 units (a template on H like
+//                      the forward one); each lane keeps its unit's row of U (3H f32 = 3H/4 VGPRs, 96 at H = 128) as the B
+//                      operand of dh_prev = dh⊙z + dR·Uᵀ (3H/4 MFMA per step); dR passes through LDS, double buffered (one
+//                      barrier per step)
 //   wgrad_kernel + combine_kernel  every weight gradient as Aᵀ·B over the M = n·T rows on v_mfma_f32_16x16x4_f32: dW = Xᵀ·dA,
 //                      dU = H_prevᵀ·dR, Conv1D dW per tap from row-shifted inputs; split over M in a fixed partition, the
 //                      partial sums combined in a fixed order by a second launch (colsum_kernel: the bias gradients so)
@@ -43,7 +44,6 @@
 
 namespace {
 
-constexpr int GS = G + 1;        // LDS row stride of dR (one pad word: the 16 rows of an MFMA operand hit distinct banks)
 constexpr int WG_ROWS = 1024;    // rows per split of the M-reductions (at most MAX_SPLIT splits)
 constexpr int MAX_SPLIT = 64;
 constexpr int NSTAGE = 5;        // forward, CTC, backward recurrence, weight and input GEMMs, Adam
@@ -231,10 +231,10 @@ __global__ __launch_bounds__(256) void combine_kernel(const float* __restrict__ 
     out[e] = acc;
 }
 
-// dX[m][c] = sum_{d < nd} sum_k dA_d[m][k] * W_d[c][k], k < 384: the GRU layer's input gradient.  One wave per 16 rows x
+// dX[m][c] = sum_{d < nd} sum_k dA_d[m][k] * W_d[c][k], k < G: the GRU layer's input gradient.  One wave per 16 rows x
 // 64 columns, four waves per workgroup along the rows (gru_proj_kernel's tiling).
 __global__ __launch_bounds__(256) void dx_kernel(const float* __restrict__ dA, int64_t dastride, const float* __restrict__ W,
-                                                 int64_t wstride, int nd, int cin, float* __restrict__ dX, int64_t M) {
+                                                 int64_t wstride, int nd, int cin, float* __restrict__ dX, int64_t M, int G) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 16;
     if (m0 >= M) return;
@@ -247,13 +247,16 @@ __global__ __launch_bounds__(256) void dx_kernel(const float* __restrict__ dA, i
     for (int d = 0; d < nd; ++d) {
         const float* Ad = dA + d * dastride + (arow_ok ? arow : 0) * G;
         const float* Wd = W + d * wstride;
-        for (int k0 = 0; k0 < G; k0 += 4) {
-            const int k = k0 + kq;
-            const float a = arow_ok ? Ad[k] : 0.f;
+        for (int kb = 0; kb < G; kb += 12) {   // (G = 3 H is a multiple of 48: three k-steps per trip, in k order)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = c0 + q * 16 + i;
-                acc[q] = mfma4(a, c < cin ? Wd[(int64_t)c * G + k] : 0.f, acc[q]);
+            for (int k0 = kb; k0 < kb + 12; k0 += 4) {
+                const int k = k0 + kq;
+                const float a = arow_ok ? Ad[k] : 0.f;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = c0 + q * 16 + i;
+                    acc[q] = mfma4(a, c < cin ? Wd[(int64_t)c * G + k] : 0.f, acc[q]);
+                }
             }
         }
     }
@@ -291,10 +294,10 @@ __global__ __launch_bounds__(256) void conv_dx_kernel(const float* __restrict__ 
 }
 
 struct BackDir {
-    const float* save;  // [n * T][SV] the forward recurrence's saved values, walk order
-    const float* U;     // [128][384] recurrent kernel
-    float* dA;          // [n * T][384] input-projection gradient (daz, dar, dah) at input time t
-    float* dR;          // [n * T][384] recurrent gradient (daz, dar, dah·r), walk order
+    const float* save;  // [n * T][5 H] the forward recurrence's saved values, walk order
+    const float* U;     // [H][G] recurrent kernel
+    float* dA;          // [n * T][G] input-projection gradient (daz, dar, dah) at input time t
+    float* dR;          // [n * T][G] recurrent gradient (daz, dar, dah·r), walk order
     int backward, rev_out, col;
 };
 struct BackArgs {
@@ -306,7 +309,10 @@ struct BackArgs {
 // LDS-only barrier: the stores of dA / dR to global memory need not complete before the next step
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-__global__ __launch_bounds__(RWAVES * 64) void gru_back_recur_kernel(BackArgs a) {
+template <int H>
+__global__ __launch_bounds__(H * 4) void gru_back_recur_kernel(BackArgs a) {
+    constexpr int G = 3 * H, SV = SV_N * H;
+    constexpr int GS = G + 1;   // LDS row stride of dR (one pad word: the 16 rows of an MFMA operand hit distinct banks)
     __shared__ float ds[2][RT][GS];
     const BackDir D = a.dir[blockIdx.y];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -389,9 +395,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[e] = p[e] - lr_t * me / (sqrtf(ve) + eps);
 }
 
-__global__ __launch_bounds__(RWAVES * 64) void gru_recur_save_kernel(RecurArgs a, float* save0, float* save1) {
-    __shared__ float hs[2][RT][HS];
-    gru_recur_body<true>(a, blockIdx.y ? save1 : save0, hs);
+template <int H>
+__global__ __launch_bounds__(H * 4) void gru_recur_save_kernel(RecurArgs a, float* save0, float* save1) {
+    __shared__ float hs[2][RT][H + 1];
+    gru_recur_body<H, true>(a, blockIdx.y ? save1 : save0, hs);
 }
 
 inline unsigned blocks(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
@@ -403,11 +410,12 @@ struct po_trainer {
     std::vector<int64_t> woff;          // each layer's first weight
     int max_batch = 0, T = 0;
     int64_t nw = 0, wmax = 0;
+    int H = 0, G = 0;                   // the GRU layers' units per direction and 3 H
     int64_t step = 0;                   // Adam's t
     float *p = nullptr, *g = nullptr, *m = nullptr, *v = nullptr;
     float* sig = nullptr;
     std::vector<float*> act;            // each layer's output [max_batch * T][cout]
-    std::vector<float*> save;           // per GRU direction [max_batch * T][SV], 2 per layer (the second unused for 1-dir)
+    std::vector<float*> save;           // per GRU direction [max_batch * T][5 H], 2 per layer (the second unused for 1-dir)
     float *P = nullptr, *probs = nullptr, *dlog = nullptr, *loss = nullptr;
     float *dact[2] = {nullptr, nullptr}, *dA = nullptr, *dR = nullptr, *part = nullptr;
     double *lsm = nullptr, *logz = nullptr, *alpha = nullptr, *beta = nullptr;
@@ -503,11 +511,14 @@ struct Timer {
     }
 };
 
-int64_t per_dir_weights(const po_call_layer& l) { return (int64_t)l.cin * G + (int64_t)H * G + 2 * G; }
+int64_t per_dir_weights(const po_call_layer& l) {
+    const int64_t H = gru_units(l), G = 3 * H;
+    return l.cin * G + H * G + 2 * G;
+}
 
 // the forward pass of n windows (tr->sig) into every layer's output and the logits; the GRU recurrences save for BPTT
 int train_forward(po_trainer* tr, int n, Timer& tm) {
-    const int T = tr->T;
+    const int T = tr->T, H = tr->H, G = tr->G;
     const int64_t M = (int64_t)n * T;
     const float* x = tr->sig;
     int rc;
@@ -525,8 +536,7 @@ int train_forward(po_trainer* tr, int n, Timer& tm) {
         } else {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
             const int64_t per_dir = per_dir_weights(l);
-            hipLaunchKernelGGL(gru_proj_kernel, dim3(blocks(M, 64), (unsigned)(nd * (G / 64))), dim3(256), 0, tr->stream,
-                               x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, tr->P, M);
+            launch_gru_proj(tr->stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, tr->P, M, G, nd);
             RecurArgs ra;
             std::memset(&ra, 0, sizeof(ra));
             for (int d = 0; d < nd; ++d) {
@@ -542,8 +552,8 @@ int train_forward(po_trainer* tr, int n, Timer& tm) {
             ra.out_stride = l.cout;
             ra.n = n;
             ra.T = T;
-            hipLaunchKernelGGL(gru_recur_save_kernel, dim3(blocks(n, RT), (unsigned)nd), dim3(RWAVES * 64), 0, tr->stream,
-                               ra, tr->save[2 * k], tr->save[2 * k + 1]);
+            PO_FOR_UNITS(H, hipLaunchKernelGGL(gru_recur_save_kernel<HH>, dim3(blocks(n, RT), (unsigned)nd), dim3(HH * 4), 0,
+                                               tr->stream, ra, tr->save[2 * k], tr->save[2 * k + 1]));
         }
         x = out;
     }
@@ -551,7 +561,7 @@ int train_forward(po_trainer* tr, int n, Timer& tm) {
 }
 
 int train_backward(po_trainer* tr, int n, Timer& tm) {
-    const int T = tr->T;
+    const int T = tr->T, H = tr->H, G = tr->G, SV = SV_N * H;
     const int64_t M = (int64_t)n * T;
     const int nl = (int)tr->layers.size();
     int rc, cur = 0;
@@ -599,14 +609,15 @@ int train_backward(po_trainer* tr, int n, Timer& tm) {
             ba.n = n;
             ba.T = T;
             if ((rc = tm.begin(2)) != PO_OK) return rc;
-            hipLaunchKernelGGL(gru_back_recur_kernel, dim3(blocks(n, RT), (unsigned)nd), dim3(RWAVES * 64), 0, tr->stream, ba);
+            PO_FOR_UNITS(H, hipLaunchKernelGGL(gru_back_recur_kernel<HH>, dim3(blocks(n, RT), (unsigned)nd), dim3(HH * 4), 0,
+                                               tr->stream, ba));
             if ((rc = tm.begin(3)) != PO_OK) return rc;
             for (int d = 0; d < nd; ++d) {
                 float* gd = gw + d * per_dir;
                 const float* dAd = tr->dA + (int64_t)d * M * G;
                 const float* dRd = tr->dR + (int64_t)d * M * G;
                 if ((rc = wgrad(tr, X, l.cin, dAd, G, l.cin, G, M, 0, 0, l.cin, gd, true)) != PO_OK) return rc;
-                if ((rc = wgrad(tr, tr->save[2 * k + d] + SV_HP, SV, dRd, G, H, G, M, 0, 0, H, gd + (int64_t)l.cin * G,
+                if ((rc = wgrad(tr, tr->save[2 * k + d] + SV_HP * H, SV, dRd, G, H, G, M, 0, 0, H, gd + (int64_t)l.cin * G,
                                 true)) != PO_OK)
                     return rc;
                 float* gb = gd + (int64_t)l.cin * G + (int64_t)H * G;
@@ -615,7 +626,7 @@ int train_backward(po_trainer* tr, int n, Timer& tm) {
             }
             if (k > 0)
                 hipLaunchKernelGGL(dx_kernel, dim3(blocks(M, 64), blocks(l.cin, 64)), dim3(256), 0, tr->stream, tr->dA, M * G,
-                                   w, per_dir, nd, l.cin, dX, M);
+                                   w, per_dir, nd, l.cin, dX, M, G);
         }
         dY = dX;
         cur ^= 1;
@@ -686,7 +697,8 @@ extern "C" {
 po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max_batch, int T) {
     po_set_error("");
     int64_t nw;
-    const int64_t wmax = check_model(layers_h, n_layers, &nw);
+    int units = 0;
+    const int64_t wmax = check_model(layers_h, n_layers, &nw, &units);
     if (wmax < 0) return nullptr;
     if (max_batch < 1 || T < 1) {
         po_fail(PO_E_ARG, "po_train_create: max_batch and T must be positive");
@@ -698,6 +710,9 @@ po_trainer* po_train_create(const po_call_layer* layers_h, int n_layers, int max
     tr->T = T;
     tr->nw = nw;
     tr->wmax = wmax;
+    tr->H = units;
+    tr->G = 3 * units;
+    const int H = tr->H, G = tr->G, SV = SV_N * H;
     const int64_t M = (int64_t)max_batch * T;
     int64_t off = 0, maxkn = NOUT;
     bool ok = true;

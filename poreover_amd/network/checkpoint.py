@@ -11,7 +11,8 @@ The reference loads a Keras model (`build_model(args).conv1_bigru3()` or `tf.ker
   * a Keras JSON config (`--model`) or, without one, the default `conv1_bigru3` (network.py:30-36).
 
 `load_network` turns both into a `Network`: a list of layers in the order the device runs them, each with f32 arrays
-in Keras' own layouts (GRU kernel (Cin, 3H), recurrent kernel (H, 3H), bias (2, 3H) — gate order z, r, h —, Conv1D
+in Keras' own layouts (GRU kernel (Cin, 3H), recurrent kernel (H, 3H), bias (2, 3H) — gate order z, r, h; H units per
+direction, one of UNITS_ACCEPTED and the same in every GRU layer —, Conv1D
 kernel (K, Cin, F), Dense kernel (Cin, 5)).  Only what the four `build_model` architectures use is accepted; anything
 else raises NetworkError naming it."""
 import json
@@ -22,10 +23,12 @@ import struct
 import numpy as np
 
 __all__ = ["NetworkError", "Layer", "Network", "read_index", "read_checkpoint", "read_weights", "resolve_checkpoint",
-           "parse_model_json", "default_model_config", "load_network", "synthetic_weights", "ARCHITECTURES", "architecture",
+           "parse_model_json", "default_model_config", "UNITS", "UNITS_ACCEPTED", "load_network", "synthetic_weights", "ARCHITECTURES", "architecture",
            "write_weights", "crc32c"]
 
-UNITS = 128          # the only GRU width the device kernel is built for (build_model's num_neurons default)
+UNITS = 128          # the default GRU width (build_model's num_neurons default)
+UNITS_ACCEPTED = (16, 32, 48, 64, 80, 96, 112, 128)   # units per direction the device kernels are built for (one wave
+                     # per 16 units, at most 8 waves: csrc/po_call_kernels.h); one width for every GRU layer of a model
 NUM_LABELS = 5       # A, C, G, T, blank
 MAX_KERNEL = 64      # the longest Conv1D kernel the device takes (check_model in csrc/po_call_kernels.h); any filters >= 1
 
@@ -335,17 +338,19 @@ ARCHITECTURES = {
 }
 
 
-def architecture(name, kernel_size=9, filters=256):
-    """the Keras config of build_model(args).<name>() with its --kernel_size and --filters (network.py:14-55)"""
+def architecture(name, kernel_size=9, filters=256, units=UNITS):
+    """the Keras config of build_model(args).<name>() with its --kernel_size, --filters and --num_neurons
+    (network.py:14-55)"""
     if name not in ARCHITECTURES:
         _refuse("architecture %s" % name)
     conv = lambda first=False: _conv(k=kernel_size, filters=filters, first=first)
+    gru = lambda back=False: _gru(units, go_backwards=back)
+    bigru = lambda first=False: _bigru(units, first=first)
     return {
-        "bigru3": lambda: _sequential([_bigru(first=True), _bigru(), _bigru(), _dense()]),
-        "conv1_bigru3": lambda: _sequential([conv(True), _bigru(), _bigru(), _bigru(), _dense()]),
-        "conv2_bigru3": lambda: _sequential([conv(True), conv(), _bigru(), _bigru(), _bigru(), _dense()]),
-        "conv1_gru5": lambda: _sequential([conv(True), _gru(), _gru(go_backwards=True), _gru(), _gru(go_backwards=True),
-                                           _gru(), _dense()]),
+        "bigru3": lambda: _sequential([bigru(True), bigru(), bigru(), _dense()]),
+        "conv1_bigru3": lambda: _sequential([conv(True), bigru(), bigru(), bigru(), _dense()]),
+        "conv2_bigru3": lambda: _sequential([conv(True), conv(), bigru(), bigru(), bigru(), _dense()]),
+        "conv1_gru5": lambda: _sequential([conv(True), gru(), gru(True), gru(), gru(True), gru(), _dense()]),
     }[name]()
 
 
@@ -358,9 +363,18 @@ def _refuse(what):
     raise NetworkError("unsupported model: %s (supported: the build_model architectures %s)" % (what, ", ".join(ARCHITECTURES)))
 
 
-def _check_gru(c, where):
-    if c.get("units") != UNITS:
-        _refuse("%s has %s units (the device kernel is built for %d)" % (where, c.get("units"), UNITS))
+_ACCEPTED_TEXT = "the device kernels are built for %s units per direction, one width for every GRU layer" % \
+                 ", ".join(str(u) for u in UNITS_ACCEPTED)
+
+
+def _check_gru(c, where, model_units=None):
+    """refuse what the device does not run; returns the layer's units.  model_units: the width of the model's earlier GRU
+    layers (None for the first)"""
+    units = c.get("units")
+    if isinstance(units, bool) or not isinstance(units, int) or units not in UNITS_ACCEPTED:
+        _refuse("%s has %s units (%s)" % (where, units, _ACCEPTED_TEXT))
+    if model_units is not None and units != model_units:
+        _refuse("%s has %d units, an earlier GRU layer has %d (%s)" % (where, units, model_units, _ACCEPTED_TEXT))
     if not c.get("reset_after", False):
         _refuse("%s has reset_after=False" % where)
     if c.get("activation", "tanh") != "tanh" or c.get("recurrent_activation", "sigmoid") != "sigmoid":
@@ -371,17 +385,19 @@ def _check_gru(c, where):
         _refuse("%s must return sequences, without state" % where)
     if c.get("time_major", False):
         _refuse("%s is time-major" % where)
+    return units
 
 
 def parse_model_json(config):
     """[(kind, spec)] of a Keras Sequential model config (a JSON string, a parsed dict or a path to a JSON file);
-    kinds: conv (kernel, filters) | bigru | gru | gru_back | dense (units)"""
+    kinds: conv (kernel, filters) | bigru (units) | gru (units) | gru_back (units) | dense; units: per direction, one of
+    UNITS_ACCEPTED and the same for every GRU layer"""
     if isinstance(config, str):
         config = json.loads(open(config).read() if os.path.exists(config) else config)
     if config.get("class_name") != "Sequential":
         _refuse("model class %s (only Sequential)" % config.get("class_name"))
     layers = config["config"]["layers"] if isinstance(config["config"], dict) else config["config"]
-    out = []
+    out, units = [], None
     for i, ly in enumerate(layers):
         cls, c = ly.get("class_name"), ly.get("config", {})
         where = "layer %d (%s)" % (i, cls)
@@ -410,15 +426,15 @@ def parse_model_json(config):
             if c.get("merge_mode", "concat") != "concat":
                 _refuse("%s merge_mode %s (only concat)" % (where, c.get("merge_mode")))
             ic = inner.get("config", {})
-            _check_gru(ic, where)
+            units = _check_gru(ic, where, units)
             if ic.get("go_backwards", False):
                 _refuse("%s wraps a go_backwards GRU" % where)
             if "backward_layer" in c:
-                _check_gru(c["backward_layer"].get("config", {}), where + " backward layer")
-            out.append(("bigru", {}))
+                _check_gru(c["backward_layer"].get("config", {}), where + " backward layer", units)
+            out.append(("bigru", {"units": units}))
         elif cls == "GRU":
-            _check_gru(c, where)
-            out.append(("gru_back" if c.get("go_backwards", False) else "gru", {}))
+            units = _check_gru(c, where, units)
+            out.append(("gru_back" if c.get("go_backwards", False) else "gru", {"units": units}))
         elif cls == "Dense":
             if c.get("units") != NUM_LABELS or c.get("activation", "linear") not in ("linear", None) or not c.get("use_bias", True):
                 _refuse("%s must be Dense(%d) with bias and no activation" % (where, NUM_LABELS))
@@ -462,18 +478,19 @@ def load_network(weights, model=None):
             layers.append(Layer("dense", cin, NUM_LABELS, 0, [k, b], [p + "kernel", p + "bias"]))
         else:
             dirs = ["forward_layer/", "backward_layer/"] if kind == "bigru" else [""]
+            H = s["units"]
             ts, names = [], []
             for d in dirs:
                 q = p + d
                 k = _pick(w, q + "cell/kernel" + v, q + "kernel" + v)
                 u = _pick(w, q + "cell/recurrent_kernel" + v, q + "recurrent_kernel" + v)
                 b = _pick(w, q + "cell/bias" + v, q + "bias" + v)
-                if k.shape != (cin, 3 * UNITS) or u.shape != (UNITS, 3 * UNITS) or b.shape != (2, 3 * UNITS):
+                if k.shape != (cin, 3 * H) or u.shape != (H, 3 * H) or b.shape != (2, 3 * H):
                     raise NetworkError("%s GRU tensors have shapes %s %s %s, the model needs %s %s %s" % (
-                        q, k.shape, u.shape, b.shape, (cin, 3 * UNITS), (UNITS, 3 * UNITS), (2, 3 * UNITS)))
+                        q, k.shape, u.shape, b.shape, (cin, 3 * H), (H, 3 * H), (2, 3 * H)))
                 ts += [k, u, b]
                 names += [q + "cell/kernel", q + "cell/recurrent_kernel", q + "cell/bias"]
-            cout = UNITS * len(dirs)
+            cout = H * len(dirs)
             layers.append(Layer(kind, cin, cout, 0, ts, names))
             cin = cout
     return Network(layers)
@@ -504,10 +521,11 @@ def synthetic_weights(model=None, stats=None, seed=0):
             draw(p + "bias", (NUM_LABELS,), "dense/bias", cin)
         else:
             dirs = ["forward_layer/", "backward_layer/"] if kind == "bigru" else [""]
+            H = s["units"]
             for d in dirs:
                 q = p + d + "cell/"
-                draw(q + "kernel", (cin, 3 * UNITS), "gru/kernel" if cin > 1 else "gru_signal/kernel", cin)
-                draw(q + "recurrent_kernel", (UNITS, 3 * UNITS), "gru/recurrent_kernel", UNITS)
-                draw(q + "bias", (2, 3 * UNITS), "gru/bias", UNITS)
-            cin = UNITS * len(dirs)
+                draw(q + "kernel", (cin, 3 * H), "gru/kernel" if cin > 1 else "gru_signal/kernel", cin)
+                draw(q + "recurrent_kernel", (H, 3 * H), "gru/recurrent_kernel", H)
+                draw(q + "bias", (2, 3 * H), "gru/bias", H)
+            cin = H * len(dirs)
     return out

@@ -104,12 +104,11 @@ def _orthogonal(rng, rows, cols):
 
 def init_weights(model_config, seed=None):
     """{name: array} of Keras' initial weights for an architecture, drawn with numpy from `seed`: glorot_uniform for
-    every kernel (Conv1D fan_in = K·cin, fan_out = K·F), orthogonal for each recurrent kernel (128, 384), zero biases"""
+    every kernel (Conv1D fan_in = K·cin, fan_out = K·F), orthogonal for each recurrent kernel (H, 3H) — H the architecture's GRU units —, zero biases"""
     spec = ckpt.parse_model_json(model_config)
     rng = np.random.default_rng(seed)
     v = "/.ATTRIBUTES/VARIABLE_VALUE"
     out, cin = {}, 1
-    H = ckpt.UNITS
     for i, (kind, s) in enumerate(spec):
         p = "layer_with_weights-%d/" % i
         if kind == "conv":
@@ -122,6 +121,7 @@ def init_weights(model_config, seed=None):
             out[p + "bias" + v] = np.zeros(ckpt.NUM_LABELS)
         else:
             dirs = ["forward_layer/", "backward_layer/"] if kind == "bigru" else [""]
+            H = s["units"]
             for d in dirs:
                 q = p + d + "cell/"
                 out[q + "kernel" + v] = _glorot(rng, (cin, 3 * H), cin, 3 * H)
