@@ -477,7 +477,8 @@ int po_call_batch_h(const float* signal_h, int n, int T, const po_call_layer* la
  *                 (its time counts in stage 1); a workspace sized
  *                 under PO_CALL_F32 and used under PO_CALL_BF16 is PO_E_CAP.  Built for GRU layers of 128 units alone: a
  *                 model of another width run under PO_CALL_BF16 is PO_E_UNSUPPORTED, naming the precision and the width.
- * Any other value is PO_E_ARG and leaves the mode as it was. */
+ * Any other value is PO_E_ARG and leaves the mode as it was.  A trainer has a mode of its own, set per trainer with
+ * po_train_set_precision (below). */
 #define PO_CALL_F32 0
 #define PO_CALL_BF16 1
 int po_set_call_precision(int precision);
@@ -721,6 +722,31 @@ int po_eval_path_h(const float* probs_h, int n, int T, uint8_t* pred_h, int32_t*
 int po_train_eval(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
                   int merge_repeated, float* loss_h, int32_t* edit_h, int32_t* pred_len_h, int32_t* status_h,
                   uint8_t* pred_h, float* stage_ms_h);
+
+/* The precision of a trainer's GRU weight and input GEMMs: a property of the trainer, not of the process
+ * (po_set_call_precision does not reach it, and it does not reach po_call_batch).
+ *   PO_CALL_F32   (default) every product in f32
+ *   PO_CALL_BF16  four products of every GRU layer take both operands rounded to bf16 (round to nearest even,
+ *                 csrc/po_bf16_rules.h), with f32 products and sums on v_mfma_f32_16x16x32_bf16: the forward projection
+ *                 P = x·W + b_in (po_call_batch's kernels under PO_CALL_BF16: the training logits are its bits), dW = X^T·dA,
+ *                 dU = H_prev^T·dR and dX = sum_d dA_d·W_d^T.  Both recurrences (h·U, dR·U^T), the gates, the bias gradients
+ *                 (sums of the unrounded dA and dR), Conv1D, Dense, CTC, Adam, the parameters, the gradient and Adam's m and v
+ *                 stay f32.  No loss scaling: bf16 has f32's exponent range.  po_train_eval runs the trainer's forward pass
+ *                 and so follows its mode.  The bf16 copies of a layer's W live in a workspace the trainer allocates when
+ *                 the mode is first set.  A step stays the same bits on every run.
+ * Every refusal leaves the trainer in the mode it was in and allocates nothing: another value is PO_E_ARG; a trainer whose
+ * GRU layers are not 128 units is PO_E_UNSUPPORTED (the bf16 kernels are built for 128 units), naming bf16 and the width; a
+ * null trainer is PO_E_ARG.  Switching keeps the parameters and Adam's state; back under PO_CALL_F32 a step is the f32
+ * step's bits.  po_train_get_precision returns the mode. */
+int po_train_set_precision(po_trainer* tr, int precision);
+int po_train_get_precision(const po_trainer* tr);
+/* The two GEMM stages alone for a 128-unit layer, on host buffers, by the kernels of `precision` (explicit: no selector is
+ * read).  po_gru_wgrad_h: out_h[K][384] = sum_m a_h[m][k] · d_h[m][c] over M rows (a_h: rows lda >= K floats apart, d_h
+ * [M][384]), split over M and combined as po_train_step does.  po_gru_dx_h: dX_h[M][cin] = sum_d dA_h[d][M][384] · w_h[d][cin][384]^T,
+ * the directions in order.  M >= 0 (0: PO_OK, nothing written), K and cin >= 1, ndir 1 or 2; a null pointer, another value
+ * or another precision is PO_E_ARG naming the argument, before any allocation. */
+int po_gru_wgrad_h(const float* a_h, int64_t lda, int64_t M, int K, const float* d_h, int precision, float* out_h);
+int po_gru_dx_h(const float* dA_h, int64_t M, int ndir, const float* w_h, int cin, int precision, float* dX_h);
 
 /* ---- read-to-genome mapping for `benchmark` (replaces mappy.Aligner as benchmark.py:16-20 uses it) ----
  * minimap2's map-ont seeds (k = 15, w = 10, its hash64) and scores reduced to a fixed integer specification: one

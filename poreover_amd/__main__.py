@@ -41,6 +41,9 @@ def build_parser():
     p.add_argument('--num_neurons', type=int, default=128, help='Number of neurons in RNN layers')
     p.add_argument('--kernel_size', type=int, default=9, help='Kernel size in Conv1D layer (1 to 64)')
     p.add_argument('--filters', type=int, default=256, help='Number of filters in Conv1D layer (at least 1)')
+    p.add_argument('--gemm_precision', choices=['f32', 'bf16'], default='f32',
+                   help="Operands of the GRU layers' weight and input GEMMs: f32, or bf16 with f32 sums, f32 master weights and f32 Adam "
+                        '(128 GRU units; the recurrences stay f32)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="train")
 

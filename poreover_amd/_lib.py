@@ -195,6 +195,10 @@ PROTOTYPES = {
     "po_train_last": (C.c_int, [C.c_void_p, C.c_int, _vp, _vp]),
     "po_train_eval": (C.c_int, [C.c_void_p, _vp, C.c_int, _i32p, _i32p, C.c_int, _vp, _i32p, _i32p, _i32p, _cp,
                                 C.POINTER(C.c_float)]),
+    "po_train_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
+    "po_train_get_precision": (C.c_int, [C.c_void_p]),
+    "po_gru_wgrad_h": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
+    "po_gru_dx_h": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp]),
     "po_eval_path_h": (C.c_int, [_vp, C.c_int, C.c_int, _cp, _i32p]),
     "po_edit_distance_batch_h": (C.c_int, [_cp, _i64p, _cp, _i64p, C.c_int, _i32p, _i32p]),
     "po_map_sketch_h": (C.c_int, [_cp, _i64p, C.c_int, _vp, _vp, _vp, _i64p]),
@@ -289,6 +293,7 @@ def get_chain_mode():
 
 
 CALL_PRECISIONS = {"f32": 0, "bf16": 1}
+TRAIN_PRECISIONS = CALL_PRECISIONS     # po_train_set_precision takes the same codes (a trainer's own mode)
 
 
 def _precision_code(name):

@@ -52,23 +52,6 @@ size_t ws_bytes_for(int64_t M, int64_t wmax) {
     return 2 * al256((size_t)M * wmax * 4) + al256((size_t)2 * M * G_MAX * 4);
 }
 
-// workgroups of gru_proj_bf16_kernel: one per compute unit (each holds ~100 KB of LDS); any count gives the same bits
-int bf_blocks_cap() {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus < 1)
-        cus = 256;
-    return cus;
-}
-
-// the bf16 projection kernels own G / 2 = 192 columns per workgroup: 128 units alone
-int check_bf16_units(int units, const char* me) {
-    if (units && units != H_MAX)
-        return po_fail(PO_E_UNSUPPORTED, std::string(me) + ": bf16 precision (PO_CALL_BF16) is built for GRU layers of " +
-                       std::to_string(H_MAX) + " units, the model has " + std::to_string(units) + " (use PO_CALL_F32)");
-    return PO_OK;
-}
-
 struct Stage {
     hipEvent_t a = nullptr, b = nullptr;
     int kind;

@@ -1,5 +1,7 @@
 // The GRU input projection of `call --precision bf16`: bf16 operands, f32 products and sums.  Included
-// by po_call.hip alone (po_train.hip keeps the f32 kernels of po_call_kernels.h and its object does not change).
+// by po_call.hip and, through po_train_bf16.h, by po_train.hip: a trainer set to PO_CALL_BF16 (po_train_set_precision,
+// DESIGN.md §11.2) runs this same projection in its forward pass, so its logits are `call`'s bits.  The f32 kernels of
+// po_call_kernels.h stay both files' default.
 //
 //   w_to_bf16_kernel      a GRU layer's W[d][k][c] (f32, rows of 384) rounded by the rule of po_bf16_rules.h into
 //                         Wb[d][c][Kp] (bf16, TRANSPOSED: k runs fastest; Kp = cin rounded up to 32, zeros past cin), so that
@@ -185,6 +187,23 @@ inline void launch_gru_proj_bf16(hipStream_t stream, const float* x, int cin, in
     const int64_t per = std::max<int64_t>(1, std::min<int64_t>(ntiles, blocks_cap / nq));
     hipLaunchKernelGGL(gru_proj_bf16_kernel, dim3((unsigned)(per * nq)), dim3(BF_WAVES * 64), 0, stream, x, cin, Wb, bin,
                        bstride, P, M, ndir);
+}
+
+// workgroups of gru_proj_bf16_kernel: one per compute unit (each holds ~100 KB of LDS); any count gives the same bits
+inline int bf_blocks_cap() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 1)
+        cus = 256;
+    return cus;
+}
+
+// the bf16 projection kernels own G / 2 = 192 columns per workgroup: 128 units alone
+inline int check_bf16_units(int units, const char* me) {
+    if (units && units != H_MAX)
+        return po_fail(PO_E_UNSUPPORTED, std::string(me) + ": bf16 precision (PO_CALL_BF16) is built for GRU layers of " +
+                       std::to_string(H_MAX) + " units, the model has " + std::to_string(units) + " (use PO_CALL_F32)");
+    return PO_OK;
 }
 
 }  // namespace

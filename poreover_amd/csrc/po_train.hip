@@ -25,6 +25,11 @@
 //   adam_kernel        Keras Adam on the flat parameter vector
 // No float atomics and no hand-off between workgroups within a launch: a step's gradient is the same bits every run.
 //
+// po_train_set_precision(PO_CALL_BF16) (opt-in, per trainer) gives four products of every GRU layer bf16
+// operands with f32 sums: the forward projection by po_call_bf16.h's kernels (the logits are `call --precision bf16`'s), dW
+// and dU by wgrad_bf16_kernel (+ combine_kernel; the bias sums come out of the same pass) and dX by dx_bf16_kernel
+// (po_train_bf16.h).  Everything else, and every kernel of the default mode, is as described here.
+//
 // po_train_eval (held-out validation) is the forward pass above, ctc_lsm_kernel + ctc_alpha_beta_kernel (α
 // only) + ctc_loss_kernel where the losses are asked for, then po_eval.hip's eval_path_kernel and edit_distance_kernel on the
 // trainer's probabilities and labels: no gradient, no Adam.
@@ -39,13 +44,15 @@
 #include <vector>
 
 #include "po_call_kernels.h"
+#include "po_train_bf16.h"
+#include "po_train_rules.h"
 
 #include "po_internal.h"
 
 namespace {
 
-constexpr int WG_ROWS = 1024;    // rows per split of the M-reductions (at most MAX_SPLIT splits)
-constexpr int MAX_SPLIT = 64;
+constexpr int WG_ROWS = PO_TRAIN_WG_ROWS;    // rows per split of the M-reductions (at most MAX_SPLIT splits)
+constexpr int MAX_SPLIT = PO_TRAIN_MAX_SPLIT;
 constexpr int NSTAGE = 5;        // forward, CTC, backward recurrence, weight and input GEMMs, Adam
 
 __device__ __forceinline__ double lse2(double a, double b) {
@@ -428,6 +435,11 @@ struct po_trainer {
     int64_t* poff = nullptr;
     int32_t *pred_len = nullptr, *edit = nullptr, *estatus = nullptr;
     size_t lab8_cap = 0;
+    // po_train_set_precision: the mode, and under PO_CALL_BF16 the bf16 copies of a GRU layer's input kernels, made anew in
+    // every step: wb for the forward projection (transposed, po_call_bf16.h), wb2 for dX (native rows, po_train_bf16.h)
+    int precision = PO_CALL_F32, bf_cap = 0;
+    uint16_t *wb = nullptr, *wb2 = nullptr;
+    float* bpart = nullptr;             // [MAX_SPLIT][384]: wgrad_bf16_kernel's bias sums per split
     hipStream_t stream = nullptr;
 };
 
@@ -439,7 +451,7 @@ void trainer_free(po_trainer* tr) {
                     (void*)tr->dlog, (void*)tr->loss, (void*)tr->dact[0], (void*)tr->dact[1], (void*)tr->dA, (void*)tr->dR,
                     (void*)tr->part, (void*)tr->lsm, (void*)tr->logz, (void*)tr->alpha, (void*)tr->beta, (void*)tr->lab,
                     (void*)tr->loff, (void*)tr->pred, (void*)tr->lab8, (void*)tr->poff, (void*)tr->pred_len, (void*)tr->edit,
-                    (void*)tr->estatus})
+                    (void*)tr->estatus, (void*)tr->wb, (void*)tr->wb2, (void*)tr->bpart})
         f(q);
     for (float* q : tr->act) f(q);
     for (float* q : tr->save) f(q);
@@ -447,10 +459,7 @@ void trainer_free(po_trainer* tr) {
     delete tr;
 }
 
-int64_t split_rows(int64_t M) {
-    const int64_t nz = std::min<int64_t>(MAX_SPLIT, std::max<int64_t>(1, (M + WG_ROWS - 1) / WG_ROWS));
-    return ((M + nz - 1) / nz + 3) / 4 * 4;
-}
+int64_t split_rows(int64_t M) { return po_train_split_rows(M, 4); }
 
 // grad[0 .. K·N) = sum over the M rows of A[m + shift]ᵀ·B[m] (one call per Conv1D tap: rows p0 .. p0 + K of a K_tot x N
 // result); the partial sums of the splits, then their fixed-order combine
@@ -465,6 +474,21 @@ int wgrad(po_trainer* tr, const float* A, int64_t lda, const float* B, int64_t l
     if (combine)
         hipLaunchKernelGGL(combine_kernel, dim3(blocks(pstride, 256)), dim3(256), 0, tr->stream, tr->part, nz, pstride,
                            pstride, out);
+    return PO_OK;
+}
+
+// grad[0 .. K·384) = sum over the M rows of bf16(A[m])ᵀ·bf16(D[m]) (PO_CALL_BF16: a GRU layer's dW and dU), and bias[0 .. 384)
+// = the f32 column sums of the unrounded D (b_in's gradient from dA, b_rec's from dR)
+int wgrad_bf16(po_trainer* tr, const float* A, int64_t lda, int K, const float* D, int64_t M, float* out, float* bias) {
+    const int64_t rows = po_train_split_rows(M, PO_TRAIN_BF16_ALIGN);
+    const int nz = po_train_split_count(M, rows);
+    const int64_t pstride = (int64_t)K * G_MAX;
+    if (po_train_part_floats(M, rows, K, G_MAX) > tr->part_cap) return po_fail(PO_E_CAP, "po_train_step: split-K buffer too small");
+    launch_wgrad_bf16(tr->stream, A, lda, K, D, M, rows, nz, tr->part, pstride, tr->bpart);
+    hipLaunchKernelGGL(combine_kernel, dim3(blocks(pstride, 256)), dim3(256), 0, tr->stream, tr->part, nz, pstride, pstride,
+                       out);
+    hipLaunchKernelGGL(combine_kernel, dim3(blocks(G_MAX, 256)), dim3(256), 0, tr->stream, tr->bpart, nz, (int64_t)G_MAX,
+                       (int64_t)G_MAX, bias);
     return PO_OK;
 }
 
@@ -536,7 +560,11 @@ int train_forward(po_trainer* tr, int n, Timer& tm) {
         } else {
             const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
             const int64_t per_dir = per_dir_weights(l);
-            launch_gru_proj(tr->stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, tr->P, M, G, nd);
+            if (tr->precision == PO_CALL_BF16)   // po_call_batch's launch: the same bits
+                launch_gru_proj_bf16(tr->stream, x, l.cin, nd, w, per_dir, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, tr->wb,
+                                     tr->P, M, tr->bf_cap);
+            else
+                launch_gru_proj(tr->stream, x, l.cin, w, w + (int64_t)l.cin * G + (int64_t)H * G, per_dir, per_dir, tr->P, M, G, nd);
             RecurArgs ra;
             std::memset(&ra, 0, sizeof(ra));
             for (int d = 0; d < nd; ++d) {
@@ -612,19 +640,26 @@ int train_backward(po_trainer* tr, int n, Timer& tm) {
             PO_FOR_UNITS(H, hipLaunchKernelGGL(gru_back_recur_kernel<HH>, dim3(blocks(n, RT), (unsigned)nd), dim3(HH * 4), 0,
                                                tr->stream, ba));
             if ((rc = tm.begin(3)) != PO_OK) return rc;
+            const bool bf16 = tr->precision == PO_CALL_BF16;
             for (int d = 0; d < nd; ++d) {
                 float* gd = gw + d * per_dir;
                 const float* dAd = tr->dA + (int64_t)d * M * G;
                 const float* dRd = tr->dR + (int64_t)d * M * G;
-                if ((rc = wgrad(tr, X, l.cin, dAd, G, l.cin, G, M, 0, 0, l.cin, gd, true)) != PO_OK) return rc;
-                if ((rc = wgrad(tr, tr->save[2 * k + d] + SV_HP * H, SV, dRd, G, H, G, M, 0, 0, H, gd + (int64_t)l.cin * G,
-                                true)) != PO_OK)
-                    return rc;
+                const float* hp = tr->save[2 * k + d] + SV_HP * H;
                 float* gb = gd + (int64_t)l.cin * G + (int64_t)H * G;
-                if ((rc = colsum(tr, dAd, G, G, M, gb)) != PO_OK) return rc;
-                if ((rc = colsum(tr, dRd, G, G, M, gb + G)) != PO_OK) return rc;
+                if (bf16) {   // (the bias sums come out of the same passes over dA and dR)
+                    if ((rc = wgrad_bf16(tr, X, l.cin, l.cin, dAd, M, gd, gb)) != PO_OK) return rc;
+                    if ((rc = wgrad_bf16(tr, hp, SV, H, dRd, M, gd + (int64_t)l.cin * G, gb + G)) != PO_OK) return rc;
+                } else {
+                    if ((rc = wgrad(tr, X, l.cin, dAd, G, l.cin, G, M, 0, 0, l.cin, gd, true)) != PO_OK) return rc;
+                    if ((rc = wgrad(tr, hp, SV, dRd, G, H, G, M, 0, 0, H, gd + (int64_t)l.cin * G, true)) != PO_OK) return rc;
+                    if ((rc = colsum(tr, dAd, G, G, M, gb)) != PO_OK) return rc;
+                    if ((rc = colsum(tr, dRd, G, G, M, gb + G)) != PO_OK) return rc;
+                }
             }
-            if (k > 0)
+            if (k > 0 && bf16)
+                launch_dx_bf16(tr->stream, tr->dA, M * G, w, per_dir, nd, l.cin, tr->wb2, dX, M);
+            else if (k > 0)
                 hipLaunchKernelGGL(dx_kernel, dim3(blocks(M, 64), blocks(l.cin, 64)), dim3(256), 0, tr->stream, tr->dA, M * G,
                                    w, per_dir, nd, l.cin, dX, M, G);
         }
@@ -934,6 +969,109 @@ int po_train_eval(po_trainer* tr, const float* signal_h, int n, const int32_t* l
     }
     tm.finish(rc == PO_OK);
     return rc;
+}
+
+int po_train_set_precision(po_trainer* tr, int precision) {
+    po_set_error("");
+    // ---- every refusal, before the first allocation; the trainer stays in the mode it was in
+    if (!tr) return po_fail(PO_E_ARG, "po_train_set_precision: null trainer");
+    if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
+        return po_fail(PO_E_ARG, "po_train_set_precision: precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
+    int rc;
+    if (precision == PO_CALL_BF16 && (rc = check_bf16_units(tr->H, "po_train_set_precision")) != PO_OK) return rc;
+    if (precision == PO_CALL_BF16 && !tr->wb) {
+        size_t fwd = 1, bwd = 1;   // bf16 elements: the largest layer's copies (a layer's are made in its own stage)
+        for (const po_call_layer& l : tr->layers)
+            if (l.kind == PO_CALL_BIGRU || l.kind == PO_CALL_GRU || l.kind == PO_CALL_GRU_BACK) {
+                const int nd = l.kind == PO_CALL_BIGRU ? 2 : 1;
+                fwd = std::max(fwd, bf_w_elems(l.cin, nd));
+                bwd = std::max(bwd, (size_t)nd * l.cin * G_MAX);
+            }
+        uint16_t *a = nullptr, *b = nullptr;
+        float* c = nullptr;
+        hipError_t e = hipMalloc(&a, fwd * 2);
+        if (e == hipSuccess) e = hipMalloc(&b, bwd * 2);
+        if (e == hipSuccess) e = hipMalloc(&c, (size_t)MAX_SPLIT * G_MAX * 4);
+        if (e != hipSuccess) {
+            if (a) (void)hipFree(a);
+            if (b) (void)hipFree(b);
+            return po_fail_hip(e, "po_train_set_precision: device allocation");
+        }
+        tr->wb = a;
+        tr->wb2 = b;
+        tr->bpart = c;
+        tr->bf_cap = bf_blocks_cap();
+    }
+    tr->precision = precision;
+    return PO_OK;
+}
+
+int po_train_get_precision(const po_trainer* tr) {
+    po_set_error("");
+    if (!tr) return po_fail(PO_E_ARG, "po_train_get_precision: null trainer");
+    return tr->precision;
+}
+
+int po_gru_wgrad_h(const float* a_h, int64_t lda, int64_t M, int K, const float* d_h, int precision, float* out_h) {
+    const std::string me = "po_gru_wgrad_h: ";
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (!a_h || !d_h || !out_h) return po_fail(PO_E_ARG, me + "null argument " + (!a_h ? "a_h" : !d_h ? "d_h" : "out_h"));
+    if (M < 0) return po_fail(PO_E_ARG, me + "M " + std::to_string(M));
+    if (K < 1) return po_fail(PO_E_ARG, me + "K " + std::to_string(K) + " (at least 1)");
+    if (lda < K) return po_fail(PO_E_ARG, me + "lda " + std::to_string(lda) + " (at least K = " + std::to_string(K) + ")");
+    if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
+        return po_fail(PO_E_ARG, me + "precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
+    if (M == 0) return PO_OK;
+    const bool bf16 = precision == PO_CALL_BF16;
+    const int64_t rows = po_train_split_rows(M, bf16 ? PO_TRAIN_BF16_ALIGN : 4);
+    const int nz = po_train_split_count(M, rows);
+    const int64_t pstride = (int64_t)K * G_MAX;
+    PoDev da, dd, dpart, dout;
+    PO_HIPCHK(da.up(a_h, (size_t)((M - 1) * lda + K) * 4));   // (the last row ends at its K-th value)
+    PO_HIPCHK(dd.up(d_h, (size_t)M * G_MAX * 4));
+    PO_HIPCHK(dpart.up(nullptr, (size_t)nz * pstride * 4));
+    PO_HIPCHK(dout.up(nullptr, (size_t)pstride * 4));
+    if (bf16)
+        launch_wgrad_bf16(nullptr, da, lda, K, dd, M, rows, nz, dpart, pstride, nullptr);
+    else
+        hipLaunchKernelGGL(wgrad_kernel, dim3(blocks(K, 64), blocks(G_MAX, 64), nz), dim3(256), 0, nullptr, da.as<float>(), lda,
+                           dd.as<float>(), (int64_t)G_MAX, K, G_MAX, M, 1, 0, rows, dpart.as<float>(), G_MAX, 0, pstride);
+    hipLaunchKernelGGL(combine_kernel, dim3(blocks(pstride, 256)), dim3(256), 0, nullptr, dpart.as<float>(), nz, pstride, pstride,
+                       dout.as<float>());
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(dout.down(out_h, (size_t)pstride * 4));
+    return PO_OK;
+}
+
+int po_gru_dx_h(const float* dA_h, int64_t M, int ndir, const float* w_h, int cin, int precision, float* dX_h) {
+    const std::string me = "po_gru_dx_h: ";
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (!dA_h || !w_h || !dX_h) return po_fail(PO_E_ARG, me + "null argument " + (!dA_h ? "dA_h" : !w_h ? "w_h" : "dX_h"));
+    if (M < 0) return po_fail(PO_E_ARG, me + "M " + std::to_string(M));
+    if (ndir < 1 || ndir > 2) return po_fail(PO_E_ARG, me + "ndir " + std::to_string(ndir) + " (1 or 2)");
+    if (cin < 1) return po_fail(PO_E_ARG, me + "cin " + std::to_string(cin) + " (at least 1)");
+    if (precision != PO_CALL_F32 && precision != PO_CALL_BF16)
+        return po_fail(PO_E_ARG, me + "precision " + std::to_string(precision) + " (PO_CALL_F32 or PO_CALL_BF16)");
+    if (M == 0) return PO_OK;
+    const int64_t wstride = (int64_t)cin * G_MAX;
+    PoDev dda, dw, dwb, ddx;
+    PO_HIPCHK(dda.up(dA_h, (size_t)ndir * M * G_MAX * 4));
+    PO_HIPCHK(dw.up(w_h, (size_t)ndir * wstride * 4));
+    PO_HIPCHK(ddx.up(nullptr, (size_t)M * cin * 4));
+    if (precision == PO_CALL_BF16) {
+        PO_HIPCHK(dwb.up(nullptr, (size_t)ndir * wstride * 2));
+        launch_dx_bf16(nullptr, dda, M * G_MAX, dw, wstride, ndir, cin, dwb, ddx, M);
+    } else {
+        hipLaunchKernelGGL(dx_kernel, dim3(blocks(M, 64), blocks(cin, 64)), dim3(256), 0, nullptr, dda.as<float>(), M * G_MAX,
+                           dw.as<float>(), wstride, ndir, cin, ddx.as<float>(), M, G_MAX);
+    }
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(ddx.down(dX_h, (size_t)M * cin * 4));
+    return PO_OK;
 }
 
 }  // extern "C"

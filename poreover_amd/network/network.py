@@ -18,7 +18,7 @@ from ..decoding import hdf5_lite
 from . import checkpoint as ckpt
 
 __all__ = ["parse_fast5", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model", "round_bf16",
-           "gru_proj"]
+           "gru_proj", "gru_wgrad", "gru_dx"]
 
 SCALINGS = ("standard", "current", "median", "rescale", "raw")
 
@@ -94,6 +94,43 @@ def gru_proj(x, W, b_in, precision="f32"):
     _lib.check(lib.po_gru_proj_h(x.ctypes.data, x.shape[0], x.shape[1], W.shape[0], W.ctypes.data, b.ctypes.data,
                                  _lib._precision_code(precision), P.ctypes.data), "po_gru_proj_h")
     return P
+
+
+def gru_wgrad(A, D, precision="f32"):
+    """A GRU layer's weight-gradient stage alone on the device (po_gru_wgrad_h): A (M, K) float32 — rows may be a view
+    into wider rows, as the trainer's saved h_prev is —, D (M, 384) -> (K, 384) float32 = A.T @ D, by the kernels of
+    `precision` ("bf16": both operands rounded to bf16, f32 products and sums), split over M and combined as a step does"""
+    code = _lib._precision_code(precision)
+    lib = _lib.load()
+    A = np.asarray(A, dtype=np.float32)
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    if A.ndim != 2 or D.ndim != 2 or D.shape != (A.shape[0], 384):
+        raise ValueError("gru_wgrad: A (M, K), D (M, 384); got %s, %s" % (A.shape, D.shape))
+    M, K = A.shape
+    if M > 1 and K > 0 and not (A.strides[1] == 4 and A.strides[0] % 4 == 0 and A.strides[0] >= 4 * K):
+        A = np.ascontiguousarray(A)
+    lda = A.strides[0] // 4 if M > 1 else K
+    if M == 1:
+        A = np.ascontiguousarray(A)
+    out = np.empty((K, 384), dtype=np.float32)
+    _lib.check(lib.po_gru_wgrad_h(A.ctypes.data, lda, M, K, D.ctypes.data, code, out.ctypes.data),
+               "po_gru_wgrad_h")
+    return out
+
+
+def gru_dx(dA, W, precision="f32"):
+    """A GRU layer's input-gradient stage alone on the device (po_gru_dx_h): dA (ndir, M, 384), W (ndir, cin, 384) ->
+    dX (M, cin) float32 = sum_d dA[d] @ W[d].T (the directions in order), by the kernels of `precision`"""
+    code = _lib._precision_code(precision)
+    lib = _lib.load()
+    dA = np.ascontiguousarray(dA, dtype=np.float32)
+    W = np.ascontiguousarray(W, dtype=np.float32)
+    if dA.ndim != 3 or W.ndim != 3 or dA.shape[2] != 384 or W.shape[2] != 384 or dA.shape[0] != W.shape[0]:
+        raise ValueError("gru_dx: dA (ndir, M, 384), W (ndir, cin, 384); got %s, %s" % (dA.shape, W.shape))
+    dX = np.empty((dA.shape[1], W.shape[1]), dtype=np.float32)
+    _lib.check(lib.po_gru_dx_h(dA.ctypes.data, dA.shape[1], dA.shape[0], W.ctypes.data, W.shape[1], code,
+                               dX.ctypes.data), "po_gru_dx_h")
+    return dX
 
 
 def forward(net, windows, logits=False, stage_ms=None, precision="f32"):

@@ -131,12 +131,21 @@ def init_weights(model_config, seed=None):
     return {k: a.astype(np.float32) for k, a in out.items()}
 
 
+def _train_precision_code(name):
+    if name not in _lib.TRAIN_PRECISIONS:
+        raise ValueError("train precision %r (one of %s)" % (name, ", ".join(_lib.TRAIN_PRECISIONS)))
+    return _lib.TRAIN_PRECISIONS[name]
+
+
 class Trainer:
     """a po_trainer: the model's parameters, gradient and Adam state on the device, for batches of up to max_batch
-    windows of T samples"""
+    windows of T samples.  precision "f32" (default) or "bf16": the operands of the GRU layers' weight and input GEMMs
+    (po_train_set_precision); a property of this trainer, which _lib.set_call_precision does not touch"""
 
-    def __init__(self, net, max_batch, T):
+    def __init__(self, net, max_batch, T, precision="f32"):
         from .network import _layers_array
+        code = _train_precision_code(precision)
+        self.h = None
         self.lib = _lib.load()
         self.net, self.T, self.max_batch = net, int(T), int(max_batch)
         self._layers = _layers_array(net)
@@ -146,6 +155,19 @@ class Trainer:
             raise _lib.EngineError(_lib.E_ARG, "po_train_create", detail.decode() if detail else "")
         self.n_params = net.n_params()
         self.set_params(net.flat_weights())
+        if code != _lib.TRAIN_PRECISIONS["f32"]:
+            self.set_precision(precision)
+
+    @property
+    def precision(self):
+        """the trainer's mode, "f32" or "bf16" (po_train_get_precision)"""
+        return {v: k for k, v in _lib.TRAIN_PRECISIONS.items()}[int(self.lib.po_train_get_precision(self.h))]
+
+    def set_precision(self, name):
+        """po_train_set_precision: "f32" or "bf16"; parameters and Adam's state are kept; a refusal (a model whose GRU
+        layers are not 128 units under "bf16") leaves the mode as it was"""
+        code = _train_precision_code(name)
+        _lib.check(self.lib.po_train_set_precision(self.h, code), "po_train_set_precision")
 
     def close(self):
         if self.h:
@@ -301,6 +323,9 @@ def train(args):
                          (args.kernel_size, ckpt.MAX_KERNEL))
     if not 0.0 <= args.holdout < 1.0:
         raise TrainError("train: --holdout must be in [0, 1)")
+    gemm_precision = getattr(args, "gemm_precision", "f32")
+    if gemm_precision not in _lib.TRAIN_PRECISIONS:
+        raise TrainError("train: --gemm_precision %s (one of %s)" % (gemm_precision, ", ".join(_lib.TRAIN_PRECISIONS)))
     signal, labels, row_lengths = load_data(args.data)
     N, T = signal.shape
     check_labels(labels, row_lengths, T, args.ctc_merge_repeated)
@@ -314,6 +339,9 @@ def train(args):
         net = ckpt.load_network(init_weights(config, args.seed), config)
 
     print("PoreOver train", file=sys.stderr)
+    if gemm_precision != "f32":   # (train.log's header records the flag with the other arguments)
+        print("GRU weight and input GEMMs: {} operands, f32 sums (--gemm_precision {})".format(gemm_precision, gemm_precision),
+              file=sys.stderr)
     out_dir = "{}_{}_{}".format(args.model, args.name, datetime.datetime.now().strftime("%Y-%m-%d_%H-%M"))
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "train.log"), "w") as log:
@@ -327,7 +355,7 @@ def train(args):
 
     lab_list = _split_labels(labels, row_lengths)
     saved = []
-    with Trainer(net, args.batch_size, T) as tr:
+    with Trainer(net, args.batch_size, T, precision=gemm_precision) as tr:
         for t, b in enumerate(batches):
             loss = tr.step(signal[b], [lab_list[i] for i in b], merge_repeated=args.ctc_merge_repeated,
                            lr=args.learning_rate)
