@@ -748,6 +748,41 @@ int po_train_get_precision(const po_trainer* tr);
 int po_gru_wgrad_h(const float* a_h, int64_t lda, int64_t M, int K, const float* d_h, int precision, float* out_h);
 int po_gru_dx_h(const float* dA_h, int64_t M, int ndir, const float* w_h, int cin, int precision, float* dX_h);
 
+/* The recipe around a step (the rules are poreover_amd/csrc/po_train_recipe_rules.h): gradient accumulation
+ * over micro-batches, clipping by the global norm with a guard against non-finite gradients, AdamW, and Adam's state in and
+ * out.  The accumulator (one more vector of the model's size, flat layout) is allocated at its first use; po_train_step and
+ * po_train_eval never touch it.
+ *   - po_train_accumulate runs po_train_step's checks (the same messages under its own name), forward pass, CTC and backward
+ *     pass on n (1 .. max_batch) windows in the trainer's precision mode: update = 0's gradient g of the micro-batch's mean
+ *     loss.  The accumulator becomes weight * g where it was empty (weight 1: g's bits), else fmaf(weight, g, accumulator).
+ *     With weight n / N over micro-batches of N windows in all, the sum is the gradient of the mean loss over the N windows.
+ *     loss_h[n] and stage_ms_h (float[5], slot 4: the accumulation) as in a step.  A weight that is not finite is PO_E_ARG.
+ *   - po_train_accum_reset marks the accumulator empty: the next contribution overwrites.  po_train_get_accum copies it out
+ *     (PO_E_ARG where it is empty); po_train_set_accum loads one and counts as one contribution.  n = the weight count.
+ *   - po_train_apply: norm = the L2 norm of the whole accumulator, summed in f64 in a fixed partition (the same bits every
+ *     run), written to *grad_norm_h (before clipping; NULL skips).  scale = clip_norm / norm where clip_norm > 0 and norm >
+ *     clip_norm, else 1 (tf.clip_by_global_norm; clip_norm 0: no clipping).  Where the norm is finite: ge = scale * g, m and v
+ *     as in a step, p -= lr_t m / (sqrt(v) + eps) + lr weight_decay p (decoupled decay at the rate lr, not the bias-corrected
+ *     lr_t; weight_decay 0: none), Adam's t advances, *applied_h = 1 (NULL skips).  With scale 1 and no decay these are
+ *     po_train_step(update = 1)'s bits.  Where it is NaN or infinite: *applied_h = 0 and p, m, v and t keep their bits.  Either
+ *     way the accumulator is empty afterwards.  PO_E_ARG naming the argument, before any launch: a negative or non-finite
+ *     clip_norm or weight_decay, an empty accumulator, a null trainer.
+ *   - po_train_get_state / po_train_set_state: Adam's m and v (n = the weight count each) and its step count t (>= 0); with
+ *     po_train_get_params / po_train_set_params (which resets Adam and empties the accumulator: call it first) a run continues
+ *     in another trainer bit for bit.
+ *   - po_grad_norm_h: the norm stage alone on a host buffer of n >= 0 floats (n = 0: 0).
+ * All are synchronous. */
+int po_train_accumulate(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                        int merge_repeated, float weight, float* loss_h, float* stage_ms_h);
+int po_train_accum_reset(po_trainer* tr);
+int po_train_get_accum(po_trainer* tr, float* g_h, int64_t n);
+int po_train_set_accum(po_trainer* tr, const float* g_h, int64_t n);
+int po_train_apply(po_trainer* tr, float lr, float beta1, float beta2, float eps, float weight_decay, float clip_norm,
+                   double* grad_norm_h, int* applied_h);
+int po_train_get_state(po_trainer* tr, float* m_h, float* v_h, int64_t n, int64_t* step_h);
+int po_train_set_state(po_trainer* tr, const float* m_h, const float* v_h, int64_t n, int64_t step);
+int po_grad_norm_h(const float* g_h, int64_t n, double* norm_h);
+
 /* ---- read-to-genome mapping for `benchmark` (replaces mappy.Aligner as benchmark.py:16-20 uses it) ----
  * minimap2's map-ont seeds (k = 15, w = 10, its hash64) and scores reduced to a fixed integer specification: one
  * primary hit per read, a local affine alignment in a 512-column band around the best chain.  Sequences are upper-case

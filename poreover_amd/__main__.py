@@ -44,6 +44,22 @@ def build_parser():
     p.add_argument('--gemm_precision', choices=['f32', 'bf16'], default='f32',
                    help="Operands of the GRU layers' weight and input GEMMs: f32, or bf16 with f32 sums, f32 master weights and f32 Adam "
                         '(128 GRU units; the recurrences stay f32)')
+    p.add_argument('--accumulate', type=int, default=1,
+                   help='Batches whose gradients are accumulated into one optimizer step (effective batch: this times --batch_size); '
+                        'with it, --save_every and --loss_every count optimizer steps')
+    p.add_argument('--clip_norm', type=float, default=0.0, help='Clip the gradient to this global L2 norm (0: no clipping); a step whose '
+                                                                 'gradient is not finite is skipped either way')
+    p.add_argument('--weight_decay', type=float, default=0.0, help='Decoupled weight decay (AdamW): each step also subtracts '
+                                                                    'learning rate x this x the parameter (0: none)')
+    p.add_argument('--lr_schedule', choices=['constant', 'linear', 'cosine'], default='constant',
+                   help='Learning rate after the warm-up: constant, or falling to --min_lr over the run linearly or by a half cosine')
+    p.add_argument('--warmup_steps', type=int, default=0, help='Optimizer steps over which the learning rate rises linearly to --learning_rate')
+    p.add_argument('--min_lr', type=float, default=0.0, help='Learning rate at the end of a linear or cosine schedule')
+    p.add_argument('--save_optimizer', action='store_true', default=False,
+                   help="Write Adam's state (m, v, step) and the schedule position as <checkpoint>.opt.npz beside every checkpoint")
+    p.add_argument('--resume_optimizer', action='store_true', default=False,
+                   help="With --restart: load the .opt.npz beside the restarted checkpoint (Adam's state and the schedule position); "
+                        'the batch plan starts over')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="train")
 

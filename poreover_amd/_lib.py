@@ -199,6 +199,15 @@ PROTOTYPES = {
     "po_train_get_precision": (C.c_int, [C.c_void_p]),
     "po_gru_wgrad_h": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int, _vp, C.c_int, _vp]),
     "po_gru_dx_h": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, C.c_int, C.c_int, _vp]),
+    "po_train_accumulate": (C.c_int, [C.c_void_p, _vp, C.c_int, _i32p, _i32p, C.c_int, C.c_float, _vp, C.POINTER(C.c_float)]),
+    "po_train_accum_reset": (C.c_int, [C.c_void_p]),
+    "po_train_get_accum": (C.c_int, [C.c_void_p, _vp, C.c_int64]),
+    "po_train_set_accum": (C.c_int, [C.c_void_p, _vp, C.c_int64]),
+    "po_train_apply": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                 C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "po_train_get_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "po_train_set_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_int64]),
+    "po_grad_norm_h": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_double)]),
     "po_eval_path_h": (C.c_int, [_vp, C.c_int, C.c_int, _cp, _i32p]),
     "po_edit_distance_batch_h": (C.c_int, [_cp, _i64p, _cp, _i64p, C.c_int, _i32p, _i32p]),
     "po_map_sketch_h": (C.c_int, [_cp, _i64p, C.c_int, _vp, _vp, _vp, _i64p]),

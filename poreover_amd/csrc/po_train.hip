@@ -34,6 +34,14 @@
 // only) + ctc_loss_kernel where the losses are asked for, then po_eval.hip's eval_path_kernel and edit_distance_kernel on the
 // trainer's probabilities and labels: no gradient, no Adam.
 //
+// The recipe around a step (opt-in; DESIGN.md §11.3, the rules are po_train_recipe_rules.h): po_train_accumulate is the step
+// up to and including the backward pass, then grad_axpy_kernel adds weight·g to an accumulator of the gradient's size;
+// po_train_apply runs grad_sqsum_kernel + grad_norm_final_kernel (the accumulator's global L2 norm in f64 over a fixed
+// partition, and a 16-byte record of norm, clip scale and whether the norm is finite) and adamw_apply_kernel (Adam on the
+// clipped gradient plus decoupled weight decay; a record that is not finite leaves p, m and v alone), and reads the record
+// back with its results.  The same rules as a step: no float atomics, no hand-off between workgroups, no host
+// synchronisation between the launches.
+//
 // BPTT of one direction, walk step s (input time t, output position to), dh = dout[to] + the carried dh:
 //   dz = dh·(h_prev − h~);  dah = dh·(1 − z)·(1 − h~²);  dr = dah·u_h;  daz = dz·z(1 − z);  dar = dr·r(1 − r)
 //   dA = (daz, dar, dah) → input projection and b_in;  dR = (daz, dar, dah·r) → U and b_rec;  dh_prev = dh·z + dR·Uᵀ
@@ -45,6 +53,7 @@
 
 #include "po_call_kernels.h"
 #include "po_train_bf16.h"
+#include "po_train_recipe_rules.h"
 #include "po_train_rules.h"
 
 #include "po_internal.h"
@@ -402,6 +411,98 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     p[e] = p[e] - lr_t * me / (sqrtf(ve) + eps);
 }
 
+// ---- the recipe (the rules are po_train_recipe_rules.h): accumulation, global norm, clipping, AdamW
+
+// ga[e] = w·g[e] (FIRST: the first contribution after a reset; w = 1 gives g's bits) or fmaf(w, g[e], ga[e]).  One lane per
+// 16 bytes (both vectors are whole allocations), the last n % 4 elements one by one
+template <bool FIRST>
+__global__ __launch_bounds__(256) void grad_axpy_kernel(float* __restrict__ ga, const float* __restrict__ g, int64_t n, float w) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e0 = 4 * i;
+    if (e0 + 3 < n) {
+        const float4 x = reinterpret_cast<const float4*>(g)[i];
+        float4 a;
+        if (FIRST) {
+            a.x = w * x.x; a.y = w * x.y; a.z = w * x.z; a.w = w * x.w;
+        } else {
+            a = reinterpret_cast<const float4*>(ga)[i];
+            a.x = fmaf(w, x.x, a.x); a.y = fmaf(w, x.y, a.y); a.z = fmaf(w, x.z, a.z); a.w = fmaf(w, x.w, a.w);
+        }
+        reinterpret_cast<float4*>(ga)[i] = a;
+    } else {
+        for (int64_t e = e0; e < n; ++e) ga[e] = FIRST ? w * g[e] : fmaf(w, g[e], ga[e]);
+    }
+}
+
+// part[b] = the sum of g[e]² over chunk b in f64, by po_train_recipe_rules.h's partition: 16-byte loads where g is 16-byte
+// aligned and the group lies within n, else element by element in the same order (the same bits either way)
+__global__ __launch_bounds__(PO_RECIPE_NORM_WG) void grad_sqsum_kernel(const float* __restrict__ g, int64_t n,
+                                                                        double* __restrict__ part) {
+    __shared__ double ws[PO_RECIPE_NORM_WG / 64];
+    const bool vec = (reinterpret_cast<uintptr_t>(g) & 15) == 0;
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < PO_RECIPE_NORM_VECS; ++j) {
+        const int64_t e0 = po_recipe_norm_elem(blockIdx.x, j, threadIdx.x);
+        if (vec && e0 + 3 < n) {
+            const float4 x = *reinterpret_cast<const float4*>(g + e0);
+            acc += (double)x.x * (double)x.x;
+            acc += (double)x.y * (double)x.y;
+            acc += (double)x.z * (double)x.z;
+            acc += (double)x.w * (double)x.w;
+        } else {
+            for (int k = 0; k < 4; ++k)
+                if (e0 + k < n) {
+                    const double x = g[e0 + k];
+                    acc += x * x;
+                }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = ws[0];
+        for (int w = 1; w < PO_RECIPE_NORM_WG / 64; ++w) s += ws[w];
+        part[blockIdx.x] = s;
+    }
+}
+
+// one workgroup: the chunks' sums in chunk order, then the record
+__global__ __launch_bounds__(64) void grad_norm_final_kernel(const double* __restrict__ part, int64_t nparts, float clip_norm,
+                                                             po_recipe_record* __restrict__ rec) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int64_t b = 0; b < nparts; ++b) s += part[b];
+    *rec = po_recipe_make_record(s, clip_norm);
+}
+
+// AdamW on the flat parameter vector from the accumulated gradient and the norm stage's record; a record that is not finite
+// leaves p, m and v as they are.  One lane per 16 bytes, the last n % 4 elements one by one
+__global__ __launch_bounds__(256) void adamw_apply_kernel(float* __restrict__ p, const float* __restrict__ ga,
+                                                          float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                          const po_recipe_record* __restrict__ rec, float lr_t, float b1,
+                                                          float b2, float eps, float decay) {
+    if (!rec->finite) return;
+    const float scale = rec->scale;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t e0 = 4 * i;
+    if (e0 + 3 < n) {
+        const float4 g4 = reinterpret_cast<const float4*>(ga)[i];
+        float4 p4 = reinterpret_cast<float4*>(p)[i], m4 = reinterpret_cast<float4*>(m)[i], v4 = reinterpret_cast<float4*>(v)[i];
+        po_recipe_adamw(p4.x, m4.x, v4.x, g4.x, scale, lr_t, b1, b2, eps, decay);
+        po_recipe_adamw(p4.y, m4.y, v4.y, g4.y, scale, lr_t, b1, b2, eps, decay);
+        po_recipe_adamw(p4.z, m4.z, v4.z, g4.z, scale, lr_t, b1, b2, eps, decay);
+        po_recipe_adamw(p4.w, m4.w, v4.w, g4.w, scale, lr_t, b1, b2, eps, decay);
+        reinterpret_cast<float4*>(p)[i] = p4;
+        reinterpret_cast<float4*>(m)[i] = m4;
+        reinterpret_cast<float4*>(v)[i] = v4;
+    } else {
+        for (int64_t e = e0; e < n; ++e) po_recipe_adamw(p[e], m[e], v[e], ga[e], scale, lr_t, b1, b2, eps, decay);
+    }
+}
+
 template <int H>
 __global__ __launch_bounds__(H * 4) void gru_recur_save_kernel(RecurArgs a, float* save0, float* save1) {
     __shared__ float hs[2][RT][H + 1];
@@ -440,6 +541,12 @@ struct po_trainer {
     int precision = PO_CALL_F32, bf_cap = 0;
     uint16_t *wb = nullptr, *wb2 = nullptr;
     float* bpart = nullptr;             // [MAX_SPLIT][384]: wgrad_bf16_kernel's bias sums per split
+    // the recipe (po_train_accumulate / po_train_apply), allocated at first use: the accumulated gradient,
+    // the norm's per-chunk sums and its record; accum_n = the contributions since the last reset (0: empty)
+    float* ga = nullptr;
+    double* npart = nullptr;
+    po_recipe_record* rec = nullptr;
+    int64_t accum_n = 0;
     hipStream_t stream = nullptr;
 };
 
@@ -451,7 +558,8 @@ void trainer_free(po_trainer* tr) {
                     (void*)tr->dlog, (void*)tr->loss, (void*)tr->dact[0], (void*)tr->dact[1], (void*)tr->dA, (void*)tr->dR,
                     (void*)tr->part, (void*)tr->lsm, (void*)tr->logz, (void*)tr->alpha, (void*)tr->beta, (void*)tr->lab,
                     (void*)tr->loff, (void*)tr->pred, (void*)tr->lab8, (void*)tr->poff, (void*)tr->pred_len, (void*)tr->edit,
-                    (void*)tr->estatus, (void*)tr->wb, (void*)tr->wb2, (void*)tr->bpart})
+                    (void*)tr->estatus, (void*)tr->wb, (void*)tr->wb2, (void*)tr->bpart, (void*)tr->ga, (void*)tr->npart,
+                    (void*)tr->rec})
         f(q);
     for (float* q : tr->act) f(q);
     for (float* q : tr->save) f(q);
@@ -725,6 +833,68 @@ int grow_batch_buffers(po_trainer* tr, int64_t M, int Smax, int64_t n_labels, bo
     return PO_OK;
 }
 
+// A step up to and including the backward pass, for `me` (po_train_step / po_train_accumulate): the argument checks, buffer
+// growth, uploads, the forward pass, CTC and the backward pass on the trainer's stream; the gradient of the batch-mean
+// loss is then in tr->g and the losses in tr->loss (nothing is waited for)
+int train_grad(po_trainer* tr, const std::string& me, const float* signal_h, int n, const int32_t* labels_h,
+               const int32_t* label_len_h, int merge_repeated, float* loss_h, float* stage_ms_h, Timer& tm) {
+    if (!tr || !signal_h || !label_len_h || !loss_h) return po_fail(PO_E_ARG, me + ": null argument");
+    std::vector<int64_t> loff;
+    int64_t maxL = 0;
+    int rc = check_batch(tr, me, n, labels_h, label_len_h, merge_repeated, loff, &maxL);
+    if (rc != PO_OK) return rc;
+    const int T = tr->T;
+    const int64_t M = (int64_t)n * T;
+    const int Smax = (int)(2 * maxL + 1);
+    if ((rc = grow_batch_buffers(tr, M, Smax, loff[n], true)) != PO_OK) return rc;
+    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + NSTAGE, 0.f);
+    PO_HIPCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
+    if (loff[n] > 0) PO_HIPCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
+    PO_HIPCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
+    rc = train_forward(tr, n, tm);
+    if (rc == PO_OK) rc = tm.begin(1);
+    if (rc == PO_OK) {
+        const float* logits = tr->act.back();
+        hipLaunchKernelGGL(ctc_lsm_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, logits, tr->lsm, M);
+        hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)n), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, T,
+                           Smax, merge_repeated ? 1 : 0, 1, tr->alpha, tr->beta, tr->logz);
+        hipLaunchKernelGGL(ctc_grad_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, n, T,
+                           Smax, tr->alpha, tr->beta, tr->logz, 1.f / (float)n, tr->dlog, tr->loss);
+        rc = tm.end();
+    }
+    if (rc == PO_OK) rc = train_backward(tr, n, tm);
+    return rc;
+}
+
+// the recipe's device buffers, at first use (po_train_create's footprint does not change)
+int ensure_recipe(po_trainer* tr, const char* me) {
+    if (tr->ga) return PO_OK;
+    float* a = nullptr;
+    double* b = nullptr;
+    po_recipe_record* c = nullptr;
+    hipError_t e = hipMalloc(&a, std::max<size_t>((size_t)tr->nw * 4, 4));
+    if (e == hipSuccess) e = hipMalloc(&b, std::max<size_t>((size_t)po_recipe_norm_chunks(tr->nw) * 8, 8));
+    if (e == hipSuccess) e = hipMalloc(&c, sizeof(po_recipe_record));
+    if (e != hipSuccess) {
+        if (a) (void)hipFree(a);
+        if (b) (void)hipFree(b);
+        return po_fail_hip(e, (std::string(me) + ": device allocation").c_str());
+    }
+    tr->ga = a;
+    tr->npart = b;
+    tr->rec = c;
+    tr->accum_n = 0;
+    return PO_OK;
+}
+
+// the norm stage of g[0..n) on `stream`: part holds po_recipe_norm_chunks(n) doubles
+void launch_grad_norm(hipStream_t stream, const float* g, int64_t n, float clip_norm, double* part, po_recipe_record* rec) {
+    const int64_t nparts = po_recipe_norm_chunks(n);
+    if (nparts > 0)
+        hipLaunchKernelGGL(grad_sqsum_kernel, dim3((unsigned)nparts), dim3(PO_RECIPE_NORM_WG), 0, stream, g, n, part);
+    hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(64), 0, stream, part, nparts, clip_norm, rec);
+}
+
 }  // namespace
 
 extern "C" {
@@ -825,6 +995,7 @@ int po_train_set_params(po_trainer* tr, const float* w_h, int64_t n) {
     PO_HIPCHK(hipMemset(tr->m, 0, n * 4));
     PO_HIPCHK(hipMemset(tr->v, 0, n * 4));
     tr->step = 0;
+    tr->accum_n = 0;
     return PO_OK;
 }
 
@@ -852,32 +1023,8 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
                   int merge_repeated, float lr, float beta1, float beta2, float eps, int update, float* loss_h,
                   float* grad_h, float* stage_ms_h) {
     po_set_error("");
-    if (!tr || !signal_h || !label_len_h || !loss_h) return po_fail(PO_E_ARG, "po_train_step: null argument");
-    std::vector<int64_t> loff;
-    int64_t maxL = 0;
-    int rc = check_batch(tr, "po_train_step", n, labels_h, label_len_h, merge_repeated, loff, &maxL);
-    if (rc != PO_OK) return rc;
-    const int T = tr->T;
-    const int64_t M = (int64_t)n * T;
-    const int Smax = (int)(2 * maxL + 1);
-    if ((rc = grow_batch_buffers(tr, M, Smax, loff[n], true)) != PO_OK) return rc;
-    if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + NSTAGE, 0.f);
-    PO_HIPCHK(hipMemcpyAsync(tr->sig, signal_h, (size_t)M * 4, hipMemcpyHostToDevice, tr->stream));
-    if (loff[n] > 0) PO_HIPCHK(hipMemcpyAsync(tr->lab, labels_h, (size_t)loff[n] * 4, hipMemcpyHostToDevice, tr->stream));
-    PO_HIPCHK(hipMemcpyAsync(tr->loff, loff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, tr->stream));
     Timer tm{tr, stage_ms_h};
-    rc = train_forward(tr, n, tm);
-    if (rc == PO_OK) rc = tm.begin(1);
-    if (rc == PO_OK) {
-        const float* logits = tr->act.back();
-        hipLaunchKernelGGL(ctc_lsm_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, logits, tr->lsm, M);
-        hipLaunchKernelGGL(ctc_alpha_beta_kernel, dim3((unsigned)n), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, T,
-                           Smax, merge_repeated ? 1 : 0, 1, tr->alpha, tr->beta, tr->logz);
-        hipLaunchKernelGGL(ctc_grad_kernel, dim3(blocks(M, 256)), dim3(256), 0, tr->stream, tr->lsm, tr->lab, tr->loff, n, T,
-                           Smax, tr->alpha, tr->beta, tr->logz, 1.f / (float)n, tr->dlog, tr->loss);
-        rc = tm.end();
-    }
-    if (rc == PO_OK) rc = train_backward(tr, n, tm);
+    int rc = train_grad(tr, "po_train_step", signal_h, n, labels_h, label_len_h, merge_repeated, loss_h, stage_ms_h, tm);
     if (rc == PO_OK && update) {
         rc = tm.begin(4);
         tr->step += 1;
@@ -899,6 +1046,144 @@ int po_train_step(po_trainer* tr, const float* signal_h, int n, const int32_t* l
     }
     tm.finish(rc == PO_OK);
     return rc;
+}
+
+int po_train_accumulate(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                        int merge_repeated, float weight, float* loss_h, float* stage_ms_h) {
+    po_set_error("");
+    if (tr && !std::isfinite(weight)) return po_fail(PO_E_ARG, "po_train_accumulate: weight " + std::to_string(weight) + " (finite)");
+    int rc;
+    if (tr && (rc = ensure_recipe(tr, "po_train_accumulate")) != PO_OK) return rc;
+    Timer tm{tr, stage_ms_h};
+    rc = train_grad(tr, "po_train_accumulate", signal_h, n, labels_h, label_len_h, merge_repeated, loss_h, stage_ms_h, tm);
+    if (rc == PO_OK) rc = tm.begin(4);
+    if (rc == PO_OK) {
+        const unsigned nb = blocks((tr->nw + 3) / 4, 256);
+        if (tr->accum_n == 0)
+            hipLaunchKernelGGL(grad_axpy_kernel<true>, dim3(nb), dim3(256), 0, tr->stream, tr->ga, tr->g, tr->nw, weight);
+        else
+            hipLaunchKernelGGL(grad_axpy_kernel<false>, dim3(nb), dim3(256), 0, tr->stream, tr->ga, tr->g, tr->nw, weight);
+        rc = tm.end();
+    }
+    if (rc == PO_OK) {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_accumulate: launch");
+    }
+    if (rc == PO_OK) {
+        hipError_t e = hipMemcpyAsync(loss_h, tr->loss, (size_t)n * 4, hipMemcpyDeviceToHost, tr->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
+        if (e != hipSuccess) rc = po_fail_hip(e, "po_train_accumulate: results");
+    }
+    if (rc == PO_OK) tr->accum_n += 1;
+    tm.finish(rc == PO_OK);
+    return rc;
+}
+
+int po_train_accum_reset(po_trainer* tr) {
+    po_set_error("");
+    if (!tr) return po_fail(PO_E_ARG, "po_train_accum_reset: null trainer");
+    tr->accum_n = 0;
+    return PO_OK;
+}
+
+int po_train_get_accum(po_trainer* tr, float* g_h, int64_t n) {
+    po_set_error("");
+    if (!tr || !g_h) return po_fail(PO_E_ARG, std::string("po_train_get_accum: null argument ") + (!tr ? "tr" : "g_h"));
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_get_accum: n " + std::to_string(n) + " (the model has " +
+                                    std::to_string(tr->nw) + " weights)");
+    if (tr->accum_n == 0) return po_fail(PO_E_ARG, "po_train_get_accum: nothing is accumulated");
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    PO_HIPCHK(hipMemcpy(g_h, tr->ga, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return PO_OK;
+}
+
+int po_train_set_accum(po_trainer* tr, const float* g_h, int64_t n) {
+    po_set_error("");
+    if (!tr || !g_h) return po_fail(PO_E_ARG, std::string("po_train_set_accum: null argument ") + (!tr ? "tr" : "g_h"));
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_set_accum: n " + std::to_string(n) + " (the model has " +
+                                    std::to_string(tr->nw) + " weights)");
+    int rc;
+    if ((rc = ensure_recipe(tr, "po_train_set_accum")) != PO_OK) return rc;
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    PO_HIPCHK(hipMemcpy(tr->ga, g_h, (size_t)n * 4, hipMemcpyHostToDevice));
+    tr->accum_n = 1;
+    return PO_OK;
+}
+
+int po_train_apply(po_trainer* tr, float lr, float beta1, float beta2, float eps, float weight_decay, float clip_norm,
+                   double* grad_norm_h, int* applied_h) {
+    po_set_error("");
+    // ---- every refusal, before any launch
+    if (!tr) return po_fail(PO_E_ARG, "po_train_apply: null trainer");
+    if (!(clip_norm >= 0.f) || !std::isfinite(clip_norm))
+        return po_fail(PO_E_ARG, "po_train_apply: clip_norm " + std::to_string(clip_norm) + " (0: no clipping, or positive and finite)");
+    if (!(weight_decay >= 0.f) || !std::isfinite(weight_decay))
+        return po_fail(PO_E_ARG, "po_train_apply: weight_decay " + std::to_string(weight_decay) + " (0 or positive and finite)");
+    if (tr->accum_n == 0) return po_fail(PO_E_ARG, "po_train_apply: nothing is accumulated");
+    // Adam's t advances only when the update is applied, which the record says; the kernels are launched with t + 1 and the
+    // record comes back with the call's results
+    const float lr_t = po_recipe_lr_t(lr, beta1, beta2, tr->step + 1);
+    launch_grad_norm(tr->stream, tr->ga, tr->nw, clip_norm, tr->npart, tr->rec);
+    hipLaunchKernelGGL(adamw_apply_kernel, dim3(blocks((tr->nw + 3) / 4, 256)), dim3(256), 0, tr->stream, tr->p, tr->ga, tr->m,
+                       tr->v, tr->nw, tr->rec, lr_t, beta1, beta2, eps, po_recipe_decay(lr, weight_decay));
+    tr->accum_n = 0;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return po_fail_hip(e, "po_train_apply: launch");
+    po_recipe_record r;
+    e = hipMemcpyAsync(&r, tr->rec, sizeof(r), hipMemcpyDeviceToHost, tr->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(tr->stream);
+    if (e != hipSuccess) return po_fail_hip(e, "po_train_apply: results");
+    if (r.finite) tr->step += 1;
+    if (grad_norm_h) *grad_norm_h = r.norm;
+    if (applied_h) *applied_h = r.finite ? 1 : 0;
+    return PO_OK;
+}
+
+int po_train_get_state(po_trainer* tr, float* m_h, float* v_h, int64_t n, int64_t* step_h) {
+    po_set_error("");
+    if (!tr || !m_h || !v_h || !step_h)
+        return po_fail(PO_E_ARG, std::string("po_train_get_state: null argument ") +
+                       (!tr ? "tr" : !m_h ? "m_h" : !v_h ? "v_h" : "step_h"));
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_get_state: n " + std::to_string(n) + " (the model has " +
+                                    std::to_string(tr->nw) + " weights)");
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    PO_HIPCHK(hipMemcpy(m_h, tr->m, (size_t)n * 4, hipMemcpyDeviceToHost));
+    PO_HIPCHK(hipMemcpy(v_h, tr->v, (size_t)n * 4, hipMemcpyDeviceToHost));
+    *step_h = tr->step;
+    return PO_OK;
+}
+
+int po_train_set_state(po_trainer* tr, const float* m_h, const float* v_h, int64_t n, int64_t step) {
+    po_set_error("");
+    if (!tr || !m_h || !v_h)
+        return po_fail(PO_E_ARG, std::string("po_train_set_state: null argument ") + (!tr ? "tr" : !m_h ? "m_h" : "v_h"));
+    if (n != tr->nw) return po_fail(PO_E_ARG, "po_train_set_state: n " + std::to_string(n) + " (the model has " +
+                                    std::to_string(tr->nw) + " weights)");
+    if (step < 0) return po_fail(PO_E_ARG, "po_train_set_state: step " + std::to_string(step) + " (0 or more)");
+    PO_HIPCHK(hipStreamSynchronize(tr->stream));
+    PO_HIPCHK(hipMemcpy(tr->m, m_h, (size_t)n * 4, hipMemcpyHostToDevice));
+    PO_HIPCHK(hipMemcpy(tr->v, v_h, (size_t)n * 4, hipMemcpyHostToDevice));
+    tr->step = step;
+    return PO_OK;
+}
+
+int po_grad_norm_h(const float* g_h, int64_t n, double* norm_h) {
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (!norm_h || (!g_h && n > 0))
+        return po_fail(PO_E_ARG, std::string("po_grad_norm_h: null argument ") + (!norm_h ? "norm_h" : "g_h"));
+    if (n < 0) return po_fail(PO_E_ARG, "po_grad_norm_h: n " + std::to_string(n));
+    PoDev dg, dpart, drec;
+    PO_HIPCHK(dg.up(g_h, (size_t)n * 4));
+    PO_HIPCHK(dpart.up(nullptr, (size_t)po_recipe_norm_chunks(n) * 8));
+    PO_HIPCHK(drec.up(nullptr, sizeof(po_recipe_record)));
+    launch_grad_norm(nullptr, dg, n, 0.f, dpart, drec.as<po_recipe_record>());
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    po_recipe_record r;
+    PO_HIPCHK(drec.down(&r, sizeof(r)));
+    *norm_h = r.norm;
+    return PO_OK;
 }
 
 int po_train_eval(po_trainer* tr, const float* signal_h, int n, const int32_t* labels_h, const int32_t* label_len_h,

@@ -6,10 +6,13 @@ argmax path and its edit distance to the labels); this module 
 loads the .npz, draws the holdout and the batches, runs the schedule, prints the same stderr lines, writes train.log,
 model.json and the checkpoints.  Where the reference differs from its own flags, this honours them:
 --learning_rate and --ctc_merge_repeated take effect, T is the data's window length, the holdout is fixed for the run,
-checkpoints are .npz files of the checkpoint's tensor names next to a TF-style `checkpoint` file."""
+checkpoints are .npz files of the checkpoint's tensor names next to a TF-style `checkpoint` file.  Beyond the reference,
+and off by default: gradient accumulation over several batches, clipping by the global norm with a guard
+against non-finite gradients, decoupled weight decay, a learning-rate schedule and Adam's state saved and resumed."""
 import ctypes as C
 import datetime
 import json
+import math
 import os
 import sys
 
@@ -19,7 +22,7 @@ from .. import _lib
 from . import checkpoint as ckpt
 
 __all__ = ["TrainError", "Trainer", "load_data", "check_labels", "plan_batches", "init_weights", "validation_error",
-           "validation_error_device", "train"]
+           "validation_error_device", "lr_at", "optimizer_path", "load_optimizer", "train"]
 
 ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7)     # Keras Adam()'s defaults
 
@@ -221,6 +224,69 @@ class Trainer:
                 stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
         return (loss, g) if grad else loss
 
+    # ---- the recipe: accumulate micro-batches, then apply once
+    def accumulate(self, windows, labels, weight, merge_repeated=False, stage_ms=None):
+        """po_train_accumulate: step(update=False)'s gradient of the mean loss of these windows, times `weight`, goes into
+        the accumulator (overwrites it where it is empty, else is added by fmaf); with weight = n / N over micro-batches of
+        N windows in all, the sum is the gradient of the mean loss over the N.  Returns the per-window losses (n,) float32"""
+        x = np.ascontiguousarray(windows, dtype=np.float32)
+        n = x.shape[0]
+        lens = np.asarray([len(l) for l in labels], dtype=np.int32)
+        lab = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).ravel() for l in labels])
+                                   if lens.sum() else np.zeros(1, dtype=np.int32), dtype=np.int32)
+        loss = np.empty(n, dtype=np.float32)
+        ms = (C.c_float * len(_lib.TRAIN_STAGES))() if stage_ms is not None else None
+        rc = self.lib.po_train_accumulate(self.h, x.ctypes.data, n, lab.ctypes.data, lens.ctypes.data, 1 if merge_repeated else 0,
+                                          float(weight), loss.ctypes.data, ms)
+        _lib.check(rc, "po_train_accumulate")
+        if stage_ms is not None:
+            for k, name in enumerate(_lib.TRAIN_STAGES):
+                stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
+        return loss
+
+    def apply(self, lr=1e-3, clip_norm=0.0, weight_decay=0.0, **adam):
+        """po_train_apply: (grad_norm, applied).  grad_norm: the accumulator's global L2 norm before clipping (float64 sums
+        in a fixed order); clip_norm > 0 scales the gradient by clip_norm / grad_norm where that is below 1; then AdamW with
+        the decoupled decay lr · weight_decay · p.  applied is False where the norm is NaN or infinite: parameters, Adam's
+        m, v and step count are then untouched.  The accumulator is empty afterwards either way."""
+        a = dict(ADAM, **adam)
+        norm, applied = C.c_double(), C.c_int()
+        rc = self.lib.po_train_apply(self.h, float(lr), float(a["beta1"]), float(a["beta2"]), float(a["eps"]),
+                                     float(weight_decay), float(clip_norm), C.byref(norm), C.byref(applied))
+        _lib.check(rc, "po_train_apply")
+        return norm.value, bool(applied.value)
+
+    def accum_reset(self):
+        """mark the accumulator empty: the next contribution overwrites it"""
+        _lib.check(self.lib.po_train_accum_reset(self.h), "po_train_accum_reset")
+
+    def get_accum(self):
+        """the accumulated gradient (flat layout); an EngineError (E_ARG) where nothing is accumulated"""
+        g = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self.lib.po_train_get_accum(self.h, g.ctypes.data, g.size), "po_train_get_accum")
+        return g
+
+    def set_accum(self, g):
+        """load the accumulator (flat layout); counts as one contribution"""
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        _lib.check(self.lib.po_train_set_accum(self.h, g.ctypes.data, g.size), "po_train_set_accum")
+
+    def get_state(self):
+        """(m, v, step): Adam's moments (flat layout) and its step count"""
+        m = np.empty(self.n_params, dtype=np.float32)
+        v = np.empty(self.n_params, dtype=np.float32)
+        step = C.c_int64()
+        _lib.check(self.lib.po_train_get_state(self.h, m.ctypes.data, v.ctypes.data, m.size, C.byref(step)), "po_train_get_state")
+        return m, v, int(step.value)
+
+    def set_state(self, m, v, step):
+        """load Adam's moments and step count (after set_params, which resets them)"""
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        if m.size != v.size:
+            raise ValueError("set_state: m has %d values, v %d" % (m.size, v.size))
+        _lib.check(self.lib.po_train_set_state(self.h, m.ctypes.data, v.ctypes.data, m.size, int(step)), "po_train_set_state")
+
     def evaluate(self, windows, labels, merge_repeated=False, loss=True, predictions=False, stage_ms=None):
         """held-out validation of windows (n, T) with labels (a list of n int sequences) on the resident parameters
         (po_train_eval; no gradient, no update): a dict of edit (n,) int32, the edit distance of each window's argmax path
@@ -310,6 +376,79 @@ def _write_state(out_dir, names):
             fh.write('all_model_checkpoint_paths: "%s"\n' % n)
 
 
+LR_SCHEDULES = ("constant", "linear", "cosine")
+
+
+def lr_at(s, S, base, schedule="constant", warmup_steps=0, min_lr=0.0):
+    """the learning rate of optimizer step s (the number of steps done before it) of a run of S: for s < warmup_steps
+    base · (s + 1) / warmup_steps; after that, with x = (s − warmup_steps) / max(1, S − warmup_steps), `constant`: base,
+    `linear`: base − (base − min_lr) · x, `cosine`: min_lr + (base − min_lr) · ½(1 + cos πx)"""
+    if schedule not in LR_SCHEDULES:
+        raise ValueError("lr schedule %r (one of %s)" % (schedule, ", ".join(LR_SCHEDULES)))
+    if s < warmup_steps:
+        return base * (s + 1) / warmup_steps
+    x = (s - warmup_steps) / max(1, S - warmup_steps)
+    if schedule == "linear":
+        return base - (base - min_lr) * x
+    if schedule == "cosine":
+        return min_lr + (base - min_lr) * 0.5 * (1.0 + math.cos(math.pi * x))
+    return base
+
+
+RECIPE_DEFAULTS = dict(accumulate=1, clip_norm=0.0, weight_decay=0.0, lr_schedule="constant", warmup_steps=0, min_lr=0.0,
+                       save_optimizer=False, resume_optimizer=False)
+
+
+def _recipe(args):
+    """the recipe's flags of `args` (a namespace may lack any of them: the default then), refused by name where they make
+    no sense"""
+    r = {k: getattr(args, k, d) for k, d in RECIPE_DEFAULTS.items()}
+    if r["accumulate"] < 1:
+        raise TrainError("train: --accumulate must be positive")
+    for flag in ("clip_norm", "weight_decay", "warmup_steps", "min_lr"):
+        if not r[flag] >= 0 or not math.isfinite(r[flag]):
+            raise TrainError("train: --%s must be 0 or positive (and finite)" % flag)
+    if r["lr_schedule"] not in LR_SCHEDULES:
+        raise TrainError("train: --lr_schedule %s (one of %s)" % (r["lr_schedule"], ", ".join(LR_SCHEDULES)))
+    if r["min_lr"] > args.learning_rate:
+        raise TrainError("train: --min_lr %s is above --learning_rate %s" % (r["min_lr"], args.learning_rate))
+    if r["resume_optimizer"] and not getattr(args, "restart", False):
+        raise TrainError("train: --resume_optimizer needs --restart (it loads the .opt.npz beside that checkpoint)")
+    return r
+
+
+def optimizer_path(restart):
+    """the .opt.npz `--save_optimizer` wrote beside the checkpoint that `--restart` resolves"""
+    path = str(restart)
+    if path.endswith(".npz"):
+        return path[:-len(".npz")] + ".opt.npz"
+    return ckpt.resolve_checkpoint(path) + ".opt.npz"
+
+
+def load_optimizer(path, n_params):
+    """(m, v, step, iteration) of an .opt.npz, checked against the model's weight count"""
+    if not os.path.exists(path):
+        raise TrainError("train: --resume_optimizer: %s is missing (write it with --save_optimizer)" % path)
+    try:
+        with np.load(path) as z:
+            d = {k: z[k] for k in ("m", "v", "step", "iteration") if k in z.files}
+    except (OSError, ValueError) as e:
+        raise TrainError("train: cannot read the optimizer state %s: %s" % (path, e))
+    if len(d) < 4:
+        raise TrainError("train: %s is no optimizer file (it holds m, v, step and iteration)" % path)
+    m, v, step, it = d["m"], d["v"], int(d["step"]), int(d["iteration"])
+    if m.shape != (n_params,) or v.shape != (n_params,):
+        raise TrainError("train: %s holds m and v of %d and %d values, the model has %d weights" % (path, m.size, v.size, n_params))
+    if step < 0 or it < 0:
+        raise TrainError("train: %s holds a negative step count" % path)
+    return np.asarray(m, dtype=np.float32), np.asarray(v, dtype=np.float32), step, it
+
+
+def _write_optimizer(path, tr, iteration):
+    m, v, step = tr.get_state()
+    np.savez(path, m=m, v=v, step=np.int64(step), iteration=np.int64(iteration))
+
+
 def train(args):
     """`poreover train --data DATA.npz ...` (network.py:133-179); returns the output directory"""
     if args.num_neurons != ckpt.UNITS:
@@ -326,6 +465,8 @@ def train(args):
     gemm_precision = getattr(args, "gemm_precision", "f32")
     if gemm_precision not in _lib.TRAIN_PRECISIONS:
         raise TrainError("train: --gemm_precision %s (one of %s)" % (gemm_precision, ", ".join(_lib.TRAIN_PRECISIONS)))
+    recipe = _recipe(args)
+    plain = recipe == RECIPE_DEFAULTS      # every flag of the recipe at its default: the loop below steps as it always has
     signal, labels, row_lengths = load_data(args.data)
     N, T = signal.shape
     check_labels(labels, row_lengths, T, args.ctc_merge_repeated)
@@ -337,6 +478,9 @@ def train(args):
         net = ckpt.load_network(args.restart, config)
     else:
         net = ckpt.load_network(init_weights(config, args.seed), config)
+    opt_state = None
+    if recipe["resume_optimizer"]:
+        opt_state = load_optimizer(optimizer_path(args.restart), net.n_params())
 
     print("PoreOver train", file=sys.stderr)
     if gemm_precision != "f32":   # (train.log's header records the flag with the other arguments)
@@ -355,22 +499,48 @@ def train(args):
 
     lab_list = _split_labels(labels, row_lengths)
     saved = []
+    # the recipe: an optimizer step is K consecutive batches of the plan (a shorter last group with its own
+    # weights); t, --save_every and --loss_every count optimizer steps
+    K = recipe["accumulate"]
+    groups = [batches[i:i + K] for i in range(0, len(batches), K)]
+    S = len(groups)
     with Trainer(net, args.batch_size, T, precision=gemm_precision) as tr:
-        for t, b in enumerate(batches):
-            loss = tr.step(signal[b], [lab_list[i] for i in b], merge_repeated=args.ctc_merge_repeated,
-                           lr=args.learning_rate)
+        done = 0                          # optimizer steps before this run: the schedule goes on from there
+        if opt_state is not None:
+            tr.set_state(opt_state[0], opt_state[1], opt_state[2])
+            done = opt_state[3]
+        for t, b in enumerate(batches if plain else groups):
+            if plain:
+                loss = tr.step(signal[b], [lab_list[i] for i in b], merge_repeated=args.ctc_merge_repeated,
+                               lr=args.learning_rate)
+            else:
+                n_group = sum(len(mb) for mb in b)
+                loss = np.concatenate([tr.accumulate(signal[mb], [lab_list[i] for i in mb], len(mb) / n_group,
+                                                     merge_repeated=args.ctc_merge_repeated) for mb in b])
+                # (past the end of the schedule, which only a resumed run reaches, the rate keeps its last value)
+                lr = lr_at(min(done + t, S - 1), S, args.learning_rate, recipe["lr_schedule"], recipe["warmup_steps"],
+                           recipe["min_lr"])
+                norm, applied = tr.apply(lr, clip_norm=recipe["clip_norm"], weight_decay=recipe["weight_decay"])
             mean = np.mean(loss, dtype=np.float32)
             if t % args.save_every == 0:
                 name = "checkpoint-%d" % len(saved)
                 ckpt.write_weights(os.path.join(out_dir, name + ".npz"), tr.network())
+                if recipe["save_optimizer"]:
+                    _write_optimizer(os.path.join(out_dir, name + ".opt.npz"), tr, done + t + 1)
                 saved.append(name)
                 _write_state(out_dir, saved)
             if t % args.loss_every == 0:
                 print("Iteration:{}\tLoss:{}".format(t, mean), file=sys.stderr)
+            if not plain and recipe["clip_norm"] > 0 and t % args.loss_every == 0:
+                print("Iteration:{}\tGradient norm:{}".format(t, norm), file=sys.stderr)
+            if not plain and not applied:
+                print("Iteration:{}\tSkipped: non-finite gradient".format(t), file=sys.stderr)
             if t % args.save_every == 0 and len(held) > 0:
                 d = validation_error_device(tr, held, signal, lab_list)
                 print("Iteration:{}\tEdit distance (test):{}".format(t, d), file=sys.stderr)
         ckpt.write_weights(os.path.join(out_dir, "final.npz"), tr.network())
+        if recipe["save_optimizer"]:
+            _write_optimizer(os.path.join(out_dir, "final.opt.npz"), tr, done + S)
     saved.append("final")
     _write_state(out_dir, saved)
     return out_dir
