@@ -783,6 +783,77 @@ int po_train_get_state(po_trainer* tr, float* m_h, float* v_h, int64_t n, int64_
 int po_train_set_state(po_trainer* tr, const float* m_h, const float* v_h, int64_t n, int64_t step);
 int po_grad_norm_h(const float* g_h, int64_t n, double* norm_h);
 
+/* Data-parallel training over several devices (the rules are poreover_amd/csrc/po_train_dp_rules.h).  A group
+ * is n_replicas (1 .. 16) trainers, replica r on device devices_h[r]; a device may appear more than once.  One host thread per
+ * replica, made at create and joined at destroy, binds its device once and runs that replica's work; the calling thread's
+ * current device is never changed.  A replica's error comes back in po_last_error as "replica r (device d): <its message>".
+ * Every argument error is answered before the first allocation or launch: a null pointer, a replica count outside 1 .. 16, a
+ * device outside 0 .. po_device_count() - 1, a share outside 0 .. max_batch, no share at all, a weight that is not finite.
+ *   - po_train_group_create: po_train_create's arguments and the devices; NULL on failure (po_last_error says why).
+ *     po_train_group_size returns the replica count.
+ *   - po_train_group_set_params / po_train_group_set_state: po_train_set_params / po_train_set_state on every replica (the
+ *     same host bits to each).  po_train_group_get_params / po_train_group_get_state read replica 0;
+ *     po_train_group_get_replica_params / po_train_group_get_replica_state read the named replica (the replicas hold the same
+ *     bits after every call below; these are for checking that).  po_train_group_set_precision: po_train_set_precision on every
+ *     replica, or on none where it is refused.
+ *   - po_train_group_accumulate: n_h[r] (0: idle) windows for replica r.  The shares lie one after another, replica 0's first,
+ *     in signal_h (T samples a window), label_len_h, labels_h and loss_h; weight_h[r] is replica r's weight; stage_ms_h (or
+ *     NULL) float[n_replicas][5].  Every replica's share passes po_train_accumulate's checks (its messages) before any replica
+ *     launches: a refused share refuses the call and no accumulator changes.  Then the replicas run po_train_accumulate on
+ *     their shares at the same time.
+ *   - po_train_group_reduce: the all-reduce alone.  Every replica's accumulator becomes ((ga_r0 + ga_r1) + ga_r2) + ... in
+ *     plain f32 over the replicas whose accumulator is not empty, in ascending replica order (an empty one is skipped, not
+ *     added as zero; all empty: PO_E_ARG), the same bits on every replica and in every run, and counts as one contribution.
+ *     Replica r sums slice r (po_train_dp_rules.h) of every contributing accumulator into a staging vector on its device, and
+ *     after a hand-off between launches every replica copies each slice from its owner.  *ms_h (or NULL): the milliseconds
+ *     between events on replica 0's stream around its part.  A group of one has nothing to sum and launches nothing.
+ *   - po_train_group_apply: the all-reduce, then po_train_apply on every replica's copy; *grad_norm_h and *applied_h are
+ *     replica 0's (every replica's are the same bits).  The accumulators are empty afterwards.
+ *   - po_train_group_get_accum / po_train_group_set_accum: po_train_get_accum / po_train_set_accum of one replica (before or
+ *     after a reduce; set is how a test plants a value in one replica's share).
+ *   - po_train_group_eval: po_train_eval with n_h[n_replicas] shares laid out as for po_train_group_accumulate (pred_h: T
+ *     codes of room a window; stage_ms_h float[n_replicas][3]); the replicas evaluate their shares at the same time.
+ *   - po_set_dp_route: how the slices travel, process-wide like po_set_chain_mode and read by every reduce.
+ *     PO_DP_ROUTE_PEER: the kernels read the peers' device memory (peer access is enabled once at create; replicas on one
+ *     device need none); where a pair of the group's devices has no peer access the reduce is PO_E_UNSUPPORTED naming the two
+ *     devices, before any launch.  PO_DP_ROUTE_HOST: through pinned host buffers with hipMemcpyAsync, summed by the same
+ *     kernel in the same order: the same bits.  PO_DP_ROUTE_AUTO (default): PEER where every pair can, else HOST.  Another
+ *     value is PO_E_ARG and leaves the route as it was.
+ *   - po_dp_allreduce_h: the reduce stage alone on host buffers: bufs_h[r] (n floats; may be NULL where present_h[r] is 0) is
+ *     uploaded to a buffer on devices_h[r], the reduce runs on the current route, out_h[r] (n floats, every r) gets replica r's
+ *     result.  n = 0 is PO_OK with nothing written; no replica present is PO_E_ARG.
+ * All are synchronous. */
+#define PO_DP_ROUTE_AUTO 0
+#define PO_DP_ROUTE_PEER 1
+#define PO_DP_ROUTE_HOST 2
+typedef struct po_train_group po_train_group;
+po_train_group* po_train_group_create(const po_call_layer* layers_h, int n_layers, int max_batch, int T, const int* devices_h,
+                                      int n_replicas);
+void po_train_group_destroy(po_train_group* g);
+int po_train_group_size(po_train_group* g);
+int po_train_group_set_params(po_train_group* g, const float* w_h, int64_t n);
+int po_train_group_get_params(po_train_group* g, float* w_h, int64_t n);
+int po_train_group_get_replica_params(po_train_group* g, int replica, float* w_h, int64_t n);
+int po_train_group_set_state(po_train_group* g, const float* m_h, const float* v_h, int64_t n, int64_t step);
+int po_train_group_get_state(po_train_group* g, float* m_h, float* v_h, int64_t n, int64_t* step_h);
+int po_train_group_get_replica_state(po_train_group* g, int replica, float* m_h, float* v_h, int64_t n, int64_t* step_h);
+int po_train_group_set_precision(po_train_group* g, int precision);
+int po_train_group_accumulate(po_train_group* g, const float* signal_h, const int* n_h, const int32_t* labels_h,
+                              const int32_t* label_len_h, int merge_repeated, const float* weight_h, float* loss_h,
+                              float* stage_ms_h);
+int po_train_group_get_accum(po_train_group* g, int replica, float* g_h, int64_t n);
+int po_train_group_set_accum(po_train_group* g, int replica, const float* g_h, int64_t n);
+int po_train_group_reduce(po_train_group* g, float* ms_h);
+int po_train_group_apply(po_train_group* g, float lr, float beta1, float beta2, float eps, float weight_decay, float clip_norm,
+                         double* grad_norm_h, int* applied_h);
+int po_train_group_eval(po_train_group* g, const float* signal_h, const int* n_h, const int32_t* labels_h,
+                        const int32_t* label_len_h, int merge_repeated, float* loss_h, int32_t* edit_h, int32_t* pred_len_h,
+                        int32_t* status_h, uint8_t* pred_h, float* stage_ms_h);
+int po_set_dp_route(int route);
+int po_get_dp_route(void);
+int po_dp_allreduce_h(const int* devices_h, int R, const float* const* bufs_h, const int* present_h, int64_t n,
+                      float* const* out_h);
+
 /* ---- read-to-genome mapping for `benchmark` (replaces mappy.Aligner as benchmark.py:16-20 uses it) ----
  * minimap2's map-ont seeds (k = 15, w = 10, its hash64) and scores reduced to a fixed integer specification: one
  * primary hit per read, a local affine alignment in a 512-column band around the best chain.  Sequences are upper-case

@@ -60,6 +60,9 @@ def build_parser():
     p.add_argument('--resume_optimizer', action='store_true', default=False,
                    help="With --restart: load the .opt.npz beside the restarted checkpoint (Adam's state and the schedule position); "
                         'the batch plan starts over')
+    p.add_argument('--gpus', type=int, default=1,
+                   help='Devices to train on, data-parallel (devices 0 .. N-1): an optimizer step takes this times --accumulate batches, '
+                        'one batch per device at a time, and the gradients are summed between the devices in a fixed order')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="train")
 

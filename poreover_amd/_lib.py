@@ -208,6 +208,26 @@ PROTOTYPES = {
     "po_train_get_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "po_train_set_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_int64]),
     "po_grad_norm_h": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_double)]),
+    "po_train_group_create": (C.c_void_p, [C.POINTER(CallLayer), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int]),
+    "po_train_group_destroy": (None, [C.c_void_p]),
+    "po_train_group_size": (C.c_int, [C.c_void_p]),
+    "po_train_group_set_params": (C.c_int, [C.c_void_p, _vp, C.c_int64]),
+    "po_train_group_get_params": (C.c_int, [C.c_void_p, _vp, C.c_int64]),
+    "po_train_group_get_replica_params": (C.c_int, [C.c_void_p, C.c_int, _vp, C.c_int64]),
+    "po_train_group_set_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.c_int64]),
+    "po_train_group_get_state": (C.c_int, [C.c_void_p, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "po_train_group_get_replica_state": (C.c_int, [C.c_void_p, C.c_int, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]),
+    "po_train_group_set_precision": (C.c_int, [C.c_void_p, C.c_int]),
+    "po_train_group_accumulate": (C.c_int, [C.c_void_p, _vp, _i32p, _i32p, _i32p, C.c_int, _vp, _vp, _vp]),
+    "po_train_group_get_accum": (C.c_int, [C.c_void_p, C.c_int, _vp, C.c_int64]),
+    "po_train_group_set_accum": (C.c_int, [C.c_void_p, C.c_int, _vp, C.c_int64]),
+    "po_train_group_reduce": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "po_train_group_apply": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "po_train_group_eval": (C.c_int, [C.c_void_p, _vp, _i32p, _i32p, _i32p, C.c_int, _vp, _i32p, _i32p, _i32p, _cp, _vp]),
+    "po_set_dp_route": (C.c_int, [C.c_int]),
+    "po_get_dp_route": (C.c_int, []),
+    "po_dp_allreduce_h": (C.c_int, [_i32p, C.c_int, _vp, _i32p, C.c_int64, _vp]),
     "po_eval_path_h": (C.c_int, [_vp, C.c_int, C.c_int, _cp, _i32p]),
     "po_edit_distance_batch_h": (C.c_int, [_cp, _i64p, _cp, _i64p, C.c_int, _i32p, _i32p]),
     "po_map_sketch_h": (C.c_int, [_cp, _i64p, C.c_int, _vp, _vp, _vp, _i64p]),
@@ -303,6 +323,50 @@ def get_chain_mode():
 
 CALL_PRECISIONS = {"f32": 0, "bf16": 1}
 TRAIN_PRECISIONS = CALL_PRECISIONS     # po_train_set_precision takes the same codes (a trainer's own mode)
+
+
+DP_ROUTES = {"auto": 0, "peer": 1, "host": 2}
+
+
+def set_dp_route(route="auto"):
+    """po_set_dp_route: how the gradient slices of a TrainerGroup's all-reduce travel between replicas — "peer": the kernels
+    read the peers' device memory; "host": through pinned host buffers; "auto" (default): peer where every pair of the group's
+    devices can, else host.  The same bits either way; process-wide, read by every reduce"""
+    if route not in DP_ROUTES:
+        raise ValueError("dp route %r (one of %s)" % (route, ", ".join(DP_ROUTES)))
+    check(load(False).po_set_dp_route(DP_ROUTES[route]), "po_set_dp_route")
+
+
+def get_dp_route():
+    return {v: k for k, v in DP_ROUTES.items()}[int(load(False).po_get_dp_route())]
+
+
+@contextlib.contextmanager
+def dp_route(route):
+    """the reduces of the block run under `route`; the previous one is back afterwards, whatever happens"""
+    before = get_dp_route()
+    set_dp_route(route)
+    try:
+        yield
+    finally:
+        set_dp_route(before)
+
+
+def dp_allreduce(bufs, devices, present=None):
+    """po_dp_allreduce_h: the all-reduce stage of a TrainerGroup alone.  bufs: R float32 vectors of one length (None where
+    not present), replica r on devices[r]; returns the R results (each replica's copy of the sum in replica order)"""
+    import numpy as np
+    R = len(devices)
+    present = [b is not None for b in bufs] if present is None else [bool(x) for x in present]
+    arrs = [np.ascontiguousarray(b, dtype=np.float32) if b is not None else None for b in bufs]
+    n = next((a.size for a in arrs if a is not None), 0)
+    outs = [np.zeros(n, dtype=np.float32) for _ in range(R)]
+    dev = (C.c_int * R)(*[int(d) for d in devices])
+    pres = (C.c_int * R)(*[1 if p else 0 for p in present])
+    inp = (C.c_void_p * R)(*[a.ctypes.data if a is not None else None for a in arrs])
+    outp = (C.c_void_p * R)(*[o.ctypes.data for o in outs])
+    check(load().po_dp_allreduce_h(dev, R, inp, pres, n, outp), "po_dp_allreduce_h")
+    return outs
 
 
 def _precision_code(name):

@@ -138,6 +138,20 @@ int po_launch_fastq_pair_phred(const double* odds1, const int64_t* pos1, const i
 int po_launch_eval_path(const float* probs, int n, int T, uint8_t* pred, int32_t* pred_len, hipStream_t stream);
 int po_launch_edit_distance(const uint8_t* a, const int64_t* a_off, const int32_t* a_len, const uint8_t* b,
                             const int64_t* b_off, int n, int32_t* dist, int32_t* status, hipStream_t stream);
+
+// po_train.hip, for po_train_group.hip: what a group needs of a member trainer.  po_trainer_accum_view gives the accumulator (made
+// at first use, n floats, a whole allocation), the count of contributions since it was last emptied (0: empty; the group sets
+// it after an all-reduce) and the trainer's stream; po_trainer_check_batch runs po_train_accumulate's checks of a batch under
+// the name `me` and launches nothing
+struct po_trainer_accum {
+    float* ga;
+    int64_t n;
+    int64_t* count;
+    hipStream_t stream;
+};
+int po_trainer_accum_view(po_trainer* tr, po_trainer_accum* out);
+int po_trainer_check_batch(const po_trainer* tr, const char* me, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                           int merge_repeated);
 }  // extern "C"
 
 // ---- The pair-beam launch layer: po_beam2d_route.hip owns every process-wide setting and chooses the kernel family; po_beam2d.hip and

@@ -1139,6 +1139,26 @@ int po_train_apply(po_trainer* tr, float lr, float beta1, float beta2, float eps
     return PO_OK;
 }
 
+// ---- for po_train_group.hip (po_internal.h): a trainer's accumulator and a batch's checks, nothing launched
+int po_trainer_accum_view(po_trainer* tr, po_trainer_accum* out) {
+    if (!tr || !out) return po_fail(PO_E_ARG, "po_trainer_accum_view: null argument");
+    int rc;
+    if ((rc = ensure_recipe(tr, "po_train_group")) != PO_OK) return rc;
+    out->ga = tr->ga;
+    out->n = tr->nw;
+    out->count = &tr->accum_n;
+    out->stream = tr->stream;
+    return PO_OK;
+}
+
+int po_trainer_check_batch(const po_trainer* tr, const char* me, int n, const int32_t* labels_h, const int32_t* label_len_h,
+                           int merge_repeated) {
+    if (!tr || !me || !label_len_h) return po_fail(PO_E_ARG, std::string(me ? me : "po_trainer_check_batch") + ": null argument");
+    std::vector<int64_t> loff;
+    int64_t maxL = 0;
+    return check_batch(tr, me, n, labels_h, label_len_h, merge_repeated, loff, &maxL);
+}
+
 int po_train_get_state(po_trainer* tr, float* m_h, float* v_h, int64_t n, int64_t* step_h) {
     po_set_error("");
     if (!tr || !m_h || !v_h || !step_h)

@@ -21,7 +21,7 @@ import numpy as np
 from .. import _lib
 from . import checkpoint as ckpt
 
-__all__ = ["TrainError", "Trainer", "load_data", "check_labels", "plan_batches", "init_weights", "validation_error",
+__all__ = ["TrainError", "Trainer", "TrainerGroup", "plan_steps", "validation_error_group", "load_data", "check_labels", "plan_batches", "init_weights", "validation_error",
            "validation_error_device", "lr_at", "optimizer_path", "load_optimizer", "train"]
 
 ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-7)     # Keras Adam()'s defaults
@@ -324,6 +324,175 @@ class Trainer:
         return lg, dl
 
 
+def _flat_labels(labels):
+    lens = np.asarray([len(l) for l in labels], dtype=np.int32)
+    lab = np.ascontiguousarray(np.concatenate([np.asarray(l, dtype=np.int32).ravel() for l in labels])
+                               if lens.sum() else np.zeros(1, dtype=np.int32), dtype=np.int32)
+    return lens, lab
+
+
+class TrainerGroup:
+    """a po_train_group: len(devices) replicas of a Trainer, replica r on devices[r] (a device may appear
+    more than once), each driven by a host thread of its own.  The replicas start from the same parameters and Adam state;
+    accumulate() gives each a micro-batch, apply() all-reduces the accumulators in a fixed order (the same bits on every
+    replica and in every run) and runs Trainer.apply on every copy, so the replicas stay bit-identical without a broadcast"""
+
+    def __init__(self, net, max_batch, T, devices, precision="f32"):
+        from .network import _layers_array
+        code = _train_precision_code(precision)
+        self.h = None
+        self.lib = _lib.load()
+        self.net, self.T, self.max_batch = net, int(T), int(max_batch)
+        self.devices = [int(d) for d in devices]
+        self.R = len(self.devices)
+        self._layers = _layers_array(net)
+        dev = (C.c_int * max(self.R, 1))(*self.devices)
+        self.h = self.lib.po_train_group_create(self._layers, len(net.layers), self.max_batch, self.T, dev, self.R)
+        if not self.h:
+            detail = self.lib.po_last_error()
+            raise _lib.EngineError(_lib.E_ARG, "po_train_group_create", detail.decode() if detail else "")
+        self.n_params = net.n_params()
+        self.set_params(net.flat_weights())
+        if code != _lib.TRAIN_PRECISIONS["f32"]:
+            self.set_precision(precision)
+
+    def set_precision(self, name):
+        """Trainer.set_precision on every replica, or on none where it is refused"""
+        _lib.check(self.lib.po_train_group_set_precision(self.h, _train_precision_code(name)), "po_train_group_set_precision")
+
+    def close(self):
+        if self.h:
+            self.lib.po_train_group_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_params(self, flat):
+        """load the parameters into every replica and reset Adam"""
+        w = np.ascontiguousarray(flat, dtype=np.float32)
+        _lib.check(self.lib.po_train_group_set_params(self.h, w.ctypes.data, w.size), "po_train_group_set_params")
+
+    def get_params(self, replica=0):
+        w = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self.lib.po_train_group_get_replica_params(self.h, int(replica), w.ctypes.data, w.size),
+                   "po_train_group_get_replica_params")
+        return w
+
+    def network(self):
+        """replica 0's parameters as a Network"""
+        return self.net.with_flat(self.get_params())
+
+    def _shares(self, micro):
+        """the C layout of up to R micro-batches (None: that replica idles): counts, windows, label lengths, labels"""
+        if len(micro) > self.R:
+            raise ValueError("%d micro-batches for %d replicas" % (len(micro), self.R))
+        micro = list(micro) + [None] * (self.R - len(micro))
+        n = np.asarray([0 if mb is None else len(mb[0]) for mb in micro], dtype=np.int32)
+        xs = [np.ascontiguousarray(mb[0], dtype=np.float32).reshape(len(mb[0]), -1) for mb in micro if mb is not None and len(mb[0])]
+        x = np.ascontiguousarray(np.concatenate(xs)) if xs else np.zeros((1, self.T), dtype=np.float32)
+        if x.shape[1] != self.T:
+            raise ValueError("windows of %d samples, the group holds %d" % (x.shape[1], self.T))
+        lens, lab = _flat_labels([l for mb in micro if mb is not None for l in mb[1]])
+        if len(lens) != int(n.sum()):
+            raise ValueError("%d label sequences for %d windows" % (len(lens), int(n.sum())))
+        if not len(lens):
+            lens = np.zeros(1, dtype=np.int32)
+        return n, x, lens, lab
+
+    def accumulate(self, micro, N, merge_repeated=False, stage_ms=None):
+        """po_train_group_accumulate: micro is a list of up to R (windows, labels) pairs, micro-batch j for replica j (None:
+        idle), all at once; each runs Trainer.accumulate with weight n_j / N, N the window count of the whole optimizer step.
+        A micro-batch that is refused refuses the call for all.  Returns the micro-batches' per-window losses, a list"""
+        n, x, lens, lab = self._shares(micro)
+        weight = np.asarray([k / N for k in n], dtype=np.float32)
+        loss = np.empty(max(int(n.sum()), 1), dtype=np.float32)
+        ms = np.zeros((self.R, len(_lib.TRAIN_STAGES)), dtype=np.float32) if stage_ms is not None else None
+        rc = self.lib.po_train_group_accumulate(self.h, x.ctypes.data, n.ctypes.data, lab.ctypes.data, lens.ctypes.data,
+                                                1 if merge_repeated else 0, weight.ctypes.data, loss.ctypes.data,
+                                                ms.ctypes.data if ms is not None else None)
+        _lib.check(rc, "po_train_group_accumulate")
+        if stage_ms is not None:
+            stage_ms.append(ms)
+        off = np.concatenate([[0], np.cumsum(n)])
+        return [loss[off[j]:off[j + 1]].copy() for j in range(len(micro))]
+
+    def reduce(self):
+        """po_train_group_reduce: the all-reduce alone; the milliseconds between events on replica 0's stream"""
+        ms = C.c_float()
+        _lib.check(self.lib.po_train_group_reduce(self.h, C.byref(ms)), "po_train_group_reduce")
+        return ms.value
+
+    def apply(self, lr=1e-3, clip_norm=0.0, weight_decay=0.0, **adam):
+        """po_train_group_apply: the all-reduce, then Trainer.apply on every replica; (grad_norm, applied) of replica 0"""
+        a = dict(ADAM, **adam)
+        norm, applied = C.c_double(), C.c_int()
+        rc = self.lib.po_train_group_apply(self.h, float(lr), float(a["beta1"]), float(a["beta2"]), float(a["eps"]),
+                                           float(weight_decay), float(clip_norm), C.byref(norm), C.byref(applied))
+        _lib.check(rc, "po_train_group_apply")
+        return norm.value, bool(applied.value)
+
+    def get_accum(self, replica):
+        g = np.empty(self.n_params, dtype=np.float32)
+        _lib.check(self.lib.po_train_group_get_accum(self.h, int(replica), g.ctypes.data, g.size), "po_train_group_get_accum")
+        return g
+
+    def set_accum(self, replica, g):
+        """load one replica's accumulator (counts as one contribution): how a test plants a value in one share"""
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        _lib.check(self.lib.po_train_group_set_accum(self.h, int(replica), g.ctypes.data, g.size), "po_train_group_set_accum")
+
+    def get_state(self, replica=0):
+        """(m, v, step) of a replica (0: what a checkpoint saves)"""
+        m = np.empty(self.n_params, dtype=np.float32)
+        v = np.empty(self.n_params, dtype=np.float32)
+        step = C.c_int64()
+        _lib.check(self.lib.po_train_group_get_replica_state(self.h, int(replica), m.ctypes.data, v.ctypes.data, m.size,
+                                                             C.byref(step)), "po_train_group_get_replica_state")
+        return m, v, int(step.value)
+
+    def set_state(self, m, v, step):
+        """load Adam's moments and step count into every replica (after set_params, which resets them)"""
+        m = np.ascontiguousarray(m, dtype=np.float32)
+        v = np.ascontiguousarray(v, dtype=np.float32)
+        if m.size != v.size:
+            raise ValueError("set_state: m has %d values, v %d" % (m.size, v.size))
+        _lib.check(self.lib.po_train_group_set_state(self.h, m.ctypes.data, v.ctypes.data, m.size, int(step)), "po_train_group_set_state")
+
+    def evaluate(self, micro, merge_repeated=False, loss=True, predictions=False):
+        """po_train_group_eval: Trainer.evaluate of up to R (windows, labels) pairs, pair j on replica j, at the same time; a
+        list of Trainer.evaluate's dicts"""
+        n, x, lens, lab = self._shares(micro)
+        tot = max(int(n.sum()), 1)
+        edit, plen, st = (np.empty(tot, dtype=np.int32) for _ in range(3))
+        ls = np.empty(tot, dtype=np.float32) if loss else None
+        pred = np.empty((tot, self.T), dtype=np.uint8) if predictions else None
+        rc = self.lib.po_train_group_eval(self.h, x.ctypes.data, n.ctypes.data, lab.ctypes.data, lens.ctypes.data,
+                                          1 if merge_repeated else 0, ls.ctypes.data if loss else None, edit.ctypes.data,
+                                          plen.ctypes.data, st.ctypes.data, pred.ctypes.data if predictions else None, None)
+        _lib.check(rc, "po_train_group_eval")
+        off = np.concatenate([[0], np.cumsum(n)])
+        out = []
+        for j in range(len(micro)):
+            a, b = off[j], off[j + 1]
+            d = {"edit": edit[a:b].copy(), "pred_len": plen[a:b].copy(), "status": st[a:b].copy()}
+            if loss:
+                d["loss"] = ls[a:b].copy()
+            if predictions:
+                d["pred"] = [pred[w, :plen[w]].copy() for w in range(a, b)]
+            out.append(d)
+        return out
+
+
 def _split_labels(labels, row_lengths):
     off = np.concatenate([[0], np.cumsum(row_lengths)])
     return [labels[off[i]:off[i + 1]] for i in range(len(row_lengths))]
@@ -367,6 +536,45 @@ def validation_error_device(trainer, batches, signal, labels, stage_ms=None):
         if d:
             per_batch.append(np.mean(d))
     return float(np.mean(per_batch)) if per_batch else float("nan")
+
+
+def validation_error_group(group, batches, signal, labels):
+    """validation_error_device over a TrainerGroup: held batch i goes to replica i % R, R batches at a time; the edit
+    distances are integers and the means are taken in batch order, so the figure is the single-device one exactly"""
+    per_batch = []
+    for i in range(0, len(batches), group.R):
+        rnd = batches[i:i + group.R]
+        labs = [[labels[w] for w in b] for b in rnd]
+        res = group.evaluate([(signal[b], lab) for b, lab in zip(rnd, labs)], loss=False)
+        preds = None
+        for j, (b, lab, r) in enumerate(zip(rnd, labs, res)):
+            edit = [int(e) for e in r["edit"]]
+            capped = [k for k in range(len(b)) if r["status"][k] != _lib.OK and len(lab[k])]
+            if capped:
+                if preds is None:
+                    preds = group.evaluate([(signal[x], l) for x, l in zip(rnd, labs)], loss=False, predictions=True)
+                pred = preds[j]["pred"]
+                for k in capped:
+                    edit[k] = _edit(pred[k], lab[k])
+            d = [edit[k] / len(lab[k]) for k in range(len(b)) if len(lab[k])]
+            if d:
+                per_batch.append(np.mean(d))
+    return float(np.mean(per_batch)) if per_batch else float("nan")
+
+
+def plan_steps(batches, gpus, accumulate):
+    """the optimizer steps of a data-parallel run: a step is gpus · accumulate consecutive batches of the plan (the last
+    step may be shorter); batch j of a step goes to replica j % gpus in round j // gpus, with weight len(batch) / windows of
+    the step.  Returns, per step, its rounds: lists of (replica, batch, weight), replicas ascending from 0 (a shorter last
+    round leaves the higher replicas idle)"""
+    per = gpus * accumulate
+    steps = []
+    for i in range(0, len(batches), per):
+        group = batches[i:i + per]
+        n_step = sum(len(b) for b in group)
+        steps.append([[(j % gpus, group[j], len(group[j]) / n_step) for j in range(k, min(k + gpus, len(group)))]
+                      for k in range(0, len(group), gpus)])
+    return steps
 
 
 def _write_state(out_dir, names):
@@ -444,6 +652,22 @@ def load_optimizer(path, n_params):
     return np.asarray(m, dtype=np.float32), np.asarray(v, dtype=np.float32), step, it
 
 
+def _dp_devices(gpus):
+    """the devices of a --gpus N run, 0 .. N - 1 (the command line repeats none); refused where fewer are visible"""
+    nd = _lib.load(False).po_device_count()
+    if gpus > nd:
+        raise TrainError("train: --gpus %d, but %d device%s visible" % (gpus, nd, " is" if nd == 1 else "s are"))
+    return list(range(gpus))
+
+
+def _check_replicas(group, when):
+    """the replicas of a group hold the same parameters, bit for bit: compared on the host, first against last"""
+    a, b = group.get_params(0), group.get_params(group.R - 1)
+    if not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
+        raise TrainError("train: %s: replica 0 and replica %d hold different parameters (%d of %d values differ)" %
+                         (when, group.R - 1, int(np.sum(a.view(np.uint32) != b.view(np.uint32))), a.size))
+
+
 def _write_optimizer(path, tr, iteration):
     m, v, step = tr.get_state()
     np.savez(path, m=m, v=v, step=np.int64(step), iteration=np.int64(iteration))
@@ -466,7 +690,12 @@ def train(args):
     if gemm_precision not in _lib.TRAIN_PRECISIONS:
         raise TrainError("train: --gemm_precision %s (one of %s)" % (gemm_precision, ", ".join(_lib.TRAIN_PRECISIONS)))
     recipe = _recipe(args)
-    plain = recipe == RECIPE_DEFAULTS      # every flag of the recipe at its default: the loop below steps as it always has
+    gpus = getattr(args, "gpus", 1)        # (a namespace may lack it: one device)
+    if gpus < 1:
+        raise TrainError("train: --gpus must be positive")
+    devices = _dp_devices(gpus) if gpus > 1 else [0]
+    # every flag of the recipe at its default, on one device: the loop below steps as it always has
+    plain = recipe == RECIPE_DEFAULTS and gpus == 1
     signal, labels, row_lengths = load_data(args.data)
     N, T = signal.shape
     check_labels(labels, row_lengths, T, args.ctc_merge_repeated)
@@ -486,6 +715,9 @@ def train(args):
     if gemm_precision != "f32":   # (train.log's header records the flag with the other arguments)
         print("GRU weight and input GEMMs: {} operands, f32 sums (--gemm_precision {})".format(gemm_precision, gemm_precision),
               file=sys.stderr)
+    if gpus > 1:
+        print("Data-parallel training on devices {} (--gpus {})".format(", ".join(str(d) for d in devices), gpus),
+              file=sys.stderr)
     out_dir = "{}_{}_{}".format(args.model, args.name, datetime.datetime.now().strftime("%Y-%m-%d_%H-%M"))
     os.makedirs(out_dir, exist_ok=True)
     with open(os.path.join(out_dir, "train.log"), "w") as log:
@@ -502,9 +734,11 @@ def train(args):
     # the recipe: an optimizer step is K consecutive batches of the plan (a shorter last group with its own
     # weights); t, --save_every and --loss_every count optimizer steps
     K = recipe["accumulate"]
-    groups = [batches[i:i + K] for i in range(0, len(batches), K)]
+    # with --gpus N > 1 it is N · K batches, batch j on replica j % N in round j // N (plan_steps)
+    groups = [batches[i:i + K] for i in range(0, len(batches), K)] if gpus == 1 else plan_steps(batches, gpus, K)
     S = len(groups)
-    with Trainer(net, args.batch_size, T, precision=gemm_precision) as tr:
+    with (Trainer(net, args.batch_size, T, precision=gemm_precision) if gpus == 1 else
+          TrainerGroup(net, args.batch_size, T, devices, precision=gemm_precision)) as tr:
         done = 0                          # optimizer steps before this run: the schedule goes on from there
         if opt_state is not None:
             tr.set_state(opt_state[0], opt_state[1], opt_state[2])
@@ -513,6 +747,13 @@ def train(args):
             if plain:
                 loss = tr.step(signal[b], [lab_list[i] for i in b], merge_repeated=args.ctc_merge_repeated,
                                lr=args.learning_rate)
+            elif gpus > 1:
+                n_group = sum(len(mb) for rnd in b for _, mb, _ in rnd)
+                loss = np.concatenate([l for rnd in b for l in tr.accumulate(
+                    [(signal[mb], [lab_list[i] for i in mb]) for _, mb, _ in rnd], n_group, merge_repeated=args.ctc_merge_repeated)])
+                lr = lr_at(min(done + t, S - 1), S, args.learning_rate, recipe["lr_schedule"], recipe["warmup_steps"],
+                           recipe["min_lr"])
+                norm, applied = tr.apply(lr, clip_norm=recipe["clip_norm"], weight_decay=recipe["weight_decay"])
             else:
                 n_group = sum(len(mb) for mb in b)
                 loss = np.concatenate([tr.accumulate(signal[mb], [lab_list[i] for i in mb], len(mb) / n_group,
@@ -523,6 +764,8 @@ def train(args):
                 norm, applied = tr.apply(lr, clip_norm=recipe["clip_norm"], weight_decay=recipe["weight_decay"])
             mean = np.mean(loss, dtype=np.float32)
             if t % args.save_every == 0:
+                if gpus > 1:
+                    _check_replicas(tr, "iteration %d" % t)
                 name = "checkpoint-%d" % len(saved)
                 ckpt.write_weights(os.path.join(out_dir, name + ".npz"), tr.network())
                 if recipe["save_optimizer"]:
@@ -536,8 +779,10 @@ def train(args):
             if not plain and not applied:
                 print("Iteration:{}\tSkipped: non-finite gradient".format(t), file=sys.stderr)
             if t % args.save_every == 0 and len(held) > 0:
-                d = validation_error_device(tr, held, signal, lab_list)
+                d = (validation_error_device if gpus == 1 else validation_error_group)(tr, held, signal, lab_list)
                 print("Iteration:{}\tEdit distance (test):{}".format(t, d), file=sys.stderr)
+        if gpus > 1:
+            _check_replicas(tr, "the last iteration")
         ckpt.write_weights(os.path.join(out_dir, "final.npz"), tr.network())
         if recipe["save_optimizer"]:
             _write_optimizer(os.path.join(out_dir, "final.opt.npz"), tr, done + S)
