@@ -489,6 +489,37 @@ int po_get_call_precision(void);
 int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w_h, const float* bin_h, int precision,
                   float* P_h);
 
+/* ---- signal preparation: raw int16 reads to scaled f32 signals on the device --------
+ * network.parse_fast5's abasic filter and scaling for a ragged batch of raw reads.  A sample x is kept when lo < x < hi
+ * (the reference's 200 / 800); the kept samples of a read, in their order, become f32((f64(x) - a) / b) with a and b per
+ * read by the rule of poreover_amd/csrc/po_prep_rules.h: every statistic is an exact integer taken from the read's
+ * histogram, so a read's bits depend neither on the batch it is in nor on the schedule of the kernels.
+ *   - raw_h:      the raw samples of n_reads reads back to back; raw_off_h int64[n_reads + 1] sample offsets, raw_off_h[0]
+ *                 == 0, non-decreasing, a read of 0 to 2^31 - 1 samples
+ *   - scaling:    PO_SCALE_* below
+ *   - lo, hi:     -32769 <= lo < hi <= 32768 and hi - lo - 1 <= 4096 bins; PO_E_ARG naming both otherwise
+ *   - offset_h, alpha_h: double[n_reads], the channel's offset and digitisation / range; read (and required) for
+ *                 PO_SCALE_CURRENT alone
+ *   - signal_h:   room for raw_off_h[n_reads] f32 values; the kept samples of read i are written at sig_off_h[i]
+ *   - sig_off_h:  int64[n_reads + 1], written: from 0; a read with no kept sample has length 0
+ *   - stats_h (or NULL): po_prep_stats[n_reads]
+ *   - ms_h (or NULL): one float, SET to the device milliseconds of the call's kernels (events; the copies are outside)
+ * n_reads == 0 is PO_OK (sig_off_h[0] = 0).  A null pointer is PO_E_ARG naming the argument; every argument error is
+ * answered before the first device allocation.  Synchronous, on the current device. */
+#define PO_SCALE_STANDARD 0 /* a = mean, b = standard deviation (population) */
+#define PO_SCALE_CURRENT 1  /* a = -offset, b = alpha: picoamperes */
+#define PO_SCALE_MEDIAN 2   /* a = 0, b = median */
+#define PO_SCALE_RESCALE 3  /* a = mean, b = max - min */
+#define PO_SCALE_RAW 4      /* a = 0, b = 1 */
+typedef struct po_prep_stats {
+    int64_t n, S, Q;                     /* kept samples, their sum and their sum of squares */
+    int32_t min, max, med_lo, med_hi;    /* smallest, largest and the two middle kept values (0 when n == 0) */
+    double a, b;                         /* the scaling's subtrahend and divisor */
+} po_prep_stats;
+int po_signal_prep_h(const int16_t* raw_h, const int64_t* raw_off_h, int n_reads, int scaling, int lo, int hi,
+                     const double* offset_h, const double* alpha_h, float* signal_h, int64_t* sig_off_h,
+                     po_prep_stats* stats_h, float* ms_h);
+
 /* ---- `basecall`: scaled signals to decoded strings in one device-resident pass --------
  * The forward pass above, the log-softmax of po_ingest_batch (PO_INGEST_LOGITS_F32) and po_viterbi_batch / po_beam1d_batch
  * in one synchronous call: each read's signal goes up once, the strings come down, and nothing per frame returns to the
@@ -548,6 +579,55 @@ int po_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, i
                               char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
                               float* logits_h, int band_size, char* qual_h, int32_t* qual_status_h, double* odds_h,
                               int32_t* guide_h, float* stage_ms_h);
+
+/* ---- `basecall` over one or several devices of a node -----------------------------------
+ * A po_basecaller holds a model, the decoder's options and a list of devices.  A run cuts the reads, in input order, into
+ * groups - contiguous runs of at most min(resident budget, ceil(total samples / (2 ndev))) samples, one read at least, a
+ * longer read alone (po_basecall_group_plan, which touches no device) - and deals them from one planner to one host thread
+ * per listed device, whichever is free.  Each worker keeps its state on its device - the weights, uploaded once by
+ * po_basecaller_create, and every buffer, grow-only between groups and runs - and a stream of its own; a group runs the
+ * body of po_basecall_batch_h / po_basecall_fastq_batch_h on it, so every string, logit and quality is what ONE such call
+ * over all reads gives, bit for bit.  On the raw route the int16 samples go up and the f32 signal is made and read on the
+ * device.
+ *   - devices, ndev: 1 to 16 devices, each 0 .. po_device_count() - 1; a device may be named more than once (two workers
+ *     then share it)
+ *   - options: window, overlap, kind, beam_width, model, max_windows_per_pass as for po_basecall_batch_h; fastq != 0: the
+ *     runs make qualities with band_size as po_basecall_fastq_batch_h; scaling (PO_SCALE_*), lo, hi: the raw route's
+ *     preparation (po_signal_prep_h); resident_bytes: device bytes one group may hold per-sample state in (0: 16 GiB)
+ *   - po_basecaller_create answers every argument error of po_basecall_batch_h / po_basecall_fastq_batch_h (by that
+ *     entry, under its name) and of po_signal_prep_h's scaling and range, a device out of range and ndev outside 1 .. 16
+ *     (PO_E_ARG naming the value); it returns NULL and po_last_error says why
+ *   - po_basecaller_run_f32: scaled f32 signals; inputs and outputs laid out as po_basecall_fastq_batch_h's (qual_h and
+ *     qual_status_h are read only by a fastq engine; no odds, guides or stage times)
+ *   - po_basecaller_run_raw: raw int16 reads, raw_off_h from 0, offset_h / alpha_h for PO_SCALE_CURRENT.  kept_h[n] gets
+ *     the samples each read kept; seq_off_h gives each read room for its RAW length; logits_h (or NULL) holds room for
+ *     raw_off_h[n] rows, read i's kept_h[i] rows at row raw_off_h[i].  A read that keeps nothing gets length 0.
+ *   - when a group fails the other workers finish what they hold and take no more; the run returns that group's code and
+ *     "device d: <message>".  The engine stays usable.
+ *   - po_basecaller_stats: reads, samples, groups and busy host milliseconds of worker i in the last run
+ * The call precision (po_set_call_precision) is read by every group: set it around the whole run. */
+typedef struct po_basecaller po_basecaller;
+typedef struct po_basecaller_options {
+    int window, overlap, kind, beam_width, model, max_windows_per_pass;
+    int fastq, band_size;
+    int scaling, lo, hi;
+    int64_t resident_bytes;
+} po_basecaller_options;
+po_basecaller* po_basecaller_create(const int* devices, int ndev, const po_call_layer* layers_h, int n_layers,
+                                    const float* weights_h, int64_t n_weights, const char* alphabet,
+                                    const po_basecaller_options* options);
+void po_basecaller_destroy(po_basecaller* b);
+int po_basecaller_run_f32(po_basecaller* b, const float* signal_h, const int64_t* sig_off_h, int n_reads, char* seq_h,
+                          const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h, float* logits_h, char* qual_h,
+                          int32_t* qual_status_h);
+int po_basecaller_run_raw(po_basecaller* b, const int16_t* raw_h, const int64_t* raw_off_h, int n_reads, const double* offset_h,
+                          const double* alpha_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                          float* logits_h, char* qual_h, int32_t* qual_status_h, int64_t* kept_h);
+int po_basecaller_stats(po_basecaller* b, int i, int64_t* reads, int64_t* samples, int* groups, double* busy_ms);
+/* first[g], count[g] of the groups of n reads of len[i] samples (written for g < cap); returns the number of groups */
+int po_basecall_group_plan(const int64_t* len, int n, int64_t group_samples, int ndev, int32_t* first, int32_t* count, int cap);
+/* max(1, min(budget_samples, ceil(total / (2 ndev)))) */
+int64_t po_basecall_group_samples(int64_t total, int64_t budget_samples, int ndev);
 
 /* The three device stages of the above alone, on host buffers (tables from 0, non-decreasing; PO_E_ARG otherwise).  The
  * per-element rules are poreover_amd/csrc/po_fastq_rules.h.  mode (one int32 per read): 0 the scored string is the Viterbi

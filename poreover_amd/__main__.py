@@ -97,6 +97,11 @@ def build_parser():
     p.add_argument('--fastq', action='store_true', default=False, help='Also write {out}.fastq with a Phred quality per base')
     p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
+    p.add_argument('--gpus', type=int, default=None,
+                   help='Stream the reads through devices 0 .. N-1 (0: every visible device): files are read by --readers threads in chunks, '
+                        'filtered and scaled on the device, and records are appended as chunks complete. Without it: one device, every file parsed first')
+    p.add_argument('--readers', type=int, default=4, help='With --gpus: threads reading FAST5 files (1 to 16)')
+    p.add_argument('--chunk_files', type=int, default=None, help='With --gpus: files per chunk (default 512)')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="basecall")
 

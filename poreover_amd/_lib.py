@@ -47,6 +47,12 @@ class CallLayer(C.Structure):
     _fields_ = [("kind", C.c_int), ("cin", C.c_int), ("cout", C.c_int), ("kernel", C.c_int)]
 
 
+class BasecallerOptions(C.Structure):
+    _fields_ = [("window", C.c_int), ("overlap", C.c_int), ("kind", C.c_int), ("beam_width", C.c_int), ("model", C.c_int),
+                ("max_windows_per_pass", C.c_int), ("fastq", C.c_int), ("band_size", C.c_int), ("scaling", C.c_int),
+                ("lo", C.c_int), ("hi", C.c_int), ("resident_bytes", C.c_int64)]
+
+
 CALL_KINDS = {"conv": 0, "bigru": 1, "gru": 2, "gru_back": 3, "dense": 4}
 CALL_STAGES = ("conv", "gru_proj", "gru_recur", "dense_softmax")
 BASECALL_STAGES = CALL_STAGES + ("stitch_ingest", "decode")
@@ -166,12 +172,24 @@ PROTOTYPES = {
     "po_set_call_precision": (C.c_int, [C.c_int]),
     "po_get_call_precision": (C.c_int, []),
     "po_gru_proj_h": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "po_signal_prep_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _i64p, _vp,
+                                   C.POINTER(C.c_float)]),
     "po_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                       C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _vp,
                                       C.POINTER(C.c_float)]),
     "po_basecall_fastq_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                             C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _vp,
                                             C.c_int, _cp, _i32p, _dp, _i32p, C.POINTER(C.c_float)]),
+    "po_basecaller_create": (C.c_void_p, [C.POINTER(C.c_int), C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64, C.c_char_p,
+                                          C.POINTER(BasecallerOptions)]),
+    "po_basecaller_destroy": (None, [C.c_void_p]),
+    "po_basecaller_run_f32": (C.c_int, [C.c_void_p, _vp, _i64p, C.c_int, _cp, _i64p, _i32p, _i32p, _vp, _cp, _i32p]),
+    "po_basecaller_run_raw": (C.c_int, [C.c_void_p, _vp, _i64p, C.c_int, _dp, _dp, _cp, _i64p, _i32p, _i32p, _vp, _cp, _i32p,
+                                        _i64p]),
+    "po_basecaller_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int),
+                                      C.POINTER(C.c_double)]),
+    "po_basecall_group_plan": (C.c_int, [_i64p, C.c_int, C.c_int64, C.c_int, _i32p, _i32p, C.c_int]),
+    "po_basecall_group_samples": (C.c_int64, [C.c_int64, C.c_int64, C.c_int]),
     "po_fastq_guide_h": (C.c_int, [_i32p, _i32p, _i64p, C.c_int, _i32p, _i32p, _i32p, _i32p]),
     "po_fastq_consumed_h": (C.c_int, [_cp, _cp, _i64p, _i32p, C.c_int, _i32p, _i32p, _i64p, _i32p, _i32p]),
     "po_fastq_phred_h": (C.c_int, [_dp, _cp, _i64p, C.c_int, C.c_char_p, _i32p, _cp]),

@@ -89,8 +89,8 @@ int PoBasecallPasses::up(const PoBasecallPlan& plan, const float* signal_h, cons
     chunk = std::min<int64_t>(chunk, plan.windows);
     const int64_t Mc = chunk * window;
     ws_bytes = po_call_workspace_bytes((int)chunk, window, layers_h, n_layers);
-    PO_HIPCHK(w.up(weights_h, (size_t)n_weights * 4));
-    PO_HIPCHK(sig.up(signal_h, (size_t)plan.rows * 4));             // each read's signal once, whatever the overlap
+    if (!w_up) PO_HIPCHK(w.up(weights_h, (size_t)n_weights * 4));
+    PO_HIPCHK(sig.up(signal_h, (size_t)plan.rows * 4));             // each read's signal once, whatever the overlap (NULL: it is there)
     PO_HIPCHK(sig_off.up(sig_off_h, sizeof(int64_t) * ((size_t)n_reads + 1)));
     PO_HIPCHK(win_off.up(plan.win_off.data(), sizeof(int64_t) * plan.win_off.size()));
     PO_HIPCHK(win_read.up(plan.win_read.data(), sizeof(int32_t) * plan.win_read.size()));
@@ -128,11 +128,7 @@ int PoBasecallPasses::run(const PoBasecallPlan& plan, int window, int overlap, c
 
 namespace {
 
-// what po_basecall_fastq_batch_h adds to po_basecall_batch_h's arguments
-struct FastqOut {
-    int band_size;
-    char* qual_h; int32_t* qual_status_h; double* odds_h; int32_t* guide_h;
-};
+typedef PoBasecallFastq FastqOut;
 
 // The quality stages, enqueued behind the decoder on its stream: the table dy, the strings of `out` and
 // (Viterbi) the frame map stay where they are; lengths, statuses, modes and offsets are the only words that cross.
@@ -149,6 +145,7 @@ struct FastqStages {
 
     // before the decoder: the buffers whose size is known from the signals
     int prepare(int n, int64_t rows, int kind, int beam_width, size_t cap) {
+        al.reset();
         second = beam_width > 0 || kind != PO_KIND_POREOVER;
         PO_HIPCHK(map.up(nullptr, sizeof(int32_t) * (size_t)rows));
         PO_HIPCHK(mode.up(nullptr, sizeof(int32_t) * n));
@@ -254,19 +251,45 @@ struct FastqStages {
     }
 };
 
-// po_basecall_batch_h (fq == NULL) and po_basecall_fastq_batch_h under their own names
-int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
-                  const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights, const char* alphabet,
-                  int kind, int beam_width, int model, int max_windows_per_pass, char* seq_h, const int64_t* seq_off_h,
-                  int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h, const FastqOut* fq) {
+}  // namespace
+
+// everything a call keeps on the device: one call's, or a po_basecaller worker's between groups and runs
+struct PoBasecallResident {
+    PoBasecallPasses net;
+    PoDev dy, dws2;
+    PoSeqOut out;
+    FastqStages fs;
+};
+
+PoBasecallResident* po_basecall_resident_new() { return new PoBasecallResident; }
+void po_basecall_resident_free(PoBasecallResident* st) { delete st; }
+
+int po_basecall_resident_weights(PoBasecallResident* st, const float* weights_h, int64_t n_weights) {
+    PO_HIPCHK(st->net.w.up(weights_h, (size_t)n_weights * 4));
+    st->net.w_up = true;
+    return PO_OK;
+}
+
+int po_basecall_resident_signal(PoBasecallResident* st, int64_t samples, float** signal) {
+    PO_HIPCHK(st->net.sig.up(nullptr, (size_t)samples * 4));
+    *signal = st->net.sig.as<float>();
+    return PO_OK;
+}
+
+// po_basecall_batch_h (fq == NULL) and po_basecall_fastq_batch_h under their own names, and a po_basecaller's groups
+int po_basecall_body(PoBasecallResident* st, hipStream_t stream, bool signal_resident, const char* name, const float* signal_h,
+                     const int64_t* sig_off_h, int n_reads, int window, int overlap, const po_call_layer* layers_h, int n_layers,
+                     const float* weights_h, int64_t n_weights, const char* alphabet, int kind, int beam_width, int model,
+                     int max_windows_per_pass, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                     float* logits_h, float* stage_ms_h, const PoBasecallFastq* fq) {
     const std::string me = std::string(name) + ": ";
     const int n_stages = fq ? 8 : 6;
     po_set_error("");
     // ---- every argument error, before the first allocation
     if (n_reads < 0) return po_fail(PO_E_ARG, me + "n_reads " + std::to_string(n_reads));
-    if (!signal_h || !sig_off_h || !layers_h || !weights_h || !seq_h || !seq_off_h || !seq_len_h || !status_h)
+    if ((!signal_h && !signal_resident) || !sig_off_h || !layers_h || !weights_h || !seq_h || !seq_off_h || !seq_len_h || !status_h)
         return po_fail(PO_E_ARG, me + "null argument " +
-                       (!signal_h ? "signal_h" : !sig_off_h ? "sig_off_h" : !layers_h ? "layers_h" : !weights_h ? "weights_h" :
+                       (!signal_h && !signal_resident ? "signal_h" : !sig_off_h ? "sig_off_h" : !layers_h ? "layers_h" : !weights_h ? "weights_h" :
                         !seq_h ? "seq_h" : !seq_off_h ? "seq_off_h" : !seq_len_h ? "seq_len_h" : "status_h"));
     if (fq && (!fq->qual_h || !fq->qual_status_h))
         return po_fail(PO_E_ARG, me + "null argument " + (!fq->qual_h ? "qual_h" : "qual_status_h"));
@@ -290,12 +313,11 @@ int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_of
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + n_stages, 0.f);
     if (n_reads == 0) return PO_OK;
 
-    hipStream_t stream = nullptr;
     const int64_t rows = plan.rows;
-    PoBasecallPasses net;
-    PoDev dy, dws2;
-    PoSeqOut out;
-    rc = net.up(plan, signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
+    PoBasecallPasses& net = st->net;
+    PoDev &dy = st->dy, &dws2 = st->dws2;
+    PoSeqOut& out = st->out;
+    rc = net.up(plan, signal_resident ? nullptr : signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
     if (rc != PO_OK) return rc;
     const PoDev &dsoff = net.sig_off, &dlog = net.logits;   // resident: the stitched logits ...
     PO_HIPCHK(dy.up(nullptr, (size_t)rows * NOUT * 8));     // ... and the f64 log-probability table
@@ -303,7 +325,7 @@ int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_of
     const size_t wsb2 = beam_width <= 0 ? po_viterbi_workspace_bytes(n_reads, rows, NOUT, kind)
                                         : po_beam1d_workspace_bytes(n_reads, rows, plan.max_rows, NOUT, beam_width, model);
     PO_HIPCHK(dws2.up(nullptr, wsb2));
-    FastqStages fs;
+    FastqStages& fs = st->fs;
     if (fq) {
         rc = fs.prepare(n_reads, rows, kind, beam_width, out.cap);
         if (rc != PO_OK) return rc;
@@ -353,6 +375,17 @@ int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_of
     return PO_OK;
 }
 
+namespace {
+// a call of its own: a fresh state, freed when the call returns, on the null stream
+int basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                  const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights, const char* alphabet,
+                  int kind, int beam_width, int model, int max_windows_per_pass, char* seq_h, const int64_t* seq_off_h,
+                  int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h, const FastqOut* fq) {
+    PoBasecallResident st;
+    return po_basecall_body(&st, nullptr, false, name, signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
+                            n_weights, alphabet, kind, beam_width, model, max_windows_per_pass, seq_h, seq_off_h, seq_len_h, status_h,
+                            logits_h, stage_ms_h, fq);
+}
 }  // namespace
 
 extern "C" int po_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,

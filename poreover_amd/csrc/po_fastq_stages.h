@@ -21,6 +21,12 @@ struct PoFqAligner {
     size_t wab = 0;
 
     int m() const { return (int)reads.size(); }
+    void reset() {   // before the pairs of another call are listed (an engine's resident state)
+        reads.clear();
+        so.assign(1, 0);
+        ao.assign(1, 0);
+        slack = m1 = m2 = 0;
+    }
     // pair = (called, scored), as quality.call_guides aligns them
     void add(int read, int64_t Lc, int64_t L) {
         reads.push_back(read);

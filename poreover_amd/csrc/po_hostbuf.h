@@ -44,17 +44,27 @@ int po_fail_hip(hipError_t e, const char* what);        // "what: <HIP's error s
         if (e_ != hipSuccess) return po_fail_hip(e_, #x); \
     } while (0)
 
-// ---- a device buffer that lives for one call
+// ---- a device buffer that frees itself.  It lives for one call, or, in an engine's resident state, for many: up() keeps
+// an allocation that is large enough (grow-only; its contents stay where no source is given), so a later call allocates
+// only what has grown.
 struct PoDev {
     void* p = nullptr;
+    size_t cap = 0;     // bytes allocated
     PoDev() = default;
     PoDev(const PoDev&) = delete;
     PoDev& operator=(const PoDev&) = delete;
     ~PoDev() { if (p) (void)hipFree(p); }
     // allocates `bytes` (256 at least, so that an empty array still has an address) and copies src_h up if there is one
     hipError_t up(const void* src_h, size_t bytes) {
-        hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 256));
-        if (e != hipSuccess) { p = nullptr; return e; }
+        const size_t need = std::max<size_t>(bytes, 256);
+        if (!p || cap < need) {
+            if (p) (void)hipFree(p);
+            p = nullptr;
+            cap = 0;
+            hipError_t e = hipMalloc(&p, need);
+            if (e != hipSuccess) { p = nullptr; return e; }
+            cap = need;
+        }
         return src_h && bytes ? hipMemcpy(p, src_h, bytes, hipMemcpyHostToDevice) : hipSuccess;
     }
     hipError_t down(void* dst_h, size_t bytes) const {

@@ -110,6 +110,14 @@ int po_launch_gamma(const double* y1, const int64_t* y1_off, const double* y2, c
 int po_launch_ingest(const void* src, const int64_t* row_off, int n, int C, int mode, const int* perm, int reverse,
                      int64_t total_rows, double* out, hipStream_t stream);
 
+// po_prep.hip (enqueue only; the rules are po_prep_rules.h's): device pointers throughout, raw 16-byte aligned, slab_off / slab_read
+// a PoPrepPlan's tables, stats required (a and b travel through it), ws of po_prep_workspace_bytes
+size_t po_prep_workspace_bytes(int n_reads, int64_t n_slabs, int bins);
+int po_launch_signal_prep(const int16_t* raw, const int64_t* raw_off, int n_reads, int64_t total, const int64_t* slab_off,
+                          const int32_t* slab_read, int64_t n_slabs, int scaling, int lo, int hi, const double* offset,
+                          const double* alpha, float* signal, int64_t* sig_off, po_prep_stats* stats, void* ws, size_t ws_bytes,
+                          hipStream_t stream);
+
 // po_fastq.hip (enqueue only; the rules are po_fastq_rules.h's)
 int po_launch_fastq_mode(const char* seq, const int32_t* len, const char* vseq, const int32_t* vlen, const int32_t* vstatus,
                          const int64_t* seq_off, int n, int32_t* mode, hipStream_t stream);

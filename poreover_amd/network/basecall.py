@@ -24,9 +24,16 @@ import numpy as np
 
 from .. import _lib, _marshal
 from . import checkpoint as ckpt
-from .network import _layers_array, load_model, parse_fast5
+from .network import SCALINGS, _layers_array, load_model, parse_fast5, read_fast5_raw
 
-__all__ = ["window_plan", "frame_window", "check_time_order", "basecall_signals", "basecall", "check_window_args"]
+__all__ = ["window_plan", "frame_window", "check_time_order", "basecall_signals", "basecall_raw", "basecall", "check_window_args",
+           "Basecaller", "group_plan", "stream_devices", "check_readers"]
+
+# `basecall --gpus`: files per chunk and raw samples per chunk (two chunks are in memory at most), reader threads
+CHUNK_FILES = 512
+CHUNK_SAMPLES = 1 << 28
+DEFAULT_READERS = 4
+MAX_READERS = 16
 
 # Device memory that one engine call may hold for its per-sample state (the stitched logits, the log-probability table,
 # the decoder's workspace, the signal and the strings): 16 GiB, an eighteenth of an MI355X's 288 GB.  The network's pass
@@ -181,8 +188,230 @@ def _groups(todo, lens, fits):
     return out
 
 
+def group_plan(lens, group_samples):
+    """po_basecall_group_plan in Python, which the engine test pins: (first, count) of the groups — contiguous runs of reads
+    in input order of at most group_samples samples, one read at least (a longer read goes alone)"""
+    out, i, n = [], 0, len(lens)
+    while i < n:
+        f, total = i, 0
+        while i < n and (i == f or total + lens[i] <= group_samples):
+            total += lens[i]
+            i += 1
+        out.append((f, i - f))
+    return out
+
+
+def group_samples(total, budget_samples, ndev):
+    """the group size of a run (po_basecall_group_samples): min(budget, ceil(total / (2 ndev))) samples, 1 at least"""
+    return max(1, min(int(budget_samples), -(-int(total) // (2 * int(ndev)))))
+
+
+def check_readers(readers, what="basecall"):
+    if not 1 <= readers <= MAX_READERS:
+        raise SystemExit("%s: --readers %d must be 1 to %d" % (what, readers, MAX_READERS))
+
+
+def stream_devices(gpus, what="basecall"):
+    """the devices of a --gpus N run: 0 .. N - 1, every visible device for N = 0; refused where fewer are visible"""
+    if gpus < 0:
+        raise SystemExit("%s: --gpus must not be negative" % what)
+    nd = _lib.load(False).po_device_count()
+    if gpus > nd or (gpus == 0 and nd < 1):
+        raise SystemExit("%s: --gpus %d, but %d device%s visible" % (what, gpus, nd, " is" if nd == 1 else "s are"))
+    return list(range(gpus if gpus else nd))
+
+
+class Basecaller:
+    """po_basecaller: a model, the decoder's options and a list of devices (a device may be named more
+    than once); run_f32 / run_raw deal groups of reads to one host thread per listed device.  A context manager."""
+
+    def __init__(self, net, devices, window, overlap, kind, beam_width, model, max_windows_per_pass=0, fastq=False, band=0,
+                 scaling="standard", lo=200, hi=800, resident_bytes=0):
+        if scaling not in SCALINGS:
+            raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
+        self.lib = _lib.load()
+        self.fastq = bool(fastq)
+        self.devices = [int(d) for d in devices]
+        w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+        opt = _lib.BasecallerOptions(int(window), int(overlap), int(kind), int(beam_width), int(model), int(max_windows_per_pass),
+                                     1 if fastq else 0, int(band), SCALINGS.index(scaling), int(lo), int(hi), int(resident_bytes))
+        dev = (C.c_int * max(len(self.devices), 1))(*self.devices)
+        self.h = self.lib.po_basecaller_create(dev, len(self.devices), _layers_array(net), len(net.layers), w.ctypes.data, w.size,
+                                               b"ACGT", C.byref(opt))
+        if not self.h:
+            detail = self.lib.po_last_error()
+            raise _lib.EngineError(_lib.E_ARG, "po_basecaller_create", detail.decode() if detail else "")
+
+    def close(self):
+        if self.h:
+            self.lib.po_basecaller_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _run(self, what, call, data, off, n, rows, want_logits, kept=None):
+        seq = np.zeros(max(rows, 1), dtype=np.uint8)
+        qual = np.zeros(max(rows, 1), dtype=np.uint8) if self.fastq else None
+        lens = np.zeros(n, dtype=np.int32)
+        st = np.zeros(n, dtype=np.int32)
+        qst = np.zeros(n, dtype=np.int32)
+        lg = np.zeros((max(rows, 1), ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
+        _lib.check(call(seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data, lg.ctypes.data if want_logits else None,
+                        qual.ctypes.data if self.fastq else None, qst.ctypes.data if self.fastq else None), what)
+        _marshal.raise_on_status(st, n, "basecall of read")
+        frames = [int(off[i + 1] - off[i]) for i in range(n)] if kept is None else [int(k) for k in kept]
+        res = {"strings": _marshal.strings(seq, off, lens), "qual_status": qst}
+        if self.fastq:
+            res["quals"] = [qual[off[i]:off[i] + lens[i]] - 33 for i in range(n)]
+        if want_logits:
+            res["logits"] = [lg[off[i]:off[i] + frames[i]] for i in range(n)]
+        return res
+
+    def run_f32(self, sigs, want_logits=False):
+        """a dict: strings, qual_status, and where made quals (uint8 Phred arrays) and logits ((T, 5) float32 per read)"""
+        n = len(sigs)
+        off = _marshal.offsets([len(s) for s in sigs])
+        signal = np.ascontiguousarray(np.concatenate(sigs) if n else np.zeros(0), dtype=np.float32)
+        call = lambda *out: self.lib.po_basecaller_run_f32(self.h, signal.ctypes.data, off.ctypes.data, n, *out)
+        return self._run("po_basecaller_run_f32", call, signal, off, n, int(off[-1]), want_logits)
+
+    def run_raw(self, raws, offsets=None, alphas=None, want_logits=False):
+        """run_f32's dict from raw int16 reads, with "kept": the samples each read kept (its logits' rows)"""
+        n = len(raws)
+        off = _marshal.offsets([len(r) for r in raws])
+        raw = np.ascontiguousarray(np.concatenate(raws) if n else np.zeros(0), dtype=np.int16)
+        o = np.ascontiguousarray(offsets, dtype=np.float64) if offsets is not None else None
+        a = np.ascontiguousarray(alphas, dtype=np.float64) if alphas is not None else None
+        kept = np.zeros(n, dtype=np.int64)
+        call = lambda *out: self.lib.po_basecaller_run_raw(self.h, raw.ctypes.data, off.ctypes.data, n,
+                                                           o.ctypes.data if o is not None else None,
+                                                           a.ctypes.data if a is not None else None, *out, kept.ctypes.data)
+        res = self._run("po_basecaller_run_raw", call, raw, off, n, int(off[-1]), want_logits, kept=kept)
+        res["kept"] = kept
+        return res
+
+    def stats(self):
+        """per worker: dict(device, reads, samples, groups, busy_ms) of the last run"""
+        out = []
+        for i, d in enumerate(self.devices):
+            r, s, g, ms = C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
+            _lib.check(self.lib.po_basecaller_stats(self.h, i, C.byref(r), C.byref(s), C.byref(g), C.byref(ms)), "po_basecaller_stats")
+            out.append({"device": d, "reads": r.value, "samples": s.value, "groups": g.value, "busy_ms": ms.value})
+        return out
+
+
+def _stream(make, run, n_all, todo, logits, qualities, band, empty, worker_stats=None, engines=None):
+    """basecall_signals' results over the engine: make(fastq, band) -> Basecaller, run(engine, reads, want_logits) -> its dict
+    for those reads.  The unbanded retry, the warning and the output tuples are basecall_signals'.  engines (a dict, or
+    None): the caller's engines by (fastq, band), made here when first needed and left open for its later calls — the
+    weights go up once per engine; without it an engine lives for this call."""
+    out = [empty] * n_all
+
+    def go(reads, fastq, band_, want_logits):
+        key = (bool(fastq), int(band_))
+        eng = engines.get(key) if engines is not None else None
+        if eng is None:
+            eng = make(fastq, band_)
+            if engines is not None:
+                engines[key] = eng
+        try:
+            r = run(eng, reads, want_logits)
+            if worker_stats is not None:
+                worker_stats.append(eng.stats())
+        finally:
+            if engines is None:
+                eng.close()
+        return r
+
+    if not todo:
+        return out
+    if not qualities:
+        r = go(todo, False, 0, logits)
+        for j, k in enumerate(todo):
+            out[k] = (r["strings"][j], r["logits"][j]) if logits else r["strings"][j]
+        return out
+    from .. import quality
+    r = go(todo, True, band, logits)
+    strings = {k: r["strings"][j] for j, k in enumerate(todo)}
+    quals = {k: r["quals"][j] for j, k in enumerate(todo)}
+    status = {k: int(r["qual_status"][j]) for j, k in enumerate(todo)}
+    retry = [k for k in todo if status[k] == _lib.E_ENVELOPE] if band > 0 else []
+    if retry:
+        r2 = go(retry, True, 0, False)
+        for j, k in enumerate(retry):
+            if r2["strings"][j] != strings[k]:
+                raise RuntimeError("basecall_signals: read %d decodes differently in the unbanded retry" % k)
+            quals[k], status[k] = r2["quals"][j], int(r2["qual_status"][j])
+    bad = [k for k in todo if status[k] != 0]
+    if bad:
+        quality.warn_unscored(["read %d (%s)" % (k, _lib._CODE_NAMES.get(status[k], status[k])) for k in bad])
+    for j, k in enumerate(todo):
+        q = quals[k] if status[k] == 0 else np.zeros(len(strings[k]), dtype=np.uint8)
+        out[k] = (strings[k], r["logits"][j], q) if logits else (strings[k], q)
+    return out
+
+
+def _decoder_args(algorithm, beam_width, merge_repeats, what):
+    if algorithm not in ("viterbi", "beam"):
+        raise ValueError("%s: algorithm %r (viterbi or beam)" % (what, algorithm))
+    if algorithm == "beam" and not 1 <= beam_width <= 64:
+        raise ValueError("%s: beam_width %d (1 to 64)" % (what, beam_width))
+    return (_lib.KINDS["bonito" if merge_repeats else "poreover"], _lib.MODELS["ctc_merge_repeats" if merge_repeats else "ctc"],
+            int(beam_width) if algorithm == "beam" else 0)
+
+
+def basecall_raw(net, raws, channels=None, scaling="standard", devices=(0,), window=1000, overlap=0, algorithm="viterbi",
+                 beam_width=25, merge_repeats=False, logits=False, max_windows_per_pass=0, qualities=False, qual_band=None,
+                 precision="f32", lo=200, hi=800, resident_bytes=None, worker_stats=None, engines=None):
+    """basecall_signals(..., devices=devices) from RAW int16 reads: the abasic filter (lo < x < hi) and `scaling` run on the
+    device (po_signal_prep_h's rule) inside the engine's groups.  channels: per read (offset, digitisation,
+    range), read for scaling "current" alone.  Returns what basecall_signals returns; a read's logits have one row per KEPT
+    sample, and a read that keeps nothing gets "".  worker_stats (a list) gets Basecaller.stats() of every run appended.
+    engines (a dict the caller keeps, then closes with close_engines): the engines are made once and serve every later call
+    with the same dict — the same net, devices and options are the caller's to keep."""
+    _lib._precision_code(precision)
+    kind, model, bw = _decoder_args(algorithm, beam_width, merge_repeats, "basecall_raw")
+    window_plan(1, window, overlap)
+    check_time_order(net.kinds)
+    raws = [np.asarray(r) for r in raws]
+    for i, r in enumerate(raws):
+        if r.dtype != np.int16 or r.ndim != 1:
+            raise ValueError("basecall_raw: read %d is %s of %d dimension(s), not a vector of int16" % (i, r.dtype, r.ndim))
+    if scaling == "current" and (channels is None or len(channels) != len(raws)):
+        raise ValueError("basecall_raw: scaling 'current' needs (offset, digitisation, range) of every read")
+    empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
+    if qualities:
+        empty = (empty if logits else (empty,)) + (np.zeros(0, dtype=np.uint8),)
+    todo = [i for i, r in enumerate(raws) if len(r)]
+    from .. import quality
+    band = quality.DEFAULT_BAND if qual_band is None else int(qual_band)
+    rb = RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
+
+    def make(fastq, band_):
+        return Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band_, scaling, lo, hi, rb)
+
+    def run(eng, reads, want_logits):
+        cur = scaling == "current"
+        return eng.run_raw([raws[k] for k in reads], [channels[k][0] for k in reads] if cur else None,
+                           [channels[k][1] / channels[k][2] for k in reads] if cur else None, want_logits)
+
+    with _lib.call_precision(precision):
+        return _stream(make, run, len(raws), todo, logits, qualities, band, empty, worker_stats, engines)
+
+
+def close_engines(engines):
+    for eng in engines.values():
+        eng.close()
+    engines.clear()
+
+
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
-                     logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None, precision="f32"):
+                     logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None, precision="f32",
+                     devices=None, resident_bytes=None, worker_stats=None, engines=None):
     """The decoded string of each scaled signal, in input order — or (string, (len(s), 5) float32 stitched logits) with
     logits=True.  qualities=True adds a uint8 (len(string),) array of Phred values as the last item: (string, q) or
     (string, logits, q), from the quality lattice (poreover_amd.quality) within qual_band label positions of the call's
@@ -195,7 +424,11 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     input order, of at most RESIDENT_BYTES // (resident bytes per sample) samples — a single longer read goes alone;
     stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES; with qualities
     _lib.BASECALL_FASTQ_STAGES).  precision "f32" or "bf16": the GRU input projections' operands
-    (_lib.set_call_precision), set around each engine call made here and restored after it."""
+    (_lib.set_call_precision), set around each engine call made here and restored after it.
+    devices (a list; None: the path above on the current device): the reads go through a Basecaller over those devices
+     in groups of at most resident_bytes (None: RESIDENT_BYTES) of per-sample state — the same strings,
+    logits and qualities; stage_ms is not filled on this route; worker_stats (a list) gets Basecaller.stats() appended;
+    engines (a dict the caller keeps and closes with close_engines): the engines outlive the call, as for basecall_raw."""
     _lib._precision_code(precision)
     if algorithm not in ("viterbi", "beam"):
         raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
@@ -216,6 +449,14 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     model = _lib.MODELS["ctc_merge_repeats" if merge_repeats else "ctc"]
     bw = int(beam_width) if algorithm == "beam" else 0
     lens = [len(s) for s in sigs]
+    if devices is not None:
+        from .. import quality
+        rb = RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
+        make = lambda fastq, band_: Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band_,
+                                               resident_bytes=rb)
+        with _lib.call_precision(precision):
+            return _stream(make, lambda eng, reads, want: eng.run_f32([sigs[k] for k in reads], want), len(sigs), todo, logits,
+                           qualities, quality.DEFAULT_BAND if qual_band is None else int(qual_band), empty, worker_stats, engines)
     if not qualities:
         budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
         for group in _groups(todo, lens, lambda n, total, longest: total <= budget):
@@ -274,11 +515,17 @@ def basecall(args):
         check_time_order([k for k, _ in ckpt.parse_model_json(model if model is not None else ckpt.default_model_config())])
     except ckpt.NetworkError as e:
         raise SystemExit(str(e))
+    gpus = getattr(args, "gpus", None)
+    if gpus is not None:
+        check_readers(getattr(args, "readers", DEFAULT_READERS))
+        devices = stream_devices(gpus)
     net = load_model(args)
     src = getattr(args, "in")
     files = sorted(glob.glob(os.path.join(src, "*.fast5"))) if os.path.isdir(src) else [src]
     if not files:
         raise SystemExit("basecall: no *.fast5 files in %s" % src)
+    if gpus is not None:
+        return _basecall_stream(args, net, files, devices)
     parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
     fastq = bool(getattr(args, "fastq", False))
     seqs = basecall_signals(net, [s for _, s in parsed], window=args.window, overlap=args.overlap, algorithm=args.algorithm,
@@ -303,4 +550,54 @@ def basecall(args):
             for name, s, q in zip(names, seqs, quals):
                 f.write(fastq_format(name, s, q))
         logging.info("basecall: %d read(s) -> %s", len(files), args.out + ".fastq")
+    return out_path
+
+
+def _basecall_stream(args, net, files, devices):
+    """`basecall --gpus`: the files in sorted order, in chunks of at most --chunk_files files; --readers threads read chunk
+    k + 1 (read_fast5_raw: the file alone; filter and scaling run on the device) while the engine runs chunk k; each
+    chunk's records are appended to {out}.fasta (and {out}.fastq) in file order as it completes.  Two chunks are in
+    memory at most; a chunk of more than CHUNK_SAMPLES raw samples goes to the engine in runs of at most that many."""
+    from concurrent.futures import ThreadPoolExecutor
+    from ..decoding.decode import fasta_format
+    from ..quality import fastq_format
+    fastq = bool(getattr(args, "fastq", False))
+    engines = {}       # one engine for the whole run (and one more if a read takes the unbanded retry): weights up once
+    per = max(1, int(getattr(args, "chunk_files", None) or CHUNK_FILES))
+    chunks = [files[i:i + per] for i in range(0, len(files), per)]
+    out_path = args.out + ".fasta"
+    with ThreadPoolExecutor(max_workers=getattr(args, "readers", DEFAULT_READERS)) as pool, open(out_path, "w") as fa:
+        fq = open(args.out + ".fastq", "w") if fastq else None
+        try:
+            pending = [pool.submit(read_fast5_raw, f) for f in chunks[0]]
+            for c, chunk in enumerate(chunks):
+                parsed = [p.result() for p in pending]
+                pending = [pool.submit(read_fast5_raw, f) for f in chunks[c + 1]] if c + 1 < len(chunks) else []
+                runs, cur, total = [], [], 0
+                for i, p in enumerate(parsed):
+                    if cur and total + len(p[1]) > CHUNK_SAMPLES:
+                        runs.append(cur)
+                        cur, total = [], 0
+                    cur.append(i)
+                    total += len(p[1])
+                runs.append(cur)
+                for idx in runs:
+                    res = basecall_raw(net, [parsed[i][1] for i in idx], [parsed[i][2:5] for i in idx], scaling=args.scaling,
+                                       devices=devices, window=args.window, overlap=args.overlap, algorithm=args.algorithm,
+                                       beam_width=args.beam_width, merge_repeats=args.merge_repeats, qualities=fastq,
+                                       qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"),
+                                       engines=engines)
+                    for i, r in zip(idx, res):
+                        rid = parsed[i][0]
+                        name = (rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid)) if args.use_id \
+                            else Path(chunk[i]).stem
+                        s = r[0] if fastq else r
+                        print(fasta_format(name, s), file=fa)
+                        if fastq:
+                            fq.write(fastq_format(name, s, r[1]))
+        finally:
+            close_engines(engines)
+            if fq is not None:
+                fq.close()
+    logging.info("basecall: %d read(s) -> %s on device(s) %s", len(files), out_path, ", ".join(map(str, devices)))
     return out_path

@@ -17,7 +17,7 @@ from .. import _lib
 from ..decoding import hdf5_lite
 from . import checkpoint as ckpt
 
-__all__ = ["parse_fast5", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model", "round_bf16",
+__all__ = ["parse_fast5", "read_fast5_raw", "prep_signals", "PREP_STATS", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model", "round_bf16",
            "gru_proj", "gru_wgrad", "gru_dx"]
 
 SCALINGS = ("standard", "current", "median", "rescale", "raw")
@@ -51,6 +51,63 @@ def parse_fast5(f, scaling="standard"):
     else:
         raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
     return read_id, signal
+
+
+def read_fast5_raw(f):
+    """(read_id, raw int16 signal, offset, digitisation, range) of a single-read FAST5 file: what parse_fast5 reads, before
+    its filter and scaling (prep_signals does those on the device)"""
+    hdf = hdf5_lite.File(f, "r")
+    read_string = list(hdf["/Raw/Reads"].keys())[0]
+    read = hdf["/Raw/Reads/" + read_string]
+    read_id = read.attrs["read_id"]
+    read_duration = read.attrs["duration"]
+    raw_signal = np.array(hdf["/Raw/Reads/" + read_string + "/Signal"])
+    if len(raw_signal) != read_duration:
+        raise ValueError("%s: %d signal samples, duration attribute %d" % (f, len(raw_signal), read_duration))
+    if raw_signal.dtype != np.int16:
+        raise ValueError("%s: the raw signal is %s, not int16" % (f, raw_signal.dtype))
+    ch = hdf["UniqueGlobalKey"]["channel_id"].attrs
+    return read_id, raw_signal, ch["offset"], ch["digitisation"], ch["range"]
+
+
+# po_prep_stats (include/poreover_hip.h)
+PREP_STATS = np.dtype([("n", "<i8"), ("S", "<i8"), ("Q", "<i8"), ("min", "<i4"), ("max", "<i4"), ("med_lo", "<i4"),
+                       ("med_hi", "<i4"), ("a", "<f8"), ("b", "<f8")])
+
+
+def prep_signals(raws, scaling="standard", lo=200, hi=800, offsets=None, alphas=None, stats=False, kernel_ms=None):
+    """parse_fast5's abasic filter (lo < x < hi) and scaling for a batch of raw int16 reads, on the device
+    (po_signal_prep_h, the rule of csrc/po_prep_rules.h): the float32 signal of each read, in input order
+    (a read with no kept sample gets an empty one); with stats=True also a PREP_STATS array, one record per read.
+    scaling "current" needs offsets and alphas (digitisation / range), one float per read.  kernel_ms (a list) gets the
+    device milliseconds of the call's kernels appended."""
+    if scaling not in SCALINGS:
+        raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
+    raws = [np.asarray(r) for r in raws]
+    for i, r in enumerate(raws):
+        if r.dtype != np.int16 or r.ndim != 1:
+            raise ValueError("prep_signals: read %d is %s of %d dimension(s), not a vector of int16" % (i, r.dtype, r.ndim))
+    n = len(raws)
+    if scaling == "current" and (offsets is None or alphas is None or len(offsets) != n or len(alphas) != n):
+        raise ValueError("prep_signals: scaling 'current' needs one offset and one alpha per read")
+    lib = _lib.load()
+    off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(r) for r in raws], out=off[1:])
+    raw = np.ascontiguousarray(np.concatenate(raws) if n else np.zeros(0), dtype=np.int16)
+    o = np.ascontiguousarray(offsets, dtype=np.float64) if scaling == "current" else None
+    a = np.ascontiguousarray(alphas, dtype=np.float64) if scaling == "current" else None
+    sig = np.empty(max(int(off[-1]), 1), dtype=np.float32)
+    sig_off = np.zeros(n + 1, dtype=np.int64)
+    st = np.zeros(n, dtype=PREP_STATS) if stats else None
+    ms = (C.c_float * 1)() if kernel_ms is not None else None
+    _lib.check(lib.po_signal_prep_h(raw.ctypes.data, off.ctypes.data, n, SCALINGS.index(scaling), int(lo), int(hi),
+                                    o.ctypes.data if o is not None else None, a.ctypes.data if a is not None else None,
+                                    sig.ctypes.data, sig_off.ctypes.data, st.ctypes.data if stats else None, ms),
+               "po_signal_prep_h")
+    if kernel_ms is not None:
+        kernel_ms.append(float(ms[0]))
+    sigs = [sig[sig_off[i]:sig_off[i + 1]] for i in range(n)]      # views of the one buffer the call filled
+    return (sigs, st) if stats else sigs
 
 
 def batch_input(signal, window_size):
