@@ -429,7 +429,9 @@ int po_wave_plan(const int64_t* rows1, const int64_t* rows2, int n, int wave_pai
 
 /* ---- basecalling network forward pass (`call`) ------------------------------------------------
  * Replaces the reference's TensorFlow forward pass of call_helper (network.py:253-282): the Keras models of build_model
- * (network.py:15-55) on windows of scaled FAST5 signal, then tf.nn.softmax.  f32 weights, f32 arithmetic.
+ * (network.py:15-55) on windows of scaled FAST5 signal, then tf.nn.softmax.  f32 weights, f32 arithmetic — by default: two
+ * opt-in selectors below put bf16 operands under the GRU input projections (po_set_call_precision) and under the
+ * recurrence's product h·U (po_set_recur_precision), each with f32 products and sums.
  *   - signal:  n windows of T f32 samples each, window-major (n * T values); each window starts from a zero state
  *   - layers_h: HOST array of n_layers po_call_layer, in the order the model applies them; layer k's cin is layer
  *              k-1's cout (1 for the first); the last layer is PO_CALL_DENSE with cout 5
@@ -488,6 +490,29 @@ int po_get_call_precision(void);
  * or 2; a null pointer, another value or another precision is PO_E_ARG naming the argument, before any allocation. */
 int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w_h, const float* bin_h, int precision,
                   float* P_h);
+
+/* The precision of the GRU recurrence's product h·U, process-wide and read once per po_call_batch call,
+ * next to the call precision and independent of it — so by po_call_batch_h, po_basecall_batch_h, po_basecall_fastq_batch_h,
+ * po_pair_basecall_batch_h, po_pair_basecall_fastq_batch_h and every group of a po_basecaller engine — set it around the whole run;
+ * po_train_* and po_train_eval are not reached:
+ *   PO_RECUR_F32     (default) f32 operands on v_mfma_f32_16x16x4_f32
+ *   PO_RECUR_BF16X3  h and U each split in two bf16 values (hi = bf16(v), lo = bf16(v - hi), round to nearest even,
+ *                    csrc/po_bf16_rules.h) and h·U taken as hh·Uh + hl·Uh + hh·Ul on v_mfma_f32_16x16x32_bf16 with f32 sums;
+ *                    the state, the bias, the gates and every store stay f32.  Every GRU width from 16 to 128; no workspace
+ *                    beyond PO_RECUR_F32's.  Logits stay within the f32 path's own bound of a float64 model (1e-3).
+ * Any other value is PO_E_ARG naming `precision <value>` and leaves the mode as it was. */
+#define PO_RECUR_F32 0
+#define PO_RECUR_BF16X3 1
+int po_set_recur_precision(int precision);
+int po_get_recur_precision(void);
+/* The recurrence stage alone, on host buffers, by the kernel po_call_batch launches under `precision` (explicit: the
+ * selector above is not read): P_h[ndir][n*T][3H] the input projections, U_h[ndir][H][3H], brec_h[ndir][3H], kind
+ * PO_CALL_BIGRU (ndir 2: forward, backward), PO_CALL_GRU or PO_CALL_GRU_BACK (ndir 1).  out_h[n*T][ndir*H] is the layer's
+ * output as po_call_batch lays it out; rec_h (or NULL) [ndir][n*T][3H] gets h_prev·U + brec of every step, at the frame the
+ * step consumed.  n = 0 is PO_OK and writes nothing.  Refused with PO_E_ARG naming the argument, before any allocation: a
+ * null required pointer, n < 0, T < 1, H not one of 16, 32 .. 128 (`H <value> units`), another kind, another precision. */
+int po_gru_recur_h(const float* P_h, const float* U_h, const float* brec_h, int n, int T, int H, int kind, int precision,
+                   float* out_h, float* rec_h);
 
 /* ---- signal preparation: raw int16 reads to scaled f32 signals on the device --------
  * network.parse_fast5's abasic filter and scaling for a ragged batch of raw reads.  A sample x is kept when lo < x < hi
@@ -605,7 +630,8 @@ int po_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, i
  *   - when a group fails the other workers finish what they hold and take no more; the run returns that group's code and
  *     "device d: <message>".  The engine stays usable.
  *   - po_basecaller_stats: reads, samples, groups and busy host milliseconds of worker i in the last run
- * The call precision (po_set_call_precision) is read by every group: set it around the whole run. */
+ * The call precision (po_set_call_precision) and the recurrence precision (po_set_recur_precision) are read by every
+ * group: set them around the whole run. */
 typedef struct po_basecaller po_basecaller;
 typedef struct po_basecaller_options {
     int window, overlap, kind, beam_width, model, max_windows_per_pass;

@@ -15,6 +15,8 @@ from . import __version__
 from .quality import DEFAULT_BAND
 
 
+RECURRENCE_HELP = ('The product h·U of the GRU recurrence: f32, or bf16x3 (both operands split in two bf16 values, three bf16 products '
+                   'with f32 sums; logits stay within the f32 path\'s own bound); independent of --precision')
 PRECISION_HELP = ('bf16: GRU input projections with bf16 operands, f32 accumulation; about one base in a thousand differs '
                   'from f32')
 
@@ -78,6 +80,7 @@ def build_parser():
     p.add_argument('--format', choices=['csv', 'npy'], default='npy', help='Save softmax probabilities to CSV file or logits to binarized NumPy format')
     p.add_argument('--no_stack', default=False, action='store_true', help='Basecall [1xSIGNAL_LENGTH] tensor instead of splitting it into windows (slower)')
     p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
+    p.add_argument('--recurrence', choices=['f32', 'bf16x3'], default='f32', help=RECURRENCE_HELP)
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="call")
 
@@ -97,6 +100,7 @@ def build_parser():
     p.add_argument('--fastq', action='store_true', default=False, help='Also write {out}.fastq with a Phred quality per base')
     p.add_argument('--qual_band', type=int, default=DEFAULT_BAND, help='Label positions either side of the basecall\'s frames that the quality lattice admits (<= 0: no band)')
     p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
+    p.add_argument('--recurrence', choices=['f32', 'bf16x3'], default='f32', help=RECURRENCE_HELP)
     p.add_argument('--gpus', type=int, default=None,
                    help='Stream the reads through devices 0 .. N-1 (0: every visible device): files are read by --readers threads in chunks, '
                         'filtered and scaled on the device, and records are appended as chunks complete. Without it: one device, every file parsed first')
@@ -130,6 +134,7 @@ def build_parser():
     p.add_argument('--method', default='envelope', help=argparse.SUPPRESS)
     p.add_argument('--threads', type=int, default=1, help=argparse.SUPPRESS)
     p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
+    p.add_argument('--recurrence', choices=['f32', 'bf16x3'], default='f32', help=RECURRENCE_HELP)
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="pair-basecall")
 

@@ -172,6 +172,9 @@ PROTOTYPES = {
     "po_set_call_precision": (C.c_int, [C.c_int]),
     "po_get_call_precision": (C.c_int, []),
     "po_gru_proj_h": (C.c_int, [_vp, C.c_int64, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]),
+    "po_set_recur_precision": (C.c_int, [C.c_int]),
+    "po_get_recur_precision": (C.c_int, []),
+    "po_gru_recur_h": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     "po_signal_prep_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _vp, _i64p, _vp,
                                    C.POINTER(C.c_float)]),
     "po_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
@@ -416,6 +419,42 @@ def call_precision(name):
         yield
     finally:
         lib.po_set_call_precision(before)
+
+
+RECUR_PRECISIONS = {"f32": 0, "bf16x3": 1}
+
+
+def _recur_code(name):
+    if name not in RECUR_PRECISIONS:
+        raise ValueError("recurrence precision %r (one of %s)" % (name, ", ".join(RECUR_PRECISIONS)))
+    return RECUR_PRECISIONS[name]
+
+
+def set_recur_precision(name="f32"):
+    """po_set_recur_precision: the product h·U of the network's GRU recurrence — "f32" (default) or "bf16x3" (h and U each
+    split in two bf16 values, three bf16 products with f32 sums; logits stay within the f32 path's bound).
+    Independent of set_call_precision.  Process-wide: prefer recur_precision() or the recurrence= keyword of forward /
+    basecall_signals / pair_basecall_signals, which restore it."""
+    code = _recur_code(name)
+    check(load(False).po_set_recur_precision(code), "po_set_recur_precision")
+
+
+def get_recur_precision():
+    return {v: k for k, v in RECUR_PRECISIONS.items()}[int(load(False).po_get_recur_precision())]
+
+
+@contextlib.contextmanager
+def recur_precision(name):
+    """the engine calls of the block run under recurrence precision `name`; the previous one is back afterwards, whatever
+    happens"""
+    code = _recur_code(name)
+    lib = load(False)
+    before = int(lib.po_get_recur_precision())
+    check(lib.po_set_recur_precision(code), "po_set_recur_precision")
+    try:
+        yield
+    finally:
+        lib.po_set_recur_precision(before)
 
 
 def set_reg_fixed_shape(on=True):

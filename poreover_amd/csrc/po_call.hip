@@ -1,6 +1,8 @@
 // The basecalling network's forward pass (`poreover call`) on the device, in f32 throughout by default; under
 // po_set_call_precision(PO_CALL_BF16) the GRU input projections alone take bf16 operands (f32 products and sums): the two
-// kernels of po_call_bf16.h in place of gru_proj_kernel.  No fp16, no bf16 anywhere else.
+// kernels of po_call_bf16.h in place of gru_proj_kernel; under po_set_recur_precision(PO_RECUR_BF16X3) the recurrence's h·U
+// alone is three bf16 products of split operands with f32 sums: gru_recur_x3_kernel of po_call_recur_bf16.h in place of
+// gru_recur_kernel.  The two selectors are independent.  No fp16, no bf16 anywhere else.
 //
 // Replaces, from network/network.py of the reference: the Keras models of build_model (network.py:15-55: bigru3,
 // conv1_bigru3, conv2_bigru3, conv1_gru5) run by call_helper (network.py:253-282) on windows of the scaled signal, and
@@ -15,6 +17,8 @@
 //                      128 in steps of 16, one instantiation each) own 16 hidden units each and keep their 48 columns
 //                      of U (H x 48 f32 = 3H/4 VGPRs per lane, 96 at H = 128) in registers for the whole walk; h_t goes
 //                      through LDS (double buffered: one barrier per step)
+//   gru_recur_x3_kernel  the same launch under PO_RECUR_BF16X3: U split in two bf16 B fragments per lane, h_t through LDS as
+//                      two bf16 arrays, 36 v_mfma_f32_16x16x32_bf16 per step for 96 of the f32 form (po_call_recur_bf16.h)
 //   dense_softmax_kernel  Dense(5) + softmax, one lane per frame
 //
 // Keras' GRU (reset_after = True), gates in the order z, r, h:
@@ -30,6 +34,7 @@
 
 #include "po_call_kernels.h"
 #include "po_call_bf16.h"
+#include "po_call_recur_bf16.h"
 
 #include "po_host.h"
 #include "po_internal.h"
@@ -37,6 +42,7 @@
 namespace {
 
 std::atomic<int> g_precision{PO_CALL_F32};   // po_set_call_precision: process-wide, read once per po_call_batch call
+std::atomic<int> g_recur{PO_RECUR_F32};      // po_set_recur_precision: the same
 
 // room for the bf16 copy of a GRU layer's input kernels: the largest layer's (a layer's copy is made in its own stage)
 size_t wb_bytes_for(const po_call_layer* L, int nl) {
@@ -77,6 +83,16 @@ int po_set_call_precision(int precision) {
 
 int po_get_call_precision(void) { return g_precision.load(); }
 
+int po_set_recur_precision(int precision) {
+    if (precision != PO_RECUR_F32 && precision != PO_RECUR_BF16X3)
+        return po_fail(PO_E_ARG, "po_set_recur_precision: precision " + std::to_string(precision) +
+                       " (PO_RECUR_F32 or PO_RECUR_BF16X3)");
+    g_recur.store(precision);
+    return PO_OK;
+}
+
+int po_get_recur_precision(void) { return g_recur.load(); }
+
 int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers_h, int n_layers, const float* weights,
                   int64_t n_weights, float* probs, float* logits, void* ws, size_t ws_bytes, void* stream_,
                   float* stage_ms_h) {
@@ -89,6 +105,7 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
     if (nw != n_weights) return po_fail(PO_E_ARG, "po_call_batch: the model has " + std::to_string(nw) + " weights, " +
                                         std::to_string(n_weights) + " given");
     const bool bf16 = g_precision.load() == PO_CALL_BF16;   // (a mode set after the size query finds the workspace too small)
+    const int recur = g_recur.load();
     if (bf16 && (rc0 = check_bf16_units(units, "po_call_batch")) != PO_OK) return rc0;
     if (n == 0) return PO_OK;
     const int64_t M = (int64_t)n * T;
@@ -162,8 +179,7 @@ int po_call_batch(const float* signal, int n, int T, const po_call_layer* layers
             ra.n = n;
             ra.T = T;
             if ((rc = begin(2)) != PO_OK) break;
-            PO_FOR_UNITS(H, hipLaunchKernelGGL(gru_recur_kernel<HH>, dim3((unsigned)((n + RT - 1) / RT), (unsigned)nd),
-                                               dim3(HH * 4), 0, stream, ra));
+            launch_gru_recur(stream, H, nd, ra, recur, nullptr);
             rc = end();
             w += nd * per_dir;
         }
@@ -259,6 +275,52 @@ int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w
     PO_HIPCHK(hipGetLastError());
     PO_HIPCHK(hipDeviceSynchronize());
     PO_HIPCHK(dP.down(P_h, (size_t)ndir * M * G * 4));
+    return PO_OK;
+}
+
+int po_gru_recur_h(const float* P_h, const float* U_h, const float* brec_h, int n, int T, int H, int kind, int precision,
+                   float* out_h, float* rec_h) {
+    const std::string me = "po_gru_recur_h: ";
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (!P_h || !U_h || !brec_h || !out_h)
+        return po_fail(PO_E_ARG, me + "null argument " + (!P_h ? "P_h" : !U_h ? "U_h" : !brec_h ? "brec_h" : "out_h"));
+    if (n < 0) return po_fail(PO_E_ARG, me + "n " + std::to_string(n));
+    if (T < 1) return po_fail(PO_E_ARG, me + "T " + std::to_string(T) + " (at least 1)");
+    if (H < 16 || H > H_MAX || H % 16 != 0)
+        return po_fail(PO_E_ARG, me + "H " + std::to_string(H) + " units (16, 32, 48, 64, 80, 96, 112 or 128)");
+    if (kind != PO_CALL_BIGRU && kind != PO_CALL_GRU && kind != PO_CALL_GRU_BACK)
+        return po_fail(PO_E_ARG, me + "kind " + std::to_string(kind) + " (PO_CALL_BIGRU, PO_CALL_GRU or PO_CALL_GRU_BACK)");
+    if (precision != PO_RECUR_F32 && precision != PO_RECUR_BF16X3)
+        return po_fail(PO_E_ARG, me + "precision " + std::to_string(precision) + " (PO_RECUR_F32 or PO_RECUR_BF16X3)");
+    if (n == 0) return PO_OK;
+    const int nd = kind == PO_CALL_BIGRU ? 2 : 1, G = 3 * H;
+    const int64_t M = (int64_t)n * T;
+    PoDev dP, dU, db, dout, drec;   // (drec stays NULL without a rec output)
+    PO_HIPCHK(dP.up(P_h, (size_t)nd * M * G * 4));
+    PO_HIPCHK(dU.up(U_h, (size_t)nd * H * G * 4));
+    PO_HIPCHK(db.up(brec_h, (size_t)nd * G * 4));
+    PO_HIPCHK(dout.up(nullptr, (size_t)M * nd * H * 4));
+    if (rec_h) PO_HIPCHK(drec.up(nullptr, (size_t)nd * M * G * 4));
+    RecurArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    for (int d = 0; d < nd; ++d) {   // (as po_call_batch fills it)
+        ra.dir[d].P = dP.as<float>() + (int64_t)d * M * G;
+        ra.dir[d].U = dU.as<float>() + (int64_t)d * H * G;
+        ra.dir[d].brec = db.as<float>() + (int64_t)d * G;
+        ra.dir[d].backward = (d == 1 || kind == PO_CALL_GRU_BACK) ? 1 : 0;
+        ra.dir[d].rev_out = kind == PO_CALL_GRU_BACK ? 1 : 0;
+        ra.dir[d].col = d * H;
+    }
+    ra.out = dout.as<float>();
+    ra.out_stride = nd * H;
+    ra.n = n;
+    ra.T = T;
+    launch_gru_recur(nullptr, H, nd, ra, precision, rec_h ? drec.as<float>() : nullptr);
+    PO_HIPCHK(hipGetLastError());
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(dout.down(out_h, (size_t)M * nd * H * 4));
+    if (rec_h) PO_HIPCHK(drec.down(rec_h, (size_t)nd * M * G * 4));
     return PO_OK;
 }
 

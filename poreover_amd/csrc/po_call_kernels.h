@@ -117,10 +117,23 @@ __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-
 // workgroup's direction) at row
 // w * T + s: z, r, h~, u_h = h_prev·U_h + b_rec,h and h_prev, H values each, in this order (rows of SV = 5 H)
 enum { SV_Z = 0, SV_R = 1, SV_HH = 2, SV_UH = 3, SV_HP = 4, SV_N = 5 };
+
+// The gates of one (window, unit) element of a step, for both recurrence kernels (this file's f32 one and
+// po_call_recur_bf16.h's): px its input projections x_z, x_r, x_h; az, ar, ah its element of h_prev·U per gate; br the
+// recurrent bias; h its previous state.  z, rg, hh (h~) and the new state hn come back.
+__device__ __forceinline__ void gru_gates(const float (&px)[3], float az, float ar, float ah, const float (&br)[3], float h,
+                                          float& z, float& rg, float& hh, float& hn) {
+    z = sigmoidf_(px[0] + (az + br[0]));
+    rg = sigmoidf_(px[1] + (ar + br[1]));
+    hh = tanhf(px[2] + rg * (ah + br[2]));
+    hn = z * h + (1.f - z) * hh;
+}
+
 // A workgroup of H / 16 waves, 16 units each; hs: h_t in LDS at a row stride of H + 1 (one pad word: the 16 rows of an
-// MFMA operand hit distinct banks)
-template <int H, bool SAVE>
-__device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (&hs)[2][RT][H + 1]) {
+// MFMA operand hit distinct banks).  REC (the stage entry po_gru_recur_h alone): also write the recurrent pre-activations
+// h_prev·U + b_rec to rec[((d * n + w) * T + t) * 3 H + g * H + unit], d this workgroup's direction, t the frame the step consumed.
+template <int H, bool SAVE, bool REC = false>
+__device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (&hs)[2][RT][H + 1], float* rec = nullptr) {
     constexpr int G = 3 * H, HS = H + 1, SV = SV_N * H;
     const RecurDir D = a.dir[blockIdx.y];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -171,10 +184,8 @@ __device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float z = sigmoidf_(px[r][0] + (acc[0][r] + br[0]));
-            const float rg = sigmoidf_(px[r][1] + (acc[1][r] + br[1]));
-            const float hh = tanhf(px[r][2] + rg * (acc[2][r] + br[2]));
-            const float hn = z * h[r] + (1.f - z) * hh;
+            float z, rg, hh, hn;
+            gru_gates(px[r], acc[0][r], acc[1][r], acc[2][r], br, h[r], z, rg, hh, hn);
             if (SAVE && live[r]) {
                 float* sv = save + ((int64_t)(w0 + kq * 4 + r) * T + s) * SV + unit;
                 sv[SV_Z * H] = z;
@@ -182,6 +193,11 @@ __device__ __forceinline__ void gru_recur_body(RecurArgs a, float* save, float (
                 sv[SV_HH * H] = hh;
                 sv[SV_UH * H] = acc[2][r] + br[2];
                 sv[SV_HP * H] = h[r];
+            }
+            if (REC && live[r]) {
+                float* rv = rec + (((int64_t)blockIdx.y * a.n + w0 + kq * 4 + r) * T + t) * G + unit;
+#pragma unroll
+                for (int g = 0; g < 3; ++g) rv[g * H] = acc[g][r] + br[g];
             }
             if (live[r]) {
                 h[r] = hn;
@@ -197,6 +213,13 @@ template <int H>
 __global__ __launch_bounds__(H * 4) void gru_recur_kernel(RecurArgs a) {
     __shared__ float hs[2][RT][H + 1];
     gru_recur_body<H, false>(a, nullptr, hs);
+}
+
+// gru_recur_kernel that also stores the recurrent pre-activations (REC) to rec[nd][n * T][3 H]
+template <int H>
+__global__ __launch_bounds__(H * 4) void gru_recur_rec_kernel(RecurArgs a, float* rec) {
+    __shared__ float hs[2][RT][H + 1];
+    gru_recur_body<H, false, true>(a, nullptr, hs, rec);
 }
 
 // STMT with `HH` the compile-time constant equal to H_, one of the supported widths (check_model has refused the others)

@@ -102,7 +102,7 @@ def _qual_rows_bytes(lib, n, total, longest, model):
 
 
 def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, want_logits=False, want_odds=False,
-                want_guides=False, stage_ms=None, max_windows_per_pass=0, precision="f32"):
+                want_guides=False, stage_ms=None, max_windows_per_pass=0, precision="f32", recurrence="f32"):
     """One po_basecall_fastq_batch_h call.  Returns a dict: strings, quals (uint8 Phred arrays), qual_status int32 (n,),
     and where asked for logits, odds (float64 (L, 5) per read) and guides (int32 (T,) per read; None for band <= 0)."""
     n = len(sigs)
@@ -120,7 +120,7 @@ def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, 
     od = np.zeros((rows, 5), dtype=np.float64) if want_odds else None
     gd = np.zeros(rows, dtype=np.int32) if want_guides and band > 0 else None
     ms = (C.c_float * 8)() if stage_ms is not None else None
-    with _lib.call_precision(precision):
+    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
         rc = lib.po_basecall_fastq_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
                                            w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
                                            seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
@@ -144,7 +144,7 @@ def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, 
 
 
 def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass,
-                 precision="f32"):
+                 precision="f32", recurrence="f32"):
     n = len(sigs)
     off = _marshal.offsets([len(s) for s in sigs])
     rows = int(off[-1])
@@ -156,7 +156,7 @@ def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_
     st = np.zeros(n, dtype=np.int32)
     lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
     ms = (C.c_float * 6)() if stage_ms is not None else None
-    with _lib.call_precision(precision):
+    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
         rc = lib.po_basecall_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
                                      w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
                                      seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
@@ -366,14 +366,16 @@ def _decoder_args(algorithm, beam_width, merge_repeats, what):
 
 def basecall_raw(net, raws, channels=None, scaling="standard", devices=(0,), window=1000, overlap=0, algorithm="viterbi",
                  beam_width=25, merge_repeats=False, logits=False, max_windows_per_pass=0, qualities=False, qual_band=None,
-                 precision="f32", lo=200, hi=800, resident_bytes=None, worker_stats=None, engines=None):
+                 precision="f32", lo=200, hi=800, resident_bytes=None, worker_stats=None, engines=None, recurrence="f32"):
     """basecall_signals(..., devices=devices) from RAW int16 reads: the abasic filter (lo < x < hi) and `scaling` run on the
     device (po_signal_prep_h's rule) inside the engine's groups.  channels: per read (offset, digitisation,
     range), read for scaling "current" alone.  Returns what basecall_signals returns; a read's logits have one row per KEPT
     sample, and a read that keeps nothing gets "".  worker_stats (a list) gets Basecaller.stats() of every run appended.
     engines (a dict the caller keeps, then closes with close_engines): the engines are made once and serve every later call
-    with the same dict — the same net, devices and options are the caller's to keep."""
+    with the same dict — the same net, devices and options are the caller's to keep.  precision and recurrence as
+    basecall_signals'."""
     _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
     kind, model, bw = _decoder_args(algorithm, beam_width, merge_repeats, "basecall_raw")
     window_plan(1, window, overlap)
     check_time_order(net.kinds)
@@ -399,7 +401,7 @@ def basecall_raw(net, raws, channels=None, scaling="standard", devices=(0,), win
         return eng.run_raw([raws[k] for k in reads], [channels[k][0] for k in reads] if cur else None,
                            [channels[k][1] / channels[k][2] for k in reads] if cur else None, want_logits)
 
-    with _lib.call_precision(precision):
+    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
         return _stream(make, run, len(raws), todo, logits, qualities, band, empty, worker_stats, engines)
 
 
@@ -411,7 +413,7 @@ def close_engines(engines):
 
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
                      logits=False, stage_ms=None, max_windows_per_pass=0, qualities=False, qual_band=None, precision="f32",
-                     devices=None, resident_bytes=None, worker_stats=None, engines=None):
+                     devices=None, resident_bytes=None, worker_stats=None, engines=None, recurrence="f32"):
     """The decoded string of each scaled signal, in input order — or (string, (len(s), 5) float32 stitched logits) with
     logits=True.  qualities=True adds a uint8 (len(string),) array of Phred values as the last item: (string, q) or
     (string, logits, q), from the quality lattice (poreover_amd.quality) within qual_band label positions of the call's
@@ -424,12 +426,14 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     input order, of at most RESIDENT_BYTES // (resident bytes per sample) samples — a single longer read goes alone;
     stage_ms (a dict) gets the device milliseconds per stage added (_lib.BASECALL_STAGES; with qualities
     _lib.BASECALL_FASTQ_STAGES).  precision "f32" or "bf16": the GRU input projections' operands
-    (_lib.set_call_precision), set around each engine call made here and restored after it.
+    (_lib.set_call_precision), set around each engine call made here and restored after it; recurrence "f32" or "bf16x3":
+    the recurrence's product h·U (_lib.set_recur_precision), handled the same way and independent of precision.
     devices (a list; None: the path above on the current device): the reads go through a Basecaller over those devices
      in groups of at most resident_bytes (None: RESIDENT_BYTES) of per-sample state — the same strings,
     logits and qualities; stage_ms is not filled on this route; worker_stats (a list) gets Basecaller.stats() appended;
     engines (a dict the caller keeps and closes with close_engines): the engines outlive the call, as for basecall_raw."""
     _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
     if algorithm not in ("viterbi", "beam"):
         raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
     if algorithm == "beam" and not 1 <= beam_width <= 64:
@@ -454,14 +458,14 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
         rb = RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
         make = lambda fastq, band_: Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band_,
                                                resident_bytes=rb)
-        with _lib.call_precision(precision):
+        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
             return _stream(make, lambda eng, reads, want: eng.run_f32([sigs[k] for k in reads], want), len(sigs), todo, logits,
                            qualities, quality.DEFAULT_BAND if qual_band is None else int(qual_band), empty, worker_stats, engines)
     if not qualities:
         budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
         for group in _groups(todo, lens, lambda n, total, longest: total <= budget):
             res = _engine_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, logits, stage_ms,
-                               max_windows_per_pass, precision=precision)
+                               max_windows_per_pass, precision=precision, recurrence=recurrence)
             for k, r in zip(group, res):
                 out[k] = r
         return out
@@ -478,7 +482,8 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     def run(reads, band_, want_logits):
         for group in _groups(reads, lens, fits(band_)):
             r = _fastq_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, band_, want_logits=want_logits,
-                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass, precision=precision)
+                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass, precision=precision,
+                            recurrence=recurrence)
             for j, k in enumerate(group):
                 yield k, r, j
 
@@ -530,7 +535,8 @@ def basecall(args):
     fastq = bool(getattr(args, "fastq", False))
     seqs = basecall_signals(net, [s for _, s in parsed], window=args.window, overlap=args.overlap, algorithm=args.algorithm,
                             beam_width=args.beam_width, merge_repeats=args.merge_repeats, qualities=fastq,
-                            qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"))
+                            qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"),
+                            recurrence=getattr(args, "recurrence", "f32"))
     quals = [q for _, q in seqs] if fastq else None
     seqs = [s for s, _ in seqs] if fastq else seqs
     names = []
@@ -586,7 +592,7 @@ def _basecall_stream(args, net, files, devices):
                                        devices=devices, window=args.window, overlap=args.overlap, algorithm=args.algorithm,
                                        beam_width=args.beam_width, merge_repeats=args.merge_repeats, qualities=fastq,
                                        qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"),
-                                       engines=engines)
+                                       recurrence=getattr(args, "recurrence", "f32"), engines=engines)
                     for i, r in zip(idx, res):
                         rid = parsed[i][0]
                         name = (rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid)) if args.use_id \

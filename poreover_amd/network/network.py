@@ -18,7 +18,7 @@ from ..decoding import hdf5_lite
 from . import checkpoint as ckpt
 
 __all__ = ["parse_fast5", "read_fast5_raw", "prep_signals", "PREP_STATS", "batch_input", "forward", "basecall_signals", "call_helper", "call", "load_model", "round_bf16",
-           "gru_proj", "gru_wgrad", "gru_dx"]
+           "gru_proj", "gru_wgrad", "gru_dx", "split_bf16", "gru_recur"]
 
 SCALINGS = ("standard", "current", "median", "rescale", "raw")
 
@@ -138,6 +138,46 @@ def round_bf16(a):
     return r.view(np.float32).reshape(np.shape(a))
 
 
+def split_bf16(a):
+    """(hi, lo), both float32 holding bfloat16 values: hi = round_bf16(a), lo = round_bf16(a - hi) — po_bf16_split of
+    csrc/po_bf16_rules.h.  a - hi is exact in float32, so hi + lo is `a` to 2^-16, relatively.  Where hi is not finite (NaN,
+    +-inf, an overflowing rounding) lo is +0.  What `--recurrence bf16x3` does to both operands of h·U."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    hi = round_bf16(a)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lo = round_bf16(a - hi)
+    lo = np.where(np.isfinite(hi), lo, np.float32(0.0)).astype(np.float32)
+    return hi, lo.reshape(np.shape(a))
+
+
+_RECUR_KINDS = {"bigru": 2, "gru": 1, "gru_back": 1}
+
+
+def gru_recur(P, U, brec, kind, precision="f32", return_rec=False):
+    """The GRU recurrence stage alone on the device (po_gru_recur_h): P (ndir, n, T, 3H) the input projections, U (ndir, H,
+    3H), brec (ndir, 3H), kind "bigru" (ndir 2), "gru" or "gru_back" (ndir 1) -> out (n, T, ndir * H) float32 as the layer
+    lays it out, by the kernel of `precision` ("f32" or "bf16x3"; the selector is not read); with return_rec=True also rec
+    (ndir, n, T, 3H) = h_prev·U + brec of every step, at the frame the step consumed"""
+    code = _lib._recur_code(precision)
+    if kind not in _RECUR_KINDS:
+        raise ValueError("gru_recur: kind %r (one of %s)" % (kind, ", ".join(_RECUR_KINDS)))
+    lib = _lib.load()
+    P = np.ascontiguousarray(P, dtype=np.float32)
+    U = np.ascontiguousarray(U, dtype=np.float32)
+    b = np.ascontiguousarray(brec, dtype=np.float32)
+    nd = _RECUR_KINDS[kind]
+    if P.ndim != 4 or U.ndim != 3 or P.shape[0] != nd or U.shape[0] != nd or U.shape[2] != 3 * U.shape[1] or \
+            P.shape[3] != U.shape[2] or b.shape != (nd, U.shape[2]):
+        raise ValueError("gru_recur: P (ndir, n, T, 3H), U (ndir, H, 3H), brec (ndir, 3H), ndir %d for %s; got %s, %s, %s"
+                         % (nd, kind, P.shape, U.shape, b.shape))
+    n, T, H = P.shape[1], P.shape[2], U.shape[1]
+    out = np.empty((n, T, nd * H), dtype=np.float32)
+    rec = np.empty((nd, n, T, 3 * H), dtype=np.float32) if return_rec else None
+    _lib.check(lib.po_gru_recur_h(P.ctypes.data, U.ctypes.data, b.ctypes.data, n, T, H, _lib.CALL_KINDS[kind], code,
+                                  out.ctypes.data, rec.ctypes.data if return_rec else None), "po_gru_recur_h")
+    return (out, rec) if return_rec else out
+
+
 def gru_proj(x, W, b_in, precision="f32"):
     """The GRU input projection stage alone on the device (po_gru_proj_h): x (M, cin), W (ndir, cin, 384), b_in (ndir, 384)
     -> P (ndir, M, 384) float32 = x @ W[d] + b_in[d], by the kernels of `precision`"""
@@ -190,11 +230,13 @@ def gru_dx(dA, W, precision="f32"):
     return dX
 
 
-def forward(net, windows, logits=False, stage_ms=None, precision="f32"):
+def forward(net, windows, logits=False, stage_ms=None, precision="f32", recurrence="f32"):
     """softmax probabilities (n, T, 5) float32 of `windows` (n, T) through `net` on the device; with logits=True also the
     Dense outputs; stage_ms (a dict) gets the device milliseconds per stage added (_lib.CALL_STAGES); precision "f32" or
-    "bf16" (_lib.set_call_precision; set for this call alone)"""
+    "bf16" (_lib.set_call_precision) and recurrence "f32" or "bf16x3" (_lib.set_recur_precision), each set for this call
+    alone"""
     _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
     lib = _lib.load()
     x = np.ascontiguousarray(windows, dtype=np.float32)
     n, T = x.shape
@@ -202,7 +244,7 @@ def forward(net, windows, logits=False, stage_ms=None, precision="f32"):
     probs = np.empty((n, T, ckpt.NUM_LABELS), dtype=np.float32)
     lg = np.empty_like(probs) if logits else None
     ms = (C.c_float * 4)() if stage_ms is not None else None
-    with _lib.call_precision(precision):
+    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
         rc = lib.po_call_batch_h(x.ctypes.data, n, T, _layers_array(net), len(net.layers), w.ctypes.data, w.size,
                                  probs.ctypes.data, lg.ctypes.data if logits else None, ms)
         _lib.check(rc, "po_call_batch_h")
@@ -212,10 +254,12 @@ def forward(net, windows, logits=False, stage_ms=None, precision="f32"):
     return (probs, lg) if logits else probs
 
 
-def basecall_signals(net, signals, window=1000, no_stack=False, logits=False, precision="f32"):
+def basecall_signals(net, signals, window=1000, no_stack=False, logits=False, precision="f32", recurrence="f32"):
     """[(len(s), 5) float32 probabilities] for each scaled signal: all reads' windows in shared device passes (windows
     of one length go together; --no_stack: each read is one window of its own length, reads of equal length together);
-    precision as forward's"""
+    precision and recurrence as forward's"""
+    _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
     groups = {}
     for i, s in enumerate(signals):
         T = max(1, len(s)) if no_stack else window
@@ -223,7 +267,7 @@ def basecall_signals(net, signals, window=1000, no_stack=False, logits=False, pr
     out = [None] * len(signals)
     for T, idx in groups.items():
         parts = [batch_input(signals[i], T) for i in idx]
-        res = forward(net, np.concatenate([p[0] for p in parts]), logits=logits, precision=precision)
+        res = forward(net, np.concatenate([p[0] for p in parts]), logits=logits, precision=precision, recurrence=recurrence)
         pr, lg = res if logits else (res, None)
         k = 0
         for i, (wins, frames) in zip(idx, parts):
@@ -261,7 +305,7 @@ def call_helper(args, model, files=None):
     files = [getattr(args, "in")] if files is None else files
     parsed = [parse_fast5(f, scaling=args.scaling) for f in files]
     probs = basecall_signals(model, [s for _, s in parsed], window=args.window, no_stack=getattr(args, "no_stack", False),
-                             precision=getattr(args, "precision", "f32"))
+                             precision=getattr(args, "precision", "f32"), recurrence=getattr(args, "recurrence", "f32"))
     return [_write(args, f, rid, p) for f, (rid, _), p in zip(files, parsed, probs)]
 
 

@@ -148,7 +148,7 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
 def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
                           beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
                           diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32",
-                          qualities=False, qual_band=None, odds=False):
+                          qualities=False, qual_band=None, odds=False, recurrence="f32"):
     """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
     batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
     consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
@@ -157,7 +157,8 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     merge_repeats: the decoders of a network trained with ctc_merge_repeated.  window / overlap as basecall_signals;
     method "row_col", "row" or "grid" is the pair beam search's.  Pairs go to the engine in groups (pair_groups), in input
     order; stage_ms (a dict) gets the device milliseconds per stage added (_lib.PAIR_BASECALL_STAGES).  precision "f32" or
-    "bf16": the GRU input projections' operands (_lib.set_call_precision), set for the engine calls made here alone.
+    "bf16": the GRU input projections' operands (_lib.set_call_precision), set for the engine calls made here alone;
+    recurrence "f32" or "bf16x3": the recurrence's product h·U (_lib.set_recur_precision), handled the same way.
     qualities=True (po_pair_basecall_fastq_batch_h instead of po_pair_basecall_batch_h): the record of a
     decoded pair gains qual1, qual2 (FASTQ quality strings of seq1 and seq2, None where the record has no 1-D call: the
     diagonal envelope), qual (the consensus') and qual_status (four ints: seq1, seq2, the consensus on read 1's table and
@@ -168,6 +169,7 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     unscored gets Q 0 (the consensus: the other table's evidence alone) and a line in the log (quality.warn_unscored).
     The records of pairs that are not decoded are unchanged; stage_ms then has _lib.PAIR_BASECALL_FASTQ_STAGES."""
     _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
     if not qualities and (qual_band is not None or odds):
         raise ValueError("pair_basecall_signals: qual_band and odds are options of qualities=True")
     if qualities:
@@ -213,7 +215,7 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
                 reads = sorted({r for k in group for r in pairs[k]})
                 local = {r: j for j, r in enumerate(reads)}
                 fastq = None if band_ is None else {"band": band_, "odds": odds, "flags": [flags[k] for k in group] if flags else None}
-                with _lib.call_precision(precision):
+                with _lib.call_precision(precision), _lib.recur_precision(recurrence):
                     res = _engine_call(lib, net, [sigs[r] for r in reads],
                                        [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
                                        reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass, fastq=fastq)
@@ -323,7 +325,8 @@ def pair_basecall(args):
                                 reverse_complement=args.reverse_complement, merge_repeats=args.merge_repeats,
                                 beam_width=args.beam_width, method=args.beam_search_method, padding=args.padding,
                                 alignment=args.alignment, diagonal_envelope=args.diagonal_envelope,
-                                diagonal_width=args.diagonal_width, precision=getattr(args, "precision", "f32"))
+                                diagonal_width=args.diagonal_width, precision=getattr(args, "precision", "f32"),
+                                recurrence=getattr(args, "recurrence", "f32"))
     records = [_pd.pair_record(p, Path(order[a]).stem, Path(order[b]).stem, r, args) for p, (a, b), r in zip(names, pairs, res)]
     _pd.write_pair_files(records, args)
     return records

@@ -7,8 +7,10 @@ routes alternating; device milliseconds per stage of the fused call from events.
 
     python scripts/bench_basecall.py [--arch conv1_bigru3] [--reads 256] [--samples 8000] [--window 1000] [--overlap 200]
                                      [--algorithm viterbi] [--beam_width 25] [--steps 5] [--warmup 2] [--precision f32]
+                                     [--recurrence f32]
 
---precision bf16 runs every route with bf16 GRU input projections and adds the share of reads whose string is the f32 run's.
+--precision bf16 runs every route with bf16 GRU input projections and adds the share of reads whose string is the f32 run's;
+--recurrence bf16x3 does the same with the three-product recurrence (the two combine).
 """
 import argparse
 import json
@@ -38,6 +40,7 @@ def main():
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--precision", default="f32", choices=["f32", "bf16"])
+    p.add_argument("--recurrence", default="f32", choices=["f32", "bf16x3"])
     a = p.parse_args()
     _lib.load()   # no device: fail here, not after the set-up
     cfg = C.ARCHITECTURES[a.arch]()
@@ -50,10 +53,10 @@ def main():
 
     def fused(overlap, ms=None):
         return B.basecall_signals(net, sigs, window=a.window, overlap=overlap, algorithm=a.algorithm,
-                                  beam_width=a.beam_width, stage_ms=ms, precision=a.precision)
+                                  beam_width=a.beam_width, stage_ms=ms, precision=a.precision, recurrence=a.recurrence)
 
     def two_calls():
-        probs = N.basecall_signals(net, sigs, window=a.window, precision=a.precision)
+        probs = N.basecall_signals(net, sigs, window=a.window, precision=a.precision, recurrence=a.recurrence)
         with np.errstate(divide="ignore"):
             tables = [np.log(pr).astype(np.float64) for pr in probs]
         return batch.decode_1d_batch(tables, "poreover", a.algorithm, a.beam_width)
@@ -74,8 +77,9 @@ def main():
     res = {"arch": a.arch, "reads": a.reads, "samples_per_read": a.samples, "window": a.window, "overlap": a.overlap,
            "algorithm": a.algorithm, "steps": a.steps,
            "strings_differ_fused0_vs_two_calls": sum(x != y for x, y in zip(out["fused_overlap_0"], out["two_calls"]))}
-    if a.precision != "f32":      # (the default output keeps its keys)
+    if a.precision != "f32" or a.recurrence != "f32":      # (the default output keeps its keys)
         res["precision"] = a.precision
+        res["recurrence"] = a.recurrence
         f32 = B.basecall_signals(net, sigs, window=a.window, overlap=0, algorithm=a.algorithm, beam_width=a.beam_width)
         res["strings_identical_to_f32_share"] = sum(x == y for x, y in zip(out["fused_overlap_0"], f32)) / len(f32)
     for name, _ in routes:

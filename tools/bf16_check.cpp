@@ -9,6 +9,11 @@
 //   every exponent 0..254 (subnormals included) x the tie patterns and their neighbours in the discarded half x kept parts of
 //   both parities x both signs; NaN payloads (quiet and signalling, both signs); +-inf, +-0, +-FLT_MAX; 2^22 pseudo-random
 //   patterns; every array in a heap block of exactly its size
+//
+// The split of `--recurrence bf16x3` (po_bf16_split) is held against its own statement on the same patterns: hi is the rule's
+// rounding of f; f - hi is exact (the f32 difference equals the difference in double); lo is the rule's rounding of that
+// difference; hi + lo is within 2^-16 of f, relatively, wherever the remainder is zero or a normal bf16 value (|r| >= 2^-126);
+// NaN, +-inf, an overflowing rounding and +-0 behave as the rule's comment promises.
 #include "../poreover_amd/csrc/po_bf16_rules.h"
 
 #include <cfloat>
@@ -54,6 +59,34 @@ static void check_finite(uint32_t u) {
     if (po_bf16_from_f32(r) != got) fail("idempotence", u);
 }
 
+static void check_split(uint32_t u) {   // any pattern
+    float f;
+    std::memcpy(&f, &u, 4);
+    uint16_t hi = 0xdead, lo = 0xdead;
+    po_bf16_split(f, &hi, &lo);
+    ++checked;
+    if (hi != po_bf16_bits_from_f32_bits(u)) fail("split: hi is not the rule's rounding", u, hi);
+    if ((hi & 0x7f80) == 0x7f80) {   // NaN, inf, or a finite value that overflows: no remainder
+        if (lo != 0) fail("split: lo of a non-finite hi is not +0", u, hi, lo);
+        if ((u & 0x7fffffffu) > 0x7f800000u && (hi & 0x007f) == 0) fail("split: NaN became inf", u, hi);
+        return;
+    }
+    const double d = (double)f, dh = (double)po_f32_from_bf16(hi);
+    const float rf = f - po_f32_from_bf16(hi);
+    if ((double)rf != d - dh) fail("split: f - hi is not exact in f32", u, hi);
+    uint32_t rb;
+    std::memcpy(&rb, &rf, 4);
+    if (lo != brute(rb)) fail("split: lo is not the brute-force rounding of the remainder", u, lo, brute(rb));
+    if ((u & 0x7fffffffu) == 0) {   // +-0: hi keeps the sign, lo is +0
+        if (hi != (uint16_t)(u >> 16) || lo != 0) fail("split: zero", u, hi, lo);
+        return;
+    }
+    if (rf == 0.0f || std::fabs(rf) >= 0x1p-126f) {
+        const double sum = dh + (double)po_f32_from_bf16(lo);
+        if (std::fabs(sum - d) > std::ldexp(std::fabs(d), -16)) fail("split: hi + lo is further than 2^-16 from f", u, hi, lo);
+    }
+}
+
 int main() {
     // ---- every exponent x patterns of the discarded half x kept parts of both parities x both signs
     const std::vector<uint32_t> low = {0x0000, 0x0001, 0x7ffe, 0x7fff, 0x8000, 0x8001, 0x8002, 0xfffe, 0xffff, 0x4000, 0xc000};
@@ -62,6 +95,28 @@ int main() {
         for (uint32_t k : kept)
             for (uint32_t l : low)
                 for (uint32_t s = 0; s < 2; ++s) check_finite((s << 31) | (e << 23) | (k << 16) | l);
+    for (uint32_t e = 0; e <= 255; ++e)   // (255: inf and NaN patterns)
+        for (uint32_t k : kept)
+            for (uint32_t l : low)
+                for (uint32_t s = 0; s < 2; ++s) check_split((s << 31) | (e << 23) | (k << 16) | l);
+    // ---- the split by hand: 1 + 2^-8 is a tie for hi (down to 1, remainder 2^-8 exactly); 1 + 2^-9 + 2^-17 rounds down to 1 and
+    // its remainder 2^-9 (1 + 2^-8) is a tie for lo (down to 2^-9); 1 + 2^-9 + 3 2^-17 leaves 2^-9 (1 + 3 2^-8): a tie that goes up;
+    // 1 + 3 2^-8 goes up to 1 + 2^-6 and leaves -2^-8
+    struct { float in, hi, lo; } split[] = {
+        {1.0f + 0x1p-8f, 1.0f, 0x1p-8f}, {1.0f + 0x1p-9f + 0x1p-17f, 1.0f, 0x1p-9f},
+        {1.0f + 0x1p-9f + 3 * 0x1p-17f, 1.0f, 0x1p-9f * (1.0f + 0x1p-6f)}, {1.0f + 3 * 0x1p-8f, 1.0f + 0x1p-6f, -0x1p-8f},
+        {-(1.0f + 0x1p-9f + 0x1p-17f), -1.0f, -0x1p-9f}, {1.5f, 1.5f, 0.0f}, {0.0f, 0.0f, 0.0f}, {-0.0f, -0.0f, 0.0f},
+        {INFINITY, INFINITY, 0.0f}, {-INFINITY, -INFINITY, 0.0f}, {FLT_MAX, INFINITY, 0.0f}, {-FLT_MAX, -INFINITY, 0.0f}};
+    for (const auto& h : split) {
+        uint16_t hi, lo;
+        po_bf16_split(h.in, &hi, &lo);
+        const float fh = po_f32_from_bf16(hi), fl = po_f32_from_bf16(lo);
+        if (std::memcmp(&fh, &h.hi, 4) != 0 || std::memcmp(&fl, &h.lo, 4) != 0) {
+            uint32_t a;
+            std::memcpy(&a, &h.in, 4);
+            fail("split hand vector", a, hi, lo);
+        }
+    }
     // ---- hand vectors
     struct { float in, out; } hand[] = {
         {1.0f + 0x1p-8f, 1.0f}, {1.0f + 3 * 0x1p-8f, 1.0f + 0x1p-6f}, {-(1.0f + 0x1p-8f), -1.0f},
@@ -109,6 +164,7 @@ int main() {
         std::memcpy(&u, &in[i], 4);
         ++checked;
         if (out[i] != brute(u)) fail("random pattern", u, out[i], brute(u));
+        if ((i & 3) == 0) check_split(u);
     }
     if (failures) {
         std::printf("%d failure(s)\n", failures);
