@@ -244,6 +244,10 @@ int po_envelope_batch(const char* aln1, const char* aln2, const int64_t* aln_off
  * env + 2 * env_off[i]; env == NULL: dense.  flavor 0 = Gamma.h arithmetic (logaddexp, -inf),
  * 1 = decoding_cy arithmetic (log(exp+exp), LOG_0 = -9999), 2 = decoding_cy.pair_gamma_log_envelope
  * (decoding_cy.pyx:224-271; envelope only: log(exp+exp), -inf defaults, cells [start, min(end, V-1)] computed).
+ * 3 = prefix_search.pair_gamma_log (prefix_search.py:35-65), the dense matrix of the reference's Python path: -inf defaults,
+ * the base sum log sum_c exp(y1[u][c] + y2[v][c]) shifted by its maximum as scipy.special.logsumexp shifts it (by 0 where the
+ * maximum is not finite), np.logaddexp.  Flavours 0 and 3 differ where every base sum of a cell is below exp's range (two
+ * log-probabilities that add up to less than about -745): flavour 0 then has log(0) = -inf, flavour 3 the value.
  * dense_out (optional): the full (U+1) x (V+1) gamma matrices at dense_out + dense_off[i] (-inf outside an envelope).  max_cells = largest per-pair number of
  * stored cells (sum over rows of end - start + 1), as used to size the workspace. */
 size_t po_pair_gamma_workspace_bytes(int n, int64_t max_cells, int64_t max_rows1, int64_t max_rows2);

@@ -1011,6 +1011,10 @@ static double pair_gamma_envelope_impl(const double* y1, const double* y2, const
 double oracle_pair_gamma_envelope(const double* y1, const double* y2, const int* env, int U, int V, int C) {
     return pair_gamma_envelope_impl(y1, y2, env, U, V, C, NULL);
 }
+/* the same DP, written out as the (U+1) x (V+1) matrix SparseMatrix::get shows: -inf outside the stored ranges */
+double oracle_pair_gamma_envelope_matrix(const double* y1, const double* y2, const int* env, int U, int V, int C, double* dense) {
+    return pair_gamma_envelope_impl(y1, y2, env, U, V, C, dense);
+}
 
 static double seq_logsumexp_shift(const double* a, int n, int stride) {
     /* scipy.special.logsumexp: max-shifted (summation order differs from numpy's pairwise

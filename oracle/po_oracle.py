@@ -84,6 +84,7 @@ def oracle_lib():
         L.oracle_logaddexp.argtypes = [C.c_double, C.c_double]
         L.oracle_forward.restype = C.c_double
         L.oracle_pair_gamma_envelope.restype = C.c_double
+        L.oracle_pair_gamma_envelope_matrix.restype = C.c_double
         _oracle = L
     return _oracle
 
@@ -166,10 +167,16 @@ def viterbi_acceptor(y_, label_, alphabet="ACGT", band_size=0):
     return path.astype(np.int64)
 
 
-def pair_gamma_log_envelope(y1_, y2_, envelope_inclusive):
+def pair_gamma_log_envelope(y1_, y2_, envelope_inclusive, return_matrix=False):
+    """gamma(0,0) of Gamma.h's envelope DP; return_matrix: the (U + 1, V + 1) matrix, -inf outside the stored ranges"""
     y1, y2 = _f64(y1_), _f64(y2_)
     U, V = y1.shape[0], y2.shape[0]
     env = _env(envelope_inclusive, U + 1)
+    if return_matrix:
+        g = np.zeros((U + 1, V + 1))
+        oracle_lib().oracle_pair_gamma_envelope_matrix(y1.ctypes.data_as(_dp), y2.ctypes.data_as(_dp), env.ctypes.data_as(_ip),
+                                                       U, V, y1.shape[1], g.ctypes.data_as(_dp))
+        return g
     return oracle_lib().oracle_pair_gamma_envelope(y1.ctypes.data_as(_dp), y2.ctypes.data_as(_dp),
                                                    env.ctypes.data_as(_ip), U, V, y1.shape[1])
 

@@ -358,7 +358,8 @@ def pair_gamma_batch(arrays1, arrays2, envelopes=None, flavor="cpp", return_matr
     """gamma(0,0) = log P(both reads emit the same label) for a batch of pairs.
     envelopes: list of (U_i + 1, 2) arrays with INCLUSIVE ends (Gamma.h), or None for the dense DP.
     flavor "cpp" = Gamma.h arithmetic, "cy" = decoding_cy.pair_gamma_log arithmetic (dense), "cy_env" =
-    decoding_cy.pair_gamma_log_envelope (log(exp + exp), -inf defaults, every envelope cell with u < U, v < V computed).
+    decoding_cy.pair_gamma_log_envelope (log(exp + exp), -inf defaults, every envelope cell with u < U, v < V computed),
+    "py" = prefix_search.pair_gamma_log (dense: max-shifted base sum, np.logaddexp; what the dense "py" pair prefix search uses).
     return_matrix: return the (U+1, V+1) gamma matrices instead of gamma(0,0) (-inf outside an envelope)."""
     lib = L.load()
     y1, o1, Cc = pack_rows(arrays1)
@@ -371,7 +372,7 @@ def pair_gamma_batch(arrays1, arrays2, envelopes=None, flavor="cpp", return_matr
         dof = M.offsets([(len(a) + 1) * (len(b) + 1) for a, b in zip(arrays1, arrays2)], n)
         dn = M.out(dof[-1], np.float64)
     L.check(lib.po_pair_gamma_batch_h(_ptr(y1), _ptr(o1), _ptr(y2), _ptr(o2), _ptr(env), _ptr(eo), n, Cc,
-                                      {"cpp": 0, "cy": 1, "cy_env": 2}[flavor], _ptr(g0), _ptr(dn), _ptr(dof), _ptr(st)),
+                                      {"cpp": 0, "cy": 1, "cy_env": 2, "py": 3}[flavor], _ptr(g0), _ptr(dn), _ptr(dof), _ptr(st)),
             "po_pair_gamma_batch_h")
     M.raise_on_status(st, n, "pair gamma of pair")
     if return_matrix:

@@ -559,10 +559,11 @@ int po_pair_prefix_search_env_batch_h(const double* y1_h, const int64_t* y1_off_
     PO_HIPCHK(st.up(nullptr, sizeof(int32_t) * n));
     const size_t wsb = po_pair_gamma_workspace_bytes(n, mc, r1.max, r2.max);
     PO_HIPCHK(ws.up(nullptr, wsb));
-    // gamma: dense (the Python paths' flavour), or the envelope DP of Gamma.h (its own arithmetic: logaddexp, -inf)
+    // gamma: dense in the Python paths' own arithmetic (flavor 0, prefix_search.pair_gamma_log: gamma flavour 3; flavor 1,
+    // decoding_cy.pair_gamma_log: gamma flavour 1), or the envelope DP of Gamma.h (its own arithmetic: logaddexp, -inf)
     // written out as a full matrix with -inf outside the stored ranges
-    int rc = po_pair_gamma_batch(a.data, a.off, b.data, b.off, ev, eo, n, C, env_h ? 0 : flavor, mc, g0, dn, dfo, st, ws, wsb,
-                                 nullptr);
+    int rc = po_pair_gamma_batch(a.data, a.off, b.data, b.off, ev, eo, n, C, env_h ? 0 : (flavor ? 1 : 3), mc, g0, dn, dfo, st, ws,
+                                 wsb, nullptr);
     if (rc != PO_OK) return rc;
     PO_HIPCHK(out.up(seq_off_h, n, true));
     const int64_t mr = std::max(r1.max, r2.max);

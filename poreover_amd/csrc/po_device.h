@@ -48,6 +48,16 @@ __device__ __forceinline__ double po_lae(double x1, double x2) {
     return hi + po_log_(1.0 + exp(d));
 }
 
+// np.logaddexp (npy_logaddexp), the arithmetic of the reference's Python paths (prefix_search.py): equal -> a + ln2; else
+// max + log1p(exp(-|a - b|)); NaN only from NaN inputs
+__device__ __forceinline__ double po_np_logaddexp(double a, double b) {
+    if (a == b) return a + 0.6931471805599453;
+    const double d = a - b;
+    if (d > 0) return a + log1p(exp(-d));
+    if (d <= 0) return b + log1p(exp(d));
+    return d;  // NaN
+}
+
 // ---- logaddexp policies ----------------------------------------------------------------------
 // PoLaeOcml: Log.h's formula on the device math library (generic exp + log: ~100 f64 instructions).
 // PoLaeFast: the same formula e = exp(d), z = 1 + e, log(z), with both functions specialised to the

@@ -7,6 +7,9 @@
 //       outside a row dropped; cells [start, end-1] of rows u < U are computed (Gamma.h:61-64)
 //   decoding_cy.pair_gamma_log (decoding_cy.pyx:177-220): the dense (U+1) x (V+1) matrix with LOG_0 = -9999
 //       and log(exp(a) + exp(b)) instead of logaddexp   (flavor 1)
+//   prefix_search.pair_gamma_log (prefix_search.py:35-65): the dense matrix of the Python path, -inf defaults, the base sum
+//       by scipy.special.logsumexp (shifted by its maximum, or by 0 where that is not finite) and np.logaddexp   (flavor 3)
+//       — Gamma.h's unshifted log(sum exp) is -inf where every y1[u][c] + y2[v][c] is below exp's range (about -745)
 //
 //   gamma(U,V) = gamma*(U,V) = 0; gamma(U,v) = sum_{v'>=v} y2[v'][blank]; gamma(u,V) = sum_{u'>=u} y1[u'][blank]
 //   gamma*(u,v) = lae(gamma*(u,v+1) + y2[v][blank], gamma(u+1,v+1) + log sum_c exp(y1[u][c] + y2[v][c]))
@@ -48,7 +51,8 @@ __global__ __launch_bounds__(GM_THREADS) void pair_gamma_kernel(GMArgs a) {
     const bool dense = (a.env == nullptr);
     const int32_t* env = dense ? nullptr : a.env + 2 * a.env_off[pi];
     // flavor 0: Gamma.h; 1: decoding_cy.pair_gamma_log (dense, LOG_0 = -9999); 2: decoding_cy.pair_gamma_log_envelope
-    // (decoding_cy.pyx:224-271: log(exp + exp), -inf defaults, every envelope cell with u < U and v < V is computed)
+    // (decoding_cy.pyx:224-271: log(exp + exp), -inf defaults, every envelope cell with u < U and v < V is computed);
+    // 3: prefix_search.pair_gamma_log (max-shifted base sum, np.logaddexp, -inf defaults)
     const double LOG0 = (a.flavor == 1) ? -9999.0 : PO_NEG_INF;
     double* g = a.mat + (size_t)blockIdx.x * 2 * a.mat_cap;
     double* ga = g + a.mat_cap;
@@ -106,11 +110,19 @@ __global__ __launch_bounds__(GM_THREADS) void pair_gamma_kernel(GMArgs a) {
             const double* r2 = y2 + (int64_t)v * C;
             const double gamma_eps = G(g, u + 1, v) + r1[b];
             const double gamma_ast_eps = G(ga, u, v + 1) + r2[b];
-            double total2 = 0.;
-            for (int t = 0; t < C - 1; ++t) total2 += exp(r1[t] + r2[t]);
-            const double gamma_ast_ast = G(g, u + 1, v + 1) + log(total2);
+            double shift = 0., total2 = 0.;
+            if (a.flavor == 3) {   // scipy.special.logsumexp: a maximum that is not finite shifts by 0
+                double m = PO_NEG_INF;
+                for (int t = 0; t < C - 1; ++t) m = fmax(m, r1[t] + r2[t]);
+                if (m > PO_NEG_INF && m < __builtin_inf()) shift = m;
+            }
+            for (int t = 0; t < C - 1; ++t) total2 += exp(r1[t] + r2[t] - shift);
+            const double gamma_ast_ast = G(g, u + 1, v + 1) + (log(total2) + shift);
             double x_ast, x;
-            if (a.flavor) {
+            if (a.flavor == 3) {
+                x_ast = po_np_logaddexp(gamma_ast_eps, gamma_ast_ast);
+                x = po_np_logaddexp(gamma_eps, x_ast);
+            } else if (a.flavor) {
                 x_ast = log(exp(gamma_ast_eps) + exp(gamma_ast_ast));
                 x = log(exp(gamma_eps) + exp(x_ast));
             } else {

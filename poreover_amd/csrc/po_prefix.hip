@@ -223,12 +223,7 @@ struct PPSArgs {
 };
 __device__ __forceinline__ double pps_lae(double a, double b, int flavor) {
     if (flavor) return log(exp(a) + exp(b));
-    // np.logaddexp: equal -> a + ln2; else max + log1p(exp(-|a-b|)); NaN only from NaN inputs
-    if (a == b) return a + 0.6931471805599453;
-    const double d = a - b;
-    if (d > 0) return a + log1p(exp(-d));
-    if (d <= 0) return b + log1p(exp(d));
-    return d;  // NaN
+    return po_np_logaddexp(a, b);
 }
 }  // namespace
 

@@ -153,7 +153,9 @@ def test_pair_prefix_search_with_envelope_vs_oracle(eng, oracle, flavor):
         lab, lp = oracle.pair_prefix_search_log(a1[i], a2[i], flavor, envs[i])
         assert got[i][0] == lab, i
         assert np.isclose(got[i][1], lp, rtol=1e-10, atol=1e-12), i
-    # an envelope that covers every cell is the dense search
+    # an envelope that covers every cell is the dense search — on these normalised inputs: the dense "py" search takes gamma in
+    # prefix_search.py's max-shifted arithmetic and the envelope one in Gamma.h's, which part only where exp underflows
+    # (tests/test_gpu_gamma_prefix_edges.py::test_pair_prefix_underflow_pair)
     full = [np.array([(0, len(b))] * (len(a) + 1)) for a, b in zip(a1, a2)]
     dense = eng.pair_prefix_search_batch(a1, a2, "ACGT", "py")
     for g, d in zip(eng.pair_prefix_search_batch(a1, a2, "ACGT", "py", full), dense):
