@@ -69,6 +69,8 @@ extern "C" {
 #define PO_E_HIP (-7)        /* HIP runtime error (see po_last_error)                         */
 #define PO_SKIP_LENGTH (-10) /* pair skipped: |len1 - len2| > 1000   (pair_decode.py:372-375) */
 #define PO_SKIP_IDENTITY (-11)/* pair skipped: identity < 0.5        (pair_decode.py:395-398) */
+#define PO_E_NO_ANCHOR (-12) /* --skip_matches: no run of matches / indels long enough (the reference's assert) */
+#define PO_E_BOX (-13)       /* --skip_matches: a box the reference raises IndexError on (empty, or past a basecall's end) */
 
 /* ---- library / device ----------------------------------------------------------------- */
 int po_version(void);
@@ -285,6 +287,43 @@ int po_pair_decode_batch(const double* y1, const int64_t* y1_off, const double* 
                          const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* ws,
                          size_t ws_bytes, void* stream);
 
+/* ---- pair-decode --skip_matches on the device (pair_decode.py:412-467,512-522) ----------------------
+ * Runs of at least skip_threshold matching alignment columns (and of at least indel_threshold gap columns; the reference
+ * passes 100) are ANCHORS, copied from the 1-D basecalls; the stretches between them (BOXES) go through the pair beam search
+ * inside their slice of the envelope, and the pieces are joined in signal order.  The rule is csrc/po_skip_rules.h's.  The
+ * size of the box phase depends on the data, so the route is two calls, neither of which allocates device memory:
+ *   po_pair_skip_plan   Viterbi of both reads, alignment + skips + envelope (as po_pair_decode_batch), anchors and boxes.  It
+ *                       SYNCHRONISES the stream (one small D2H read of the box totals) and returns them in *totals (host).
+ *                       status[i]: 0, a skip, PO_E_NO_ANCHOR, PO_E_BOX, or what po_pair_decode_batch's pre-stages give.
+ *                       n_anchors / n_boxes: int32[n] (a pair with a non-zero status has 0 boxes).
+ *   po_pair_skip_run    gathers the boxes' rows and shifted envelopes, runs the pair beam search on all boxes of the batch,
+ *                       and stitches anchors and box consensuses into seq.  plan_ws must still hold what the plan left in
+ *                       it (same n, offsets, options and thresholds).  A box whose beam status is non-zero gives its pair
+ *                       that status (the first such box) and no consensus; a consensus longer than its room is PO_E_CAP.
+ * opt->diagonal_envelope is PO_E_UNSUPPORTED; opt->full_alignment and all three tree models work.  The anchor and box tables
+ * (int32 x 4 per row: cs, ce, type 0 mat / 1 ins / 2 del, position | b0, b1, lo, hi) live in plan_ws; the host twin below
+ * copies them out.  Pair i's anchors start at row (rows1 before i + rows2 before i + 16 i) /
+ * min(skip_threshold, indel_threshold) + i of the anchor table, its boxes at that row + i of the box table. */
+typedef struct {
+    int64_t n_boxes;      /* boxes of all pairs whose status is 0                */
+    int64_t total_rows1;  /* their rows of read 1 / read 2 (read 2's overlap)    */
+    int64_t total_rows2;
+    int64_t max_rows1;    /* the largest box                                     */
+    int64_t max_rows2;
+} po_skip_totals;
+size_t po_pair_skip_plan_workspace_bytes(int n, int64_t total_rows1, int64_t total_rows2, int64_t max_rows1, int64_t max_rows2,
+                                         int C, const po_pair_options* opt, int skip_threshold, int indel_threshold);
+int po_pair_skip_plan(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                      const po_pair_options* opt, int skip_threshold, int indel_threshold, char* seq1d,
+                      const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity, int32_t* status,
+                      int32_t* n_anchors, int32_t* n_boxes, void* plan_ws, size_t plan_ws_bytes, po_skip_totals* totals,
+                      void* stream);
+size_t po_pair_skip_run_workspace_bytes(int n, int C, const po_pair_options* opt, const po_skip_totals* totals);
+int po_pair_skip_run(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                     const po_pair_options* opt, int skip_threshold, int indel_threshold, const po_skip_totals* totals,
+                     void* plan_ws, size_t plan_ws_bytes, char* seq, const int64_t* seq_off, int32_t* seq_len,
+                     int32_t* status, void* run_ws, size_t run_ws_bytes, void* stream);
+
 /* ---- host-buffer conveniences (numpy callers): allocate, copy in, launch, copy out, free ----
  * Same semantics as the device-pointer forms with every pointer a HOST pointer; synchronous.
  * INPUT offset tables (y_off_h, y1_off_h, y2_off_h, label_off_h, and the tables of sequences, alignments, maps and
@@ -382,6 +421,25 @@ int po_pair_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const do
                            const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h,
                            int32_t* env_out_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h,
                            int32_t* status_h);
+/* The whole --skip_matches chain on host buffers: po_pair_decode_batch_h's arguments and outputs (env_out_h: the whole
+ * pair's envelope, may be NULL) plus the two thresholds, n_anchors_h / n_boxes_h (int32[n]) and, where anchors_h / boxes_h are
+ * not NULL, the anchor and box tables (int32 x 4 per row, rows as po_pair_skip_plan places them: tab_rows_h[i], int64[n + 1], gets
+ * pair i's first anchor row; its boxes start at row tab_rows_h[i] + i; anchors_h needs tab_rows_h[n] rows, boxes_h n more).
+ * stage_ms_h (float[4] or NULL): device ms of plan, gather, beam, stitch. */
+int po_pair_skip_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n,
+                                int C, const po_pair_options* opt, int skip_threshold, int indel_threshold, char* seq1d_h,
+                                const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h,
+                                int32_t* env_out_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h,
+                                int32_t* status_h, int32_t* n_anchors_h, int32_t* n_boxes_h, int64_t* tab_rows_h,
+                                int32_t* anchors_h, int32_t* boxes_h, po_skip_totals* totals_h, float* stage_ms_h);
+/* The anchor / box stage alone, for given alignments (rows of pair i at aln*_h + aln_off_h[i], ncol_h[i] columns), frame maps,
+ * signal lengths and envelopes (rows of pair i at env_h + 2 * env_off_h[i]).  Tables as above with tab_rows_h[i] =
+ * (aln_off_h[i] - aln_off_h[0]) / min(thresholds) + i.  status_h: 0, PO_E_NO_ANCHOR, PO_E_BOX (PO_E_ARG: ncol < 1). */
+int po_skip_boxes_batch_h(const char* aln1_h, const char* aln2_h, const int64_t* aln_off_h, const int32_t* ncol_h, int n,
+                          const int32_t* map1_h, const int64_t* map1_off_h, const int32_t* map2_h, const int64_t* map2_off_h,
+                          const int32_t* U_h, const int32_t* V_h, const int32_t* env_h, const int64_t* env_off_h,
+                          int skip_threshold, int indel_threshold, int32_t* n_anchors_h, int32_t* n_boxes_h,
+                          int64_t* tab_rows_h, int32_t* anchors_h, int32_t* boxes_h, int32_t* status_h);
 
 /* ---- host-to-strings pipeline of the pair decoder ---------------------------------------------------
  * replaces the reference's fan-out of pair_decode_helper over worker processes (pair_decode.py:292-297)
@@ -707,6 +765,15 @@ int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, in
                              const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
                              int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
                              int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h);
+/* The same with --skip_matches: the pair chain is po_pair_skip_plan + po_pair_skip_run (above) on the tables the network left on
+ * the device; status_h may also be PO_E_NO_ANCHOR, PO_E_BOX or a box's beam status.  opt->diagonal_envelope: PO_E_UNSUPPORTED. */
+int po_pair_basecall_skip_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                  const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                  int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                                  const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                                  int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
+                                  int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h, int skip_threshold,
+                                  int indel_threshold);
 
 /* The table stage of the above alone, on host buffers.  logits_h: (row_off_h[n_reads], 5) f32, read-major; row_off_h from
  * 0, non-decreasing; a read that a pair names needs a row (PO_E_ARG naming the pair).  y1_h / y2_h get, pair after pair, the

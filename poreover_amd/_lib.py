@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("POREOVER_HIP_LIB") or os.path.join(HERE, "libporeover
 OK = 0
 E_CAP, E_ARG, E_ENVELOPE, E_NOMEM, E_DIVERGE, E_UNSUPPORTED, E_HIP = -1, -2, -3, -4, -5, -6, -7
 SKIP_LENGTH, SKIP_IDENTITY = -10, -11
+E_NO_ANCHOR, E_BOX = -12, -13      # --skip_matches: the reference's assert / IndexError (csrc/po_skip_rules.h)
 MODELS = {"ctc": 0, "ctc_merge_repeats": 1, "ctc_flipflop": 2}
 METHODS = {"row": 0, "row_col": 1, "grid": 2}
 KINDS = {"poreover": 0, "bonito": 1, "flipflop": 2}
@@ -24,7 +25,9 @@ _CODE_NAMES = {E_CAP: "PO_E_CAP (buffer too small)", E_ARG: "PO_E_ARG (bad argum
                E_ENVELOPE: "PO_E_ENVELOPE (envelope undefined for the reference)",
                E_NOMEM: "PO_E_NOMEM (node arena / band capacity exceeded)",
                E_DIVERGE: "PO_E_DIVERGE (the reference never terminates on this input)",
-               E_UNSUPPORTED: "PO_E_UNSUPPORTED", E_HIP: "PO_E_HIP"}
+               E_UNSUPPORTED: "PO_E_UNSUPPORTED", E_HIP: "PO_E_HIP",
+               E_NO_ANCHOR: "PO_E_NO_ANCHOR (no run of matches / indels long enough)",
+               E_BOX: "PO_E_BOX (a box that is empty or lies past a basecall's end)"}
 
 
 class EngineUnavailable(RuntimeError):
@@ -41,6 +44,11 @@ class EngineError(RuntimeError):
 class PairOptions(C.Structure):
     _fields_ = [("beam_width", C.c_int), ("model", C.c_int), ("method", C.c_int), ("padding", C.c_int),
                 ("full_alignment", C.c_int), ("diagonal_envelope", C.c_int), ("diagonal_width", C.c_int)]
+
+
+class SkipTotals(C.Structure):
+    _fields_ = [("n_boxes", C.c_int64), ("total_rows1", C.c_int64), ("total_rows2", C.c_int64), ("max_rows1", C.c_int64),
+                ("max_rows2", C.c_int64)]
 
 
 class CallLayer(C.Structure):
@@ -139,6 +147,18 @@ PROTOTYPES = {
                                          _i64p, _i32p, _i32p, _dp, _i32p, _cp, _i64p, _i32p, _i32p]),
     "po_pair_decode_from_1d_batch_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp,
                                                  _i64p, _i32p, _i32p, _i32p, _i32p, _dp, _i32p, _cp, _i64p, _i32p, _i32p]),
+    "po_pair_skip_plan_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                                       C.POINTER(PairOptions), C.c_int, C.c_int]),
+    "po_pair_skip_plan": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, C.POINTER(PairOptions), C.c_int, C.c_int, _cp, _i64p,
+                                    _i32p, _i32p, _dp, _i32p, _i32p, _i32p, _vp, C.c_size_t, C.POINTER(SkipTotals), _vp]),
+    "po_pair_skip_run_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.POINTER(PairOptions), C.POINTER(SkipTotals)]),
+    "po_pair_skip_run": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, C.POINTER(PairOptions), C.c_int, C.c_int,
+                                   C.POINTER(SkipTotals), _vp, C.c_size_t, _cp, _i64p, _i32p, _i32p, _vp, C.c_size_t, _vp]),
+    "po_pair_skip_decode_batch_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, C.POINTER(PairOptions), C.c_int, C.c_int,
+                                              _cp, _i64p, _i32p, _i32p, _dp, _i32p, _cp, _i64p, _i32p, _i32p, _i32p, _i32p, _i64p,
+                                              _i32p, _i32p, C.POINTER(SkipTotals), C.POINTER(C.c_float)]),
+    "po_skip_boxes_batch_h": (C.c_int, [_cp, _cp, _i64p, _i32p, C.c_int, _i32p, _i64p, _i32p, _i64p, _i32p, _i32p, _i32p, _i64p,
+                                        C.c_int, C.c_int, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]),
     "po_profile_update_counter": (C.c_int, [C.c_void_p]),
     "po_lae_peak": (C.c_int, [C.c_int, _dp, C.c_void_p]),
     "po_pair_prefix_search_batch_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p,
@@ -199,6 +219,9 @@ PROTOTYPES = {
     "po_pair_basecall_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                            C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp, _i64p, _i32p, _i32p, _dp,
                                            _cp, _i64p, _i32p, _i32p, _vp, C.POINTER(C.c_float)]),
+    "po_pair_basecall_skip_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
+                                                C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp, _i64p, _i32p, _i32p, _dp,
+                                                _cp, _i64p, _i32p, _i32p, _vp, C.POINTER(C.c_float), C.c_int, C.c_int]),
     "po_pair_basecall_fastq_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                                  C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(PairOptions), _cp, _i64p, _i32p, _i32p,
                                                  _dp, _cp, _i64p, _i32p, _i32p, _vp, C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p,

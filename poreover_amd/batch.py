@@ -142,6 +142,89 @@ def pair_decode_batch(arrays1, arrays2, kind="poreover", beam_width=5, method="r
     return out
 
 
+SKIP_TYPES = ("mat", "ins", "del")    # the type column of an anchor table (csrc/po_skip_rules.h)
+
+
+def _skip_tables(n, rows, anc, box, na, nb):
+    """per pair the rows of the anchor table (cs, ce, type, position) and of the box table (b0, b1, lo, hi) as int64 arrays"""
+    return ([anc[rows[i]:rows[i] + na[i]].astype(np.int64) for i in range(n)],
+            [box[rows[i] + i:rows[i] + i + nb[i]].astype(np.int64) for i in range(n)])
+
+
+def pair_skip_decode_batch(arrays1, arrays2, kind="poreover", beam_width=5, method="row_col", padding=5, alignment="banded",
+                           skip_threshold=10, indel_threshold=100, return_tables=False, return_stats=False):
+    """pair-decode --skip_matches (pair_decode.py:412-467,512-522) for a batch of pairs, all on the GPU
+    (po_pair_skip_decode_batch_h): runs of at least skip_threshold matching alignment columns (indel_threshold
+    gap columns) are copied from the 1-D basecalls, the boxes between them go through the pair beam search inside their slice
+    of the envelope, and the pieces are joined in signal order.  Returns pair_decode_batch's records plus n_anchors and n_boxes
+    (0 boxes where the status is not 0), and with return_tables `anchors` (rows cs, ce, type, position; type indexes SKIP_TYPES)
+    and `boxes` (rows b0, b1, lo, hi).  status: 0, a skip, E_NO_ANCHOR / E_BOX (where the reference raises), or a box's beam
+    status; no pair fails the batch.  return_stats: also a dict with the box totals and the device ms of plan, gather, beam,
+    stitch."""
+    lib = L.load()
+    y1, o1, Cc = pack_rows(arrays1)
+    y2, o2, _ = pack_rows(arrays2, Cc)
+    n = len(arrays1)
+    if skip_threshold < 1 or indel_threshold < 1:
+        raise ValueError("pair_skip_decode_batch: thresholds must be at least 1")
+    opt = M.pair_options(kind, beam_width, method, padding, alignment, False, 50)
+    s1o = M.offsets([len(x) for ab in zip(arrays1, arrays2) for x in ab], 2 * n)
+    so = M.offsets([len(a) + len(b) for a, b in zip(arrays1, arrays2)], n)
+    seq1d, seq = M.out(s1o[-1], np.uint8), M.out(so[-1], np.uint8)
+    l1, l2, lens, st, na, nb = (M.out(n) for _ in range(6))
+    ident = M.out(n, np.float64)
+    env = M.out(o1[-1], np.int32, 2)
+    rows = np.zeros(n + 1, dtype=np.int64)
+    m = min(int(skip_threshold), int(indel_threshold))
+    tab = int((o1[-1] + o2[-1] + 16 * n) // m + n)
+    anc = M.out(tab, np.int32, 4) if return_tables else None
+    box = M.out(tab + n, np.int32, 4) if return_tables else None
+    tot, ms = L.SkipTotals(), (C.c_float * 4)()
+    L.check(lib.po_pair_skip_decode_batch_h(_ptr(y1), _ptr(o1), _ptr(y2), _ptr(o2), n, Cc, C.byref(opt), int(skip_threshold),
+                                            int(indel_threshold), _ptr(seq1d), _ptr(s1o), _ptr(l1), _ptr(l2), _ptr(ident), _ptr(env),
+                                            _ptr(seq), _ptr(so), _ptr(lens), _ptr(st), _ptr(na), _ptr(nb), _ptr(rows), _ptr(anc),
+                                            _ptr(box), C.byref(tot), ms), "po_pair_skip_decode_batch_h")
+    out = []
+    M.pair_records(out, seq1d, s1o, seq, so, l1, l2, lens, st, ident, env, o1, strict=False)(0, n)
+    tabs = _skip_tables(n, rows, anc, box, na, nb) if return_tables else None
+    for i, r in enumerate(out):
+        r["n_anchors"], r["n_boxes"] = int(na[i]), int(nb[i])
+        if tabs:
+            r["anchors"], r["boxes"] = tabs[0][i], tabs[1][i]
+    if return_stats:
+        return out, {"n_boxes": tot.n_boxes, "total_rows1": tot.total_rows1, "total_rows2": tot.total_rows2,
+                     "max_rows1": tot.max_rows1, "max_rows2": tot.max_rows2, "stage_ms": dict(zip(("plan", "gather", "beam", "stitch"), ms))}
+    return out
+
+
+def skip_boxes_batch(alignments, maps1, maps2, Us, Vs, envelopes, skip_threshold=10, indel_threshold=100):
+    """The anchor / box stage of --skip_matches alone (po_skip_boxes_batch_h): alignments = [(row1, row2) strings], maps = frame
+    of every base, Us / Vs = signal lengths, envelopes = (U_i, 2) arrays.  Returns (anchors, boxes, status): per pair the int64
+    rows (cs, ce, type, position) and (b0, b1, lo, hi), and int32 status (n,): 0, E_NO_ANCHOR, E_BOX.  A pair with E_BOX keeps
+    its anchors' columns; no pair fails the batch."""
+    lib = L.load()
+    n = len(alignments)
+    a1, ao = M.pack_text([a for a, _ in alignments])
+    a2 = M.pack_text([b for _, b in alignments])[0]
+    nc = np.array([len(a) for a, _ in alignments] or [0], dtype=np.int32)
+    m1o, m2o = M.offsets([len(m) for m in maps1], n), M.offsets([len(m) for m in maps2], n)
+    m1, m2 = M.concat_spare(maps1, np.int32), M.concat_spare(maps2, np.int32)
+    Us = list(Us)
+    U = np.array(Us or [0], dtype=np.int32)
+    V = np.array(list(Vs) or [0], dtype=np.int32)
+    env, eo = M.pack_envelopes(envelopes, [np.zeros((u, 0)) for u in Us], 0)
+    m = min(int(skip_threshold), int(indel_threshold))
+    tab = int(ao[-1] // m + n)
+    anc, box = M.out(tab, np.int32, 4), M.out(tab + n, np.int32, 4)
+    na, nb, st = M.out(n), M.out(n), M.out(n)
+    rows = np.zeros(n + 1, dtype=np.int64)
+    L.check(lib.po_skip_boxes_batch_h(_ptr(a1), _ptr(a2), _ptr(ao), _ptr(nc), n, _ptr(m1), _ptr(m1o), _ptr(m2), _ptr(m2o), _ptr(U),
+                                      _ptr(V), _ptr(env), _ptr(eo), int(skip_threshold), int(indel_threshold), _ptr(na), _ptr(nb),
+                                      _ptr(rows), _ptr(anc), _ptr(box), _ptr(st)), "po_skip_boxes_batch_h")
+    anchors, boxes = _skip_tables(n, rows, anc, box, na, nb)
+    return anchors, boxes, st[:n].copy()
+
+
 def forward_batch(arrays, labels, alphabet="ACGT", model="ctc"):
     """decoding_cpp.cpp_forward for a batch: log P(label_i | y_i)."""
     lib = L.load()

@@ -861,6 +861,193 @@ int po_pair_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const do
                          identity_h, env_out_h, seq_h, seq_off_h, seq_len_h, status_h);
 }
 
+// -------------------------------------------------------------------------------- pair decode --skip_matches
+namespace {
+// total and largest rows of the two reads of a batch whose tables are on the device
+struct SkipRows { int64_t t1, t2, m1, m2; };
+int skip_rows(const int64_t* y1_off, const int64_t* y2_off, int n, hipStream_t s, SkipRows* r) {
+    std::vector<int64_t> h(2 * (size_t)(n + 1));
+    PO_HIPCHK(po_read_tables(y1_off, y2_off, n, s, h.data()));
+    *r = SkipRows{h[n] - h[0], h[2 * n + 1] - h[n + 1], 0, 0};
+    for (int i = 0; i < n; ++i) {
+        r->m1 = std::max<int64_t>(r->m1, h[i + 1] - h[i]);
+        r->m2 = std::max<int64_t>(r->m2, h[n + 1 + i + 1] - h[n + 1 + i]);
+    }
+    return PO_OK;
+}
+}  // namespace
+
+size_t po_pair_skip_plan_workspace_bytes(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, const po_pair_options* opt,
+                                         int skip_threshold, int indel_threshold) {
+    g_err.clear();
+    return po_skip_plan_ws_bytes(n, tr1, tr2, mr1, mr2, C, opt, skip_threshold, indel_threshold);
+}
+
+int po_pair_skip_plan(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                      const po_pair_options* opt, int skip_threshold, int indel_threshold, char* seq1d, const int64_t* seq1d_off,
+                      int32_t* len1, int32_t* len2, double* identity, int32_t* status, int32_t* n_anchors, int32_t* n_boxes,
+                      void* plan_ws, size_t plan_ws_bytes, po_skip_totals* totals, void* stream) {
+    g_err.clear();
+    if (n < 0 || !y1 || !y1_off || !y2 || !y2_off || !opt || !seq1d || !seq1d_off || !len1 || !len2 || !identity || !status ||
+        !n_anchors || !n_boxes || !plan_ws || !totals) return po_fail(PO_E_ARG, "po_pair_skip_plan: null argument");
+    if (opt->diagonal_envelope) return po_fail(PO_E_UNSUPPORTED, "po_pair_skip_plan: diagonal_envelope has no alignment to take anchors from");
+    if (skip_threshold < 1 || indel_threshold < 1) return po_fail(PO_E_ARG, "po_pair_skip_plan: thresholds must be at least 1");
+    *totals = po_skip_totals{0, 0, 0, 0, 0};
+    if (n == 0) return PO_OK;
+    SkipRows r;
+    int rc = skip_rows(y1_off, y2_off, n, (hipStream_t)stream, &r);
+    if (rc != PO_OK) return rc;
+    rc = po_launch_skip_plan(y1, y1_off, y2, y2_off, n, C, opt, skip_threshold, indel_threshold, r.t1, r.t2, r.m1, r.m2, seq1d, seq1d_off,
+                             len1, len2, identity, status, n_anchors, n_boxes, plan_ws, plan_ws_bytes, totals, (hipStream_t)stream);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_skip_plan: launch refused (options, or workspace too small)");
+    PO_HIPCHK(hipGetLastError());
+    return PO_OK;
+}
+
+size_t po_pair_skip_run_workspace_bytes(int n, int C, const po_pair_options* opt, const po_skip_totals* totals) {
+    g_err.clear();
+    return po_skip_run_ws_bytes(n, C, opt, totals);
+}
+
+int po_pair_skip_run(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                     const po_pair_options* opt, int skip_threshold, int indel_threshold, const po_skip_totals* totals, void* plan_ws,
+                     size_t plan_ws_bytes, char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* run_ws,
+                     size_t run_ws_bytes, void* stream) {
+    g_err.clear();
+    if (n < 0 || !y1 || !y1_off || !y2 || !y2_off || !opt || !totals || !plan_ws || !seq || !seq_off || !seq_len || !status || !run_ws)
+        return po_fail(PO_E_ARG, "po_pair_skip_run: null argument");
+    if (n == 0) return PO_OK;
+    SkipRows r;
+    int rc = skip_rows(y1_off, y2_off, n, (hipStream_t)stream, &r);
+    if (rc != PO_OK) return rc;
+    rc = po_launch_skip_run(y1, y1_off, y2, y2_off, n, C, opt, skip_threshold, indel_threshold, r.t1, r.t2, r.m1, r.m2, totals, plan_ws,
+                            plan_ws_bytes, seq, seq_off, seq_len, status, run_ws, run_ws_bytes, nullptr, (hipStream_t)stream);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_skip_run: launch refused (options, totals, or a workspace too small)");
+    PO_HIPCHK(hipGetLastError());
+    return PO_OK;
+}
+
+int po_pair_skip_decode_batch_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n, int C,
+                                const po_pair_options* opt, int skip_threshold, int indel_threshold, char* seq1d_h,
+                                const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h, int32_t* env_out_h,
+                                char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h, int32_t* n_anchors_h,
+                                int32_t* n_boxes_h, int64_t* tab_rows_h, int32_t* anchors_h, int32_t* boxes_h, po_skip_totals* totals_h,
+                                float* stage_ms_h) {
+    g_err.clear();
+    if (!opt || !n_anchors_h || !n_boxes_h) return po_fail(PO_E_ARG, "po_pair_skip_decode_batch_h: null argument");
+    if (opt->diagonal_envelope) return po_fail(PO_E_UNSUPPORTED, "po_pair_skip_decode_batch_h: diagonal_envelope has no alignment to take anchors from");
+    if (skip_threshold < 1 || indel_threshold < 1) return po_fail(PO_E_ARG, "po_pair_skip_decode_batch_h: thresholds must be at least 1");
+    if (n <= 0) return PO_OK;
+    const PoRagged r1(y1_off_h, n), r2(y2_off_h, n);
+    const size_t s1b = (size_t)seq1d_off_h[2 * n], per = sizeof(int32_t) * n;
+    PoRows a, b;
+    PoSeqOut out;
+    PoDev s1o, s1, l1, l2, idn, na, nb, pws, rws;
+    PO_HIPCHK(a.up(y1_h, r1, sizeof(double) * C));
+    PO_HIPCHK(b.up(y2_h, r2, sizeof(double) * C));
+    PO_HIPCHK(out.up(seq_off_h, n));
+    PO_HIPCHK(s1o.up(seq1d_off_h, sizeof(int64_t) * (2 * n + 1)));
+    PO_HIPCHK(s1.up(nullptr, s1b));
+    PO_HIPCHK(l1.up(nullptr, per));
+    PO_HIPCHK(l2.up(nullptr, per));
+    PO_HIPCHK(idn.up(nullptr, sizeof(double) * n));
+    PO_HIPCHK(na.up(nullptr, per));
+    PO_HIPCHK(nb.up(nullptr, per));
+    const size_t pwsb = po_skip_plan_ws_bytes(n, r1.total, r2.total, r1.max, r2.max, C, opt, skip_threshold, indel_threshold);
+    if (pwsb == 0) return po_fail(PO_E_ARG, "po_pair_skip_decode_batch_h: model and column count do not fit");
+    PO_HIPCHK(pws.up(nullptr, pwsb));
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } guard{ev};
+    if (stage_ms_h) {
+        for (int i = 0; i < 5; ++i) PO_HIPCHK(hipEventCreate(&ev[i]));
+        PO_HIPCHK(hipEventRecord(ev[4], nullptr));
+    }
+    po_skip_totals tot;
+    int rc = po_launch_skip_plan(a.data, a.off, b.data, b.off, n, C, opt, skip_threshold, indel_threshold, r1.total, r2.total, r1.max, r2.max,
+                                 s1, s1o, l1, l2, idn, out.status, na, nb, pws, pwsb, &tot, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_skip_decode_batch_h: plan refused");
+    PO_HIPCHK(hipGetLastError());
+    const size_t rwsb = po_skip_run_ws_bytes(n, C, opt, &tot);
+    PO_HIPCHK(rws.up(nullptr, rwsb));
+    rc = po_launch_skip_run(a.data, a.off, b.data, b.off, n, C, opt, skip_threshold, indel_threshold, r1.total, r2.total, r1.max, r2.max, &tot,
+                            pws, pwsb, out.seq, out.off, out.len, out.status, rws, rwsb, stage_ms_h ? ev : nullptr, nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_skip_decode_batch_h: run refused");
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(hipGetLastError());
+    if (stage_ms_h) {
+        PO_HIPCHK(hipEventElapsedTime(&stage_ms_h[0], ev[4], ev[0]));
+        for (int k = 0; k < 3; ++k) PO_HIPCHK(hipEventElapsedTime(&stage_ms_h[1 + k], ev[k], ev[k + 1]));
+    }
+    PO_HIPCHK(out.down(seq_h, seq_len_h, status_h));
+    PO_HIPCHK(s1.down(seq1d_h, s1b));
+    PO_HIPCHK(l1.down(len1_h, per));
+    PO_HIPCHK(l2.down(len2_h, per));
+    PO_HIPCHK(idn.down(identity_h, sizeof(double) * n));
+    PO_HIPCHK(na.down(n_anchors_h, per));
+    PO_HIPCHK(nb.down(n_boxes_h, per));
+    const int32_t *anc = nullptr, *box = nullptr, *env = nullptr;
+    int64_t rows = 0;
+    rc = po_skip_plan_tables(pws, n, r1.total, r2.total, r1.max, r2.max, C, opt, skip_threshold, indel_threshold, &anc, &box, &env, &rows);
+    if (rc != PO_OK) return po_fail(rc, "po_pair_skip_decode_batch_h: tables");
+    if (env_out_h) PO_HIPCHK(hipMemcpy(env_out_h, env, sizeof(int32_t) * 2 * (size_t)r1.total, hipMemcpyDeviceToHost));
+    if (anchors_h) PO_HIPCHK(hipMemcpy(anchors_h, anc, sizeof(int32_t) * 4 * (size_t)rows, hipMemcpyDeviceToHost));
+    if (boxes_h) PO_HIPCHK(hipMemcpy(boxes_h, box, sizeof(int32_t) * 4 * (size_t)(rows + n), hipMemcpyDeviceToHost));
+    if (tab_rows_h)
+        for (int i = 0; i <= n; ++i) tab_rows_h[i] = (r1.off[i] + r2.off[i] + 16ll * i) / std::min(skip_threshold, indel_threshold) + i;
+    if (totals_h) *totals_h = tot;
+    return PO_OK;
+}
+
+int po_skip_boxes_batch_h(const char* aln1_h, const char* aln2_h, const int64_t* aln_off_h, const int32_t* ncol_h, int n,
+                          const int32_t* map1_h, const int64_t* map1_off_h, const int32_t* map2_h, const int64_t* map2_off_h,
+                          const int32_t* U_h, const int32_t* V_h, const int32_t* env_h, const int64_t* env_off_h, int skip_threshold,
+                          int indel_threshold, int32_t* n_anchors_h, int32_t* n_boxes_h, int64_t* tab_rows_h, int32_t* anchors_h,
+                          int32_t* boxes_h, int32_t* status_h) {
+    g_err.clear();
+    if (skip_threshold < 1 || indel_threshold < 1) return po_fail(PO_E_ARG, "po_skip_boxes_batch_h: thresholds must be at least 1");
+    if (n <= 0) return PO_OK;
+    const int m = std::min(skip_threshold, indel_threshold);
+    for (int i = 0; i < n; ++i) {
+        if (aln_off_h[i + 1] < aln_off_h[i] || map1_off_h[i + 1] < map1_off_h[i] || map2_off_h[i + 1] < map2_off_h[i] ||
+            env_off_h[i + 1] - env_off_h[i] < U_h[i] || U_h[i] < 0)
+            return po_fail(PO_E_ARG, "po_skip_boxes_batch_h: pair " + std::to_string(i) + ": a table decreases, or fewer envelope rows than frames");
+    }
+    const size_t tab = sizeof(int64_t) * (n + 1), per = sizeof(int32_t) * n;
+    const int64_t rows = (aln_off_h[n] - aln_off_h[0]) / m + n;
+    PoDev a1, a2, ao, nc, m1, m1o, m2, m2o, u, v, ev, eo, st, na, nb, anc, box, pinfo;
+    PO_HIPCHK(a1.up(aln1_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(a2.up(aln2_h, (size_t)aln_off_h[n]));
+    PO_HIPCHK(ao.up(aln_off_h, tab));
+    PO_HIPCHK(nc.up(ncol_h, per));
+    PO_HIPCHK(m1.up(map1_h, sizeof(int32_t) * (size_t)map1_off_h[n]));
+    PO_HIPCHK(m1o.up(map1_off_h, tab));
+    PO_HIPCHK(m2.up(map2_h, sizeof(int32_t) * (size_t)map2_off_h[n]));
+    PO_HIPCHK(m2o.up(map2_off_h, tab));
+    PO_HIPCHK(u.up(U_h, per));
+    PO_HIPCHK(v.up(V_h, per));
+    PO_HIPCHK(ev.up(env_h, sizeof(int32_t) * 2 * (size_t)env_off_h[n]));
+    PO_HIPCHK(eo.up(env_off_h, tab));
+    PO_HIPCHK(st.up(nullptr, per));
+    PO_HIPCHK(hipMemset(st.p, 0, per));
+    PO_HIPCHK(na.up(nullptr, per));
+    PO_HIPCHK(nb.up(nullptr, per));
+    PO_HIPCHK(anc.up(nullptr, sizeof(int32_t) * 4 * (size_t)(rows + 1)));
+    PO_HIPCHK(box.up(nullptr, sizeof(int32_t) * 4 * (size_t)(rows + n + 1)));
+    PO_HIPCHK(pinfo.up(nullptr, sizeof(long long) * 6 * (size_t)n));
+    int rc = po_launch_skip_boxes(a1, a2, ao, nc, n, m1, m1o, m2, m2o, u, v, ev, eo, skip_threshold, indel_threshold, na, nb, anc, box, st,
+                                  pinfo.as<long long>(), nullptr);
+    if (rc != PO_OK) return po_fail(rc, "po_skip_boxes_batch_h: launch refused");
+    PO_HIPCHK(hipDeviceSynchronize());
+    PO_HIPCHK(na.down(n_anchors_h, per));
+    PO_HIPCHK(nb.down(n_boxes_h, per));
+    PO_HIPCHK(anc.down(anchors_h, sizeof(int32_t) * 4 * (size_t)rows));
+    PO_HIPCHK(box.down(boxes_h, sizeof(int32_t) * 4 * (size_t)(rows + n)));
+    PO_HIPCHK(st.down(status_h, per));
+    if (tab_rows_h)
+        for (int i = 0; i <= n; ++i) tab_rows_h[i] = (aln_off_h[i] - aln_off_h[0]) / m + i;
+    return PO_OK;
+}
+
 // -------------------------------------------------------------------------------- events / profile
 void* po_event_create(void) {
     hipEvent_t e;

@@ -77,6 +77,33 @@ int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_off, const do
                                const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes,
                                hipStream_t stream);
 
+int po_launch_pair_prep_hand(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                             const po_pair_options* opt, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, char* seq1d,
+                             const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity, int32_t* env_out,
+                             int32_t* status, char* aln1, char* aln2, const int64_t* aln_off, int32_t* ncol, const int32_t** map1,
+                             const int32_t** map2, const int32_t** env, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// po_skip.hip (--skip_matches; the rules are po_skip_rules.h's).  matches / indels: skip_threshold / indel_threshold; tr / mr: total and
+// largest rows of the two reads, as po_launch_pair_decode_geom takes them
+size_t po_skip_plan_ws_bytes(int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, const po_pair_options* opt, int matches,
+                             int indels);
+int po_launch_skip_plan(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                        const po_pair_options* opt, int matches, int indels, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                        char* seq1d, const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity, int32_t* status,
+                        int32_t* n_anchors, int32_t* n_boxes, void* ws, size_t ws_bytes, po_skip_totals* totals, hipStream_t stream);
+size_t po_skip_run_ws_bytes(int n, int C, const po_pair_options* opt, const po_skip_totals* totals);
+int po_launch_skip_run(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                       const po_pair_options* opt, int matches, int indels, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                       const po_skip_totals* totals, void* plan_ws, size_t plan_ws_bytes, char* seq, const int64_t* seq_off,
+                       int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes, hipEvent_t* ev, hipStream_t stream);
+int po_skip_plan_tables(void* plan_ws, int n, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, int C, const po_pair_options* opt,
+                        int matches, int indels, const int32_t** anchors, const int32_t** boxes, const int32_t** env,
+                        int64_t* tab_rows);
+int po_launch_skip_boxes(const char* aln1, const char* aln2, const int64_t* aln_off, const int32_t* ncol, int n, const int32_t* map1,
+                         const int64_t* map1_off, const int32_t* map2, const int64_t* map2_off, const int32_t* U, const int32_t* V,
+                         const int32_t* env, const int64_t* env_off, int matches, int indels, int32_t* n_anchors, int32_t* n_boxes,
+                         int32_t* anchors, int32_t* boxes, int32_t* status, long long* pinfo, hipStream_t stream);
+
 // po_lattice.hip
 size_t po_lattice_ws_bytes(int n, int64_t max_rows, int64_t max_label, int model, int acceptor);
 int po_launch_forward(const double* y, const int64_t* y_off, int n, int C, int A, uint32_t alphabet, int model,

@@ -68,7 +68,9 @@ __device__ __forceinline__ int py_idx(int i, int len) { return i < 0 ? i + len :
 }  // namespace
 
 // SKEW (one-wave workgroups, banded alignment): the DP as a skewed wavefront — see the block comment at its code.
-template <int NT, bool SKEW>
+// HAND (mode 0 only): the alignment of every pair that passes the identity skip is also handed out, forward order, through
+// aln_out1 / aln_out2 / aln_off / ncol_out (the --skip_matches chain reads it); ncol_out of any other pair is 0.
+template <int NT, bool SKEW, bool HAND = false>
 __global__ __launch_bounds__(NT) void pair_prep_kernel(PPArgs a) {
     static_assert(!SKEW || NT == PO_WAVE, "the skewed wavefront is a one-wave schedule");
     constexpr int PERMAX = (NT == 64) ? 16 : 8;  // consecutive DP cells per thread: a banded row (<= 1001 cells) fits one wave
@@ -610,6 +612,13 @@ __global__ __launch_bounds__(NT) void pair_prep_kernel(PPArgs a) {
             continue;
         }
 
+        if constexpr (HAND) {
+            const int64_t ao = a.aln_off[pi];
+            const int nout = (ncol <= (int)(a.aln_off[pi + 1] - ao)) ? ncol : 0;   // (cannot exceed it: ncol <= l1 + l2 <= U + V)
+            for (int k = tid; k < nout; k += NT) { a.aln_out1[ao + k] = al1[ncol - 1 - k]; a.aln_out2[ao + k] = al2[ncol - 1 - k]; }
+            if (tid == 0) a.ncol_out[pi] = nout;
+        }
+
         PPTK(2);  // trace-back + identity
         if constexpr (SKEW) if (a.maps_increasing) {
             // ------------------------------------------------------------------ envelope by base (envelope.py:46-87)
@@ -787,6 +796,12 @@ void pp_launch(PPArgs a, int blocks, int one_wave, hipStream_t stream, long long
     const bool legacy = pp_legacy();
     // (a basecall of read 2 beyond SK_MAXB column blocks — 131 072 bases — keeps the row-at-a-time kernel)
     const bool skew = one_wave && !a.full_alignment && a.mode != 2 && !legacy && max_len2 <= (long long)SK_MAXB * SK_BW;
+    if (a.mode == 0 && a.ncol_out) {   // the alignment is handed out (po_launch_pair_prep_hand)
+        if (skew) hipLaunchKernelGGL((pair_prep_kernel<64, true, true>), dim3(blocks), dim3(64), lds, stream, a);
+        else if (one_wave) hipLaunchKernelGGL((pair_prep_kernel<64, false, true>), dim3(blocks), dim3(64), lds, stream, a);
+        else hipLaunchKernelGGL((pair_prep_kernel<256, false, true>), dim3(blocks), dim3(256), lds, stream, a);
+        return;
+    }
     if (skew) hipLaunchKernelGGL((pair_prep_kernel<64, true>), dim3(blocks), dim3(64), lds, stream, a);
     else if (one_wave) hipLaunchKernelGGL((pair_prep_kernel<64, false>), dim3(blocks), dim3(64), lds, stream, a);
     else hipLaunchKernelGGL((pair_prep_kernel<256, false>), dim3(blocks), dim3(256), lds, stream, a);
@@ -895,13 +910,14 @@ extern "C" size_t po_pair_ws_bytes_impl(int n, int64_t tr1, int64_t tr2, int64_t
     return pp_geometry(n, tr1, tr2, mr1, mr2, C, opt).total;
 }
 
-extern "C" int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_off, const double* y2,
-                                          const int64_t* y2_off, int n, int C, const po_pair_options* opt,
-                                          int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
-                                          const int32_t* ext_map1, const int32_t* ext_map2, char* seq1d,
-                                          const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity,
-                                          int32_t* env_out, char* seq, const int64_t* seq_off, int32_t* seq_len,
-                                          int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream) {
+// The stages before the pair beam search: (1) the two 1-D basecalls, (2) alignment, skips, envelope.  hand (or NULL): where
+// the alignments, the frame maps and the envelope go for the --skip_matches chain, which stops before (3), the pair beam search.
+struct PPHand { char* aln1; char* aln2; const int64_t* aln_off; int32_t* ncol; const int32_t** map1; const int32_t** map2; const int32_t** env; };
+static int pp_chain(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int C,
+                    const po_pair_options* opt, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2, const int32_t* ext_map1,
+                    const int32_t* ext_map2, char* seq1d, const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity,
+                    int32_t* env_out, char* seq, const int64_t* seq_off, int32_t* seq_len, int32_t* status, void* ws, size_t ws_bytes,
+                    hipStream_t stream, const PPHand* hand) {
     if (n <= 0) return PO_OK;
     const int A = PO_A;
     const uint32_t alphabet = 'A' | ('C' << 8) | ('G' << 16) | ((uint32_t)'T' << 24);
@@ -953,6 +969,11 @@ extern "C" int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_of
     a.match = NW_MATCH; a.mismatch = NW_MISMATCH; a.gap = NW_GAP;
     a.lenU = a.lenV = nullptr; a.map1_off = a.map2_off = nullptr; a.aln_out1 = a.aln_out2 = nullptr;
     a.aln_off = nullptr; a.ncol_out = nullptr; a.env_off = nullptr;
+    if (hand) {
+        a.aln_out1 = hand->aln1; a.aln_out2 = hand->aln2; a.aln_off = hand->aln_off; a.ncol_out = hand->ncol;
+        *hand->map1 = map1; *hand->map2 = map2; *hand->env = env;
+        if (po_zero_async(hand->ncol, sizeof(int32_t) * n, stream) != hipSuccess) return PO_E_HIP;
+    }
     a.env = env; a.identity = identity; a.status = status;
     a.queue = (int*)(w + g.off_queue);
     a.cap_flag = a.queue + 32;   // (inside the 256 bytes cleared below)
@@ -972,12 +993,39 @@ extern "C" int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_of
         pp_launch(b, g.big_blocks, g.one_wave, stream, mr2 + 8);
     }
     po_prof_stage(PO_K_ALIGN, stream, 0, &tok);
+    if (hand) return hipGetLastError() == hipSuccess ? PO_OK : PO_E_HIP;
     // (3) the pair beam search inside the envelope (pair_decode.py:166-173,511)
     po_prof_stage(PO_K_BEAM2D, stream, 1, &tok);
     rc = po_launch_beam2d_geom(y1, y1_off, y2, y2_off, env, n, C, A, alphabet, opt->beam_width, opt->model, opt->method,
                                tr1, tr2, mr1, mr2, seq, seq_off, seq_len, status, 1, w + g.off_b2, g.b2_bytes, stream);
     po_prof_stage(PO_K_BEAM2D, stream, 0, &tok);
     return rc;
+}
+
+extern "C" int po_launch_pair_decode_geom(const double* y1, const int64_t* y1_off, const double* y2,
+                                          const int64_t* y2_off, int n, int C, const po_pair_options* opt,
+                                          int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                                          const int32_t* ext_map1, const int32_t* ext_map2, char* seq1d,
+                                          const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity,
+                                          int32_t* env_out, char* seq, const int64_t* seq_off, int32_t* seq_len,
+                                          int32_t* status, void* ws, size_t ws_bytes, hipStream_t stream) {
+    return pp_chain(y1, y1_off, y2, y2_off, n, C, opt, tr1, tr2, mr1, mr2, ext_map1, ext_map2, seq1d, seq1d_off, len1, len2,
+                    identity, env_out, seq, seq_off, seq_len, status, ws, ws_bytes, stream, nullptr);
+}
+
+// The pre-stages alone, for the --skip_matches chain (po_skip.hip): ws of po_pair_ws_bytes_impl; the alignments of the pairs
+// with status 0 at aln1 / aln2 + aln_off[i] (forward order, ncol[i] columns; 0 for every other pair), and where the frame maps
+// (at y*_off[i], in ws) and the envelope (env_out, or in ws) are.
+extern "C" int po_launch_pair_prep_hand(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n,
+                                        int C, const po_pair_options* opt, int64_t tr1, int64_t tr2, int64_t mr1, int64_t mr2,
+                                        char* seq1d, const int64_t* seq1d_off, int32_t* len1, int32_t* len2, double* identity,
+                                        int32_t* env_out, int32_t* status, char* aln1, char* aln2, const int64_t* aln_off,
+                                        int32_t* ncol, const int32_t** map1, const int32_t** map2, const int32_t** env,
+                                        void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (opt->diagonal_envelope) return PO_E_UNSUPPORTED;
+    const PPHand hand = {aln1, aln2, aln_off, ncol, map1, map2, env};
+    return pp_chain(y1, y1_off, y2, y2_off, n, C, opt, tr1, tr2, mr1, mr2, nullptr, nullptr, seq1d, seq1d_off, len1, len2,
+                    identity, env_out, nullptr, nullptr, nullptr, status, ws, ws_bytes, stream, &hand);
 }
 
 extern "C" int po_launch_pair_decode(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off,

@@ -347,7 +347,8 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
                        int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
                        const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
                        double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
-                       float* logits_h, float* stage_ms_h, const PairFastqOut* fq) {
+                       float* logits_h, float* stage_ms_h, const PairFastqOut* fq, const int* skip = nullptr) {
+    // skip (or NULL): {skip_threshold, indel_threshold} of --skip_matches: the pair chain is po_skip.hip's plan + run
     const int n_stages = fq ? 8 : 6;
     const std::string me = std::string(name) + ": ";
     po_set_error("");
@@ -378,6 +379,10 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
         return po_fail(PO_E_ARG, me + "beam_width " + std::to_string(opt->beam_width) + " (1 to 25)");
     if (opt->method != PO_METHOD_ROW && opt->method != PO_METHOD_ROW_COL && opt->method != PO_METHOD_GRID)
         return po_fail(PO_E_ARG, me + "method " + std::to_string(opt->method));
+    if (skip && (skip[0] < 1 || skip[1] < 1))
+        return po_fail(PO_E_ARG, me + "skip_threshold " + std::to_string(skip[0]) + ", indel_threshold " + std::to_string(skip[1]) + " (1 at least)");
+    if (skip && opt->diagonal_envelope)
+        return po_fail(PO_E_UNSUPPORTED, me + "diagonal_envelope: there is no alignment to take anchors from");
     // the model and the weights' length: po_call_batch's own checks, which come before it looks at a buffer (no windows:
     // the pointers are not followed)
     rc = po_call_batch(weights_h, 0, window, layers_h, n_layers, weights_h, n_weights, (float*)weights_h, nullptr, nullptr, 0,
@@ -391,7 +396,7 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
     PoBasecallPasses net;
     PairTables t;
     PoSeqOut out;
-    PoDev s1o, s1, l1, l2, idn, ws;
+    PoDev s1o, s1, l1, l2, idn, ws, nab, rws;
     const size_t s1b = (size_t)seq1d_off_h[2 * (size_t)n_pairs], per = sizeof(int32_t) * (size_t)n_pairs;
     rc = net.up(plan, signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
     if (rc != PO_OK) return rc;
@@ -403,8 +408,10 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
     PO_HIPCHK(l1.up(nullptr, per));
     PO_HIPCHK(l2.up(nullptr, per));
     PO_HIPCHK(idn.up(nullptr, sizeof(double) * (size_t)n_pairs));
-    const size_t wsb = po_pair_decode_workspace_bytes(n_pairs, pp.rows[0], pp.rows[1], pp.max_rows[0], pp.max_rows[1], NOUT, opt);
+    const size_t wsb = skip ? po_skip_plan_ws_bytes(n_pairs, pp.rows[0], pp.rows[1], pp.max_rows[0], pp.max_rows[1], NOUT, opt, skip[0], skip[1])
+                            : po_pair_decode_workspace_bytes(n_pairs, pp.rows[0], pp.rows[1], pp.max_rows[0], pp.max_rows[1], NOUT, opt);
     PO_HIPCHK(ws.up(nullptr, wsb));
+    if (skip) PO_HIPCHK(nab.up(nullptr, 2 * per));   // anchors and boxes per pair
     PairFastqStages fs;
     PairQualIn qin;
     if (fq) {
@@ -424,9 +431,23 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
     if (rc != PO_OK) return rc;
     PO_HIPCHK(stitch.mark(stream));
     PO_HIPCHK(decode.mark(stream));
-    rc = po_pair_decode_batch(t.y[0], t.off[0], t.y[1], t.off[1], n_pairs, NOUT, opt, s1, s1o, l1, l2, idn, nullptr, out.seq, out.off,
-                              out.len, out.status, ws, wsb, stream);
-    if (rc != PO_OK) return rc;
+    if (skip) {   // plan (synchronises: the box totals), the run workspace for those totals, run
+        po_skip_totals tot;
+        rc = po_launch_skip_plan(t.y[0], t.off[0], t.y[1], t.off[1], n_pairs, NOUT, opt, skip[0], skip[1], pp.rows[0], pp.rows[1],
+                                 pp.max_rows[0], pp.max_rows[1], s1, s1o, l1, l2, idn, out.status, nab.as<int32_t>(),
+                                 nab.as<int32_t>() + n_pairs, ws, wsb, &tot, stream);
+        if (rc != PO_OK) return po_fail(rc, me + "the skip-matches plan was refused");
+        const size_t rwsb = po_skip_run_ws_bytes(n_pairs, NOUT, opt, &tot);
+        PO_HIPCHK(rws.up(nullptr, rwsb));
+        rc = po_launch_skip_run(t.y[0], t.off[0], t.y[1], t.off[1], n_pairs, NOUT, opt, skip[0], skip[1], pp.rows[0], pp.rows[1],
+                                pp.max_rows[0], pp.max_rows[1], &tot, ws, wsb, out.seq, out.off, out.len, out.status, rws, rwsb, nullptr,
+                                stream);
+        if (rc != PO_OK) return po_fail(rc, me + "the skip-matches run was refused");
+    } else {
+        rc = po_pair_decode_batch(t.y[0], t.off[0], t.y[1], t.off[1], n_pairs, NOUT, opt, s1, s1o, l1, l2, idn, nullptr, out.seq, out.off,
+                                  out.len, out.status, ws, wsb, stream);
+        if (rc != PO_OK) return rc;
+    }
     PO_HIPCHK(decode.mark(stream));
     if (fq) {   // the quality stages, on the tables and the strings the pair chain left on the device
         PO_HIPCHK(guides.mark(stream));
@@ -479,6 +500,20 @@ extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* si
     return pair_basecall_impl("po_pair_basecall_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
                               n_weights, max_windows_per_pass, pair_idx_h, n_pairs, reverse_complement, opt, seq1d_h, seq1d_off_h,
                               len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h, nullptr);
+}
+
+extern "C" int po_pair_basecall_skip_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                                             const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                                             int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                                             const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                                             int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h,
+                                             int32_t* seq_len_h, int32_t* status_h, float* logits_h, float* stage_ms_h,
+                                             int skip_threshold, int indel_threshold) {
+    const int skip[2] = {skip_threshold, indel_threshold};
+    return pair_basecall_impl("po_pair_basecall_skip_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers,
+                              weights_h, n_weights, max_windows_per_pass, pair_idx_h, n_pairs, reverse_complement, opt, seq1d_h,
+                              seq1d_off_h, len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h, nullptr,
+                              skip);
 }
 
 extern "C" int po_pair_basecall_fastq_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,

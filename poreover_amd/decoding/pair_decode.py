@@ -68,11 +68,66 @@ def get_anchors(alignment, matches, indels):
     return ranges, types
 
 
+NO_ANCHOR_MESSAGE = 'No matches/indels of sufficient length found in alignment. Try decreasing --matches or --indels'
+INDEL_THRESHOLD = 100            # get_anchors(..., indels=100) at the reference's call (pair_decode.py:412)
+# which route --skip_matches takes: "device" (batch.pair_skip_decode_batch: the whole chain in one engine call)
+# or "host" (three batched stage calls with the anchors, boxes and join in Python: the A/B baseline and checker).
+# args.skip_route or POREOVER_SKIP_ROUTE choose; the default is the one scripts/bench_skip.py measured faster at 1 000 pairs.
+SKIP_ROUTE_DEFAULT = "device"
+
+
 def _decode_pairs_skip_matches(in_paths, loaded, args, out):
     """--skip_matches (pair_decode.py:412-467,512-522): long runs of matching columns are copied from read 1's
     basecall, the stretches between them ("boxes") are decoded with the pair beam search inside their slice of
-    the envelope, and the pieces are joined in signal order.  Viterbi, alignment, envelope and every box of
-    every pair run as batched GPU calls."""
+    the envelope, and the pieces are joined in signal order."""
+    route = getattr(args, 'skip_route', None) or os.environ.get("POREOVER_SKIP_ROUTE") or SKIP_ROUTE_DEFAULT
+    if route not in ("device", "host"):
+        raise ValueError("skip route %r (device or host)" % (route,))
+    return (_decode_pairs_skip_matches_device if route == "device" else _decode_pairs_skip_matches_host)(in_paths, loaded, args, out)
+
+
+def _decode_pairs_skip_matches_device(in_paths, loaded, args, out):
+    """The device route: one engine call per kind (po_pair_skip_decode_batch_h).  Raises what the host route raises, for the
+    first pair in the order that route meets them: EngineError for a pair the stages before the anchors refuse, then the
+    reference's AssertionError (no anchor) / IndexError (a box it cannot index), then EngineError for a box's beam status."""
+    by_kind = {}
+    for i, (_, _, m1, _) in enumerate(loaded):
+        by_kind.setdefault(m1.kind, []).append(i)
+    for kind, idx in by_kind.items():
+        res = _batch.pair_skip_decode_batch([loaded[i][2].log_prob for i in idx], [loaded[i][3].log_prob for i in idx], kind,
+                                            args.beam_width, args.beam_search_method, args.padding, args.alignment,
+                                            skip_threshold=args.skip_threshold, indel_threshold=INDEL_THRESHOLD)
+        skips = (0, _lib.SKIP_LENGTH, _lib.SKIP_IDENTITY)
+        for i, r in zip(idx, res):
+            if r["status"] not in skips + (_lib.E_NO_ANCHOR, _lib.E_BOX) and r["n_boxes"] == 0:
+                raise _lib.EngineError(r["status"], "pair decode of pair %d" % i)
+        for i, r in zip(idx, res):
+            assert r["status"] != _lib.E_NO_ANCHOR, NO_ANCHOR_MESSAGE
+            if r["status"] == _lib.E_BOX:
+                raise IndexError("pair %d: a box of the alignment is empty or lies past a basecall's end" % i)
+        for i, r in zip(idx, res):
+            if r["status"] not in skips:
+                raise _lib.EngineError(r["status"], "pair beam search of a box of pair %d" % i)
+        for i, r in zip(idx, res):
+            in_path, path1, path2 = in_paths[i], loaded[i][0], loaded[i][1]
+            summary = {'read1': in_path[0], 'read2': in_path[1], 'length1': r["length1"], 'length2': r["length2"]}
+            if r["status"] == _lib.SKIP_LENGTH:
+                summary['skipped'] = 1
+                out[i] = [summary]
+                continue
+            summary['sequence_identity'] = r["sequence_identity"]
+            summary['skipped'] = 1 if r["status"] == _lib.SKIP_IDENTITY else 0
+            if summary['skipped']:
+                out[i] = [summary]
+                continue
+            out[i] = (fasta_format(in_path[0], r["seq1"]) + fasta_format(in_path[1], r["seq2"]),
+                      fasta_format('consensus;{};{}'.format(path1.stem, path2.stem), r["consensus"]), summary)
+    return out
+
+
+def _decode_pairs_skip_matches_host(in_paths, loaded, args, out):
+    """The host route: Viterbi, alignment, envelope and every box of every pair run as batched GPU calls; the anchors, the
+    boxes and the join are Python."""
     import numpy as np
     by_kind = {}
     for i, (_, _, m1, _) in enumerate(loaded):
@@ -118,8 +173,8 @@ def _decode_pairs_skip_matches(in_paths, loaded, args, out):
                 for c, ch in enumerate(aln[r]):
                     acc = acc if ch == '-' else acc + 1
                     a2s[r, c] = acc
-            ranges, types = get_anchors(aln, matches=args.skip_threshold, indels=100)
-            assert len(ranges) > 0, 'No matches/indels of sufficient length found in alignment. Try decreasing --matches or --indels'
+            ranges, types = get_anchors(aln, matches=args.skip_threshold, indels=INDEL_THRESHOLD)
+            assert len(ranges) > 0, NO_ANCHOR_MESSAGE
             anchors, boxes = [], []
             for k, (cs, ce) in enumerate(ranges):
                 row = 1 if types[k] == 'ins' else 0

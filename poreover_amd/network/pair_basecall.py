@@ -99,10 +99,11 @@ def pair_tables(logits, pairs, reverse2=False, perm2=None):
 
 
 def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass,
-                 fastq=None):
+                 fastq=None, skip=None):
     """One po_pair_basecall_batch_h call on the reads sigs and the index pairs `pairs` into them.  Returns (records as
     batch.pair_decode_batch's, per-read logits or None).  fastq (a dict: band, flags — per pair the four items' "no band"
-    flags, or None — and odds): po_pair_basecall_fastq_batch_h instead, and a third item, quality.pair_fields' dicts."""
+    flags, or None — and odds): po_pair_basecall_fastq_batch_h instead, and a third item, quality.pair_fields' dicts.
+    skip ((skip_threshold, indel_threshold), without fastq): po_pair_basecall_skip_batch_h, the --skip_matches pair chain."""
     n, P = len(sigs), len(pairs)
     off = _marshal.offsets([len(s) for s in sigs])
     rows = int(off[-1])
@@ -123,7 +124,9 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
     common = (ptr(signal), ptr(off), n, window, overlap, layers, len(net.layers), ptr(w), w.size, int(max_windows_per_pass),
               ptr(idx), P, 1 if reverse_complement else 0, C.byref(opt), ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2), ptr(ident),
               ptr(seq), ptr(so), ptr(lens), ptr(st), ptr(lg))
-    if fastq is None:
+    if skip is not None:
+        _lib.check(lib.po_pair_basecall_skip_batch_h(*common, ms, int(skip[0]), int(skip[1])), "po_pair_basecall_skip_batch_h")
+    elif fastq is None:
         _lib.check(lib.po_pair_basecall_batch_h(*common, ms), "po_pair_basecall_batch_h")
     else:
         flags = fastq.get("flags")
@@ -148,7 +151,7 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
 def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
                           beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
                           diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32",
-                          qualities=False, qual_band=None, odds=False, recurrence="f32"):
+                          qualities=False, qual_band=None, odds=False, recurrence="f32", skip_matches=False, skip_threshold=10):
     """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
     batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
     consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
@@ -167,11 +170,20 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     whose banded lattice is lost (E_ENVELOPE) is scored again without a band, that item alone, in a second engine call for
     its pair (a window's bits do not depend on its call: the strings are the same, and are checked); an item still
     unscored gets Q 0 (the consensus: the other table's evidence alone) and a line in the log (quality.warn_unscored).
-    The records of pairs that are not decoded are unchanged; stage_ms then has _lib.PAIR_BASECALL_FASTQ_STAGES."""
+    The records of pairs that are not decoded are unchanged; stage_ms then has _lib.PAIR_BASECALL_FASTQ_STAGES.
+    skip_matches=True (po_pair_basecall_skip_batch_h): pair-decode --skip_matches' consensus — runs of at least
+    skip_threshold matching alignment columns are copied from the 1-D basecalls, the boxes between them decoded — with the
+    statuses E_NO_ANCHOR / E_BOX where the reference raises; not together with qualities or diagonal_envelope."""
     _lib._precision_code(precision)
     _lib._recur_code(recurrence)
     if not qualities and (qual_band is not None or odds):
         raise ValueError("pair_basecall_signals: qual_band and odds are options of qualities=True")
+    if skip_matches and qualities:
+        raise ValueError("pair_basecall_signals: skip_matches is not built together with qualities")
+    if skip_matches and diagonal_envelope:
+        raise ValueError("pair_basecall_signals: skip_matches is not built together with diagonal_envelope (no alignment to take anchors from)")
+    if skip_matches and int(skip_threshold) < 1:
+        raise ValueError("pair_basecall_signals: skip_threshold %d (1 at least)" % skip_threshold)
     if qualities:
         from .. import quality
         band = quality.check_band("pair_basecall_signals", qual_band)
@@ -201,7 +213,12 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
         opt = _marshal.pair_options(kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width)
         lens = [len(s) for s in sigs]
 
+        skip = (int(skip_threshold), 100) if skip_matches else None     # (the reference's get_anchors(..., indels=100))
+
         def ws_bytes(n, t1, t2, m1, m2):
+            if skip:   # the plan's workspace and, at most, every row again in the box batch
+                return int(lib.po_pair_skip_plan_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt), *skip)) + \
+                    (t1 + t2) * (8 * ckpt.NUM_LABELS + 32)
             return int(lib.po_pair_decode_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt)))
 
         def run(which, want_logits, band_=None, flags=None):
@@ -218,7 +235,8 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
                 with _lib.call_precision(precision), _lib.recur_precision(recurrence):
                     res = _engine_call(lib, net, [sigs[r] for r in reads],
                                        [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
-                                       reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass, fastq=fastq)
+                                       reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass, fastq=fastq,
+                                       skip=skip)
                 if want_logits:
                     for r, lg in zip(reads, res[1]):
                         read_logits[r] = lg
