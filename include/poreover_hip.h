@@ -555,7 +555,8 @@ int po_gru_proj_h(const float* x_h, int64_t M, int cin, int ndir, const float* w
 
 /* The precision of the GRU recurrence's product h·U, process-wide and read once per po_call_batch call,
  * next to the call precision and independent of it — so by po_call_batch_h, po_basecall_batch_h, po_basecall_fastq_batch_h,
- * po_pair_basecall_batch_h, po_pair_basecall_fastq_batch_h and every group of a po_basecaller engine — set it around the whole run;
+ * po_pair_basecall_batch_h, po_pair_basecall_fastq_batch_h and every group of a po_basecaller or po_pair_basecaller engine — set it
+ * around the whole run;
  * po_train_* and po_train_eval are not reached:
  *   PO_RECUR_F32     (default) f32 operands on v_mfma_f32_16x16x4_f32
  *   PO_RECUR_BF16X3  h and U each split in two bf16 values (hi = bf16(v), lo = bf16(v - hi), round to nearest even,
@@ -835,6 +836,71 @@ int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const double* y2
                    const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h,
                    int band_size, const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h,
                    double* odds1d_h, double* odds_cons_h, int32_t* guide_h);
+
+/* ---- `pair-basecall` over one or several devices of a node ----------------------------------
+ * A po_pair_basecaller holds a model, the pair decoder's options and a list of devices, as a po_basecaller does for
+ * `basecall`.  A run cuts the pairs, in input order, into groups (po_pair_basecall_group_plan, which touches no device) and
+ * deals them from one planner to one host thread per listed device, whichever is free.  A group's distinct reads are
+ * compacted and indexed locally; a read that pairs of two groups name runs in each.  Each worker keeps its state on its
+ * device - the weights, uploaded once by po_pair_basecaller_create, and every buffer, grow-only between groups and runs -
+ * and a stream of its own; a group runs the body of po_pair_basecall_batch_h / po_pair_basecall_fastq_batch_h on it, so
+ * every string, identity, status, logit and quality is what ONE such call over all pairs gives, bit for bit.  The
+ * --skip_matches chain is not carried: it stays on po_pair_basecall_skip_batch_h.
+ *   - devices, ndev: 1 to 16 devices, each 0 .. po_device_count() - 1; a device may be named more than once
+ *   - options: window, overlap, max_windows_per_pass, reverse_complement and pair as for po_pair_basecall_batch_h; fastq != 0:
+ *     the runs make qualities with band_size as po_pair_basecall_fastq_batch_h; scaling (PO_SCALE_*), lo, hi: the raw route's
+ *     preparation (po_signal_prep_h); resident_bytes: the device bytes one group may hold (0: 16 GiB)
+ *   - groups: a pair joins the run while the run's resident bytes with it - 24 per sample of its distinct reads, 40 per
+ *     frame of every pair side, po_pair_decode_workspace_bytes and, for a fastq engine, the quality stages' bytes - stay
+ *     within resident_bytes and, with ndev > 1, its pair-side frames within ceil(all pair-side frames / (2 ndev)); a pair
+ *     that does not fit alone goes alone.  The raw route plans on raw lengths.
+ *   - po_pair_basecaller_create answers every argument error of po_pair_basecall_batch_h / po_pair_basecall_fastq_batch_h
+ *     (by that entry, under its name) and of po_signal_prep_h's scaling and range, a device out of range and ndev outside
+ *     1 .. 16 (PO_E_ARG naming the value); it returns NULL and po_last_error says why
+ *   - po_pair_basecaller_run_f32: scaled f32 signals and index pairs; outputs laid out as po_pair_basecall_fastq_batch_h's
+ *     (unbanded_h, qual1d_h, qual_h and qual_status_h are read only by a fastq engine; no odds, guides or stage times;
+ *     logits_h or NULL: a read no pair names gets no logits).  Only the reads that pairs name need a sample.
+ *   - po_pair_basecaller_run_raw: raw int16 reads, raw_off_h from 0, offset_h / alpha_h for PO_SCALE_CURRENT.  kept_h[n_reads]
+ *     gets the samples each read kept (-1: no pair names it, it was not prepared); the rooms of seq1d_off_h are for the RAW
+ *     lengths; logits_h (or NULL) holds room for raw_off_h[n_reads] rows, read i's kept_h[i] rows at row raw_off_h[i].  A
+ *     pair that names a read which keeps nothing is not run: its status is PO_E_ARG, its lengths are 0; its neighbours
+ *     are not affected.
+ *   - per-pair statuses (PO_SKIP_*, PO_E_NOMEM, ...) come back as from the one-call entry and do not fail the run.  When a
+ *     group fails as a call the other workers finish what they hold and take no more; the run returns that group's code
+ *     and "device d: <message>".  The engine stays usable.
+ *   - po_pair_basecaller_stats: pairs, reads (distinct per group, summed), their samples, groups and busy host
+ *     milliseconds of worker i in the last run
+ * The call precision (po_set_call_precision) and the recurrence precision (po_set_recur_precision) are read by every
+ * group: set them around the whole run. */
+typedef struct po_pair_basecaller po_pair_basecaller;
+typedef struct po_pair_basecaller_options {
+    int window, overlap, max_windows_per_pass, reverse_complement;
+    po_pair_options pair;
+    int fastq, band_size;
+    int scaling, lo, hi;
+    int64_t resident_bytes;
+} po_pair_basecaller_options;
+po_pair_basecaller* po_pair_basecaller_create(const int* devices, int ndev, const po_call_layer* layers_h, int n_layers,
+                                              const float* weights_h, int64_t n_weights,
+                                              const po_pair_basecaller_options* options);
+void po_pair_basecaller_destroy(po_pair_basecaller* b);
+int po_pair_basecaller_run_f32(po_pair_basecaller* b, const float* signal_h, const int64_t* sig_off_h, int n_reads,
+                               const int32_t* pair_idx_h, int n_pairs, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h,
+                               int32_t* len2_h, double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h,
+                               int32_t* status_h, float* logits_h, const int32_t* unbanded_h, char* qual1d_h, char* qual_h,
+                               int32_t* qual_status_h);
+int po_pair_basecaller_run_raw(po_pair_basecaller* b, const int16_t* raw_h, const int64_t* raw_off_h, int n_reads,
+                               const double* offset_h, const double* alpha_h, const int32_t* pair_idx_h, int n_pairs,
+                               char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h, double* identity_h,
+                               char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h, float* logits_h,
+                               const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h, int64_t* kept_h);
+int po_pair_basecaller_stats(po_pair_basecaller* b, int i, int64_t* pairs, int64_t* reads, int64_t* samples, int* groups,
+                             double* busy_ms);
+/* first[g], count[g] of the groups of n_pairs pairs over reads of len[r] samples (written for g < cap); band_size: the
+ * quality lattice's band the groups are sized for (fastq != 0; <= 0: no band); resident_bytes 0: 16 GiB.  Returns the
+ * number of groups, or PO_E_ARG. */
+int po_pair_basecall_group_plan(const int64_t* len, int n_reads, const int32_t* pair_idx, int n_pairs, const po_pair_options* opt,
+                                int fastq, int band_size, int64_t resident_bytes, int ndev, int32_t* first, int32_t* count, int cap);
 
 /* The consensus Phred kernel alone (poreover_amd/csrc/po_fastq_rules.h: po_fq_pair_phred).  odds1_h / odds2_h: five
  * float64 per base, labels and qual at label_off_h[i] (from 0, non-decreasing); item i gets quality.phred of

@@ -135,6 +135,11 @@ def build_parser():
     p.add_argument('--threads', type=int, default=1, help=argparse.SUPPRESS)
     p.add_argument('--precision', choices=['f32', 'bf16'], default='f32', help=PRECISION_HELP)
     p.add_argument('--recurrence', choices=['f32', 'bf16x3'], default='f32', help=RECURRENCE_HELP)
+    p.add_argument('--gpus', type=int, default=None,
+                   help='Stream the pairs through devices 0 .. N-1 (0: every visible device): the pairs file is cut into chunks of --chunk_pairs lines, '
+                        'their FAST5 files are read by --readers threads while the chunk before runs, filter and scaling run on the device')
+    p.add_argument('--readers', type=int, default=4, help='With --gpus: threads reading FAST5 files (1 to 16)')
+    p.add_argument('--chunk_pairs', type=int, default=256, help='With --gpus: lines of the pairs file per chunk')
     p.add_argument('-v', '--version', action='version', version=__version__)
     p.set_defaults(func="pair-basecall")
 

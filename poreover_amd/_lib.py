@@ -61,6 +61,12 @@ class BasecallerOptions(C.Structure):
                 ("lo", C.c_int), ("hi", C.c_int), ("resident_bytes", C.c_int64)]
 
 
+class PairBasecallerOptions(C.Structure):
+    _fields_ = [("window", C.c_int), ("overlap", C.c_int), ("max_windows_per_pass", C.c_int), ("reverse_complement", C.c_int),
+                ("pair", PairOptions), ("fastq", C.c_int), ("band_size", C.c_int), ("scaling", C.c_int), ("lo", C.c_int),
+                ("hi", C.c_int), ("resident_bytes", C.c_int64)]
+
+
 CALL_KINDS = {"conv": 0, "bigru": 1, "gru": 2, "gru_back": 3, "dense": 4}
 CALL_STAGES = ("conv", "gru_proj", "gru_recur", "dense_softmax")
 BASECALL_STAGES = CALL_STAGES + ("stitch_ingest", "decode")
@@ -229,6 +235,17 @@ PROTOTYPES = {
     "po_pair_qual_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _cp, _i64p, _i32p, _i32p,
                                  C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p]),
     "po_fastq_pair_phred_h": (C.c_int, [_dp, _dp, _cp, _i64p, C.c_int, C.c_char_p, _i32p, _i32p, _cp]),
+    "po_pair_basecaller_create": (C.c_void_p, [C.POINTER(C.c_int), C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
+                                               C.POINTER(PairBasecallerOptions)]),
+    "po_pair_basecaller_destroy": (None, [C.c_void_p]),
+    "po_pair_basecaller_run_f32": (C.c_int, [C.c_void_p, _vp, _i64p, C.c_int, _i32p, C.c_int, _cp, _i64p, _i32p, _i32p, _dp, _cp, _i64p,
+                                             _i32p, _i32p, _vp, _i32p, _cp, _cp, _i32p]),
+    "po_pair_basecaller_run_raw": (C.c_int, [C.c_void_p, _vp, _i64p, C.c_int, _dp, _dp, _i32p, C.c_int, _cp, _i64p, _i32p, _i32p, _dp,
+                                             _cp, _i64p, _i32p, _i32p, _vp, _i32p, _cp, _cp, _i32p, _i64p]),
+    "po_pair_basecaller_stats": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int), C.POINTER(C.c_double)]),
+    "po_pair_basecall_group_plan": (C.c_int, [_i64p, C.c_int, _i32p, C.c_int, C.POINTER(PairOptions), C.c_int, C.c_int, C.c_int64,
+                                              C.c_int, _i32p, _i32p, C.c_int]),
     "po_pair_tables_h": (C.c_int, [_vp, _i64p, C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _dp]),
     "po_train_create": (C.c_void_p, [C.POINTER(CallLayer), C.c_int, C.c_int, C.c_int]),
     "po_train_destroy": (None, [C.c_void_p]),

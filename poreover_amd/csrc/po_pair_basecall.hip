@@ -24,6 +24,7 @@
 #include "po_fastq_rules.h"
 #include "po_fastq_stages.h"
 #include "po_ingest_rules.h"
+#include "po_pair_basecall_pass.h"
 #include "po_pair_basecall_plan.h"
 #include "po_pair_fastq_plan.h"
 
@@ -87,11 +88,7 @@ struct PairTables {
     }
 };
 
-// what po_pair_basecall_fastq_batch_h adds to po_pair_basecall_batch_h's arguments
-struct PairFastqOut {
-    int band_size; const int32_t* unbanded_h;
-    char* qual1d_h; char* qual_h; int32_t* qual_status_h; double* odds1d_h; double* odds_cons_h; int32_t* guide_h;
-};
+typedef PoPairBasecallFastq PairFastqOut;
 
 // what the quality stages read: the two tables and the strings on the device, the strings' offset tables on both sides
 struct PairQualIn {
@@ -124,6 +121,8 @@ struct PairFastqStages {
     // before the decoder: the buffers whose size is known from the tables
     int prepare(const PairQualIn& in, const PairFastqOut& fq) {
         const int n = in.n;
+        al.reset();   // (a resident state: the pairs of the call before are not this call's)
+        wvb = 0;
         banded = fq.band_size > 0;
         kind = in.model == PO_MODEL_MERGE ? PO_KIND_BONITO : PO_KIND_POREOVER;
         s1b = (size_t)in.seq1d_off_h[2 * (size_t)n];
@@ -339,15 +338,39 @@ extern "C" int po_pair_tables_h(const float* logits_h, const int64_t* row_off_h,
     return PO_OK;
 }
 
-namespace {
+// everything a call keeps on the device: one call's, or a po_pair_basecaller worker's between groups and runs
+struct PoPairBasecallResident {
+    PoBasecallPasses net;
+    PairTables t;
+    PoSeqOut out;
+    PoDev s1o, s1, l1, l2, idn, ws;
+    PairFastqStages fs;
+};
 
-// po_pair_basecall_batch_h (fq == NULL) and po_pair_basecall_fastq_batch_h under their own names
-int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
-                       const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
-                       int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
-                       const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
-                       double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
-                       float* logits_h, float* stage_ms_h, const PairFastqOut* fq, const int* skip = nullptr) {
+PoPairBasecallResident* po_pair_basecall_resident_new() { return new PoPairBasecallResident; }
+void po_pair_basecall_resident_free(PoPairBasecallResident* st) { delete st; }
+
+int po_pair_basecall_resident_weights(PoPairBasecallResident* st, const float* weights_h, int64_t n_weights) {
+    PO_HIPCHK(st->net.w.up(weights_h, (size_t)n_weights * 4));
+    st->net.w_up = true;
+    return PO_OK;
+}
+
+int po_pair_basecall_resident_signal(PoPairBasecallResident* st, int64_t samples, float** signal) {
+    PO_HIPCHK(st->net.sig.up(nullptr, (size_t)samples * 4));
+    *signal = st->net.sig.as<float>();
+    return PO_OK;
+}
+
+// po_pair_basecall_batch_h (fq == NULL), po_pair_basecall_fastq_batch_h and po_pair_basecall_skip_batch_h under their own
+// names, and a po_pair_basecaller's groups
+int po_pair_basecall_body(PoPairBasecallResident* st, hipStream_t stream, bool signal_resident, const char* name,
+                          const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                          const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                          int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                          const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
+                          double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                          float* logits_h, float* stage_ms_h, const PoPairBasecallFastq* fq, const int* skip) {
     // skip (or NULL): {skip_threshold, indel_threshold} of --skip_matches: the pair chain is po_skip.hip's plan + run
     const int n_stages = fq ? 8 : 6;
     const std::string me = std::string(name) + ": ";
@@ -360,7 +383,7 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
         {opt, "opt"}, {seq1d_h, "seq1d_h"}, {seq1d_off_h, "seq1d_off_h"}, {len1_h, "len1_h"}, {len2_h, "len2_h"},
         {identity_h, "identity_h"}, {seq_h, "seq_h"}, {seq_off_h, "seq_off_h"}, {seq_len_h, "seq_len_h"}, {status_h, "status_h"}};
     for (const auto& a : ptrs)
-        if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
+        if (!a.p && !(signal_resident && &a == &ptrs[0])) return po_fail(PO_E_ARG, me + "null argument " + a.name);
     if (fq && null_quality_pointer(me, *fq) != PO_OK) return PO_E_ARG;
     PoBasecallPlan plan;
     PoPairBasecallPlan pp;
@@ -391,14 +414,14 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
     if (stage_ms_h) std::fill(stage_ms_h, stage_ms_h + n_stages, 0.f);
     if (n_pairs == 0 || n_reads == 0) return PO_OK;
 
-    hipStream_t stream = nullptr;
     static const int RC_PERM[NOUT] = {3, 2, 1, 0, 4};   // the complement: A <-> T, C <-> G, blank stays
-    PoBasecallPasses net;
-    PairTables t;
-    PoSeqOut out;
-    PoDev s1o, s1, l1, l2, idn, ws, nab, rws;
+    PoBasecallPasses& net = st->net;
+    PairTables& t = st->t;
+    PoSeqOut& out = st->out;
+    PoDev &s1o = st->s1o, &s1 = st->s1, &l1 = st->l1, &l2 = st->l2, &idn = st->idn, &ws = st->ws;
+    PoDev nab, rws;   // --skip_matches' alone: one-call entries only
     const size_t s1b = (size_t)seq1d_off_h[2 * (size_t)n_pairs], per = sizeof(int32_t) * (size_t)n_pairs;
-    rc = net.up(plan, signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
+    rc = net.up(plan, signal_resident ? nullptr : signal_h, sig_off_h, n_reads, window, layers_h, n_layers, weights_h, n_weights, max_windows_per_pass);
     if (rc != PO_OK) return rc;
     rc = t.up(pp, pair_idx_h, n_pairs);
     if (rc != PO_OK) return rc;
@@ -412,7 +435,7 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
                             : po_pair_decode_workspace_bytes(n_pairs, pp.rows[0], pp.rows[1], pp.max_rows[0], pp.max_rows[1], NOUT, opt);
     PO_HIPCHK(ws.up(nullptr, wsb));
     if (skip) PO_HIPCHK(nab.up(nullptr, 2 * per));   // anchors and boxes per pair
-    PairFastqStages fs;
+    PairFastqStages& fs = st->fs;
     PairQualIn qin;
     if (fq) {
         for (int s = 0; s < 2; ++s) { qin.y[s] = t.y[s]; qin.y_off[s] = t.off[s]; qin.rows[s] = pp.rows[s]; qin.max_rows[s] = pp.max_rows[s]; }
@@ -489,6 +512,20 @@ int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* s
     return PO_OK;
 }
 
+namespace {
+// a call of its own: a fresh state, freed when the call returns, on the null stream
+int pair_basecall_impl(const char* name, const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,
+                       const po_call_layer* layers_h, int n_layers, const float* weights_h, int64_t n_weights,
+                       int max_windows_per_pass, const int32_t* pair_idx_h, int n_pairs, int reverse_complement,
+                       const po_pair_options* opt, char* seq1d_h, const int64_t* seq1d_off_h, int32_t* len1_h, int32_t* len2_h,
+                       double* identity_h, char* seq_h, const int64_t* seq_off_h, int32_t* seq_len_h, int32_t* status_h,
+                       float* logits_h, float* stage_ms_h, const PairFastqOut* fq, const int* skip = nullptr) {
+    PoPairBasecallResident st;
+    return po_pair_basecall_body(&st, nullptr, false, name, signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers,
+                                 weights_h, n_weights, max_windows_per_pass, pair_idx_h, n_pairs, reverse_complement, opt, seq1d_h,
+                                 seq1d_off_h, len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h,
+                                 fq, skip);
+}
 }  // namespace
 
 extern "C" int po_pair_basecall_batch_h(const float* signal_h, const int64_t* sig_off_h, int n_reads, int window, int overlap,

@@ -399,22 +399,35 @@ def pair_record(in_path, stem1, stem2, r, args):
 
 def write_pair_files(results, args):
     """{out}.1d.fasta, {out}.2d.fasta and {out}.log of a list of pair_record's tuples (pair_decode.py:277-300)"""
-    keys = ["read1", "read2", "length1", "length2", "sequence_identity", "skipped"]
     with open(args.out + '.1d.fasta', 'w') as out_1d_f, open(args.out + '.2d.fasta', 'w') as out_2d_f, \
             open(args.out + '.log', 'w', 1) as log_f:
-        print('# PoreOver pair-decode', file=log_f)
-        print('# ' + str(vars(args)), file=log_f)
-        print('# ' + '\t'.join(keys), file=log_f)
-        for x in results:   # input order (the reference: process-completion order)
-            if len(x) == 3:
-                print(x[0], file=out_1d_f)
-                print(x[1], file=out_2d_f)
-                print('\t'.join(map(str, [x[2].get(k, "") for k in keys])), file=log_f)
-            elif len(x) == 2:
-                print(x[0], file=out_2d_f)
-                print('\t'.join(map(str, [x[1].get(k, "") for k in ["read1", "read2"]])), file=log_f)
-            elif len(x) == 1:
-                print('\t'.join(map(str, [x[0].get(k, "") for k in keys])), file=log_f)
+        write_pair_header(log_f, vars(args))
+        write_pair_records(results, out_1d_f, out_2d_f, log_f)
+
+
+LOG_KEYS = ["read1", "read2", "length1", "length2", "sequence_identity", "skipped"]
+
+
+def write_pair_header(log_f, settings):
+    """the three comment lines that open {out}.log; settings: the dict of the command's arguments"""
+    print('# PoreOver pair-decode', file=log_f)
+    print('# ' + str(settings), file=log_f)
+    print('# ' + '\t'.join(LOG_KEYS), file=log_f)
+
+
+def write_pair_records(results, out_1d_f, out_2d_f, log_f):
+    """pair_record's tuples appended to the three open files, in the order given (`pair-basecall --gpus` writes chunk by chunk)"""
+    keys = LOG_KEYS
+    for x in results:   # input order (the reference: process-completion order)
+        if len(x) == 3:
+            print(x[0], file=out_1d_f)
+            print(x[1], file=out_2d_f)
+            print('\t'.join(map(str, [x[2].get(k, "") for k in keys])), file=log_f)
+        elif len(x) == 2:
+            print(x[0], file=out_2d_f)
+            print('\t'.join(map(str, [x[1].get(k, "") for k in ["read1", "read2"]])), file=log_f)
+        elif len(x) == 1:
+            print('\t'.join(map(str, [x[0].get(k, "") for k in keys])), file=log_f)
 
 
 def decode_pairs_local(in_paths, args, devices=None):

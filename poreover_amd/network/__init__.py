@@ -4,5 +4,5 @@
 from . import basecall  # noqa: F401
 from .basecall import basecall_raw, basecall_signals, frame_window, window_plan  # noqa: F401
 from . import pair_basecall  # noqa: F401
-from .pair_basecall import pair_basecall_signals  # noqa: F401
+from .pair_basecall import pair_basecall_raw, pair_basecall_signals  # noqa: F401
 from .network import batch_input, call, call_helper, parse_fast5, prep_signals, read_fast5_raw, round_bf16, split_bf16  # noqa: F401

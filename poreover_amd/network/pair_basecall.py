@@ -18,10 +18,11 @@ import numpy as np
 from .. import _lib, _marshal
 from . import basecall as _basecall
 from . import checkpoint as ckpt
-from .network import _layers_array, load_model, parse_fast5
+from .network import SCALINGS, _layers_array, load_model, parse_fast5, read_fast5_raw
 
 __all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read", "qual_bytes_query",
-           "write_pair_fastq"]
+           "write_pair_fastq", "PairBasecaller", "pair_basecall_raw", "engine_group_plan"]
+DEFAULT_CHUNK_PAIRS = 256
 
 RC_PERM = [3, 2, 1, 0, 4]   # the complement's column order: A <-> T, C <-> G, blank stays
 
@@ -75,6 +76,277 @@ def pair_groups(pairs, lens, ws_bytes, budget=None, qual_bytes=None):
     if group:
         out.append(group)
     return out
+
+
+def engine_group_plan(pairs, lens, ws_bytes, budget=None, ndev=1, qual_bytes=None):
+    """po_pair_basecall_group_plan in Python, which the engine test pins: (first, count) of a po_pair_basecaller's groups —
+    contiguous runs of pairs in input order by pair_groups' rule and byte sum (a pair joins the run while the run's resident
+    bytes with it stay within budget; a pair that does not fit alone goes alone), and, with ndev > 1, of at most
+    ceil(all pair-side frames / (2 ndev)) pair-side frames each, so that every device gets about two groups.  With
+    ndev == 1 the budget alone bounds a group: a second group on one device is a second full recurrence."""
+    budget = _basecall.RESIDENT_BYTES if budget is None else budget
+    frames = sum(lens[a] + lens[b] for a, b in pairs)
+    share = max(1, -(-frames // (2 * int(ndev)))) if ndev > 1 else None
+    out, first = [], 0
+    reads, samples, tr, mr = set(), 0, [0, 0], [0, 0]
+    for k, (a, b) in enumerate(pairs):
+        s = samples + sum(lens[r] for r in {a, b} - reads)
+        t = [tr[0] + lens[a], tr[1] + lens[b]]
+        m = [max(mr[0], lens[a]), max(mr[1], lens[b])]
+        if k > first:
+            n = k - first + 1
+            need = s * 24 + (t[0] + t[1]) * 40 + ws_bytes(n, t[0], t[1], m[0], m[1])
+            if qual_bytes is not None:
+                need += qual_bytes(n, t[0], t[1], m[0], m[1])
+            if (share is not None and t[0] + t[1] > share) or need > budget:
+                out.append((first, k - first))
+                first, reads = k, set()
+                s, t, m = sum(lens[r] for r in {a, b}), [lens[a], lens[b]], [lens[a], lens[b]]
+        reads |= {a, b}
+        samples, tr, mr = s, t, m
+    if len(pairs) > first:
+        out.append((first, len(pairs) - first))
+    return out
+
+
+class PairBasecaller:
+    """po_pair_basecaller: a model, the pair decoder's options (a _lib.PairOptions) and a list of devices
+    (a device may be named more than once); run_f32 / run_raw deal groups of pairs to one host thread per listed device.
+    A context manager."""
+
+    def __init__(self, net, devices, window, overlap, reverse_complement, opt, max_windows_per_pass=0, fastq=False, band=0,
+                 scaling="standard", lo=200, hi=800, resident_bytes=0):
+        if scaling not in SCALINGS:
+            raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
+        self.lib = _lib.load()
+        self.fastq = bool(fastq)
+        self.devices = [int(d) for d in devices]
+        w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
+        o = _lib.PairBasecallerOptions(int(window), int(overlap), int(max_windows_per_pass), 1 if reverse_complement else 0, opt,
+                                       1 if fastq else 0, int(band), SCALINGS.index(scaling), int(lo), int(hi), int(resident_bytes))
+        dev = (C.c_int * max(len(self.devices), 1))(*self.devices)
+        self.h = self.lib.po_pair_basecaller_create(dev, len(self.devices), _layers_array(net), len(net.layers), w.ctypes.data, w.size,
+                                                    C.byref(o))
+        if not self.h:
+            detail = self.lib.po_last_error()
+            raise _lib.EngineError(_lib.E_ARG, "po_pair_basecaller_create", detail.decode() if detail else "")
+
+    def close(self):
+        if self.h:
+            self.lib.po_pair_basecaller_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _run(self, what, call, lens, off, pairs, want_logits, flags, kept=None):
+        n, P = len(lens), len(pairs)
+        idx = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1)) if P else np.zeros(2, dtype=np.int32)
+        room = lambda r: lens[r] if 0 <= r < n else 0
+        s1o = _marshal.offsets([room(r) for ab in pairs for r in ab], 2 * P)
+        so = _marshal.offsets([room(a) + room(b) for a, b in pairs], P)
+        o1 = _marshal.offsets([room(a) for a, _ in pairs], P)
+        seq1d, seq = np.zeros(max(int(s1o[-1]), 1), dtype=np.uint8), np.zeros(max(int(so[-1]), 1), dtype=np.uint8)
+        l1, l2, ln, st = (np.zeros(max(P, 1), dtype=np.int32) for _ in range(4))
+        ident = np.zeros(max(P, 1), dtype=np.float64)
+        lg = np.zeros((max(int(off[-1]), 1), ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
+        ub = np.ascontiguousarray(np.asarray(flags, dtype=np.int32).reshape(-1)) if (flags is not None and self.fastq) else None
+        qual1d = np.zeros(len(seq1d), dtype=np.uint8) if self.fastq else None
+        qual = np.zeros(len(seq), dtype=np.uint8) if self.fastq else None
+        qst = np.zeros(4 * max(P, 1), dtype=np.int32) if self.fastq else None
+        ptr = _marshal.ptr
+        _lib.check(call(ptr(idx), P, ptr(seq1d), ptr(s1o), ptr(l1), ptr(l2), ptr(ident), ptr(seq), ptr(so), ptr(ln), ptr(st), ptr(lg),
+                        ptr(ub), ptr(qual1d), ptr(qual), ptr(qst)), what)
+        recs = []
+        _marshal.pair_records(recs, seq1d, s1o, seq, so, l1, l2, ln, st, ident, None, o1, strict=False)(0, P)
+        res = {"records": recs}
+        if want_logits:
+            rows = lens if kept is None else [max(int(k), 0) for k in kept]
+            named = {r for ab in pairs for r in ab}
+            res["logits"] = [lg[off[i]:off[i] + rows[i]] if i in named else None for i in range(n)]
+        if self.fastq:
+            from .. import quality
+            res["fields"] = quality.pair_fields(recs, s1o, so, qual1d, qual, qst)
+        return res
+
+    def run_f32(self, sigs, pairs, want_logits=False, flags=None):
+        """a dict: records (batch.pair_decode_batch's, one per pair), and where made logits (per read (T, 5) float32, None for
+        a read no pair names) and fields (quality.pair_fields' dicts).  flags (a fastq engine): per pair the four items'
+        "no band" flags"""
+        n = len(sigs)
+        off = _marshal.offsets([len(s) for s in sigs])
+        signal = np.ascontiguousarray(np.concatenate(sigs) if n else np.zeros(0), dtype=np.float32)
+        call = lambda *a: self.lib.po_pair_basecaller_run_f32(self.h, signal.ctypes.data, off.ctypes.data, n, *a)
+        return self._run("po_pair_basecaller_run_f32", call, [len(s) for s in sigs], off, pairs, want_logits, flags)
+
+    def run_raw(self, raws, pairs, offsets=None, alphas=None, want_logits=False, flags=None):
+        """run_f32's dict from raw int16 reads, with "kept": the samples each read kept (its logits' rows; -1 for a read no
+        pair names).  A pair that names a read which kept nothing has status E_ARG."""
+        n = len(raws)
+        off = _marshal.offsets([len(r) for r in raws])
+        raw = np.ascontiguousarray(np.concatenate(raws) if n else np.zeros(0), dtype=np.int16)
+        o = np.ascontiguousarray(offsets, dtype=np.float64) if offsets is not None else None
+        a = np.ascontiguousarray(alphas, dtype=np.float64) if alphas is not None else None
+        kept = np.zeros(max(n, 1), dtype=np.int64)
+        call = lambda *x: self.lib.po_pair_basecaller_run_raw(self.h, raw.ctypes.data, off.ctypes.data, n,
+                                                              o.ctypes.data if o is not None else None,
+                                                              a.ctypes.data if a is not None else None, *x, kept.ctypes.data)
+        res = self._run("po_pair_basecaller_run_raw", call, [len(r) for r in raws], off, pairs, want_logits, flags, kept=kept[:n])
+        res["kept"] = kept[:n]
+        return res
+
+    def stats(self):
+        """per worker: dict(device, pairs, reads, samples, groups, busy_ms) of the last run"""
+        out = []
+        for i, d in enumerate(self.devices):
+            p, r, s, g, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
+            _lib.check(self.lib.po_pair_basecaller_stats(self.h, i, C.byref(p), C.byref(r), C.byref(s), C.byref(g), C.byref(ms)),
+                       "po_pair_basecaller_stats")
+            out.append({"device": d, "pairs": p.value, "reads": r.value, "samples": s.value, "groups": g.value, "busy_ms": ms.value})
+        return out
+
+
+def _stream(what, make, run, pairs, n_reads, logits, qualities, band, worker_stats=None, engines=None):
+    """pair_basecall_signals' results over the engine: make(fastq, band) -> PairBasecaller; run(engine, which, want_logits,
+    flags) -> its dict for the pairs at positions `which` with "reads", the indices of the reads it was given.  The unbanded
+    retry, the check and the warning are pair_basecall_signals'.  engines (a dict, or None): the caller's engines by
+    (fastq, band), made here when first needed and left open for its later calls; without it an engine lives for this call."""
+    results, read_logits = [None] * len(pairs), [None] * n_reads
+
+    def go(which, fastq, band_, want_logits, flags):
+        band_ = int(band_ or 0)
+        key = (bool(fastq), band_)
+        eng = engines.get(key) if engines is not None else None
+        if eng is None:
+            eng = make(fastq, band_)
+            if engines is not None:
+                engines[key] = eng
+        try:
+            r = run(eng, which, want_logits, flags)
+            if worker_stats is not None:
+                worker_stats.append(eng.stats())
+        finally:
+            if engines is None:
+                eng.close()
+        return r
+
+    if not pairs:
+        return results, read_logits
+    every = list(range(len(pairs)))
+    r = go(every, qualities, band if qualities else 0, logits, None)
+    results = r["records"]
+    if logits:
+        for j, i in enumerate(r["reads"]):
+            read_logits[i] = r["logits"][j]
+    if qualities:
+        from .. import quality
+        fields = r["fields"]
+        retry = quality.pair_retry_flags(fields, band)
+        if retry:
+            which = sorted(retry)
+            r2 = go(which, True, band, False, [retry[k] for k in which])
+            for j, k in enumerate(which):
+                if any(r2["records"][j][key] != results[k][key] for key in ("status", "seq1", "seq2", "consensus")):
+                    raise RuntimeError("%s: pair %d decodes differently in the unbanded retry" % (what, k))
+                quality.pair_retry_merge(fields[k], r2["fields"][j], retry[k])
+        quality.pair_warn_unscored(fields)
+        for rec, f in zip(results, fields):
+            if f is not None:
+                rec.update(f)
+    return results, read_logits
+
+
+def _compact(pairs, which):
+    """the distinct reads of the pairs at `which`, ascending, and those pairs indexed into them"""
+    reads = sorted({r for k in which for r in pairs[k]})
+    local = {r: j for j, r in enumerate(reads)}
+    return reads, [(local[pairs[k][0]], local[pairs[k][1]]) for k in which]
+
+
+def close_engines(engines):
+    for eng in engines.values():
+        eng.close()
+    engines.clear()
+
+
+def pair_basecall_raw(net, raws, pairs, channels=None, scaling="standard", devices=(0,), window=1000, overlap=0,
+                      reverse_complement=False, merge_repeats=False, beam_width=5, method="row_col", padding=5, alignment="banded",
+                      diagonal_envelope=False, diagonal_width=50, logits=False, max_windows_per_pass=0, precision="f32",
+                      qualities=False, qual_band=None, recurrence="f32", lo=200, hi=800, resident_bytes=None, worker_stats=None,
+                      engines=None, kept=None):
+    """pair_basecall_signals(..., devices=devices) from RAW int16 reads: the abasic filter (lo < x < hi) and `scaling` run on
+    the device (po_signal_prep_h's rule) inside the engine's groups.  channels: per read (offset,
+    digitisation, range), read for scaling "current" alone.  A read's logits have one row per KEPT sample.  A pair that
+    names a read which keeps nothing (an empty one included) is not decoded: its record has status E_ARG and lengths 0.
+    kept (a list): gets the kept samples of every read appended (-1 for a read no pair names: it was not prepared)."""
+    _lib._precision_code(precision)
+    _lib._recur_code(recurrence)
+    opt, band = _check_decoder("pair_basecall_raw", merge_repeats, beam_width, method, padding, alignment, diagonal_envelope,
+                               diagonal_width, qualities, qual_band)
+    _basecall.window_plan(1, window, overlap)
+    _basecall.check_time_order(net.kinds)
+    raws = [np.asarray(r) for r in raws]
+    for i, r in enumerate(raws):
+        if r.dtype != np.int16 or r.ndim != 1:
+            raise ValueError("pair_basecall_raw: read %d is %s of %d dimension(s), not a vector of int16" % (i, r.dtype, r.ndim))
+    if scaling == "current" and (channels is None or len(channels) != len(raws)):
+        raise ValueError("pair_basecall_raw: scaling 'current' needs (offset, digitisation, range) of every read")
+    pairs = _check_pairs("pair_basecall_raw", pairs, len(raws))
+    rb = _basecall.RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
+    counts = [-1] * len(raws)
+
+    def make(fastq, band_):
+        return PairBasecaller(net, devices, window, overlap, reverse_complement, opt, max_windows_per_pass, fastq, band_, scaling,
+                              lo, hi, rb)
+
+    def run(eng, which, want_logits, flags):
+        reads, local = _compact(pairs, which)
+        cur = scaling == "current"
+        r = eng.run_raw([raws[i] for i in reads], local, [channels[i][0] for i in reads] if cur else None,
+                        [channels[i][1] / channels[i][2] for i in reads] if cur else None, want_logits, flags)
+        for j, i in enumerate(reads):
+            counts[i] = int(r["kept"][j])
+        r["reads"] = reads
+        return r
+
+    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
+        results, read_logits = _stream("pair_basecall_raw", make, run, pairs, len(raws), logits, qualities, band, worker_stats, engines)
+    if kept is not None:
+        kept.extend(counts)
+    return (results, read_logits) if logits else results
+
+
+def _check_decoder(what, merge_repeats, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width, qualities,
+                   qual_band):
+    """the pair decoder's options as pair_basecall_signals checks them: (PairOptions, band or None)"""
+    band = None
+    if not qualities and qual_band is not None:
+        raise ValueError("%s: qual_band is an option of qualities=True" % what)
+    if qualities:
+        from .. import quality
+        band = quality.check_band(what, qual_band)
+    if method not in _lib.METHODS:
+        raise ValueError("%s: method %r (row_col, row or grid; the split method is not built here)" % (what, method))
+    if alignment not in ("banded", "full"):
+        raise ValueError("%s: alignment %r (banded or full)" % (what, alignment))
+    if not 1 <= int(beam_width) <= 25:
+        raise ValueError("%s: beam_width %d (1 to 25)" % (what, beam_width))
+    kind = "bonito" if merge_repeats else "poreover"
+    return _marshal.pair_options(kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width), band
+
+
+def _check_pairs(what, pairs, n_reads):
+    pairs = [tuple(p) for p in pairs]
+    for k, p in enumerate(pairs):
+        if len(p) != 2:
+            raise ValueError("%s: pair %d has %d entries (two read indices)" % (what, k, len(p)))
+        for r in p:
+            if not (isinstance(r, (int, np.integer)) and 0 <= r < n_reads):
+                raise ValueError("%s: pair %d names read %r (reads 0 to %d)" % (what, k, r, n_reads - 1))
+    return [(int(a), int(b)) for a, b in pairs]
 
 
 def pair_tables(logits, pairs, reverse2=False, perm2=None):
@@ -151,7 +423,8 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
 def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_complement=False, merge_repeats=False,
                           beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
                           diagonal_width=50, logits=False, stage_ms=None, max_windows_per_pass=0, precision="f32",
-                          qualities=False, qual_band=None, odds=False, recurrence="f32", skip_matches=False, skip_threshold=10):
+                          qualities=False, qual_band=None, odds=False, recurrence="f32", skip_matches=False, skip_threshold=10,
+                          devices=None, resident_bytes=None, worker_stats=None, engines=None):
     """The 1D² consensus of each pair (i, j) of scaled signals, in input order: one dict per pair with the keys of
     batch.pair_decode_batch — status (0, SKIP_LENGTH, SKIP_IDENTITY or an engine code for that pair alone), seq1, seq2,
     consensus (None unless status is 0), length1, length2, sequence_identity (None for a length skip), skipped.  With
@@ -173,9 +446,19 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
     The records of pairs that are not decoded are unchanged; stage_ms then has _lib.PAIR_BASECALL_FASTQ_STAGES.
     skip_matches=True (po_pair_basecall_skip_batch_h): pair-decode --skip_matches' consensus — runs of at least
     skip_threshold matching alignment columns are copied from the 1-D basecalls, the boxes between them decoded — with the
-    statuses E_NO_ANCHOR / E_BOX where the reference raises; not together with qualities or diagonal_envelope."""
+    statuses E_NO_ANCHOR / E_BOX where the reference raises; not together with qualities or diagonal_envelope.
+    devices (a list of device indices): the pairs go through a PairBasecaller — po_pair_basecaller: one
+    worker per listed device, groups of at most resident_bytes (None: basecall.RESIDENT_BYTES) dealt to whichever is free —
+    with the same records, logits and qualities, bit for bit; worker_stats (a list) gets PairBasecaller.stats() of every
+    engine run appended; engines (a dict the caller keeps, then closes with close_engines): the engines are made once, by
+    (qualities, band), and serve every later call with the same dict.  Not together with skip_matches or odds (the engine
+    carries neither); stage_ms is not filled.  Without devices nothing changes."""
     _lib._precision_code(precision)
     _lib._recur_code(recurrence)
+    if devices is not None and skip_matches:
+        raise ValueError("pair_basecall_signals: skip_matches is not carried by the engine (devices=%r)" % (devices,))
+    if devices is not None and odds:
+        raise ValueError("pair_basecall_signals: odds are not returned by the engine (devices=%r)" % (devices,))
     if not qualities and (qual_band is not None or odds):
         raise ValueError("pair_basecall_signals: qual_band and odds are options of qualities=True")
     if skip_matches and qualities:
@@ -207,6 +490,25 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
                 raise ValueError("pair_basecall_signals: pair %d: read %d has no samples" % (k, r))
     pairs = [(int(a), int(b)) for a, b in pairs]
     results, read_logits = [None] * len(pairs), [None] * len(sigs)
+    if devices is not None:
+        opt = _marshal.pair_options("bonito" if merge_repeats else "poreover", beam_width, method, padding, alignment,
+                                    diagonal_envelope, diagonal_width)
+        rb = _basecall.RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
+
+        def make(fastq, band_):
+            return PairBasecaller(net, devices, window, overlap, reverse_complement, opt, max_windows_per_pass, fastq, band_,
+                                  resident_bytes=rb)
+
+        def run_engine(eng, which, want_logits, flags):
+            reads, local = _compact(pairs, which)
+            r = eng.run_f32([sigs[i] for i in reads], local, want_logits, flags)
+            r["reads"] = reads
+            return r
+
+        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
+            results, read_logits = _stream("pair_basecall_signals", make, run_engine, pairs, len(sigs), logits, qualities,
+                                           band if qualities else 0, worker_stats, engines)
+        return (results, read_logits) if logits else results
     if pairs:
         lib = _lib.load()
         kind = "bonito" if merge_repeats else "poreover"
@@ -317,6 +619,12 @@ def pair_basecall(args):
     writes {out}.1d.fasta, {out}.2d.fasta and {out}.log as `pair-decode` does for a list of pairs"""
     from ..decoding import pair_decode as _pd
     check_args(args)
+    gpus = getattr(args, "gpus", None)
+    if gpus is not None:   # the streaming flags, before the weights or any file are read
+        _basecall.check_readers(getattr(args, "readers", _basecall.DEFAULT_READERS), "pair-basecall")
+        if getattr(args, "chunk_pairs", DEFAULT_CHUNK_PAIRS) < 1:
+            raise SystemExit("pair-basecall: --chunk_pairs %d must be 1 at least" % args.chunk_pairs)
+        devices = _basecall.stream_devices(gpus, "pair-basecall")
     with open(getattr(args, "in"), "r") as f:
         names = [line.split() for line in f if line.split()]
     for k, p in enumerate(names):
@@ -333,6 +641,8 @@ def pair_basecall(args):
                 order.append(path)
     logging.getLogger("poreover_amd").info("found {} read pairs in {}".format(len(names), getattr(args, "in")))
     net = load_model(args)
+    if gpus is not None:
+        return _pair_basecall_stream(args, net, names, devices)
     signals = [parse_fast5(path, scaling=args.scaling)[1] for path in order]   # each distinct file once
     pairs = [(files[resolve_read(a, args.dir)], files[resolve_read(b, args.dir)]) for a, b in names]
     for k, (a, b) in enumerate(pairs):
@@ -347,4 +657,72 @@ def pair_basecall(args):
                                 recurrence=getattr(args, "recurrence", "f32"))
     records = [_pd.pair_record(p, Path(order[a]).stem, Path(order[b]).stem, r, args) for p, (a, b), r in zip(names, pairs, res)]
     _pd.write_pair_files(records, args)
+    return records
+
+
+def stream_chunks(names, resolve, read, run, emit, chunk_pairs=DEFAULT_CHUNK_PAIRS, readers=_basecall.DEFAULT_READERS):
+    """The chunked driver of `pair-basecall --gpus`, with its parts handed in.  names: the pairs file's lines (two names
+    each), cut into chunks of chunk_pairs lines.  `readers` threads read chunk k + 1's distinct files — read(resolve(name)),
+    a file that a chunk names twice once, a file that two chunks name in each — while run(parsed, pairs) works on chunk k:
+    parsed are the chunk's files in first-seen order, pairs the chunk's index pairs into them.  emit(lines, paths, pairs,
+    results) gets each chunk in input order as it completes.  Two chunks' reads are in memory at most."""
+    from concurrent.futures import ThreadPoolExecutor
+    per = max(1, int(chunk_pairs))
+    chunks = [names[i:i + per] for i in range(0, len(names), per)]
+
+    def plan(chunk):
+        files, order = {}, []
+        for p in chunk:
+            for name in p:
+                path = resolve(name)
+                if path not in files:
+                    files[path] = len(order)
+                    order.append(path)
+        return order, [(files[resolve(a)], files[resolve(b)]) for a, b in chunk]
+
+    with ThreadPoolExecutor(max_workers=readers) as pool:
+        def start(chunk):
+            order, pairs = plan(chunk)
+            return order, pairs, [pool.submit(read, path) for path in order]
+
+        nxt = start(chunks[0]) if chunks else None
+        for c, chunk in enumerate(chunks):
+            order, pairs, pending = nxt
+            parsed = [p.result() for p in pending]
+            nxt = start(chunks[c + 1]) if c + 1 < len(chunks) else None
+            del pending
+            emit(chunk, order, pairs, run(parsed, pairs))
+            del parsed
+
+
+def _pair_basecall_stream(args, net, names, devices):
+    """`pair-basecall --gpus`: stream_chunks with read_fast5_raw as the reader (filter and scaling run on the device) and
+    one engine for the whole run; each chunk's records are appended to {out}.1d.fasta, {out}.2d.fasta and {out}.log."""
+    from ..decoding import pair_decode as _pd
+    engines = {}
+    settings = {k: v for k, v in vars(args).items() if k not in ("readers", "chunk_pairs")}   # (how the files are read: no part of the result)
+    records = []
+
+    def run(parsed, pairs):
+        return pair_basecall_raw(net, [p[1] for p in parsed], pairs, [p[2:5] for p in parsed], scaling=args.scaling, devices=devices,
+                                 window=args.window, overlap=args.overlap, reverse_complement=args.reverse_complement,
+                                 merge_repeats=args.merge_repeats, beam_width=args.beam_width, method=args.beam_search_method,
+                                 padding=args.padding, alignment=args.alignment, diagonal_envelope=args.diagonal_envelope,
+                                 diagonal_width=args.diagonal_width, precision=getattr(args, "precision", "f32"),
+                                 recurrence=getattr(args, "recurrence", "f32"), engines=engines)
+
+    with open(args.out + '.1d.fasta', 'w') as f1, open(args.out + '.2d.fasta', 'w') as f2, open(args.out + '.log', 'w', 1) as log_f:
+        _pd.write_pair_header(log_f, settings)
+
+        def emit(lines, paths, pairs, res):
+            recs = [_pd.pair_record(p, Path(paths[a]).stem, Path(paths[b]).stem, r, args) for p, (a, b), r in zip(lines, pairs, res)]
+            _pd.write_pair_records(recs, f1, f2, log_f)
+            records.extend(recs)
+
+        try:
+            stream_chunks(names, lambda name: resolve_read(name, args.dir), read_fast5_raw, run, emit,
+                          getattr(args, "chunk_pairs", DEFAULT_CHUNK_PAIRS), getattr(args, "readers", _basecall.DEFAULT_READERS))
+        finally:
+            close_engines(engines)
+    logging.getLogger("poreover_amd").info("pair-basecall: %d pair(s) on device(s) %s", len(names), ", ".join(map(str, devices)))
     return records
