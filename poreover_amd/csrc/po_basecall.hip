@@ -263,18 +263,7 @@ struct PoBasecallResident {
 
 PoBasecallResident* po_basecall_resident_new() { return new PoBasecallResident; }
 void po_basecall_resident_free(PoBasecallResident* st) { delete st; }
-
-int po_basecall_resident_weights(PoBasecallResident* st, const float* weights_h, int64_t n_weights) {
-    PO_HIPCHK(st->net.w.up(weights_h, (size_t)n_weights * 4));
-    st->net.w_up = true;
-    return PO_OK;
-}
-
-int po_basecall_resident_signal(PoBasecallResident* st, int64_t samples, float** signal) {
-    PO_HIPCHK(st->net.sig.up(nullptr, (size_t)samples * 4));
-    *signal = st->net.sig.as<float>();
-    return PO_OK;
-}
+PoBasecallPasses& po_basecall_resident_net(PoBasecallResident* st) { return st->net; }
 
 // po_basecall_batch_h (fq == NULL) and po_basecall_fastq_batch_h under their own names, and a po_basecaller's groups
 int po_basecall_body(PoBasecallResident* st, hipStream_t stream, bool signal_resident, const char* name, const float* signal_h,

@@ -49,6 +49,18 @@ struct PoBasecallPasses {
     // kernels are bracketed in `stitch`
     int run(const PoBasecallPlan& plan, int window, int overlap, const po_call_layer* layers_h, int n_layers, int64_t n_weights,
             hipStream_t stream, float* stage_ms_h, PoSpans& stitch);
+    // an engine's resident state.  The weights, once: up() then leaves them where they are
+    int weights_resident(const float* weights_h, int64_t n_weights) {
+        PO_HIPCHK(w.up(weights_h, (size_t)n_weights * 4));
+        w_up = true;
+        return PO_OK;
+    }
+    // `sig` with room for `samples` f32 values: where po_launch_signal_prep writes for a body call with signal_resident
+    int signal_room(int64_t samples, float** signal) {
+        PO_HIPCHK(sig.up(nullptr, (size_t)samples * 4));
+        *signal = sig.as<float>();
+        return PO_OK;
+    }
 };
 
 // ---- the body of po_basecall_batch_h / po_basecall_fastq_batch_h (po_basecall.hip) on a state that may outlive the call.
@@ -61,11 +73,7 @@ struct PoBasecallFastq {   // what po_basecall_fastq_batch_h adds to po_basecall
 struct PoBasecallResident;
 PoBasecallResident* po_basecall_resident_new();
 void po_basecall_resident_free(PoBasecallResident* st);
-// the weights, once: the body then leaves them where they are
-int po_basecall_resident_weights(PoBasecallResident* st, const float* weights_h, int64_t n_weights);
-// the state's signal buffer with room for `samples` f32 values: where po_launch_signal_prep writes for a body call with
-// signal_h == NULL (signal_resident)
-int po_basecall_resident_signal(PoBasecallResident* st, int64_t samples, float** signal);
+PoBasecallPasses& po_basecall_resident_net(PoBasecallResident* st);
 int po_basecall_body(PoBasecallResident* st, hipStream_t stream, bool signal_resident, const char* name, const float* signal_h,
                      const int64_t* sig_off_h, int n_reads, int window, int overlap, const po_call_layer* layers_h, int n_layers,
                      const float* weights_h, int64_t n_weights, const char* alphabet, int kind, int beam_width, int model,

@@ -1,52 +1,23 @@
-// po_basecaller: `basecall` over one or several devices of a node.  One object holds the model, the
-// decoder's options and one worker per listed device: its resident state (po_basecall_pass.h: the weights, uploaded once
-// at create, and every buffer of the body, grow-only between groups and runs), its stream and the raw route's buffers.  A
-// run cuts the reads, in input order, into groups (po_basecall_group_plan) and deals them from one planner under a mutex
-// to one host thread per worker, whichever is free.  A group runs po_basecall_body — the body of po_basecall_batch_h /
-// po_basecall_fastq_batch_h; a read's bits do not depend on its batch, DESIGN.md §16.3 — on the worker's state and stream.
-// On the raw route the int16 samples go up, po_launch_signal_prep writes the f32 signal into the state's signal buffer,
-// the kept counts (per-read words) come back for the window plan, and the body runs on the signal where it lies.  Results
-// land in the caller's arrays at the reads' own indices.  The error message is thread-local (po_capi.hip) and carried from
-// the worker to the caller.
-//
-// Streams: a worker's stream is a blocking one (hipStreamCreate), so the body's blocking copies, which are null-stream
-// work, are ordered against it in both directions; the body synchronises the stream before its downloads.
+// po_basecaller: `basecall` over one or several devices of a node, on the engine layer (po_engine.h).  Its
+// items are reads; a group is a contiguous run of them (po_basecall_group_plan) and runs po_basecall_body — the body of
+// po_basecall_batch_h / po_basecall_fastq_batch_h; a read's bits do not depend on its batch, DESIGN.md §16.3.  On the raw
+// route the kept counts are per-read words, and a read that kept nothing is left out of the body's call.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "po_basecall_pass.h"
-#include "po_hostbuf.h"
-#include "po_prep_rules.h"
+#include "po_engine.h"
 
-namespace {
-constexpr int NOUT = 5;
-constexpr int MAX_WORKERS = 16;
-constexpr int64_t DEFAULT_RESIDENT = (int64_t)16 << 30;
-}  // namespace
-
-struct PoBasecallWorker {
-    int dev = 0;
+struct PoBasecallWorker : PoEngineWorker {
     PoBasecallResident* st = nullptr;
-    hipStream_t stream = nullptr;
-    PoDev raw, raw_off, slab_off, slab_read, offset, alpha, sig_off, stats, ws;   // the raw route's, grow-only
 };
 
-struct po_basecaller {
-    std::vector<PoBasecallWorker*> workers;
-    std::vector<int> devices;
-    std::vector<po_call_layer> layers;
-    std::vector<float> weights;
+struct po_basecaller : PoEngine<PoBasecallWorker> {
     std::string alphabet;
     bool has_alphabet = false;
     po_basecaller_options opt;
     int64_t budget_samples = 1;     // resident bytes / resident bytes per sample
     struct Stat { int64_t reads = 0, samples = 0; int groups = 0; double busy_ms = 0; };
-    std::vector<Stat> stats;
+    std::vector<Stat> stats;        // per worker, of the last run
 };
 
 // Groups are contiguous runs of reads in input order, of at most `group_samples` samples (at least one read: a longer
@@ -100,10 +71,6 @@ struct Run {
     char* qual; int32_t* qual_status; int64_t* kept;
     std::vector<int32_t> first, count;
     const char* name = "";
-    std::mutex mu;
-    int next = 0;
-    int rc = PO_OK, rc_worker = -1;
-    std::string msg;
 };
 
 // one group through the body on the worker's state and stream: c reads, their offsets from 0 in so; sig == NULL: the signal
@@ -130,36 +97,11 @@ int run_group_f32(Run& r, PoBasecallWorker& w, int f, int c) {
 // raw route: prepare, leave out the reads that kept nothing, call, and put every read's results at its own raw offsets
 int run_group_raw(Run& r, PoBasecallWorker& w, int f, int c) {
     const po_basecaller_options& o = r.b->opt;
-    std::vector<int64_t> ro((size_t)c + 1), ko((size_t)c + 1, 0);
+    std::vector<int64_t> ro((size_t)c + 1), ko;
     for (int i = 0; i <= c; ++i) ro[i] = r.off[f + i] - r.off[f];
-    PoPrepPlan plan;
-    std::string err;
-    int rc = po_prep_make_plan(ro.data(), c, o.scaling, o.lo, o.hi, &plan, &err, r.name);
-    if (rc != PO_OK) return po_fail(rc, err);
-    if (plan.total > 0) {   // int16 up, the f32 signal made where the body reads it, the kept counts back
-        const int64_t slabs = (int64_t)plan.slab_read.size();
-        const size_t wsb = po_prep_workspace_bytes(c, slabs, plan.bins);
-        float* sig = nullptr;
-        PO_HIPCHK(w.raw.up(r.raw + r.off[f], (size_t)plan.total * 2));
-        PO_HIPCHK(w.raw_off.up(ro.data(), sizeof(int64_t) * ro.size()));
-        PO_HIPCHK(w.slab_off.up(plan.slab_off.data(), sizeof(int64_t) * plan.slab_off.size()));
-        PO_HIPCHK(w.slab_read.up(plan.slab_read.data(), sizeof(int32_t) * plan.slab_read.size()));
-        if (r.offset) {
-            PO_HIPCHK(w.offset.up(r.offset + f, sizeof(double) * c));
-            PO_HIPCHK(w.alpha.up(r.alpha + f, sizeof(double) * c));
-        }
-        PO_HIPCHK(w.sig_off.up(nullptr, sizeof(int64_t) * ((size_t)c + 1)));
-        PO_HIPCHK(w.stats.up(nullptr, sizeof(po_prep_stats) * (size_t)c));
-        PO_HIPCHK(w.ws.up(nullptr, wsb));
-        rc = po_basecall_resident_signal(w.st, plan.total, &sig);
-        if (rc != PO_OK) return rc;
-        rc = po_launch_signal_prep(w.raw, w.raw_off, c, plan.total, w.slab_off, w.slab_read, slabs, o.scaling, o.lo, o.hi,
-                                   r.offset ? w.offset.as<double>() : nullptr, r.offset ? w.alpha.as<double>() : nullptr, sig, w.sig_off,
-                                   w.stats, w.ws, wsb, w.stream);
-        if (rc != PO_OK) return rc;
-        PO_HIPCHK(hipMemcpyAsync(ko.data(), w.sig_off.p, sizeof(int64_t) * ((size_t)c + 1), hipMemcpyDeviceToHost, w.stream));
-        PO_HIPCHK(hipStreamSynchronize(w.stream));
-    }
+    int rc = w.prepare_raw(r.raw + r.off[f], ro.data(), c, r.offset ? r.offset + f : nullptr, r.offset ? r.alpha + f : nullptr,
+                           o.scaling, o.lo, o.hi, r.name, po_basecall_resident_net(w.st), ko);
+    if (rc != PO_OK) return rc;
     std::vector<int> idx;                 // the group's reads that kept a sample
     std::vector<int64_t> so(1, 0);
     for (int i = 0; i < c; ++i) {
@@ -194,32 +136,6 @@ int run_group_raw(Run& r, PoBasecallWorker& w, int f, int c) {
     return PO_OK;
 }
 
-void worker(Run* r, int w) {
-    po_basecaller::Stat& s = r->b->stats[w];
-    PoBasecallWorker& wk = *r->b->workers[w];
-    int rc = po_set_device(wk.dev);
-    for (;;) {
-        int g = -1;
-        {
-            std::lock_guard<std::mutex> lk(r->mu);
-            if (rc != PO_OK && r->rc == PO_OK) {          // the first failure: the others finish what they hold, take no more
-                r->rc = rc;
-                r->rc_worker = w;
-                r->msg = po_last_error();
-            }
-            if (r->rc == PO_OK && r->next < (int)r->first.size()) g = r->next++;
-        }
-        if (g < 0) return;
-        const int f = r->first[g], c = r->count[g];
-        const auto t0 = std::chrono::steady_clock::now();
-        rc = r->raw ? run_group_raw(*r, wk, f, c) : run_group_f32(*r, wk, f, c);
-        s.busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        s.groups += 1;
-        s.reads += c;
-        s.samples += r->off[f + c] - r->off[f];
-    }
-}
-
 int run(Run& r, const char* name) {
     po_basecaller* b = r.b;
     r.name = name;
@@ -227,7 +143,7 @@ int run(Run& r, const char* name) {
     if (r.n == 0) return PO_OK;
     std::vector<int64_t> len((size_t)r.n);
     for (int i = 0; i < r.n; ++i) len[i] = r.off[i + 1] - r.off[i];
-    const int ndev = (int)b->devices.size();
+    const int ndev = (int)b->workers.size();
     const int64_t gs = po_basecall_group_samples(r.off[r.n], b->budget_samples, ndev);
     r.first.resize((size_t)r.n);
     r.count.resize((size_t)r.n);
@@ -235,11 +151,12 @@ int run(Run& r, const char* name) {
     if (ng < 0) return ng;
     r.first.resize((size_t)ng);
     r.count.resize((size_t)ng);
-    std::vector<std::thread> th;
-    for (int w = 0; w < ndev; ++w) th.emplace_back(worker, &r, w);
-    for (auto& t : th) t.join();
-    if (r.rc != PO_OK) return po_fail(r.rc, "device " + std::to_string(b->devices[r.rc_worker]) + ": " + r.msg);
-    return PO_OK;
+    return po_engine_run(b, ng, [&r](PoBasecallWorker& w, po_basecaller::Stat& s, int g) {
+        const int f = r.first[g], c = r.count[g];
+        s.reads += c;
+        s.samples += r.off[f + c] - r.off[f];
+        return r.raw ? run_group_raw(r, w, f, c) : run_group_f32(r, w, f, c);
+    });
 }
 
 // the offsets' and pointers' checks of a run, before any work: tables from 0, non-decreasing, room for every read
@@ -250,8 +167,9 @@ int check_run(const std::string& me, const void* data, const char* data_name, co
     const char* null = !data ? data_name : !off ? off_name : !seq ? "seq_h" : !seq_off ? "seq_off_h" : !seq_len ? "seq_len_h" :
                        !status ? "status_h" : fastq && !qual ? "qual_h" : fastq && !qual_status ? "qual_status_h" : nullptr;
     if (null) return po_fail(PO_E_ARG, me + "null argument " + null);
-    if (off[0] != 0 || seq_off[0] != 0)
-        return po_fail(PO_E_ARG, me + (off[0] ? std::string(off_name) + "[0] is " + std::to_string(off[0]) : "seq_off[0] is " + std::to_string(seq_off[0])) + " (must be 0)");
+    int rc = po_engine_check_from_zero(me, off, off_name);
+    if (rc == PO_OK) rc = po_engine_check_from_zero(me, seq_off, "seq_off");
+    if (rc != PO_OK) return rc;
     for (int i = 0; i < n; ++i) {
         const int64_t L = off[i + 1] - off[i];
         if (L < (empty_ok ? 0 : 1) || L > INT32_MAX)
@@ -270,20 +188,7 @@ extern "C" po_basecaller* po_basecaller_create(const int* devices, int ndev, con
                                                const po_basecaller_options* opt) {
     const std::string me = "po_basecaller_create: ";
     po_set_error("");
-    if (!devices || !layers_h || !weights_h || !opt) {
-        po_fail(PO_E_ARG, me + "null argument " + (!devices ? "devices" : !layers_h ? "layers_h" : !weights_h ? "weights_h" : "options"));
-        return nullptr;
-    }
-    if (ndev < 1 || ndev > MAX_WORKERS) {
-        po_fail(PO_E_ARG, me + "ndev " + std::to_string(ndev) + " (1 to " + std::to_string(MAX_WORKERS) + ")");
-        return nullptr;
-    }
-    const int nd = po_device_count();
-    for (int i = 0; i < ndev; ++i)
-        if (devices[i] < 0 || devices[i] >= nd) {
-            po_fail(PO_E_ARG, me + "device " + std::to_string(devices[i]) + " (0 to " + std::to_string(nd - 1) + ")");
-            return nullptr;
-        }
+    if (po_engine_check_devices(me, devices, ndev, layers_h, weights_h, opt) != PO_OK) return nullptr;
     // every argument error of the single-device entry, by that entry (no reads: it stops after its checks)
     {
         const int64_t zero = 0;
@@ -298,37 +203,16 @@ extern "C" po_basecaller* po_basecaller_create(const int* devices, int ndev, con
                                                         &w, &w, nullptr, nullptr);
         if (rc != PO_OK) return nullptr;
     }
-    {   // the raw route's scaling and range (po_signal_prep_h's messages)
-        const int64_t zero = 0;
-        PoPrepPlan plan;
-        std::string err;
-        const int rc = po_prep_make_plan(&zero, 0, opt->scaling, opt->lo, opt->hi, &plan, &err, "po_basecaller_create");
-        if (rc != PO_OK) { po_fail(rc, err); return nullptr; }
-    }
-    if (opt->resident_bytes < 0) { po_fail(PO_E_ARG, me + "resident_bytes " + std::to_string(opt->resident_bytes)); return nullptr; }
+    if (po_engine_check_options("po_basecaller_create", opt->scaling, opt->lo, opt->hi, opt->resident_bytes) != PO_OK) return nullptr;
     po_basecaller* b = new po_basecaller;
-    b->devices.assign(devices, devices + ndev);
-    b->layers.assign(layers_h, layers_h + n_layers);
-    b->weights.assign(weights_h, weights_h + n_weights);
     if (alphabet) { b->alphabet = alphabet; b->has_alphabet = true; }
     b->opt = *opt;
     b->budget_samples = std::max<int64_t>(1, (opt->resident_bytes ? opt->resident_bytes : DEFAULT_RESIDENT) / bytes_per_sample(*opt));
     b->stats.resize((size_t)ndev);
-    // a worker per listed device: its state, its stream, and the weights, uploaded here and never again
-    int before = 0;
-    (void)hipGetDevice(&before);
-    int rc = PO_OK;
-    for (int i = 0; i < ndev && rc == PO_OK; ++i) {
-        PoBasecallWorker* w = new PoBasecallWorker;
-        w->dev = devices[i];
-        b->workers.push_back(w);
-        rc = po_set_device(w->dev);
-        if (rc != PO_OK) break;
-        w->st = po_basecall_resident_new();
-        if (hipStreamCreate(&w->stream) != hipSuccess) { w->stream = nullptr; rc = po_fail(PO_E_HIP, me + "hipStreamCreate"); break; }
-        rc = po_basecall_resident_weights(w->st, weights_h, n_weights);
-    }
-    (void)hipSetDevice(before);
+    const int rc = po_engine_init(b, me, devices, ndev, layers_h, n_layers, weights_h, n_weights, [](PoBasecallWorker& w) -> PoBasecallPasses& {
+        w.st = po_basecall_resident_new();
+        return po_basecall_resident_net(w.st);
+    });
     if (rc != PO_OK) {
         const std::string msg = po_last_error();
         po_basecaller_destroy(b);
@@ -340,15 +224,7 @@ extern "C" po_basecaller* po_basecaller_create(const int* devices, int ndev, con
 
 extern "C" void po_basecaller_destroy(po_basecaller* b) {
     if (!b) return;
-    int before = 0;
-    (void)hipGetDevice(&before);
-    for (PoBasecallWorker* w : b->workers) {
-        (void)hipSetDevice(w->dev);
-        if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
-        if (w->st) po_basecall_resident_free(w->st);
-        delete w;      // (its buffers free themselves)
-    }
-    (void)hipSetDevice(before);
+    po_engine_free(b, po_basecall_resident_free);
     delete b;
 }
 
@@ -374,10 +250,9 @@ extern "C" int po_basecaller_run_raw(po_basecaller* b, const int16_t* raw_h, con
     const std::string me = "po_basecaller_run_raw: ";
     po_set_error("");
     if (!b) return po_fail(PO_E_ARG, me + "null argument basecaller");
-    if (!kept_h) return po_fail(PO_E_ARG, me + "null argument kept_h");
-    if (b->opt.scaling == PO_SCALE_CURRENT && (!offset_h || !alpha_h))
-        return po_fail(PO_E_ARG, me + "null argument " + (!offset_h ? "offset_h" : "alpha_h") + " (PO_SCALE_CURRENT)");
-    const int rc = check_run(me, raw_h, "raw_h", raw_off_h, "raw_off", n_reads, seq_h, seq_off_h, seq_len_h, status_h, b->opt.fastq != 0,
+    int rc = po_engine_check_raw_args(me, kept_h, b->opt.scaling, offset_h, alpha_h);
+    if (rc != PO_OK) return rc;
+    rc = check_run(me, raw_h, "raw_h", raw_off_h, "raw_off", n_reads, seq_h, seq_off_h, seq_len_h, status_h, b->opt.fastq != 0,
                              qual_h, qual_status_h, true);
     if (rc != PO_OK) return rc;
     Run r;

@@ -349,18 +349,7 @@ struct PoPairBasecallResident {
 
 PoPairBasecallResident* po_pair_basecall_resident_new() { return new PoPairBasecallResident; }
 void po_pair_basecall_resident_free(PoPairBasecallResident* st) { delete st; }
-
-int po_pair_basecall_resident_weights(PoPairBasecallResident* st, const float* weights_h, int64_t n_weights) {
-    PO_HIPCHK(st->net.w.up(weights_h, (size_t)n_weights * 4));
-    st->net.w_up = true;
-    return PO_OK;
-}
-
-int po_pair_basecall_resident_signal(PoPairBasecallResident* st, int64_t samples, float** signal) {
-    PO_HIPCHK(st->net.sig.up(nullptr, (size_t)samples * 4));
-    *signal = st->net.sig.as<float>();
-    return PO_OK;
-}
+PoBasecallPasses& po_pair_basecall_resident_net(PoPairBasecallResident* st) { return st->net; }
 
 // po_pair_basecall_batch_h (fq == NULL), po_pair_basecall_fastq_batch_h and po_pair_basecall_skip_batch_h under their own
 // names, and a po_pair_basecaller's groups

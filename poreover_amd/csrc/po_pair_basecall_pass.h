@@ -19,11 +19,7 @@ struct PoPairBasecallFastq {
 struct PoPairBasecallResident;
 PoPairBasecallResident* po_pair_basecall_resident_new();
 void po_pair_basecall_resident_free(PoPairBasecallResident* st);
-// the weights, once: the body then leaves them where they are
-int po_pair_basecall_resident_weights(PoPairBasecallResident* st, const float* weights_h, int64_t n_weights);
-// the state's signal buffer with room for `samples` f32 values: where po_launch_signal_prep writes for a body call with
-// signal_resident
-int po_pair_basecall_resident_signal(PoPairBasecallResident* st, int64_t samples, float** signal);
+PoBasecallPasses& po_pair_basecall_resident_net(PoPairBasecallResident* st);
 // signal_resident: signal_h is not read, the signal lies in the state's buffer, sig_off_h[n_reads] values from 0.
 // skip (or NULL): {skip_threshold, indel_threshold} of --skip_matches (its run workspace depends on the data and lives for
 // the call: not part of the state)

@@ -1,56 +1,25 @@
-// po_pair_basecaller: `pair-basecall` over one or several devices of a node.  One object holds the model,
-// the pair decoder's options and one worker per listed device: its resident state (po_pair_basecall_pass.h: the weights,
-// uploaded once at create, and every buffer of the body, grow-only between groups and runs), its stream and the raw route's
-// buffers.  A run cuts the pairs, in input order, into groups (po_pair_basecall_group_plan) and deals them from one planner
-// under a mutex to one host thread per worker, whichever is free.  A group's distinct reads are compacted and indexed
-// locally; it runs po_pair_basecall_body — the body of po_pair_basecall_batch_h / po_pair_basecall_fastq_batch_h; a
-// window's bits do not depend on its call, DESIGN.md §16.3, and a pair's chain reads its own two tables alone — on the
-// worker's state and stream.  On the raw route the int16 samples of the group's reads go up, po_launch_signal_prep writes
-// the f32 signal into the state's signal buffer, the kept counts come back for the window plan, and the body runs on the
-// signal where it lies; a pair that names a read which kept nothing is not run (PO_E_ARG in its status).  Results land in
-// the caller's arrays at the pairs' own indices; a read's logits and kept count are written by the first group that names
-// it.  The error message is thread-local (po_capi.hip) and carried from the worker to the caller.
-//
-// Streams: a worker's stream is a blocking one (hipStreamCreate), for the reason po_basecall_stream.hip gives: the body's
-// blocking copies are null-stream work and must be ordered against it in both directions.
-//
-// The slice pool of beam2d_reg_kernel (po_beam2d_route.hip) is one per device and is made by the workspace-size query on
-// the thread whose current device it is: the body makes that query (po_pair_decode_workspace_bytes) on the worker's own
-// thread, after po_set_device, before the group's first launch, so the launch path never allocates.
+// po_pair_basecaller: `pair-basecall` over one or several devices of a node, on the engine layer (po_engine.h, DESIGN.md
+// §17.6).  Its items are pairs; a group is a contiguous run of them (po_pair_basecall_group_plan).  A group's distinct reads
+// are compacted and indexed locally; it runs po_pair_basecall_body — the body of po_pair_basecall_batch_h /
+// po_pair_basecall_fastq_batch_h; a window's bits do not depend on its call, DESIGN.md §16.3, and a pair's chain reads its
+// own two tables alone.  On the raw route a pair that names a read which kept nothing is not run (PO_E_ARG in its status).
+// A read's logits and kept count are written by the first group that names it.  The body's slice-pool query (po_engine.h)
+// is po_pair_decode_workspace_bytes.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
 
+#include "po_engine.h"
 #include "po_pair_basecall_group_rules.h"
 #include "po_pair_basecall_pass.h"
-#include "po_hostbuf.h"
-#include "po_prep_rules.h"
 
-namespace {
-constexpr int NOUT = 5;
-constexpr int MAX_WORKERS = 16;
-constexpr int64_t DEFAULT_RESIDENT = (int64_t)16 << 30;
-}  // namespace
-
-struct PoPairBasecallWorker {
-    int dev = 0;
+struct PoPairBasecallWorker : PoEngineWorker {
     PoPairBasecallResident* st = nullptr;
-    hipStream_t stream = nullptr;
-    PoDev raw, raw_off, slab_off, slab_read, offset, alpha, sig_off, stats, ws;   // the raw route's, grow-only
 };
 
-struct po_pair_basecaller {
-    std::vector<PoPairBasecallWorker*> workers;
-    std::vector<int> devices;
-    std::vector<po_call_layer> layers;
-    std::vector<float> weights;
+struct po_pair_basecaller : PoEngine<PoPairBasecallWorker> {
     po_pair_basecaller_options opt;
     struct Stat { int64_t pairs = 0, reads = 0, samples = 0; int groups = 0; double busy_ms = 0; };
-    std::vector<Stat> stats;
+    std::vector<Stat> stats;        // per worker, of the last run
 };
 
 // The groups of a run (po_pair_basecall_group_rules.h has the rule): the byte sum is pair_basecall.pair_groups' — 24 per
@@ -106,54 +75,11 @@ struct Run {
     const int32_t* unbanded; char* qual1d; char* qual; int32_t* qual_status; int64_t* kept;
     std::vector<int32_t> first, count, owner;   // owner[r]: the first group that names read r (-1: none does)
     const char* name = "";
-    std::mutex mu;
-    int next = 0;
-    int rc = PO_OK, rc_worker = -1;
-    std::string msg;
 };
-
-// the raw route's preparation of the group's reads (their samples back to back in `raw`, offsets ro): the f32 signal is
-// left in the state's buffer, ko gets the kept samples' offsets
-int prepare_raw(const Run& r, PoPairBasecallWorker& w, const std::vector<int16_t>& raw, const std::vector<int64_t>& ro,
-                const std::vector<int>& reads, std::vector<int64_t>& ko) {
-    const po_pair_basecaller_options& o = r.b->opt;
-    const int c = (int)reads.size();
-    PoPrepPlan plan;
-    std::string err;
-    int rc = po_prep_make_plan(ro.data(), c, o.scaling, o.lo, o.hi, &plan, &err, r.name);
-    if (rc != PO_OK) return po_fail(rc, err);
-    ko.assign((size_t)c + 1, 0);
-    if (plan.total == 0) return PO_OK;
-    const int64_t slabs = (int64_t)plan.slab_read.size();
-    const size_t wsb = po_prep_workspace_bytes(c, slabs, plan.bins);
-    float* sig = nullptr;
-    PO_HIPCHK(w.raw.up(raw.data(), (size_t)plan.total * 2));
-    PO_HIPCHK(w.raw_off.up(ro.data(), sizeof(int64_t) * ro.size()));
-    PO_HIPCHK(w.slab_off.up(plan.slab_off.data(), sizeof(int64_t) * plan.slab_off.size()));
-    PO_HIPCHK(w.slab_read.up(plan.slab_read.data(), sizeof(int32_t) * plan.slab_read.size()));
-    if (r.offset) {
-        std::vector<double> of((size_t)c), al((size_t)c);
-        for (int j = 0; j < c; ++j) { of[j] = r.offset[reads[j]]; al[j] = r.alpha[reads[j]]; }
-        PO_HIPCHK(w.offset.up(of.data(), sizeof(double) * c));
-        PO_HIPCHK(w.alpha.up(al.data(), sizeof(double) * c));
-    }
-    PO_HIPCHK(w.sig_off.up(nullptr, sizeof(int64_t) * ((size_t)c + 1)));
-    PO_HIPCHK(w.stats.up(nullptr, sizeof(po_prep_stats) * (size_t)c));
-    PO_HIPCHK(w.ws.up(nullptr, wsb));
-    rc = po_pair_basecall_resident_signal(w.st, plan.total, &sig);
-    if (rc != PO_OK) return rc;
-    rc = po_launch_signal_prep(w.raw, w.raw_off, c, plan.total, w.slab_off, w.slab_read, slabs, o.scaling, o.lo, o.hi,
-                               r.offset ? w.offset.as<double>() : nullptr, r.offset ? w.alpha.as<double>() : nullptr, sig, w.sig_off,
-                               w.stats, w.ws, wsb, w.stream);
-    if (rc != PO_OK) return rc;
-    PO_HIPCHK(hipMemcpyAsync(ko.data(), w.sig_off.p, sizeof(int64_t) * ((size_t)c + 1), hipMemcpyDeviceToHost, w.stream));
-    PO_HIPCHK(hipStreamSynchronize(w.stream));
-    return PO_OK;
-}
 
 // one group: pairs f .. f + c - 1.  Its distinct reads in ascending order are the call's reads; the pairs that run are
 // indexed into them; outputs go through buffers of the call's own layout and from there to the pairs' places.
-int run_group(Run& r, PoPairBasecallWorker& w, int g, po_pair_basecaller::Stat& stat) {
+int run_group(Run& r, PoPairBasecallWorker& w, po_pair_basecaller::Stat& stat, int g) {
     const po_pair_basecaller* b = r.b;
     const po_pair_basecaller_options& o = b->opt;
     const int f = r.first[g], c = r.count[g];
@@ -175,7 +101,11 @@ int run_group(Run& r, PoPairBasecallWorker& w, int g, po_pair_basecaller::Stat& 
         std::vector<int16_t> raw((size_t)ro[nr]);
         for (int j = 0; j < nr; ++j)
             if (ro[j + 1] > ro[j]) std::memcpy(raw.data() + ro[j], r.raw + r.off[reads[j]], sizeof(int16_t) * (size_t)(ro[j + 1] - ro[j]));
-        const int rc = prepare_raw(r, w, raw, ro, reads, so);
+        std::vector<double> of, al;   // in the group's order
+        if (r.offset)
+            for (int j = 0; j < nr; ++j) { of.push_back(r.offset[reads[j]]); al.push_back(r.alpha[reads[j]]); }
+        const int rc = w.prepare_raw(raw.data(), ro.data(), nr, r.offset ? of.data() : nullptr, r.offset ? al.data() : nullptr, o.scaling,
+                                     o.lo, o.hi, r.name, po_pair_basecall_resident_net(w.st), so);
         if (rc != PO_OK) return rc;
         for (int j = 0; j < nr; ++j)
             if (r.owner[reads[j]] == g) r.kept[reads[j]] = so[j + 1] - so[j];
@@ -250,29 +180,6 @@ int run_group(Run& r, PoPairBasecallWorker& w, int g, po_pair_basecaller::Stat& 
     return PO_OK;
 }
 
-void worker(Run* r, int w) {
-    po_pair_basecaller::Stat& s = r->b->stats[w];
-    PoPairBasecallWorker& wk = *r->b->workers[w];
-    int rc = po_set_device(wk.dev);
-    for (;;) {
-        int g = -1;
-        {
-            std::lock_guard<std::mutex> lk(r->mu);
-            if (rc != PO_OK && r->rc == PO_OK) {          // the first failure: the others finish what they hold, take no more
-                r->rc = rc;
-                r->rc_worker = w;
-                r->msg = po_last_error();
-            }
-            if (r->rc == PO_OK && r->next < (int)r->first.size()) g = r->next++;
-        }
-        if (g < 0) return;
-        const auto t0 = std::chrono::steady_clock::now();
-        rc = run_group(*r, wk, g, s);
-        s.busy_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        s.groups += 1;
-    }
-}
-
 int run(Run& r, const char* name) {
     po_pair_basecaller* b = r.b;
     r.name = name;
@@ -281,7 +188,7 @@ int run(Run& r, const char* name) {
     if (r.n_pairs == 0) return PO_OK;
     std::vector<int64_t> len((size_t)r.n_reads);
     for (int i = 0; i < r.n_reads; ++i) len[i] = r.off[i + 1] - r.off[i];
-    const int ndev = (int)b->devices.size();
+    const int ndev = (int)b->workers.size();
     r.first.resize((size_t)r.n_pairs);
     r.count.resize((size_t)r.n_pairs);
     // (a run with "no band" flags scores those items on the lattice without a band: its groups are sized for that workspace)
@@ -295,11 +202,7 @@ int run(Run& r, const char* name) {
     for (int g = 0; g < ng; ++g)
         for (int i = 2 * r.first[g]; i < 2 * (r.first[g] + r.count[g]); ++i)
             if (r.owner[r.pair_idx[i]] < 0) r.owner[r.pair_idx[i]] = g;
-    std::vector<std::thread> th;
-    for (int w = 0; w < ndev; ++w) th.emplace_back(worker, &r, w);
-    for (auto& t : th) t.join();
-    if (r.rc != PO_OK) return po_fail(r.rc, "device " + std::to_string(b->devices[r.rc_worker]) + ": " + r.msg);
-    return PO_OK;
+    return po_engine_run(b, ng, [&r](PoPairBasecallWorker& w, po_pair_basecaller::Stat& s, int g) { return run_group(r, w, s, g); });
 }
 
 // the checks of a run, before any work: pointers, tables from 0 and non-decreasing, every pair's reads and its room
@@ -316,9 +219,10 @@ int check_run(const std::string& me, const po_pair_basecaller* b, const void* da
         {fq ? qual1d : &fq, "qual1d_h"}, {fq ? qual : &fq, "qual_h"}, {fq ? qual_status : &fq, "qual_status_h"}};
     for (const auto& a : ptrs)
         if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
-    if (off[0] != 0) return po_fail(PO_E_ARG, me + off_name + "[0] is " + std::to_string(off[0]) + " (must be 0)");
-    if (seq1d_off[0] != 0) return po_fail(PO_E_ARG, me + "seq1d_off[0] is " + std::to_string(seq1d_off[0]) + " (must be 0)");
-    if (seq_off[0] != 0) return po_fail(PO_E_ARG, me + "seq_off[0] is " + std::to_string(seq_off[0]) + " (must be 0)");
+    int rc = po_engine_check_from_zero(me, off, off_name);
+    if (rc == PO_OK) rc = po_engine_check_from_zero(me, seq1d_off, "seq1d_off");
+    if (rc == PO_OK) rc = po_engine_check_from_zero(me, seq_off, "seq_off");
+    if (rc != PO_OK) return rc;
     for (int i = 0; i < n_reads; ++i) {
         const int64_t L = off[i + 1] - off[i];
         if (L < 0 || L > INT32_MAX) return po_fail(PO_E_ARG, me + "read " + std::to_string(i) + " has " + std::to_string(L) + " samples");
@@ -350,20 +254,7 @@ extern "C" po_pair_basecaller* po_pair_basecaller_create(const int* devices, int
                                                          const po_pair_basecaller_options* opt) {
     const std::string me = "po_pair_basecaller_create: ";
     po_set_error("");
-    if (!devices || !layers_h || !weights_h || !opt) {
-        po_fail(PO_E_ARG, me + "null argument " + (!devices ? "devices" : !layers_h ? "layers_h" : !weights_h ? "weights_h" : "options"));
-        return nullptr;
-    }
-    if (ndev < 1 || ndev > MAX_WORKERS) {
-        po_fail(PO_E_ARG, me + "ndev " + std::to_string(ndev) + " (1 to " + std::to_string(MAX_WORKERS) + ")");
-        return nullptr;
-    }
-    const int nd = po_device_count();
-    for (int i = 0; i < ndev; ++i)
-        if (devices[i] < 0 || devices[i] >= nd) {
-            po_fail(PO_E_ARG, me + "device " + std::to_string(devices[i]) + " (0 to " + std::to_string(nd - 1) + ")");
-            return nullptr;
-        }
+    if (po_engine_check_devices(me, devices, ndev, layers_h, weights_h, opt) != PO_OK) return nullptr;
     // every argument error of the single-device entry, by that entry (no reads, no pairs: it stops after its checks)
     {
         const int64_t zero[1] = {0};
@@ -380,35 +271,14 @@ extern "C" po_pair_basecaller* po_pair_basecaller_create(const int* devices, int
                                                              &w, &w, &d, &c, zero, &w, &w, nullptr, nullptr);
         if (rc != PO_OK) return nullptr;
     }
-    {   // the raw route's scaling and range (po_signal_prep_h's messages)
-        const int64_t zero = 0;
-        PoPrepPlan plan;
-        std::string err;
-        const int rc = po_prep_make_plan(&zero, 0, opt->scaling, opt->lo, opt->hi, &plan, &err, "po_pair_basecaller_create");
-        if (rc != PO_OK) { po_fail(rc, err); return nullptr; }
-    }
-    if (opt->resident_bytes < 0) { po_fail(PO_E_ARG, me + "resident_bytes " + std::to_string(opt->resident_bytes)); return nullptr; }
+    if (po_engine_check_options("po_pair_basecaller_create", opt->scaling, opt->lo, opt->hi, opt->resident_bytes) != PO_OK) return nullptr;
     po_pair_basecaller* b = new po_pair_basecaller;
-    b->devices.assign(devices, devices + ndev);
-    b->layers.assign(layers_h, layers_h + n_layers);
-    b->weights.assign(weights_h, weights_h + n_weights);
     b->opt = *opt;
     b->stats.resize((size_t)ndev);
-    // a worker per listed device: its state, its stream, and the weights, uploaded here and never again
-    int before = 0;
-    (void)hipGetDevice(&before);
-    int rc = PO_OK;
-    for (int i = 0; i < ndev && rc == PO_OK; ++i) {
-        PoPairBasecallWorker* w = new PoPairBasecallWorker;
-        w->dev = devices[i];
-        b->workers.push_back(w);
-        rc = po_set_device(w->dev);
-        if (rc != PO_OK) break;
-        w->st = po_pair_basecall_resident_new();
-        if (hipStreamCreate(&w->stream) != hipSuccess) { w->stream = nullptr; rc = po_fail(PO_E_HIP, me + "hipStreamCreate"); break; }
-        rc = po_pair_basecall_resident_weights(w->st, weights_h, n_weights);
-    }
-    (void)hipSetDevice(before);
+    const int rc = po_engine_init(b, me, devices, ndev, layers_h, n_layers, weights_h, n_weights, [](PoPairBasecallWorker& w) -> PoBasecallPasses& {
+        w.st = po_pair_basecall_resident_new();
+        return po_pair_basecall_resident_net(w.st);
+    });
     if (rc != PO_OK) {
         const std::string msg = po_last_error();
         po_pair_basecaller_destroy(b);
@@ -420,15 +290,7 @@ extern "C" po_pair_basecaller* po_pair_basecaller_create(const int* devices, int
 
 extern "C" void po_pair_basecaller_destroy(po_pair_basecaller* b) {
     if (!b) return;
-    int before = 0;
-    (void)hipGetDevice(&before);
-    for (PoPairBasecallWorker* w : b->workers) {
-        (void)hipSetDevice(w->dev);
-        if (w->stream) { (void)hipStreamSynchronize(w->stream); (void)hipStreamDestroy(w->stream); }
-        if (w->st) po_pair_basecall_resident_free(w->st);
-        delete w;      // (its buffers free themselves)
-    }
-    (void)hipSetDevice(before);
+    po_engine_free(b, po_pair_basecall_resident_free);
     delete b;
 }
 
@@ -462,10 +324,9 @@ extern "C" int po_pair_basecaller_run_raw(po_pair_basecaller* b, const int16_t* 
     const std::string me = "po_pair_basecaller_run_raw: ";
     po_set_error("");
     if (!b) return po_fail(PO_E_ARG, me + "null argument basecaller");
-    if (!kept_h) return po_fail(PO_E_ARG, me + "null argument kept_h");
-    if (b->opt.scaling == PO_SCALE_CURRENT && (!offset_h || !alpha_h))
-        return po_fail(PO_E_ARG, me + "null argument " + (!offset_h ? "offset_h" : "alpha_h") + " (PO_SCALE_CURRENT)");
-    const int rc = check_run(me, b, raw_h, "raw_h", raw_off_h, "raw_off", n_reads, pair_idx_h, n_pairs, seq1d_h, seq1d_off_h, len1_h, len2_h,
+    int rc = po_engine_check_raw_args(me, kept_h, b->opt.scaling, offset_h, alpha_h);
+    if (rc != PO_OK) return rc;
+    rc = check_run(me, b, raw_h, "raw_h", raw_off_h, "raw_off", n_reads, pair_idx_h, n_pairs, seq1d_h, seq1d_off_h, len1_h, len2_h,
                              identity_h, seq_h, seq_off_h, seq_len_h, status_h, qual1d_h, qual_h, qual_status_h, true);
     if (rc != PO_OK) return rc;
     const bool fq = b->opt.fastq != 0, cur = b->opt.scaling == PO_SCALE_CURRENT;

@@ -24,7 +24,8 @@ import numpy as np
 
 from .. import _lib, _marshal
 from . import checkpoint as ckpt
-from .network import SCALINGS, _layers_array, load_model, parse_fast5, read_fast5_raw
+from ._engine import Engine, close_engines, with_engine
+from .network import _layers_array, load_model, parse_fast5, read_fast5_raw
 
 __all__ = ["window_plan", "frame_window", "check_time_order", "basecall_signals", "basecall_raw", "basecall", "check_window_args",
            "Basecaller", "group_plan", "stream_devices", "check_readers"]
@@ -221,39 +222,20 @@ def stream_devices(gpus, what="basecall"):
     return list(range(gpus if gpus else nd))
 
 
-class Basecaller:
+class Basecaller(Engine):
     """po_basecaller: a model, the decoder's options and a list of devices (a device may be named more
     than once); run_f32 / run_raw deal groups of reads to one host thread per listed device.  A context manager."""
+    NAME = "po_basecaller"
+    STAT_FIELDS = (("reads", C.c_int64), ("samples", C.c_int64), ("groups", C.c_int), ("busy_ms", C.c_double))
 
     def __init__(self, net, devices, window, overlap, kind, beam_width, model, max_windows_per_pass=0, fastq=False, band=0,
                  scaling="standard", lo=200, hi=800, resident_bytes=0):
-        if scaling not in SCALINGS:
-            raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
-        self.lib = _lib.load()
-        self.fastq = bool(fastq)
-        self.devices = [int(d) for d in devices]
-        w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
-        opt = _lib.BasecallerOptions(int(window), int(overlap), int(kind), int(beam_width), int(model), int(max_windows_per_pass),
-                                     1 if fastq else 0, int(band), SCALINGS.index(scaling), int(lo), int(hi), int(resident_bytes))
-        dev = (C.c_int * max(len(self.devices), 1))(*self.devices)
-        self.h = self.lib.po_basecaller_create(dev, len(self.devices), _layers_array(net), len(net.layers), w.ctypes.data, w.size,
-                                               b"ACGT", C.byref(opt))
-        if not self.h:
-            detail = self.lib.po_last_error()
-            raise _lib.EngineError(_lib.E_ARG, "po_basecaller_create", detail.decode() if detail else "")
+        super().__init__(net, devices, fastq, scaling, lambda s: _lib.BasecallerOptions(
+            int(window), int(overlap), int(kind), int(beam_width), int(model), int(max_windows_per_pass), 1 if fastq else 0, int(band),
+            s, int(lo), int(hi), int(resident_bytes)), b"ACGT")
 
-    def close(self):
-        if self.h:
-            self.lib.po_basecaller_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _run(self, what, call, data, off, n, rows, want_logits, kept=None):
+    def _run(self, what, call, off, want_logits, kept=None):
+        n, rows = len(off) - 1, int(off[-1])
         seq = np.zeros(max(rows, 1), dtype=np.uint8)
         qual = np.zeros(max(rows, 1), dtype=np.uint8) if self.fastq else None
         lens = np.zeros(n, dtype=np.int32)
@@ -273,35 +255,15 @@ class Basecaller:
 
     def run_f32(self, sigs, want_logits=False):
         """a dict: strings, qual_status, and where made quals (uint8 Phred arrays) and logits ((T, 5) float32 per read)"""
-        n = len(sigs)
-        off = _marshal.offsets([len(s) for s in sigs])
-        signal = np.ascontiguousarray(np.concatenate(sigs) if n else np.zeros(0), dtype=np.float32)
-        call = lambda *out: self.lib.po_basecaller_run_f32(self.h, signal.ctypes.data, off.ctypes.data, n, *out)
-        return self._run("po_basecaller_run_f32", call, signal, off, n, int(off[-1]), want_logits)
+        call, off = self._call_f32(sigs)
+        return self._run("po_basecaller_run_f32", call, off, want_logits)
 
     def run_raw(self, raws, offsets=None, alphas=None, want_logits=False):
         """run_f32's dict from raw int16 reads, with "kept": the samples each read kept (its logits' rows)"""
-        n = len(raws)
-        off = _marshal.offsets([len(r) for r in raws])
-        raw = np.ascontiguousarray(np.concatenate(raws) if n else np.zeros(0), dtype=np.int16)
-        o = np.ascontiguousarray(offsets, dtype=np.float64) if offsets is not None else None
-        a = np.ascontiguousarray(alphas, dtype=np.float64) if alphas is not None else None
-        kept = np.zeros(n, dtype=np.int64)
-        call = lambda *out: self.lib.po_basecaller_run_raw(self.h, raw.ctypes.data, off.ctypes.data, n,
-                                                           o.ctypes.data if o is not None else None,
-                                                           a.ctypes.data if a is not None else None, *out, kept.ctypes.data)
-        res = self._run("po_basecaller_run_raw", call, raw, off, n, int(off[-1]), want_logits, kept=kept)
+        call, off, kept = self._call_raw(raws, offsets, alphas)
+        res = self._run("po_basecaller_run_raw", call, off, want_logits, kept=kept)
         res["kept"] = kept
         return res
-
-    def stats(self):
-        """per worker: dict(device, reads, samples, groups, busy_ms) of the last run"""
-        out = []
-        for i, d in enumerate(self.devices):
-            r, s, g, ms = C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
-            _lib.check(self.lib.po_basecaller_stats(self.h, i, C.byref(r), C.byref(s), C.byref(g), C.byref(ms)), "po_basecaller_stats")
-            out.append({"device": d, "reads": r.value, "samples": s.value, "groups": g.value, "busy_ms": ms.value})
-        return out
 
 
 def _stream(make, run, n_all, todo, logits, qualities, band, empty, worker_stats=None, engines=None):
@@ -312,20 +274,8 @@ def _stream(make, run, n_all, todo, logits, qualities, band, empty, worker_stats
     out = [empty] * n_all
 
     def go(reads, fastq, band_, want_logits):
-        key = (bool(fastq), int(band_))
-        eng = engines.get(key) if engines is not None else None
-        if eng is None:
-            eng = make(fastq, band_)
-            if engines is not None:
-                engines[key] = eng
-        try:
-            r = run(eng, reads, want_logits)
-            if worker_stats is not None:
-                worker_stats.append(eng.stats())
-        finally:
-            if engines is None:
-                eng.close()
-        return r
+        return with_engine(engines, (bool(fastq), int(band_)), lambda: make(fastq, band_), lambda eng: run(eng, reads, want_logits),
+                           worker_stats)
 
     if not todo:
         return out
@@ -403,12 +353,6 @@ def basecall_raw(net, raws, channels=None, scaling="standard", devices=(0,), win
 
     with _lib.call_precision(precision), _lib.recur_precision(recurrence):
         return _stream(make, run, len(raws), todo, logits, qualities, band, empty, worker_stats, engines)
-
-
-def close_engines(engines):
-    for eng in engines.values():
-        eng.close()
-    engines.clear()
 
 
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,

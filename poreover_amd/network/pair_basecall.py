@@ -18,7 +18,8 @@ import numpy as np
 from .. import _lib, _marshal
 from . import basecall as _basecall
 from . import checkpoint as ckpt
-from .network import SCALINGS, _layers_array, load_model, parse_fast5, read_fast5_raw
+from ._engine import Engine, close_engines, with_engine
+from .network import _layers_array, load_model, parse_fast5, read_fast5_raw
 
 __all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read", "qual_bytes_query",
            "write_pair_fastq", "PairBasecaller", "pair_basecall_raw", "engine_group_plan"]
@@ -109,38 +110,18 @@ def engine_group_plan(pairs, lens, ws_bytes, budget=None, ndev=1, qual_bytes=Non
     return out
 
 
-class PairBasecaller:
+class PairBasecaller(Engine):
     """po_pair_basecaller: a model, the pair decoder's options (a _lib.PairOptions) and a list of devices
     (a device may be named more than once); run_f32 / run_raw deal groups of pairs to one host thread per listed device.
     A context manager."""
+    NAME = "po_pair_basecaller"
+    STAT_FIELDS = (("pairs", C.c_int64), ("reads", C.c_int64), ("samples", C.c_int64), ("groups", C.c_int), ("busy_ms", C.c_double))
 
     def __init__(self, net, devices, window, overlap, reverse_complement, opt, max_windows_per_pass=0, fastq=False, band=0,
                  scaling="standard", lo=200, hi=800, resident_bytes=0):
-        if scaling not in SCALINGS:
-            raise ValueError("unknown scaling %r (one of %s)" % (scaling, ", ".join(SCALINGS)))
-        self.lib = _lib.load()
-        self.fastq = bool(fastq)
-        self.devices = [int(d) for d in devices]
-        w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
-        o = _lib.PairBasecallerOptions(int(window), int(overlap), int(max_windows_per_pass), 1 if reverse_complement else 0, opt,
-                                       1 if fastq else 0, int(band), SCALINGS.index(scaling), int(lo), int(hi), int(resident_bytes))
-        dev = (C.c_int * max(len(self.devices), 1))(*self.devices)
-        self.h = self.lib.po_pair_basecaller_create(dev, len(self.devices), _layers_array(net), len(net.layers), w.ctypes.data, w.size,
-                                                    C.byref(o))
-        if not self.h:
-            detail = self.lib.po_last_error()
-            raise _lib.EngineError(_lib.E_ARG, "po_pair_basecaller_create", detail.decode() if detail else "")
-
-    def close(self):
-        if self.h:
-            self.lib.po_pair_basecaller_destroy(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(net, devices, fastq, scaling, lambda s: _lib.PairBasecallerOptions(
+            int(window), int(overlap), int(max_windows_per_pass), 1 if reverse_complement else 0, opt, 1 if fastq else 0, int(band), s,
+            int(lo), int(hi), int(resident_bytes)))
 
     def _run(self, what, call, lens, off, pairs, want_logits, flags, kept=None):
         n, P = len(lens), len(pairs)
@@ -176,37 +157,16 @@ class PairBasecaller:
         """a dict: records (batch.pair_decode_batch's, one per pair), and where made logits (per read (T, 5) float32, None for
         a read no pair names) and fields (quality.pair_fields' dicts).  flags (a fastq engine): per pair the four items'
         "no band" flags"""
-        n = len(sigs)
-        off = _marshal.offsets([len(s) for s in sigs])
-        signal = np.ascontiguousarray(np.concatenate(sigs) if n else np.zeros(0), dtype=np.float32)
-        call = lambda *a: self.lib.po_pair_basecaller_run_f32(self.h, signal.ctypes.data, off.ctypes.data, n, *a)
+        call, off = self._call_f32(sigs)
         return self._run("po_pair_basecaller_run_f32", call, [len(s) for s in sigs], off, pairs, want_logits, flags)
 
     def run_raw(self, raws, pairs, offsets=None, alphas=None, want_logits=False, flags=None):
         """run_f32's dict from raw int16 reads, with "kept": the samples each read kept (its logits' rows; -1 for a read no
         pair names).  A pair that names a read which kept nothing has status E_ARG."""
-        n = len(raws)
-        off = _marshal.offsets([len(r) for r in raws])
-        raw = np.ascontiguousarray(np.concatenate(raws) if n else np.zeros(0), dtype=np.int16)
-        o = np.ascontiguousarray(offsets, dtype=np.float64) if offsets is not None else None
-        a = np.ascontiguousarray(alphas, dtype=np.float64) if alphas is not None else None
-        kept = np.zeros(max(n, 1), dtype=np.int64)
-        call = lambda *x: self.lib.po_pair_basecaller_run_raw(self.h, raw.ctypes.data, off.ctypes.data, n,
-                                                              o.ctypes.data if o is not None else None,
-                                                              a.ctypes.data if a is not None else None, *x, kept.ctypes.data)
-        res = self._run("po_pair_basecaller_run_raw", call, [len(r) for r in raws], off, pairs, want_logits, flags, kept=kept[:n])
-        res["kept"] = kept[:n]
+        call, off, kept = self._call_raw(raws, offsets, alphas)
+        res = self._run("po_pair_basecaller_run_raw", call, [len(r) for r in raws], off, pairs, want_logits, flags, kept=kept)
+        res["kept"] = kept
         return res
-
-    def stats(self):
-        """per worker: dict(device, pairs, reads, samples, groups, busy_ms) of the last run"""
-        out = []
-        for i, d in enumerate(self.devices):
-            p, r, s, g, ms = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_double()
-            _lib.check(self.lib.po_pair_basecaller_stats(self.h, i, C.byref(p), C.byref(r), C.byref(s), C.byref(g), C.byref(ms)),
-                       "po_pair_basecaller_stats")
-            out.append({"device": d, "pairs": p.value, "reads": r.value, "samples": s.value, "groups": g.value, "busy_ms": ms.value})
-        return out
 
 
 def _stream(what, make, run, pairs, n_reads, logits, qualities, band, worker_stats=None, engines=None):
@@ -218,20 +178,8 @@ def _stream(what, make, run, pairs, n_reads, logits, qualities, band, worker_sta
 
     def go(which, fastq, band_, want_logits, flags):
         band_ = int(band_ or 0)
-        key = (bool(fastq), band_)
-        eng = engines.get(key) if engines is not None else None
-        if eng is None:
-            eng = make(fastq, band_)
-            if engines is not None:
-                engines[key] = eng
-        try:
-            r = run(eng, which, want_logits, flags)
-            if worker_stats is not None:
-                worker_stats.append(eng.stats())
-        finally:
-            if engines is None:
-                eng.close()
-        return r
+        return with_engine(engines, (bool(fastq), band_), lambda: make(fastq, band_), lambda eng: run(eng, which, want_logits, flags),
+                           worker_stats)
 
     if not pairs:
         return results, read_logits
@@ -264,12 +212,6 @@ def _compact(pairs, which):
     reads = sorted({r for k in which for r in pairs[k]})
     local = {r: j for j, r in enumerate(reads)}
     return reads, [(local[pairs[k][0]], local[pairs[k][1]]) for k in which]
-
-
-def close_engines(engines):
-    for eng in engines.values():
-        eng.close()
-    engines.clear()
 
 
 def pair_basecall_raw(net, raws, pairs, channels=None, scaling="standard", devices=(0,), window=1000, overlap=0,
