@@ -1158,10 +1158,26 @@ void beam2d_reg_kernel(RegArgs a) {
                 if (p_isnew && lo_half && n_id < arena_cap) { apl[n_id] = po_pack_node(p_id, c); afc[n_id] = -1; acrow[n_id] = -1; }
             }
             // a child slot whose node is also a beam slot is the same node pushed twice (Beam::prune's std::unique)
-            each_beam(nbn, [&](int i) {
-                const int bid = __builtin_amdgcn_readlane(n_id, i);
-                if (rc && bid == n_id) n_alias = i;
-            });
+            // ... and, from the same pass over the new beam's ids (a beam lane's n_id, n_par, n_gpar and n_sym are final since
+            // part A: one v_readlane per beam slot serves the three comparisons), the parent slot of the beam nodes: a beam
+            // node, a child of a beam node (the grandparent is a beam node), the root, or none (frozen).  Ids are distinct
+            // within the beam, so at most one slot matches each.
+            {
+                int ps_par = -1, ps_gpar = -1;
+                each_beam(nbn, [&](int i) {   // (wave-uniform loop: v_readlane)
+                    const int bid = __builtin_amdgcn_readlane(n_id, i);
+                    if (rc && bid == n_id) n_alias = i;
+                    if (bid == n_par) ps_par = i;
+                    if (bid == n_gpar) ps_gpar = i;
+                });
+                if (rb) {
+                    n_ps = PS_FROZEN;
+                    if (n_par == 0) n_ps = PS_ROOT;
+                    else if (ps_par >= 0) n_ps = ps_par;
+                    else if (ps_gpar >= 0) n_ps = nbn + A * ps_gpar + sym_plast(n_sym);
+                }
+            }
+            KC(53, sm_pop(smask_of(rc && n_alias >= 0))); KC(55, (nbn == W && sm_pop(smask_of(rb && mysel >= nbo)) == nbn) ? 1 : 0);
             KT(42);
             // ---- D. which old slot continues here
             int src = -1;
@@ -1234,20 +1250,8 @@ void beam2d_reg_kernel(RegArgs a) {
             }
             live = nlive;
             KT(45);
-            // ---- the parent slot of the beam nodes: a beam node, a child of a beam node, the root, or none (frozen)
+            // ---- the parent slot of the beam nodes (found in part C's pass over the new beam's ids)
             nb = nbn; ne = nen;
-            {   // (wave-uniform loops: v_readlane)
-                if (rb) n_ps = (n_par == 0) ? PS_ROOT : PS_FROZEN;
-                each_beam(nbn, [&](int i) {
-                    const int bid = __builtin_amdgcn_readlane(e_id, i);
-                    if (rb && n_par != 0 && bid == n_par) n_ps = i;
-                });
-                const bool fz = rb && n_ps == PS_FROZEN;
-                each_beam(nbn, [&](int i) {
-                    const int bid = __builtin_amdgcn_readlane(e_id, i);
-                    if (fz && bid == n_gpar) n_ps = nbn + A * i + sym_plast(e_sym);
-                });
-            }
             e_ps = n_ps;
             KT(46);
             // ---- G. a frozen parent that is an element again.  A beam node whose parent had left the table computed its
@@ -1260,6 +1264,7 @@ void beam2d_reg_kernel(RegArgs a) {
             {
                 bool rew = rb && nlive && src >= 0 && op == PS_FROZEN && n_ps >= 0;
                 if (__builtin_expect(__ballot(rew) != 0ull, 0)) {
+                    KC(54, 1);
                     for (int it = 0; it < W; ++it) {   // ... and their descendants in the table, generation by generation
                         const bool prew = __shfl((int)rew, hb | max(e_ps, 0)) != 0;
                         if (live && e_ps >= 0 && prew) rew = true;
@@ -1299,6 +1304,7 @@ void beam2d_reg_kernel(RegArgs a) {
             sh_step = mstep; sh_u = u; sh_v = v;
 #endif
             double sc = PO_NEG_INF;
+            double sc_min = PO_NEG_INF;   // the smallest score of a full beam at the step that goes to the ranking (wave-uniform)
             bool viol = false, run_viol = false;
             KT(6);
             // ---- a RUN of main steps on the table as it stands.  After a step that kept the set of beam nodes, with every
@@ -1440,7 +1446,8 @@ void beam2d_reg_kernel(RegArgs a) {
                     }
                     auto score = [&]() -> double { return (NR == 1) ? po_sum32(smx[0]) : smx[0] + smx[NR - 1]; };
                     sc = score();
-                    const double scmin = rk_row0_min(sc, nb, lane);
+                    const double scmin = rk_row0_min(sc, nb, lane);   // (only children's scores change below: it stands for the ranking)
+                    sc_min = scmin;
                     viol = live && child && !(scmin > sc);
                     // a child that reaches the smallest beam score on a bound: its exact maximum now (the stored values are
                     // looked at), then the score and the test again — the decision is the one exact maxima give
@@ -1525,9 +1532,9 @@ void beam2d_reg_kernel(RegArgs a) {
             // children), ties are decided on node ids, and the order matters only where nodes are created — the step in which
             // the set changes ranks everybody — and for the label: the last main step is always ranked.
             viol = (nb != W) || (mstep + 1 == nmain);
-            if (!viol) {   // (wave-uniform: nb == W and not the last step)
-                const double scmin = rk_row0_min(sc, nb, lane);
-                if (live && s >= nb) viol = !(scmin > sc);
+            if (nb == W) {   // (wave-uniform; the last step is ranked whatever the test says, with this threshold)
+                sc_min = rk_row0_min(sc, nb, lane);
+                if (!viol && live && s >= nb) viol = !(sc_min > sc);
             }
             up = u; vp = v;
             mstep++;
@@ -1549,29 +1556,42 @@ void beam2d_reg_kernel(RegArgs a) {
             // (the 1-D kernels' higher threshold — the smallest FAMILY maximum, a beam node and its children — was tried here in
             //  round 5: a ranking sees 10.9 candidates at W = 5 and would see ~ 6, but the permutes that find the family maxima
             //  cost more than the trips they save: 51.9 against 51.1 ms)
+            // (the threshold is the smallest beam score both ways here have just taken for their prune test: sc_min)
             SMask smask = cm;
-            if (nb == W) {
-                const double thr = rk_row0_min(sc, nb, lane);
-                smask = smask_of(cand && (s < nb || sc >= thr));
-            }
+            if (nb == W) smask = smask_of(cand && (s < nb || sc >= sc_min));
+            const bool in_set = ((smask >> s) & (SMask)1) != 0;
+            // The common case has no two equal scores in the set: a candidate's rank is then the number of scores strictly
+            // above its own, and node ids — which only decide between equal scores — are not looked at.  One pass counts the
+            // greater and the equal ones (a candidate equals itself: neq == 1; a NaN equals nothing: neq == 0); only if some
+            // candidate of the set has another count the ranking is taken again with the ids.
             int rank = 0, neq = 0;
             for (SMask mm = smask; mm != 0; mm &= mm - (SMask)1) {
-                const int o = sm_ctz(mm);
-                const double so = rk_readlane_d(sc, o);
-                const int io = __builtin_amdgcn_readlane(e_id, o);
-                rank += ((so > sc) | (!(sc > so) & (io < e_id))) ? 1 : 0;
+                const double so = rk_readlane_d(sc, sm_ctz(mm));
+                rank += (so > sc) ? 1 : 0;
                 neq += (so == sc) ? 1 : 0;
             }
-            if (!((smask >> s) & (SMask)1)) { rank = 64; neq = 0; }
+            const bool eq_any = __ballot(in_set && neq != 1) != 0ull;   // (wave-uniform)
+            KC(39, 1); KC(51, eq_any ? 1 : 0);
+            if (__builtin_expect(eq_any, 0)) {
+                rank = 0;
+                for (SMask mm = smask; mm != 0; mm &= mm - (SMask)1) {
+                    const int o = sm_ctz(mm);
+                    const double so = rk_readlane_d(sc, o);
+                    const int io = __builtin_amdgcn_readlane(e_id, o);
+                    rank += ((so > sc) | (!(sc > so) & (io < e_id))) ? 1 : 0;
+                }
+            }
+            if (!in_set) { rank = 64; neq = 0; }
             const int nbn = min(W, ncand);
 #pragma unroll
             for (int jx = 0; jx < WSEL; ++jx) {
                 const SMask bj = smask_of(cand && rank == jx);
                 sel[jx] = (bj != 0) ? sm_ctz(bj) : 0;
             }
-            if (__builtin_expect(__ballot(cand && neq > 1 && rank < W) != 0ull, 0)) {
+            if (__builtin_expect(eq_any && __ballot(cand && neq > 1 && rank < W) != 0ull, 0)) {
                 // exact ties reaching into the beam: what libstdc++'s partial_sort / sort leave on the candidates in
                 // creation order (po_device.h), replayed by one lane
+                KC(52, 1);
                 int pos = 0;   // (the replay runs over ALL candidates in creation order)
                 for (int o = 0; o < ne; ++o) {
                     const int io = __builtin_amdgcn_readlane(e_id, o);
@@ -1738,6 +1758,7 @@ extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wid
         fprintf(stderr, "   row groups handed out: %lld; B by part: marks + arena look-up %lld, expansion %lld, row groups (in B above)\n", h[47], h[49], h[50]);
         fprintf(stderr, "   closed-form chains: %lld passes (a staged parent's children on both reads), %lld of them left to the serial chain\n", h[34], h[35]);
         fprintf(stderr, "   nodes entering the beam: %lld, of them expanded before %lld, with their children's row group still theirs %lld\n", h[36], h[37], h[38]);
+        fprintf(stderr, "   rankings: %lld, of them with equal scores in the set (ids looked at) %lld, tie replays %lld; child slots that are aliases of beam slots: %lld; rewinds (part G): %lld; table builds that replace the whole beam: %lld\n", h[39], h[51], h[52], h[53], h[54], h[55]);
         fprintf(stderr, "   table builds that ask the arena for a node's children: %lld; window rescans: %lld lanes in %lld calls; bounds made exact in %lld steps\n", h[20], h[21], h[10], h[31]);
     }
 #endif

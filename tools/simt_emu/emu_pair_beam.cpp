@@ -35,7 +35,8 @@ extern "C" int emu_ring_pair_beam(const double* y1, const int64_t* y1_off, const
     a.pool_bytes = pool_bytes; a.arena_cap = (long long)arena_cap;
     for (int c = 0; c < 8; ++c) a.slice_chunk[c] = nullptr;
     a.slice_chunk[0] = pool.data(); a.slice_spc_log2 = 30; a.nslices = blocks; a.slice_bytes = slice_bytes; a.slice_claim = claim.data();
-    a.slice_tickets = tickets; a.persist = 1; a.defer_count = nullptr; a.starve = 0;
+    a.slice_tickets = tickets; a.persist = 1; a.defer_count = nullptr;
+    a.starve = getenv("EMU_STARVE") ? atoi(getenv("EMU_STARVE")) : 0;   // (po_set_pair_route's starve bits: 1 = a dozen row groups, 2 = a tiny arena)
     a.dbg = nullptr; a.upd_count = upd_count; a.defer_odd = 0; a.order = nullptr;
     a.ngl = po_reg_ngl(wide);
     a.chain_scan = getenv("EMU_CHAIN_SCAN") ? atoi(getenv("EMU_CHAIN_SCAN")) : 0;
