@@ -102,75 +102,55 @@ def _qual_rows_bytes(lib, n, total, longest, model):
     return int(lib.po_qual_workspace_bytes(n, total, longest, total, 0, model))
 
 
+def _net_args(net, sigs):
+    """the network arguments of one device call: the signals back to back (contiguous float32), their int64 offsets, the flat
+    weights and the layers array"""
+    off = _marshal.offsets([len(s) for s in sigs])
+    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
+    return signal, off, np.ascontiguousarray(net.flat_weights(), dtype=np.float32), _layers_array(net)
+
+
 def _fastq_call(lib, net, sigs, window, overlap, kind, beam_width, model, band, want_logits=False, want_odds=False,
                 want_guides=False, stage_ms=None, max_windows_per_pass=0, precision="f32", recurrence="f32"):
-    """One po_basecall_fastq_batch_h call.  Returns a dict: strings, quals (uint8 Phred arrays), qual_status int32 (n,),
-    and where asked for logits, odds (float64 (L, 5) per read) and guides (int32 (T,) per read; None for band <= 0)."""
+    """One po_basecall_fastq_batch_h call, or with band None one po_basecall_batch_h call.  Returns a dict: strings,
+    qual_status int32 (n,), with a band quals (uint8 Phred arrays), and where asked for logits, odds (float64 (L, 5) per read)
+    and guides (int32 (T,) per read; None for band <= 0)."""
     n = len(sigs)
-    off = _marshal.offsets([len(s) for s in sigs])
+    signal, off, w, layers = _net_args(net, sigs)
     rows = int(off[-1])
-    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
-    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
-    layers = _layers_array(net)
     seq = np.zeros(rows, dtype=np.uint8)
-    qual = np.zeros(rows, dtype=np.uint8)
     lens = np.zeros(n, dtype=np.int32)
     st = np.zeros(n, dtype=np.int32)
     qst = np.zeros(n, dtype=np.int32)
     lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
-    od = np.zeros((rows, 5), dtype=np.float64) if want_odds else None
-    gd = np.zeros(rows, dtype=np.int32) if want_guides and band > 0 else None
-    ms = (C.c_float * 8)() if stage_ms is not None else None
+    entry, stages, tail = "po_basecall_batch_h", _lib.BASECALL_STAGES, ()
+    od = gd = None
+    if band is not None:
+        entry, stages = "po_basecall_fastq_batch_h", _lib.BASECALL_FASTQ_STAGES
+        qual = np.zeros(rows, dtype=np.uint8)
+        od = np.zeros((rows, 5), dtype=np.float64) if want_odds else None
+        gd = np.zeros(rows, dtype=np.int32) if want_guides and band > 0 else None
+        tail = (int(band), qual.ctypes.data, qst.ctypes.data, _marshal.ptr(od), _marshal.ptr(gd))
+    ms = (C.c_float * len(stages))() if stage_ms is not None else None
     with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-        rc = lib.po_basecall_fastq_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
-                                           w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
-                                           seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
-                                           lg.ctypes.data if want_logits else None, int(band), qual.ctypes.data, qst.ctypes.data,
-                                           od.ctypes.data if od is not None else None, gd.ctypes.data if gd is not None else None,
-                                           ms)
-    _lib.check(rc, "po_basecall_fastq_batch_h")
+        rc = getattr(lib, entry)(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers), w.ctypes.data,
+                                 w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass), seq.ctypes.data,
+                                 off.ctypes.data, lens.ctypes.data, st.ctypes.data, _marshal.ptr(lg), *tail, ms)
+    _lib.check(rc, entry)
     _marshal.raise_on_status(st, n, "basecall of read")
     if stage_ms is not None:
-        for k, name in enumerate(_lib.BASECALL_FASTQ_STAGES):
+        for k, name in enumerate(stages):
             stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
-    res = {"strings": _marshal.strings(seq, off, lens), "qual_status": qst,
-           "quals": [qual[off[i]:off[i] + lens[i]] - 33 for i in range(n)]}
+    res = {"strings": _marshal.strings(seq, off, lens), "qual_status": qst}
+    if band is not None:
+        res["quals"] = [qual[off[i]:off[i] + lens[i]] - 33 for i in range(n)]
     if want_logits:
         res["logits"] = [lg[off[i]:off[i + 1]] for i in range(n)]
-    if want_odds:
+    if od is not None:
         res["odds"] = [od[off[i]:off[i] + lens[i]].copy() for i in range(n)]
     if want_guides:
         res["guides"] = [gd[off[i]:off[i + 1]] for i in range(n)] if gd is not None else None
     return res
-
-
-def _engine_call(lib, net, sigs, window, overlap, kind, beam_width, model, want_logits, stage_ms, max_windows_per_pass,
-                 precision="f32", recurrence="f32"):
-    n = len(sigs)
-    off = _marshal.offsets([len(s) for s in sigs])
-    rows = int(off[-1])
-    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
-    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
-    layers = _layers_array(net)
-    seq = np.zeros(rows, dtype=np.uint8)
-    lens = np.zeros(n, dtype=np.int32)
-    st = np.zeros(n, dtype=np.int32)
-    lg = np.empty((rows, ckpt.NUM_LABELS), dtype=np.float32) if want_logits else None
-    ms = (C.c_float * 6)() if stage_ms is not None else None
-    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-        rc = lib.po_basecall_batch_h(signal.ctypes.data, off.ctypes.data, n, window, overlap, layers, len(net.layers),
-                                     w.ctypes.data, w.size, b"ACGT", kind, beam_width, model, int(max_windows_per_pass),
-                                     seq.ctypes.data, off.ctypes.data, lens.ctypes.data, st.ctypes.data,
-                                     lg.ctypes.data if want_logits else None, ms)
-    _lib.check(rc, "po_basecall_batch_h")
-    _marshal.raise_on_status(st, n, "basecall of read")
-    if stage_ms is not None:
-        for k, name in enumerate(_lib.BASECALL_STAGES):
-            stage_ms[name] = stage_ms.get(name, 0.0) + float(ms[k])
-    strings = _marshal.strings(seq, off, lens)
-    if want_logits:
-        return [(s, lg[off[i]:off[i + 1]]) for i, s in enumerate(strings)]
-    return strings
 
 
 def _groups(todo, lens, fits):
@@ -266,42 +246,56 @@ class Basecaller(Engine):
         return res
 
 
-def _stream(make, run, n_all, todo, logits, qualities, band, empty, worker_stats=None, engines=None):
-    """basecall_signals' results over the engine: make(fastq, band) -> Basecaller, run(engine, reads, want_logits) -> its dict
-    for those reads.  The unbanded retry, the warning and the output tuples are basecall_signals'.  engines (a dict, or
-    None): the caller's engines by (fastq, band), made here when first needed and left open for its later calls — the
-    weights go up once per engine; without it an engine lives for this call."""
+def _answers(reads, r):
+    """a call's dict for `reads` as a route's answer: position -> (string, logits or None, Phred array or None, qual_status)"""
+    lg, q = r.get("logits"), r.get("quals")
+    return {k: (r["strings"][j], lg[j] if lg is not None else None, q[j] if q is not None else None, int(r["qual_status"][j]))
+            for j, k in enumerate(reads)}
+
+
+def _engine_route(make, run, precision, recurrence, worker_stats, engines):
+    """The engine route: make(fastq, band) -> Basecaller, run(engine, reads, want_logits) -> its dict for
+    those reads.  engines (a dict, or None): the caller's engines by (fastq, band), made here when first needed and left open
+    for its later calls — the weights go up once per engine; without it an engine lives for one call of the route."""
+    def route(reads, band, want_logits):
+        fastq, band = band is not None, int(band or 0)
+        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
+            return _answers(reads, with_engine(engines, (fastq, band), lambda: make(fastq, band),
+                                               lambda eng: run(eng, reads, want_logits), worker_stats))
+    return route
+
+
+def _results(route, n_all, todo, logits, qualities, qual_band):
+    """basecall_signals' results of n_all reads, of which those at the positions `todo` have samples, whatever runs them:
+    route(reads, band, want_logits) -> {position: (string, logits or None, Phred array or None, qual_status)}, band None for a
+    call without qualities, else qual_band as basecall_signals reads it.  The unbanded retry is quality.retry_unbanded's; Q 0 and the line in the log for what is still
+    unscored, and the output tuples, are here."""
+    empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
+    if qualities:
+        empty = (empty if logits else (empty,)) + (np.zeros(0, dtype=np.uint8),)
     out = [empty] * n_all
-
-    def go(reads, fastq, band_, want_logits):
-        return with_engine(engines, (bool(fastq), int(band_)), lambda: make(fastq, band_), lambda eng: run(eng, reads, want_logits),
-                           worker_stats)
-
     if not todo:
         return out
     if not qualities:
-        r = go(todo, False, 0, logits)
-        for j, k in enumerate(todo):
-            out[k] = (r["strings"][j], r["logits"][j]) if logits else r["strings"][j]
+        for k, (s, lg, _, _) in route(todo, None, logits).items():
+            out[k] = (s, lg) if logits else s
         return out
     from .. import quality
-    r = go(todo, True, band, logits)
-    strings = {k: r["strings"][j] for j, k in enumerate(todo)}
-    quals = {k: r["quals"][j] for j, k in enumerate(todo)}
-    status = {k: int(r["qual_status"][j]) for j, k in enumerate(todo)}
-    retry = [k for k in todo if status[k] == _lib.E_ENVELOPE] if band > 0 else []
-    if retry:
-        r2 = go(retry, True, 0, False)
-        for j, k in enumerate(retry):
-            if r2["strings"][j] != strings[k]:
-                raise RuntimeError("basecall_signals: read %d decodes differently in the unbanded retry" % k)
-            quals[k], status[k] = r2["quals"][j], int(r2["qual_status"][j])
-    bad = [k for k in todo if status[k] != 0]
-    if bad:
-        quality.warn_unscored(["read %d (%s)" % (k, _lib._CODE_NAMES.get(status[k], status[k])) for k in bad])
-    for j, k in enumerate(todo):
-        q = quals[k] if status[k] == 0 else np.zeros(len(strings[k]), dtype=np.uint8)
-        out[k] = (strings[k], r["logits"][j], q) if logits else (strings[k], q)
+    band = quality.DEFAULT_BAND if qual_band is None else int(qual_band)
+    lgs = {}
+
+    def run(reads, band_):    # (the first call is the one with the caller's band: the logits are its alone)
+        got = route(reads, band_, logits and band_ == band)
+        if band_ == band:
+            lgs.update((k, v[1]) for k, v in got.items())
+        return {k: ((s, q), st) for k, (s, _, q, st) in got.items()}
+
+    got, _ = quality.retry_unbanded(run, todo, band, same=lambda first, second: first[0] == second[0], what="basecall_signals")
+    quality.warn_unscored_reads({k: got[k][1] for k in todo})
+    for k in todo:
+        (s, q), st = got[k]
+        q = q if st == 0 else np.zeros(len(s), dtype=np.uint8)
+        out[k] = (s, lgs[k], q) if logits else (s, q)
     return out
 
 
@@ -335,24 +329,18 @@ def basecall_raw(net, raws, channels=None, scaling="standard", devices=(0,), win
             raise ValueError("basecall_raw: read %d is %s of %d dimension(s), not a vector of int16" % (i, r.dtype, r.ndim))
     if scaling == "current" and (channels is None or len(channels) != len(raws)):
         raise ValueError("basecall_raw: scaling 'current' needs (offset, digitisation, range) of every read")
-    empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
-    if qualities:
-        empty = (empty if logits else (empty,)) + (np.zeros(0, dtype=np.uint8),)
-    todo = [i for i, r in enumerate(raws) if len(r)]
-    from .. import quality
-    band = quality.DEFAULT_BAND if qual_band is None else int(qual_band)
     rb = RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
 
-    def make(fastq, band_):
-        return Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band_, scaling, lo, hi, rb)
+    def make(fastq, band):
+        return Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band, scaling, lo, hi, rb)
 
     def run(eng, reads, want_logits):
         cur = scaling == "current"
         return eng.run_raw([raws[k] for k in reads], [channels[k][0] for k in reads] if cur else None,
                            [channels[k][1] / channels[k][2] for k in reads] if cur else None, want_logits)
 
-    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-        return _stream(make, run, len(raws), todo, logits, qualities, band, empty, worker_stats, engines)
+    return _results(_engine_route(make, run, precision, recurrence, worker_stats, engines), len(raws),
+                    [i for i, r in enumerate(raws) if len(r)], logits, qualities, qual_band)
 
 
 def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", beam_width=25, merge_repeats=False,
@@ -378,76 +366,45 @@ def basecall_signals(net, signals, window=1000, overlap=0, algorithm="viterbi", 
     engines (a dict the caller keeps and closes with close_engines): the engines outlive the call, as for basecall_raw."""
     _lib._precision_code(precision)
     _lib._recur_code(recurrence)
-    if algorithm not in ("viterbi", "beam"):
-        raise ValueError("basecall_signals: algorithm %r (viterbi or beam)" % (algorithm,))
-    if algorithm == "beam" and not 1 <= beam_width <= 64:
-        raise ValueError("basecall_signals: beam_width %d (1 to 64)" % beam_width)
+    kind, model, bw = _decoder_args(algorithm, beam_width, merge_repeats, "basecall_signals")
     window_plan(1, window, overlap)
     check_time_order(net.kinds)
     sigs = [np.asarray(s, dtype=np.float32).ravel() for s in signals]
-    empty = ("", np.zeros((0, ckpt.NUM_LABELS), dtype=np.float32)) if logits else ""
-    if qualities:
-        empty = (empty if logits else (empty,)) + (np.zeros(0, dtype=np.uint8),)
-    out = [empty] * len(sigs)
-    todo = [i for i, s in enumerate(sigs) if len(s)]
-    if not todo:
-        return out
-    lib = _lib.load()
-    kind = _lib.KINDS["bonito" if merge_repeats else "poreover"]
-    model = _lib.MODELS["ctc_merge_repeats" if merge_repeats else "ctc"]
-    bw = int(beam_width) if algorithm == "beam" else 0
-    lens = [len(s) for s in sigs]
     if devices is not None:
-        from .. import quality
         rb = RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
-        make = lambda fastq, band_: Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass, fastq, band_,
-                                               resident_bytes=rb)
-        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-            return _stream(make, lambda eng, reads, want: eng.run_f32([sigs[k] for k in reads], want), len(sigs), todo, logits,
-                           qualities, quality.DEFAULT_BAND if qual_band is None else int(qual_band), empty, worker_stats, engines)
-    if not qualities:
-        budget = max(1, RESIDENT_BYTES // _bytes_per_sample(lib, bw, model))
-        for group in _groups(todo, lens, lambda n, total, longest: total <= budget):
-            res = _engine_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, logits, stage_ms,
-                               max_windows_per_pass, precision=precision, recurrence=recurrence)
-            for k, r in zip(group, res):
-                out[k] = r
-        return out
+        route = _engine_route(lambda fastq, band: Basecaller(net, devices, window, overlap, kind, bw, model, max_windows_per_pass,
+                                                             fastq, band, resident_bytes=rb),
+                              lambda eng, reads, want_logits: eng.run_f32([sigs[k] for k in reads], want_logits), precision,
+                              recurrence, worker_stats, engines)
+    else:
+        lens = [len(s) for s in sigs]
 
-    from .. import quality
-    band = quality.DEFAULT_BAND if qual_band is None else int(qual_band)
+        def route(reads, band, want_logits):
+            lib = _lib.load()
+            per = _bytes_per_sample(lib, bw, model, band)
+            if band is None:
+                budget = max(1, RESIDENT_BYTES // per)
+                fits = lambda n, total, longest: total <= budget
+            elif band > 0:
+                fits = lambda n, total, longest: total * per <= RESIDENT_BYTES
+            else:
+                fits = lambda n, total, longest: total * per + _qual_rows_bytes(lib, n, total, longest, model) <= RESIDENT_BYTES
+            out = {}
+            for group in _groups(reads, lens, fits):
+                out.update(_answers(group, _fastq_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, band,
+                                                       want_logits=want_logits, stage_ms=stage_ms,
+                                                       max_windows_per_pass=max_windows_per_pass, precision=precision,
+                                                       recurrence=recurrence)))
+            return out
 
-    def fits(band_):
-        per = _bytes_per_sample(lib, bw, model, band_)
-        if band_ > 0:
-            return lambda n, total, longest: total * per <= RESIDENT_BYTES
-        return lambda n, total, longest: total * per + _qual_rows_bytes(lib, n, total, longest, model) <= RESIDENT_BYTES
+    return _results(route, len(sigs), [i for i, s in enumerate(sigs) if len(s)], logits, qualities, qual_band)
 
-    def run(reads, band_, want_logits):
-        for group in _groups(reads, lens, fits(band_)):
-            r = _fastq_call(lib, net, [sigs[k] for k in group], window, overlap, kind, bw, model, band_, want_logits=want_logits,
-                            stage_ms=stage_ms, max_windows_per_pass=max_windows_per_pass, precision=precision,
-                            recurrence=recurrence)
-            for j, k in enumerate(group):
-                yield k, r, j
 
-    strings, quals, status, lgs = {}, {}, {}, {}
-    for k, r, j in run(todo, band, logits):
-        strings[k], quals[k], status[k] = r["strings"][j], r["quals"][j], int(r["qual_status"][j])
-        if logits:
-            lgs[k] = r["logits"][j]
-    retry = [k for k in todo if status[k] == _lib.E_ENVELOPE] if band > 0 else []
-    for k, r, j in run(retry, 0, False):
-        if r["strings"][j] != strings[k]:
-            raise RuntimeError("basecall_signals: read %d decodes differently in the unbanded retry" % k)
-        quals[k], status[k] = r["quals"][j], int(r["qual_status"][j])
-    bad = [k for k in todo if status[k] != 0]
-    if bad:
-        quality.warn_unscored(["read %d (%s)" % (k, _lib._CODE_NAMES.get(status[k], status[k])) for k in bad])
-    for k in todo:
-        q = quals[k] if status[k] == 0 else np.zeros(len(strings[k]), dtype=np.uint8)
-        out[k] = (strings[k], lgs[k], q) if logits else (strings[k], q)
-    return out
+def _read_name(args, path, read_id):
+    """the name of a read's record: the file's stem, or with --use_id the read id (bytes or str)"""
+    if args.use_id:
+        return read_id.decode("utf-8") if isinstance(read_id, (bytes, np.bytes_)) else str(read_id)
+    return Path(path).stem
 
 
 def basecall(args):
@@ -483,12 +440,7 @@ def basecall(args):
                             recurrence=getattr(args, "recurrence", "f32"))
     quals = [q for _, q in seqs] if fastq else None
     seqs = [s for s, _ in seqs] if fastq else seqs
-    names = []
-    for path, (rid, _) in zip(files, parsed):
-        if args.use_id:
-            names.append(rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid))
-        else:
-            names.append(Path(path).stem)
+    names = [_read_name(args, path, rid) for path, (rid, _) in zip(files, parsed)]
     out_path = args.out + ".fasta"
     with open(out_path, "w") as f:
         for name, s in zip(names, seqs):
@@ -538,9 +490,7 @@ def _basecall_stream(args, net, files, devices):
                                        qual_band=getattr(args, "qual_band", None), precision=getattr(args, "precision", "f32"),
                                        recurrence=getattr(args, "recurrence", "f32"), engines=engines)
                     for i, r in zip(idx, res):
-                        rid = parsed[i][0]
-                        name = (rid.decode("utf-8") if isinstance(rid, (bytes, np.bytes_)) else str(rid)) if args.use_id \
-                            else Path(chunk[i]).stem
+                        name = _read_name(args, chunk[i], parsed[i][0])
                         s = r[0] if fastq else r
                         print(fasta_format(name, s), file=fa)
                         if fastq:

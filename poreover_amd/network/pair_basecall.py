@@ -19,7 +19,7 @@ from .. import _lib, _marshal
 from . import basecall as _basecall
 from . import checkpoint as ckpt
 from ._engine import Engine, close_engines, with_engine
-from .network import _layers_array, load_model, parse_fast5, read_fast5_raw
+from .network import load_model, parse_fast5, read_fast5_raw
 
 __all__ = ["pair_basecall_signals", "pair_basecall", "pair_groups", "pair_tables", "resolve_read", "qual_bytes_query",
            "write_pair_fastq", "PairBasecaller", "pair_basecall_raw", "engine_group_plan"]
@@ -169,42 +169,42 @@ class PairBasecaller(Engine):
         return res
 
 
-def _stream(what, make, run, pairs, n_reads, logits, qualities, band, worker_stats=None, engines=None):
-    """pair_basecall_signals' results over the engine: make(fastq, band) -> PairBasecaller; run(engine, which, want_logits,
-    flags) -> its dict for the pairs at positions `which` with "reads", the indices of the reads it was given.  The unbanded
-    retry, the check and the warning are pair_basecall_signals'.  engines (a dict, or None): the caller's engines by
-    (fastq, band), made here when first needed and left open for its later calls; without it an engine lives for this call."""
-    results, read_logits = [None] * len(pairs), [None] * n_reads
+def _engine_route(make, run, precision, recurrence, worker_stats, engines):
+    """The engine route: make(fastq, band) -> PairBasecaller; run(engine, which, want_logits, flags) -> its
+    dict for the pairs at positions `which` with "reads", the indices of the reads it was given.  engines (a dict, or None):
+    the caller's engines by (fastq, band), made here when first needed and left open for its later calls; without it an
+    engine lives for one call of the route."""
+    def route(which, band, want_logits, flags):
+        fastq, band = band is not None, int(band or 0)
+        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
+            r = with_engine(engines, (fastq, band), lambda: make(fastq, band), lambda eng: run(eng, which, want_logits, flags),
+                            worker_stats)
+        return r["records"], r.get("fields"), dict(zip(r["reads"], r["logits"])) if want_logits else {}
+    return route
 
-    def go(which, fastq, band_, want_logits, flags):
-        band_ = int(band_ or 0)
-        return with_engine(engines, (bool(fastq), band_), lambda: make(fastq, band_), lambda eng: run(eng, which, want_logits, flags),
-                           worker_stats)
 
-    if not pairs:
-        return results, read_logits
-    every = list(range(len(pairs)))
-    r = go(every, qualities, band if qualities else 0, logits, None)
-    results = r["records"]
-    if logits:
-        for j, i in enumerate(r["reads"]):
-            read_logits[i] = r["logits"][j]
-    if qualities:
+def _results(what, route, n_pairs, n_reads, logits, band):
+    """pair_basecall_signals' return value for n_pairs pairs of n_reads reads, whatever runs them: route(which, band,
+    want_logits, flags) -> (records, fields or None, {read: logits}) of the pairs at positions `which`; band None: no
+    qualities; flags: per pair of `which` the four items' "no band" flags, or None.  The unbanded retry, its check and the
+    warning are quality.pair_retry's, reported under the name `what`; a decoded pair's record takes its fields here."""
+    read_logits = [None] * n_reads
+
+    def run(which, flags):    # (the logits are the first call's)
+        records, fields, lgs = route(which, band, logits and flags is None, flags)
+        for r, lg in lgs.items():
+            read_logits[r] = lg
+        return records, fields
+
+    if band is None:
+        results = run(list(range(n_pairs)), None)[0] if n_pairs else []
+    else:
         from .. import quality
-        fields = r["fields"]
-        retry = quality.pair_retry_flags(fields, band)
-        if retry:
-            which = sorted(retry)
-            r2 = go(which, True, band, False, [retry[k] for k in which])
-            for j, k in enumerate(which):
-                if any(r2["records"][j][key] != results[k][key] for key in ("status", "seq1", "seq2", "consensus")):
-                    raise RuntimeError("%s: pair %d decodes differently in the unbanded retry" % (what, k))
-                quality.pair_retry_merge(fields[k], r2["fields"][j], retry[k])
-        quality.pair_warn_unscored(fields)
+        results, fields = quality.pair_retry(run, n_pairs, band, what)
         for rec, f in zip(results, fields):
             if f is not None:
                 rec.update(f)
-    return results, read_logits
+    return (results, read_logits) if logits else results
 
 
 def _compact(pairs, which):
@@ -254,11 +254,11 @@ def pair_basecall_raw(net, raws, pairs, channels=None, scaling="standard", devic
         r["reads"] = reads
         return r
 
-    with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-        results, read_logits = _stream("pair_basecall_raw", make, run, pairs, len(raws), logits, qualities, band, worker_stats, engines)
+    out = _results("pair_basecall_raw", _engine_route(make, run, precision, recurrence, worker_stats, engines), len(pairs), len(raws),
+                   logits, band)
     if kept is not None:
         kept.extend(counts)
-    return (results, read_logits) if logits else results
+    return out
 
 
 def _check_decoder(what, merge_repeats, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width, qualities,
@@ -280,7 +280,9 @@ def _check_decoder(what, merge_repeats, beam_width, method, padding, alignment, 
     return _marshal.pair_options(kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width), band
 
 
-def _check_pairs(what, pairs, n_reads):
+def _check_pairs(what, pairs, n_reads, lens=None):
+    """the pairs as tuples of two ints; ValueError for anything but two indices of reads — with lens (the reads' sample counts)
+    of reads that have samples"""
     pairs = [tuple(p) for p in pairs]
     for k, p in enumerate(pairs):
         if len(p) != 2:
@@ -288,6 +290,8 @@ def _check_pairs(what, pairs, n_reads):
         for r in p:
             if not (isinstance(r, (int, np.integer)) and 0 <= r < n_reads):
                 raise ValueError("%s: pair %d names read %r (reads 0 to %d)" % (what, k, r, n_reads - 1))
+            if lens is not None and not lens[r]:
+                raise ValueError("%s: pair %d: read %d has no samples" % (what, k, r))
     return [(int(a), int(b)) for a, b in pairs]
 
 
@@ -319,11 +323,8 @@ def _engine_call(lib, net, sigs, pairs, window, overlap, reverse_complement, opt
     flags, or None — and odds): po_pair_basecall_fastq_batch_h instead, and a third item, quality.pair_fields' dicts.
     skip ((skip_threshold, indel_threshold), without fastq): po_pair_basecall_skip_batch_h, the --skip_matches pair chain."""
     n, P = len(sigs), len(pairs)
-    off = _marshal.offsets([len(s) for s in sigs])
+    signal, off, w, layers = _basecall._net_args(net, sigs)
     rows = int(off[-1])
-    signal = np.ascontiguousarray(np.concatenate(sigs), dtype=np.float32)
-    w = np.ascontiguousarray(net.flat_weights(), dtype=np.float32)
-    layers = _layers_array(net)
     idx = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
     s1o = _marshal.offsets([len(sigs[r]) for ab in pairs for r in ab], 2 * P)
     so = _marshal.offsets([len(sigs[a]) + len(sigs[b]) for a, b in pairs], P)
@@ -409,98 +410,57 @@ def pair_basecall_signals(net, signals, pairs, window=1000, overlap=0, reverse_c
         raise ValueError("pair_basecall_signals: skip_matches is not built together with diagonal_envelope (no alignment to take anchors from)")
     if skip_matches and int(skip_threshold) < 1:
         raise ValueError("pair_basecall_signals: skip_threshold %d (1 at least)" % skip_threshold)
-    if qualities:
-        from .. import quality
-        band = quality.check_band("pair_basecall_signals", qual_band)
-    if method not in _lib.METHODS:
-        raise ValueError("pair_basecall_signals: method %r (row_col, row or grid; the split method is not built here)" % (method,))
-    if alignment not in ("banded", "full"):
-        raise ValueError("pair_basecall_signals: alignment %r (banded or full)" % (alignment,))
-    if not 1 <= int(beam_width) <= 25:
-        raise ValueError("pair_basecall_signals: beam_width %d (1 to 25)" % beam_width)
+    opt, band = _check_decoder("pair_basecall_signals", merge_repeats, beam_width, method, padding, alignment, diagonal_envelope,
+                               diagonal_width, qualities, qual_band)
     _basecall.window_plan(1, window, overlap)
     _basecall.check_time_order(net.kinds)
     sigs = [np.asarray(s, dtype=np.float32).ravel() for s in signals]
-    pairs = [tuple(p) for p in pairs]
-    for k, p in enumerate(pairs):
-        if len(p) != 2:
-            raise ValueError("pair_basecall_signals: pair %d has %d entries (two read indices)" % (k, len(p)))
-        for r in p:
-            if not (isinstance(r, (int, np.integer)) and 0 <= r < len(sigs)):
-                raise ValueError("pair_basecall_signals: pair %d names read %r (reads 0 to %d)" % (k, r, len(sigs) - 1))
-            if not len(sigs[r]):
-                raise ValueError("pair_basecall_signals: pair %d: read %d has no samples" % (k, r))
-    pairs = [(int(a), int(b)) for a, b in pairs]
-    results, read_logits = [None] * len(pairs), [None] * len(sigs)
+    lens = [len(s) for s in sigs]
+    pairs = _check_pairs("pair_basecall_signals", pairs, len(sigs), lens)
     if devices is not None:
-        opt = _marshal.pair_options("bonito" if merge_repeats else "poreover", beam_width, method, padding, alignment,
-                                    diagonal_envelope, diagonal_width)
         rb = _basecall.RESIDENT_BYTES if resident_bytes is None else int(resident_bytes)
 
         def make(fastq, band_):
             return PairBasecaller(net, devices, window, overlap, reverse_complement, opt, max_windows_per_pass, fastq, band_,
                                   resident_bytes=rb)
 
-        def run_engine(eng, which, want_logits, flags):
+        def run(eng, which, want_logits, flags):
             reads, local = _compact(pairs, which)
             r = eng.run_f32([sigs[i] for i in reads], local, want_logits, flags)
             r["reads"] = reads
             return r
 
-        with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-            results, read_logits = _stream("pair_basecall_signals", make, run_engine, pairs, len(sigs), logits, qualities,
-                                           band if qualities else 0, worker_stats, engines)
-        return (results, read_logits) if logits else results
-    if pairs:
-        lib = _lib.load()
-        kind = "bonito" if merge_repeats else "poreover"
-        opt = _marshal.pair_options(kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width)
-        lens = [len(s) for s in sigs]
-
+        route = _engine_route(make, run, precision, recurrence, worker_stats, engines)
+    else:
         skip = (int(skip_threshold), 100) if skip_matches else None     # (the reference's get_anchors(..., indels=100))
 
-        def ws_bytes(n, t1, t2, m1, m2):
-            if skip:   # the plan's workspace and, at most, every row again in the box batch
-                return int(lib.po_pair_skip_plan_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt), *skip)) + \
-                    (t1 + t2) * (8 * ckpt.NUM_LABELS + 32)
-            return int(lib.po_pair_decode_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt)))
+        def route(which, band_, want_logits, flags):
+            lib = _lib.load()
 
-        def run(which, want_logits, band_=None, flags=None):
-            """the engine calls of the pairs `which` (positions in pairs), group by group: (position, record, fields or None)"""
-            model = _lib.MODELS[_lib.MODEL_OF_KIND[kind]]
-            sub = [pairs[k] for k in which]
+            def ws_bytes(n, t1, t2, m1, m2):
+                if skip:   # the plan's workspace and, at most, every row again in the box batch
+                    return int(lib.po_pair_skip_plan_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt), *skip)) + \
+                        (t1 + t2) * (8 * ckpt.NUM_LABELS + 32)
+                return int(lib.po_pair_decode_workspace_bytes(n, t1, t2, m1, m2, ckpt.NUM_LABELS, C.byref(opt)))
+
             # (a retry call scores its flagged items without a band: its groups are sized for that workspace)
-            query = qual_bytes_query(lib, 0 if flags else band_, model) if band_ is not None else None
-            for group in pair_groups(sub, lens, ws_bytes, qual_bytes=query):
-                group = [which[g] for g in group]
-                reads = sorted({r for k in group for r in pairs[k]})
-                local = {r: j for j, r in enumerate(reads)}
-                fastq = None if band_ is None else {"band": band_, "odds": odds, "flags": [flags[k] for k in group] if flags else None}
+            query = qual_bytes_query(lib, 0 if flags else band_, opt.model) if band_ is not None else None
+            records, fields, lgs = [None] * len(which), [None] * len(which) if band_ is not None else None, {}
+            for group in pair_groups([pairs[k] for k in which], lens, ws_bytes, qual_bytes=query):
+                reads, local = _compact(pairs, [which[g] for g in group])
+                fastq = None if band_ is None else {"band": band_, "odds": odds, "flags": [flags[g] for g in group] if flags else None}
                 with _lib.call_precision(precision), _lib.recur_precision(recurrence):
-                    res = _engine_call(lib, net, [sigs[r] for r in reads],
-                                       [(local[pairs[k][0]], local[pairs[k][1]]) for k in group], window, overlap,
-                                       reverse_complement, opt, want_logits, stage_ms, max_windows_per_pass, fastq=fastq,
-                                       skip=skip)
+                    res = _engine_call(lib, net, [sigs[r] for r in reads], local, window, overlap, reverse_complement, opt,
+                                       want_logits, stage_ms, max_windows_per_pass, fastq=fastq, skip=skip)
                 if want_logits:
-                    for r, lg in zip(reads, res[1]):
-                        read_logits[r] = lg
-                for j, k in enumerate(group):
-                    yield k, res[0][j], (res[2][j] if fastq else None)
+                    lgs.update(zip(reads, res[1]))
+                for j, g in enumerate(group):
+                    records[g] = res[0][j]
+                    if fastq:
+                        fields[g] = res[2][j]
+            return records, fields, lgs
 
-        fields = [None] * len(pairs)
-        for k, rec, f in run(list(range(len(pairs))), logits, band if qualities else None):
-            results[k], fields[k] = rec, f
-        if qualities:
-            retry = quality.pair_retry_flags(fields, band)
-            for k, rec, g in run(sorted(retry), False, band, retry):
-                if any(rec[key] != results[k][key] for key in ("status", "seq1", "seq2", "consensus")):
-                    raise RuntimeError("pair_basecall_signals: pair %d decodes differently in the unbanded retry" % k)
-                quality.pair_retry_merge(fields[k], g, retry[k])
-            quality.pair_warn_unscored(fields)
-            for rec, f in zip(results, fields):
-                if f is not None:
-                    rec.update(f)
-    return (results, read_logits) if logits else results
+    return _results("pair_basecall_signals", route, len(pairs), len(sigs), logits, band)
 
 
 def resolve_read(name, reads_dir):

@@ -83,6 +83,33 @@ def warn_unscored(what):
                                               len(what), ", ".join(what[:8]), " ..." if len(what) > 8 else "")
 
 
+def warn_unscored_reads(status):
+    """one log line (warn_unscored) naming the reads of {read: status} whose status is not 0: they are written with Q 0"""
+    bad = [k for k, st in status.items() if st != 0]
+    if bad:
+        warn_unscored(["read %d (%s)" % (k, _lib._CODE_NAMES.get(int(status[k]), int(status[k]))) for k in bad])
+
+
+RETRY_DIFFERS = "%s: %s %d decodes differently in the unbanded retry"
+
+
+def retry_unbanded(run, keys, band, same=None, what="call_qualities"):
+    """The retry rule of a banded quality call on reads, whatever runs it.  run(keys, band) ->
+    {key: (value, status)}.  Every key is run with `band`; with band > 0 the keys whose banded lattice is lost (E_ENVELOPE) are
+    run once more, together, with band 0 and take that call's value and status.  same(first value, second value), where
+    given, must hold for each of them: RuntimeError under the name `what`.  Returns ({key: (value, status)}, the retried keys)."""
+    keys = list(keys)
+    got = dict(run(keys, band)) if keys else {}
+    retried = [k for k in keys if got[k][1] == _lib.E_ENVELOPE] if band > 0 else []
+    if retried:
+        second = run(retried, 0)
+        for k in retried:
+            if same is not None and not same(got[k][0], second[k][0]):
+                raise RuntimeError(RETRY_DIFFERS % (what, "read", k))
+            got[k] = second[k]
+    return got, retried
+
+
 def call_guides(tables, seqs, kind):
     """Band guides for scoring seqs[i] on tables[i]: the Viterbi call's frame map says how many called bases every frame
     has behind it; when seqs[i] is not that call (beam, prefix, consensus) the two are aligned and the count is taken
@@ -130,12 +157,15 @@ def call_qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND, return_guide
     t0 = time.perf_counter()
     guides = call_guides(tables, seqs, kind)
     t1 = time.perf_counter()
-    odds, _, status = _batch.qual_batch(tables, seqs, guides, band_size=band, model=model) if tables else ([], None, np.zeros(0, np.int32))
-    retried = [i for i in range(len(tables)) if status[i] == _lib.E_ENVELOPE] if band > 0 else []
-    if retried:
-        o2, _, s2 = _batch.qual_batch([tables[i] for i in retried], [seqs[i] for i in retried], None, band_size=0, model=model)
-        for j, i in enumerate(retried):
-            odds[i], status[i] = o2[j], s2[j]
+
+    def run(idx, band_):    # (the first call, the one with the caller's band, is on every read: the guides are its alone)
+        o, _, st = _batch.qual_batch([tables[i] for i in idx], [seqs[i] for i in idx], guides if band_ == band else None,
+                                     band_size=band_, model=model)
+        return {i: (o[j], st[j]) for j, i in enumerate(idx)}
+
+    got, retried = retry_unbanded(run, range(len(tables)), band)
+    odds = [got[i][0] for i in range(len(tables))]
+    status = np.array([got[i][1] for i in range(len(tables))], dtype=np.int32)
     if timings is not None:
         timings["guides"] = timings.get("guides", 0.0) + t1 - t0
         timings["lattice"] = timings.get("lattice", 0.0) + time.perf_counter() - t1
@@ -146,9 +176,7 @@ def call_qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND, return_guide
 def qualities(models_or_arrays, seqs, kind, band=DEFAULT_BAND):
     """Phred arrays of seqs[i] on read i; a read that cannot be scored at all (status != 0) gets Q 0 throughout"""
     odds, status, _ = call_qualities(models_or_arrays, seqs, kind, band)
-    bad = [i for i, st in enumerate(status) if st != 0]
-    if bad:
-        warn_unscored(["read %d (%s)" % (i, _lib._CODE_NAMES.get(int(status[i]), int(status[i]))) for i in bad])
+    warn_unscored_reads(dict(enumerate(status)))
     return [phred(o, s) if st == 0 else np.zeros(len(s), dtype=np.uint8) for o, s, st in zip(odds, seqs, status)]
 
 
@@ -221,6 +249,27 @@ def pair_warn_unscored(fields, what="pair"):
         warn_unscored(bad)
 
 
+def pair_retry(run, n, band, what, check_strings=True):
+    """The retry rule of a pair quality call, whatever runs it.  run(which, flags) -> (records, fields) of
+    the pairs at positions `which`; flags: per pair of `which` the four items' "no band" flags, or None.  One call on all n
+    pairs; one more on the pairs with a lost item (pair_retry_flags), those items flagged, merged by pair_retry_merge;
+    check_strings: that call must decode each pair as the first did (RuntimeError under the name `what`); then the line in
+    the log for what is still unscored.  Returns (records, fields) of the first call, the fields after the merge."""
+    if not n:
+        return [], []
+    records, fields = run(list(range(n)), None)
+    retry = pair_retry_flags(fields, band)
+    if retry:
+        which = sorted(retry)
+        records2, fields2 = run(which, [retry[k] for k in which])
+        for j, k in enumerate(which):
+            if check_strings and any(records2[j][key] != records[k][key] for key in ("status", "seq1", "seq2", "consensus")):
+                raise RuntimeError(RETRY_DIFFERS % (what, "pair", k))
+            pair_retry_merge(fields[k], fields2[j], retry[k])
+    pair_warn_unscored(fields)
+    return records, fields
+
+
 def _pair_qual_call(lib, tables1, tables2, records, model, band, flags=None, odds=False, guides=False):
     """one po_pair_qual_h call on the records' strings; flags: per record the four items' "no band" flags, or None"""
     from . import _marshal
@@ -272,13 +321,10 @@ def pair_qualities(tables1, tables2, records, kind, band=DEFAULT_BAND, odds=Fals
         return []
     lib = _lib.load()
     model = MODEL_OF_KIND[kind]
-    fields = _pair_qual_call(lib, tables1, tables2, records, model, band, None, odds, guides)
-    retry = pair_retry_flags(fields, band)
-    if retry:
-        idx = sorted(retry)
-        second = _pair_qual_call(lib, [tables1[i] for i in idx], [tables2[i] for i in idx], [records[i] for i in idx], model, band,
-                                 [retry[i] for i in idx], odds)
-        for i, g in zip(idx, second):
-            pair_retry_merge(fields[i], g, retry[i])
-    pair_warn_unscored(fields)
-    return fields
+
+    def run(which, flags):   # (the strings are the caller's: nothing to check in the retry; the guides are the first call's)
+        recs = [records[i] for i in which]
+        return recs, _pair_qual_call(lib, [tables1[i] for i in which], [tables2[i] for i in which], recs, model, band, flags, odds,
+                                     guides and flags is None)
+
+    return pair_retry(run, len(records), band, "pair_qualities", check_strings=False)[1]

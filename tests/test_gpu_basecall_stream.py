@@ -70,6 +70,24 @@ def test_qualities_equal_one_call(arch, algorithm, band):
     assert all(len(q) == len(s) for s, _, q in got)
 
 
+@pytest.mark.parametrize("algorithm,merge,lost", [("viterbi", False, 0), ("beam", True, 6)])
+def test_retry_happens_on_both_routes(algorithm, merge, lost):
+    """Case A on conv1_bigru3 at band 1, (string, q) tuples: the single-call route and the engine route on devices=[0] give
+    the same, and the engine ran once more for the reads that lost their banded lattice.  Measured before the two routes
+    shared their retry rule (quality.retry_unbanded): with Viterbi no read of the nine loses its lattice at band 1, 2 or 4
+    (the guide is the call's own frame map) — one engine run; with the beam search (width 5) and merge_repeats reads 3 to 8,
+    six of the nine, lose it at each of the three bands — a second run, of those six.  A retry that stops happening, or
+    that takes every read, fails here."""
+    from poreover_amd.network import basecall_signals
+    net, sigs = B.net("conv1_bigru3"), B.signals("A")
+    kw = dict(window=40, overlap=8, algorithm=algorithm, beam_width=5, merge_repeats=merge, qualities=True, qual_band=1)
+    want = basecall_signals(net, sigs, **kw)
+    stats = []
+    got = basecall_signals(net, sigs, devices=[0], worker_stats=stats, **kw)
+    _same(got, want)
+    assert [sum(w["reads"] for w in run) for run in stats] == ([len(sigs), lost] if lost else [len(sigs)])
+
+
 def test_runs_engines_and_one_device_agree():
     from poreover_amd import _lib
     from poreover_amd.network import basecall as N
