@@ -294,8 +294,8 @@ void beam2d_reg_kernel(RegArgs a) {
 
 #ifdef PO_REG_TIMING
     // phase timers of workgroup 0 (wall_clock64: 100 MHz) and counts: see po_reg_launch for the names
-    long long tk[56], tlast = wall_clock64();
-    for (int i = 0; i < 56; ++i) tk[i] = 0;
+    long long tk[60], tlast = wall_clock64();
+    for (int i = 0; i < 60; ++i) tk[i] = 0;
 #define KT(i) do { const long long n_ = wall_clock64(); tk[(i)] += n_ - tlast; tlast = n_; } while (0)
 #define KC(i, n) do { tk[(i)] += (n); } while (0)
 #else
@@ -756,6 +756,7 @@ void beam2d_reg_kernel(RegArgs a) {
             const int sym = sym_last(e_sym), cb = (MODEL == PO_MODEL_FLIPFLOP) ? sym + A : A;
             const bool same = sym_plast(e_sym) == sym;
             KT(1); KC(13, 1);
+            KC(11, (d0 - u) != (d1 - v) ? 1 : 0); KC(15, (d0 - u == 0) != (d1 - v == 0) ? 1 : 0); KC(58, (d0 - u == 0 && d1 - v > 0) ? 1 : 0);
 #pragma unroll
             for (int q = 0; q < NR; ++q) {
             const int r = RD(q);
@@ -783,8 +784,11 @@ void beam2d_reg_kernel(RegArgs a) {
             // of the iteration before.
             const int n1max = (NR == 1) ? max(d0 - u, d1 - v) : n1;
             KC(14, n1max);
+            // (per read: a part ends exactly at the block's end; one time is left over for a block of its own)
+            KC(56, __ballot(n1 > 0 && (n1 & (RK_NY - 1)) == 0) != 0ull ? 1 : 0); KC(57, __ballot((n1 & (RK_NY - 1)) == 1 && n1 > RK_NY) != 0ull ? 1 : 0);
             const double* const ps_ = &sm.pst[(NR == 1) ? r : 0][myk * RK_NY][0];
             for (int k0 = 0; k0 < n1max; k0 += RK_NY) {
+                KC(3, k0 > 0 ? 1 : 0);
                 rk_sync();   // (every lane is done with the rows and staged values of the block before)
                 // (the first two parents' entries are asked for BEFORE the y rows: one memory round trip for the rows and the
                 //  staged values of the usual step — one or two nodes entered the beam — instead of one after the other)
@@ -992,36 +996,51 @@ void beam2d_reg_kernel(RegArgs a) {
                     }
                 }
                 } else {
+                // The chain loop without its per-iteration bookkeeping.  Which lanes take part is decided once per PART of the
+                // block, not per iteration — NR = 1: the block is cut where the shorter read ends; up to there every fresh lane
+                // runs, from there on the fresh lanes of the longer read; NR = 2: one part —, and two iterations are written out
+                // with the roles of the value going in and the value coming out swapped, so that no copy remains: two vector
+                // instructions, five scalar ones and a branch less per iteration than `if (fresh && k < n1)` around one
+                // iteration.  (A wave's own time per iteration counts as much as the instructions it issues: forms of this
+                // loop with fewer vector instructions still — running addresses with the rings' wraps behind a scalar test —
+                // were slower for their scalar work and branches: profiles/chain_loop_ab.txt.)
                 // (the operands of an iteration are asked for one iteration ahead: a lone wave then waits for the LDS only
-                //  inside logaddexp's own table lookups)
-                double nya = 0.0, nyb = 0.0;
-                PVal npp;
-                for (int c = 0; c < KP; ++c) npp.v[c] = 0.0;
-                if (fresh[q] && k0 < n1) {
-                    const double* yrow = yb_ + ((ws + k0) & (RK_NY - 1)) * RK_YC;
-                    nya = yrow[sym]; nyb = yrow[cb];
-                    for (int c = 0; c < KP; ++c) npp.v[c] = ps_[c];
-                }
-                for (int k = k0; k < k1; ++k) {
-                    if (fresh[q] && k < n1) {
-                        const int t = ws + k;
-                        const double ya = nya, yb = nyb;
-                        const PVal pp = npp;
-                        {   // (one past the end of the block: read, never used — the slots exist)
-                            const double* yrow = yb_ + ((t + 1) & (RK_NY - 1)) * RK_YC;
-                            nya = yrow[sym]; nyb = yrow[cb];
-                            const double* pn = ps_ + min(k - k0 + 1, RK_NY - 1) * KP;
-                            for (int c = 0; c < KP; ++c) npp.v[c] = pn[c];
-                        }
-                        const Val out = upd(self, pp, ya, yb, same);
+                //  inside logaddexp's own table lookups; one past the end of the part: read, never used — the slots exist)
+                auto ahead = [&](int k, double& ya, double& yb, PVal& pp) {   // the operands of time ws + k
+                    const double* yrow = yb_ + ((ws + k) & (RK_NY - 1)) * RK_YC;
+                    ya = yrow[sym]; yb = yrow[cb];
+                    const double* pn = ps_ + min(k - k0, RK_NY - 1) * KP;
+                    for (int c = 0; c < KP; ++c) pp.v[c] = pn[c];
+                };
+                auto chain1 = [&](const Val& in, const PVal& pp, double ya, double yb, int k) -> Val {   // time ws + k of the chain
+                    const int t = ws + k;
+                    const Val out = upd(in, pp, ya, yb, same);
 #ifdef PO_RING_TRACE_NODE
-                        if (pi == 0 && e_id == PO_RING_TRACE_NODE) printf("V %d %d %d %.17g %.17g %.17g P1\n", e_id, r, t, out.v[0], pp.v[0], self.v[0]);
+                    if (pi == 0 && e_id == PO_RING_TRACE_NODE) printf("V %d %d %d %.17g %.17g %.17g P1\n", e_id, r, t, out.v[0], pp.v[0], in.v[0]);
 #endif
-                        t2_write(r, e_row2, t, out); SH_WRITE(r, e_row2, t, e_id);
-                        if (out.v[0] > self.v[0]) tr = t;
-                        self = out;
-                        mt = (out.v[0] >= mx) ? t : mt;
-                        mx = po_vmax(mx, out.v[0]);
+                    t2_write(r, e_row2, t, out); SH_WRITE(r, e_row2, t, e_id);
+                    if (out.v[0] > in.v[0]) tr = t;
+                    mt = (out.v[0] >= mx) ? t : mt;
+                    mx = po_vmax(mx, out.v[0]);
+                    return out;
+                };
+                const int ncut = (NR == 1) ? min(d0 - u, d1 - v) : n1;   // (wave-uniform)
+#pragma unroll 1
+                for (int part = 0; part < ((NR == 1) ? 2 : 1); ++part) {
+                    const int ka = part ? max(k0, ncut) : k0, kb = part ? k1 : min(k1, ncut);
+                    if (ka >= kb) continue;                                // (wave-uniform)
+                    if (fresh[q] && (part == 0 || n1 > ncut)) {            // (the same for every k of the part)
+                        double ya, yb, nya, nyb;
+                        PVal pp, npp;
+                        ahead(ka, ya, yb, pp);
+                        for (int k = ka;; k += 2) {
+                            ahead(k + 1, nya, nyb, npp);
+                            const Val o = chain1(self, pp, ya, yb, k);
+                            if (k + 1 >= kb) { self = o; break; }
+                            ahead(k + 2, ya, yb, pp);
+                            self = chain1(o, npp, nya, nyb, k + 1);
+                            if (k + 2 >= kb) break;
+                        }
                     }
                 }
                 }   // (!SCAN)
@@ -1400,6 +1419,7 @@ void beam2d_reg_kernel(RegArgs a) {
                         // (a frozen parent's captured value can only be asked for by the first new time — the test above — : one select
                         //  per iteration instead of two compares and two)
                         PVal pp_fz = (fzl && dr - 1 == fz_t[q]) ? fz_val[q] : pval_neg();
+                        KC(19, __ballot(live && n2 > 0 && fzl && dr - 1 == fz_t[q]) != 0ull ? 1 : 0);
                         for (int k0 = 0; k0 < n2max; k0 += RK_NY) {   // (blocks of RK_NY times: the y rows are loaded between the loops)
                             {
                                 const int lo = dr + k0, hi = min(lo + RK_NY, we);
@@ -1641,7 +1661,7 @@ void beam2d_reg_kernel(RegArgs a) {
     }
 #ifdef PO_REG_TIMING
     if (lane == 0 && a.dbg && slotid == 0)
-        for (int i = 0; i < 56; ++i) a.dbg[i] = tk[i];
+        for (int i = 0; i < 60; ++i) a.dbg[i] = tk[i];
 #endif
     if (COUNT && lane == 0 && a.upd_count) { atomicAdd(a.upd_count, sm.nupd); atomicAdd(a.upd_count + 1, sm.nupd_x); }
     // (everything this wave wrote into the slice leaves this XCD's L2 before another wave — any CU, any XCD — may claim it)
@@ -1731,8 +1751,8 @@ extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wid
     a.reg_slots = slots;
 #ifdef PO_REG_TIMING
     static long long* dbg = nullptr;
-    if (!dbg) { (void)hipMalloc((void**)&dbg, 56 * sizeof(long long)); }
-    (void)hipMemsetAsync(dbg, 0, 56 * sizeof(long long), stream);
+    if (!dbg) { (void)hipMalloc((void**)&dbg, 60 * sizeof(long long)); }
+    (void)hipMemsetAsync(dbg, 0, 60 * sizeof(long long), stream);
     a.dbg = dbg;
 #endif
     if (wide) {
@@ -1744,7 +1764,7 @@ extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wid
     }
 #ifdef PO_REG_TIMING
     {
-        long long h[56];
+        long long h[60];
         (void)hipStreamSynchronize(stream);
         (void)hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost);
         fprintf(stderr, "[po_reg_timing] pair slot 0, 10 ns ticks\n");
@@ -1759,6 +1779,7 @@ extern "C" void po_reg_launch(const void* regargs, int slots, int model, int wid
         fprintf(stderr, "   closed-form chains: %lld passes (a staged parent's children on both reads), %lld of them left to the serial chain\n", h[34], h[35]);
         fprintf(stderr, "   nodes entering the beam: %lld, of them expanded before %lld, with their children's row group still theirs %lld\n", h[36], h[37], h[38]);
         fprintf(stderr, "   rankings: %lld, of them with equal scores in the set (ids looked at) %lld, tie replays %lld; child slots that are aliases of beam slots: %lld; rewinds (part G): %lld; table builds that replace the whole beam: %lld\n", h[39], h[51], h[52], h[53], h[54], h[55]);
+        fprintf(stderr, "   chain loops: phase-1 blocks after a step's first %lld; new-element steps with unequal n1 %lld, with n1 = 0 on one read only %lld (on read 0: %lld); a read's n1 a multiple of the block %lld, one more than a multiple %lld; run steps whose first new time reads a frozen parent's captured value %lld\n", h[3], h[11], h[15], h[58], h[56], h[57], h[19]);
         fprintf(stderr, "   table builds that ask the arena for a node's children: %lld; window rescans: %lld lanes in %lld calls; bounds made exact in %lld steps\n", h[20], h[21], h[10], h[31]);
     }
 #endif
