@@ -147,6 +147,52 @@ int po_set_align_route(int legacy);
 int po_ingest_batch(const void* src, const int64_t* row_off, int n, int C, int mode, const int* perm_h,
                     int reverse, double* out, void* stream);
 
+/* ---- ingest of a model's output as it lies in memory (poreover_amd/tensors.py) ---------------------------
+ * Item i is a (T_i, C) view of `dtype` elements: element (t, c) at base + (t * row_stride + c * col_stride) * sizeof(dtype),
+ * T_i = row_off[i+1] - row_off[i].  A padded batch in either layout, a slice, a transposed or an expanded view (stride 0) are
+ * all item tables.  out[(row_off[i] + t) * C + c] = v[perm[c]] of source row t (reverse != 0: of row T_i - 1 - t), where v is
+ *   normalize != 0, F32 / F16 / BF16: the row widened to float32 (exact), x - logsumexp(x) in float32, widened: the bits of
+ *                  po_ingest_batch(PO_INGEST_LOGITS_F32) on the widened rows;   F64: PO_E_UNSUPPORTED
+ *   normalize == 0: the values widened to double (F64: the bits of PO_INGEST_F64).
+ * items and row_off are DEVICE arrays (n and n + 1 entries); total_rows = row_off[n] (row_off[0] == 0), given by the caller,
+ * so that the call is enqueue-only: no allocation, no synchronisation, no read of device memory by the host.
+ * Two kernels give the same bits.  The default takes one frame per lane, consecutive lanes along `out`: right where an item's
+ * rows are adjacent in the source (batch-major).  PO_INGEST_TILED or-ed into dtype selects the tiled kernel: a workgroup takes
+ * 32 consecutive items x 16 time steps and reads with lanes running along the ITEMS, for sources whose items interleave
+ * (time-major, (T, N, C): item i + 1 starts C elements after item i), and writes through LDS along out's rows.  The caller
+ * knows its strides; the host twin below looks at them itself (PO_INGEST_PER_FRAME or-ed in keeps it from choosing).
+ * PO_E_ARG before any launch: n < 0 or total_rows < 0, C outside 1..8, an unknown dtype, a perm entry outside [0, C), null
+ * items / row_off / out with total_rows > 0.  n == 0 or total_rows == 0: PO_OK, nothing launched. */
+typedef struct { const void* base; int64_t row_stride; int64_t col_stride; } po_ingest_item;  /* strides in ELEMENTS, >= 0 */
+#define PO_DTYPE_F32 0
+#define PO_DTYPE_F16 1
+#define PO_DTYPE_BF16 2
+#define PO_DTYPE_F64 3
+#define PO_INGEST_TILED 0x100
+#define PO_INGEST_PER_FRAME 0x200
+int po_ingest_strided(const po_ingest_item* items, const int64_t* row_off, int n, int C, int dtype, int normalize,
+                      const int* perm_h, int reverse, int64_t total_rows, double* out, void* stream);
+/* host twin: src_h is one host block of src_elems elements; item i's element (0, 0) is element item_off_h[i] of it, its strides
+ * row_stride_h[i] / col_stride_h[i].  Also PO_E_ARG: row_off_h[0] != 0 or decreasing, a negative offset or stride, an item that
+ * reaches past src_elems. */
+int po_ingest_strided_h(const void* src_h, int64_t src_elems, const int64_t* item_off_h, const int64_t* row_stride_h,
+                        const int64_t* col_stride_h, const int64_t* row_off_h, int n, int C, int dtype, int normalize,
+                        const int* perm_h, int reverse, double* out_h);
+
+/* ---- compaction of a decode's strings -----------------------------------------------------------------------------------
+ * The decoders write string i at seq + seq_off[i] in a buffer sized for the longest possible answer.  po_pack_strings puts the
+ * strings back to back: packed_off (device, n + 1) = exclusive scan of (status[i] == 0 ? seq_len[i] : 0) (status NULL: every
+ * length counts; a length is taken as at least 0 and at most the string's room seq_off[i+1] - seq_off[i], so `packed` never
+ * needs more than seq's own size), packed + packed_off[i] = the string.  Enqueue-only.  The 1-D basecalls of a pair decode have
+ * no status of their own: status NULL, n = 2 * pairs.  PO_E_ARG: n < 0, a null seq / seq_off / seq_len / packed with n > 0, a
+ * null packed_off; PO_E_CAP: ws_bytes < po_pack_strings_workspace_bytes(n). */
+size_t po_pack_strings_workspace_bytes(int n);
+int po_pack_strings(const char* seq, const int64_t* seq_off, const int32_t* seq_len, const int32_t* status, int n,
+                    char* packed, int64_t* packed_off, void* ws, size_t ws_bytes, void* stream);
+/* host twin: packed_h has room for seq_off_h[n] - seq_off_h[0] bytes (what is past packed_off_h[n] is left alone) */
+int po_pack_strings_h(const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h, int n,
+                      char* packed_h, int64_t* packed_off_h);
+
 /* ---- transducer.argmax_decode / viterbi_decode ------------------------------------------
  * replaces transducer.py:27-33 (argmax), :72-73 (poreover), :83-89 (bonito), :35-59 +
  * :94-103 (flip-flop Viterbi) and pair_decode.get_sequence_mapping (pair_decode.py:114-142).

@@ -20,6 +20,8 @@ MODELS = {"ctc": 0, "ctc_merge_repeats": 1, "ctc_flipflop": 2}
 METHODS = {"row": 0, "row_col": 1, "grid": 2}
 KINDS = {"poreover": 0, "bonito": 1, "flipflop": 2}
 MODEL_OF_KIND = {"poreover": "ctc", "bonito": "ctc_merge_repeats", "flipflop": "ctc_flipflop"}   # the tree model that decodes a basecaller kind
+DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2, "float64": 3}   # PO_DTYPE_* of po_ingest_strided
+INGEST_TILED, INGEST_PER_FRAME = 0x100, 0x200
 K_VITERBI, K_BEAM1D, K_BEAM2D, K_ALIGN, K_ENVELOPE, K_BEAM2D_MAIN = range(6)
 _CODE_NAMES = {E_CAP: "PO_E_CAP (buffer too small)", E_ARG: "PO_E_ARG (bad argument)",
                E_ENVELOPE: "PO_E_ENVELOPE (envelope undefined for the reference)",
@@ -97,6 +99,12 @@ PROTOTYPES = {
     "po_set_align_route": (C.c_int, [C.c_int]),
     "po_ingest_batch": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _vp]),
     "po_ingest_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dp]),
+    "po_ingest_strided": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int64, _dp, _vp]),
+    "po_ingest_strided_h": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.POINTER(C.c_int), C.c_int, _dp]),
+    "po_pack_strings_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "po_pack_strings": (C.c_int, [_cp, _i64p, _i32p, _i32p, C.c_int, _cp, _i64p, _vp, C.c_size_t, _vp]),
+    "po_pack_strings_h": (C.c_int, [_cp, _i64p, _i32p, _i32p, C.c_int, _cp, _i64p]),
     "po_viterbi_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "po_viterbi_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _vp, _cp, _i64p, _i32p,
                                    _i32p, _i32p, _vp, C.c_size_t, _vp]),

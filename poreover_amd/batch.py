@@ -3,7 +3,8 @@
 These are what the drivers (decode / pair-decode) call instead of the reference's
 multiprocessing.Pool fan-out (decode.py:158-162, pair_decode.py:292-297): one launch per batch.
 Host buffers go through the *_h entry points of the C-ABI (which copy to the device, launch,
-and copy back); device-resident callers use the device-pointer forms directly (see bench.py).
+and copy back); callers whose tables are torch tensors on the device already use poreover_amd.tensors, which runs the
+device-pointer forms in the caller's stream.
 
 Every wrapper is: marshal with _marshal.py's helpers, one engine call, check the statuses, unpack.  The pipelined host
 layer (pair_decode_stream, pair_decode_batch_sharded and their cached pipelines) lives in stream.py and is re-exported here.

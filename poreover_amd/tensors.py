@@ -1,0 +1,389 @@
+"""PyTorch front end of the engine for tables that are on the device already: torch tensors in, decoded records out.
+
+A basecaller that is a PyTorch model leaves its output in GPU memory — Bonito: a (T, N, 5) half-precision tensor, blank first.
+batch.py would have it copied to the host, widened to float64, cut into a list, packed again and uploaded at eight bytes per
+value.  Here the tensor is read where it lies:
+
+    tables = Tables.from_logits(scores, lengths, layout="TNC", kind="bonito")     # one launch of po_ingest_strided
+    seqs = viterbi(tables)                                                           # batch.viterbi_batch's return
+    records = pair_decode(tables1, tables2)                                          # batch.pair_decode_batch's records
+
+Stream contract: everything is enqueued on torch.cuda.current_stream(device) of the tables' device, the caller's earlier work on
+that stream (the model's forward pass) is ordered before the ingest by the stream alone, and outputs and workspace come from
+torch's caching allocator.  A decode makes one engine call (po_viterbi_batch / po_beam1d_batch / po_pair_decode_batch), runs
+po_pack_strings on each text buffer, copies the packed text and lens / status / identity (map and envelope only when asked for)
+into pinned host tensors and synchronises the stream once; nothing else here synchronises.  (The engine's own calls read their
+offset tables back where include/poreover_hip.h says so.  The size of the packed text is known only after that one synchronise:
+the copy takes the share of the buffer that the previous call's text needed, with a margin, and the rare call whose text is
+longer fetches the rest with a second copy and synchronise.)
+
+The first workspace query of a process that selects the register-state pair kernel makes that kernel's multi-GB slice pool with
+hipMalloc, outside torch's allocator: _lib.reg_pool_prewarm / _lib.reg_pool_release (po_reg_pool_prewarm / po_reg_pool_release)
+are the handles.
+
+torch is imported here only: `import poreover_amd` works without it.  uint8 traces are not taken (batch.decode_1d_batch).
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import _marshal as M
+
+__all__ = ["Tables", "viterbi", "beam_search", "pair_decode"]
+
+LAYOUTS = ("NTC", "TNC")
+KIND_COLUMNS = {"poreover": 5, "bonito": 5, "flipflop": 8}
+KIND_PERM = {"poreover": None, "bonito": [1, 2, 3, 4, 0], "flipflop": None}     # decode.py:79 / :114
+RC_PERM = {5: [3, 2, 1, 0, 4], 8: [3, 2, 1, 0, 7, 6, 5, 4]}                      # transducer.reverse_complement
+_DTYPES = {torch.float32: L.DTYPES["float32"], torch.float16: L.DTYPES["float16"], torch.bfloat16: L.DTYPES["bfloat16"],
+           torch.float64: L.DTYPES["float64"]}
+
+
+def _perm(kind, reverse_complement):
+    """the column order of the ingest, out[:, c] = v[:, perm[c]]: the kind's, then reverse_complement's, composed as
+    transducer._permute records them; None = identity"""
+    perm = KIND_PERM[kind]
+    if reverse_complement:
+        rc = RC_PERM[KIND_COLUMNS[kind]]
+        perm = [perm[c] for c in rc] if perm is not None else list(rc)
+    return perm
+
+
+def _items(tensors, layout=None):
+    """The item table of po_ingest_strided, a pure function of data_ptr, strides and dtype: int64 (n, 3) rows
+    (address of element (0, 0), row stride, column stride), strides in elements.  tensors: one 3-D tensor with `layout`
+    ("NTC": item i is x[i]; "TNC": x[:, i]) or a sequence of 2-D (T_i, C) tensors."""
+    if layout is not None:
+        x = tensors
+        dn, dt = (0, 1) if layout == "NTC" else (1, 0)
+        out = np.empty((x.shape[dn], 3), dtype=np.int64)
+        out[:, 0] = x.data_ptr() + np.arange(x.shape[dn], dtype=np.int64) * (x.stride(dn) * x.element_size())
+        out[:, 1], out[:, 2] = x.stride(dt), x.stride(2)
+        return out
+    return np.array([(t.data_ptr(), t.stride(0), t.stride(1)) for t in tensors], dtype=np.int64).reshape(len(tensors), 3)
+
+
+def _interleaved(items, Cc, itemsize):
+    """whether the items lie in memory as a time-major batch does — item i + 1 starts C elements after item i, a frame's
+    values adjacent: the tiled ingest kernel's case"""
+    if len(items) < 2 or np.any(items[:, 2] != 1):
+        return False
+    return bool(np.all(np.diff(items[:, 0]) == Cc * itemsize))
+
+
+def _check_tensor(x, what, rank, Cc):
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor, not %s" % (what, type(x).__name__))
+    if x.dtype not in _DTYPES:
+        raise TypeError("%s: dtype %s (float32, float16, bfloat16 or float64)" % (what, x.dtype))
+    if x.dim() != rank:
+        raise ValueError("%s must have %d dimensions, has %d" % (what, rank, x.dim()))
+    if x.shape[-1] != Cc:
+        raise ValueError("%s has C = %d columns, the kind takes %d" % (what, x.shape[-1], Cc))
+
+
+def _check_device(x, what):
+    """last of a constructor's checks, so that the others can be met on any machine"""
+    if x.device.type != "cuda":
+        raise ValueError("%s is on %s: tensors on the GPU are taken here, host arrays by poreover_amd.batch" % (what, x.device))
+
+
+def _check_kind(kind):
+    if kind not in KIND_COLUMNS:
+        raise ValueError("kind %r (one of %s)" % (kind, ", ".join(KIND_COLUMNS)))
+
+
+class Tables:
+    """Ragged float64 log-probability tables on one device: what the decoders read.
+    y: torch.float64 (rows, C), contiguous; off: torch.int64 (n + 1,) row offsets, off_h the same as numpy; kind; device."""
+
+    def __init__(self, y, off, off_h, kind):
+        self.y, self.off, self.off_h, self.kind = y, off, off_h, kind
+        self.device = y.device
+        self.n = len(off_h) - 1
+        self.C = y.shape[1]
+
+    def __len__(self):
+        return self.n
+
+    @classmethod
+    def from_logits(cls, x, lengths=None, layout="NTC", kind="poreover", normalized=False, reverse_complement=False):
+        """A padded batch as the model left it: x is a device tensor (N, T, C) (layout "NTC") or (T, N, C) ("TNC") of float32,
+        float16, bfloat16 or float64, with any strides torch can produce (slices, transpose, expand, storage offsets): nothing is
+        made contiguous, nothing is copied.  lengths: N ints in [0, T], a sequence or a CPU tensor (None: T each); a device
+        tensor is accepted and costs one synchronising .cpu().  normalized=False: x holds logits (log-softmax per frame in
+        float32, as the reference does; float64 logits are refused); True: log-probabilities, widened.  kind fixes the column
+        order (bonito: [1, 2, 3, 4, 0]) and the tree model; reverse_complement=True adds transducer.reverse_complement's column
+        order and reverses every item in time, as pair-decode --reverse_complement does to read 2.  One launch on the current
+        stream of x's device."""
+        _check_kind(kind)
+        if layout not in LAYOUTS:
+            raise ValueError("layout %r (one of %s)" % (layout, ", ".join(LAYOUTS)))
+        _check_tensor(x, "x", 3, KIND_COLUMNS[kind])
+        n, T = (x.shape[0], x.shape[1]) if layout == "NTC" else (x.shape[1], x.shape[0])
+        if lengths is None:
+            lens = np.full(n, T, dtype=np.int64)
+        else:
+            if isinstance(lengths, torch.Tensor):
+                lengths = lengths.cpu().numpy()
+            lens = np.asarray(lengths)
+            if lens.ndim != 1 or len(lens) != n:
+                raise ValueError("lengths must hold one length per item: %d items, lengths of shape %s" % (n, lens.shape))
+            if len(lens) and (not np.issubdtype(lens.dtype, np.integer) or lens.min() < 0 or lens.max() > T):
+                raise ValueError("lengths must be integers in [0, T = %d]" % T)
+            lens = lens.astype(np.int64)
+        _check_device(x, "x")
+        return cls._ingest(_items(x, layout), lens, x.dtype, x.device, kind, normalized, reverse_complement)
+
+    @classmethod
+    def from_list(cls, tensors, kind="poreover", normalized=False, reverse_complement=False):
+        """(T_i, C) device tensors of one dtype on one device, each with any strides; otherwise as from_logits."""
+        _check_kind(kind)
+        tensors = list(tensors)
+        if not tensors:
+            raise ValueError("tensors is empty")
+        for i, t in enumerate(tensors):
+            _check_tensor(t, "tensors[%d]" % i, 2, KIND_COLUMNS[kind])
+            if t.dtype != tensors[0].dtype:
+                raise TypeError("tensors[%d] is %s, tensors[0] is %s: one dtype per call" % (i, t.dtype, tensors[0].dtype))
+            if t.device != tensors[0].device:
+                raise ValueError("tensors[%d] is on %s, tensors[0] on %s: one device per call" % (i, t.device, tensors[0].device))
+        _check_device(tensors[0], "tensors")
+        lens = np.array([t.shape[0] for t in tensors], dtype=np.int64)
+        return cls._ingest(_items(tensors), lens, tensors[0].dtype, tensors[0].device, kind, normalized, reverse_complement)
+
+    @classmethod
+    def from_numpy(cls, arrays, device=None, kind="poreover"):
+        """What batch.* would pack — (T_i, C) float64 log-probabilities on the host — uploaded as they are."""
+        _check_kind(kind)
+        y, off, Cc = M.pack_rows(arrays, KIND_COLUMNS[kind])
+        if Cc != KIND_COLUMNS[kind]:
+            raise ValueError("arrays have C = %d columns, the kind takes %d" % (Cc, KIND_COLUMNS[kind]))
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        return cls(torch.from_numpy(y).to(dev), torch.from_numpy(off).to(dev), off, kind)
+
+    @classmethod
+    def _ingest(cls, items, lens, dtype, device, kind, normalized, reverse_complement, route=None):
+        """route: None = by the items' strides; L.INGEST_TILED / L.INGEST_PER_FRAME force a kernel (the tests compare them)"""
+        if dtype == torch.float64 and not normalized:
+            raise TypeError("float64 logits are not normalised here (the reference normalises in the array's own precision): "
+                            "pass log-probabilities with normalized=True, or float32 logits")
+        n, Cc = len(lens), KIND_COLUMNS[kind]
+        off_h = M.offsets(lens)
+        rows = int(off_h[-1])
+        perm = _perm(kind, reverse_complement)
+        if route is None:
+            route = L.INGEST_TILED if _interleaved(items, Cc, _itemsize(dtype)) else 0
+        lib = L.load()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device)
+            host = torch.empty(4 * n + 1, dtype=torch.int64, pin_memory=True)   # the item table and the offsets: one small copy
+            h = host.numpy()
+            h[:3 * n] = items.reshape(-1)
+            h[3 * n:] = off_h
+            dev = host.to(device, non_blocking=True)
+            y = torch.empty((rows, Cc), dtype=torch.float64, device=device)
+            L.check(lib.po_ingest_strided(dev.data_ptr(), dev[3 * n:].data_ptr(), n, Cc, _DTYPES[dtype] | route,
+                                          0 if normalized else 1, M.perm_array(perm, Cc), 1 if reverse_complement else 0,
+                                          rows, y.data_ptr(), stream.cuda_stream), "po_ingest_strided")
+            off = dev[3 * n:]
+        return cls(y, off, off_h, kind)
+
+    def numpy(self, i):
+        """table i on the host (tests, debugging); synchronises"""
+        return self.y[int(self.off_h[i]):int(self.off_h[i + 1])].cpu().numpy()
+
+
+def _itemsize(dtype):
+    return 8 if dtype == torch.float64 else (4 if dtype == torch.float32 else 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------- decodes
+def _check_tables(tables, what="tables"):
+    if not isinstance(tables, Tables):
+        raise TypeError("%s must be a tensors.Tables, not %s" % (what, type(tables).__name__))
+    if tables.n and np.diff(tables.off_h).min() < 1:
+        raise ValueError("%s: item %d has no rows; the decoders take tables of at least one frame"
+                         % (what, int(np.argmin(np.diff(tables.off_h)))))
+
+
+_FIRST_COPY_MARGIN = 4096
+_TEXT_SHARE = {}    # per decode and text buffer: the share of the buffer's capacity that the first copy takes
+
+
+class _Text:
+    """One text buffer of a decode and its way to the host: po_pack_strings on the device, one copy of the share of the packed
+    buffer that the text is expected to fill, and after the call's synchronise the strings' offsets and bytes as numpy."""
+
+    def __init__(self, lib, key, seq, seq_off, lens, status, n, stream, copy=True):
+        self.key, self.n, self.cap, self.stream = key, n, seq.numel(), stream
+        dev = seq.device
+        self.packed = torch.empty(max(self.cap, 1), dtype=torch.uint8, device=dev)
+        self.poff = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        wsb = lib.po_pack_strings_workspace_bytes(n)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        L.check(lib.po_pack_strings(seq.data_ptr(), seq_off.data_ptr(), lens.data_ptr(), status.data_ptr() if status is not None else None,
+                                    n, self.packed.data_ptr(), self.poff.data_ptr(), ws.data_ptr(), wsb, stream.cuda_stream),
+                "po_pack_strings")
+        if copy:
+            self.copy()
+
+    def copy(self):
+        self.first = min(self.cap, int(self.cap * _TEXT_SHARE.get(self.key, 0.25)) + _FIRST_COPY_MARGIN)
+        self.text_h = torch.empty(max(self.first, 1), dtype=torch.uint8, pin_memory=True)
+        self.text_h[:self.first].copy_(self.packed[:self.first], non_blocking=True)
+        self.poff_h = _to_host(self.poff)
+
+    def arrays(self):
+        """after the stream's synchronise: (uint8 text, int64 offsets)"""
+        off = self.poff_h.numpy()
+        total = int(off[self.n])
+        text = self.text_h
+        if total > self.first:   # the text outgrew the share: the rest comes with a second copy
+            text = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            text[:self.first].copy_(self.text_h[:self.first])
+            with torch.cuda.stream(self.stream):
+                text[self.first:].copy_(self.packed[self.first:total], non_blocking=True)
+            self.stream.synchronize()
+        _TEXT_SHARE[self.key] = min(1.0, 1.25 * total / max(self.cap, 1))
+        self.copied = max(self.first, total)
+        return text.numpy(), off
+
+
+def _to_host(t):
+    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    h.copy_(t, non_blocking=True)
+    return h
+
+
+def _decode_1d(tables, entry, return_map=False, beam_width=0):
+    lib = L.load()
+    n, Cc, dev = tables.n, tables.C, tables.device
+    rows = int(tables.off_h[-1])
+    model = L.MODELS[L.MODEL_OF_KIND[tables.kind]]
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        seq = torch.empty(max(rows, 1), dtype=torch.uint8, device=dev)
+        lens, st = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        mp = torch.zeros(max(rows, 1), dtype=torch.int32, device=dev) if return_map else None
+        if entry == "viterbi":
+            wsb = lib.po_viterbi_workspace_bytes(n, rows, Cc, L.KINDS[tables.kind])
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            L.check(lib.po_viterbi_batch(tables.y.data_ptr(), tables.off.data_ptr(), n, Cc, b"ACGT", L.KINDS[tables.kind], None,
+                                         seq.data_ptr(), tables.off.data_ptr(), lens.data_ptr(), mp.data_ptr() if return_map else None,
+                                         st.data_ptr(), ws.data_ptr(), wsb, stream.cuda_stream), "po_viterbi_batch")
+        else:
+            wsb = lib.po_beam1d_workspace_bytes(n, rows, int(np.diff(tables.off_h).max()), Cc, int(beam_width), model)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            L.check(lib.po_beam1d_batch(tables.y.data_ptr(), tables.off.data_ptr(), n, Cc, b"ACGT", int(beam_width), model,
+                                        seq.data_ptr(), tables.off.data_ptr(), lens.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb,
+                                        stream.cuda_stream), "po_beam1d_batch")
+        # (a Viterbi string is whole whatever its status says about the map: every length counts)
+        text = _Text(lib, entry, seq[:rows], tables.off, lens, None if entry == "viterbi" else st, n, stream)
+        lens_h, st_h = _to_host(lens), _to_host(st)
+        mp_h = _to_host(mp) if return_map else None
+        stream.synchronize()
+    return text, lens_h.numpy(), st_h.numpy(), (mp_h.numpy() if return_map else None)
+
+
+def viterbi(tables, return_map=False):
+    """batch.viterbi_batch on resident tables: the sequences, and with return_map (sequences, maps, status)"""
+    _check_tables(tables)
+    if tables.n == 0:
+        return ([], [], np.zeros(0, np.int32)) if return_map else []
+    text, lens, st, mp = _decode_1d(tables, "viterbi", return_map)
+    M.raise_on_status(st, tables.n, "viterbi decode of read", allowed=(L.E_ARG,) if return_map else ())
+    buf, off = text.arrays()
+    seqs = M.strings(buf, off, lens)
+    if not return_map:
+        return seqs
+    o = tables.off_h
+    return seqs, [mp[o[i]:o[i] + lens[i]].astype(np.int64) for i in range(tables.n)], st[:tables.n].copy()
+
+
+def beam_search(tables, beam_width=25):
+    """batch.beam_search_batch on resident tables (the tree model is the kind's)"""
+    _check_tables(tables)
+    if tables.n == 0:
+        return []
+    text, lens, st, _ = _decode_1d(tables, "beam", beam_width=beam_width)
+    M.raise_on_status(st, tables.n, "beam search of read")
+    buf, off = text.arrays()
+    return M.strings(buf, off, lens)
+
+
+def pair_decode(tables1, tables2, beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
+                diagonal_width=50, envelope=False, stats=None):
+    """batch.pair_decode_batch (single="viterbi") on resident tables: its records, the envelope (None unless envelope=True: it is
+    as large as the tables' rows, and is neither written nor copied otherwise).  Both tables are of one n, kind and device.
+    stats: a dict that receives the bytes of text (text_bytes), of text copied (copied_bytes) and of the text buffers
+    (capacity_bytes), and the device milliseconds of the engine call, the compaction and the copies (decode_ms, pack_ms, copy_ms:
+    events on the stream, read after the synchronise)."""
+    _check_tables(tables1, "tables1")
+    _check_tables(tables2, "tables2")
+    if tables1.n != tables2.n:
+        raise ValueError("tables1 has %d items, tables2 %d" % (tables1.n, tables2.n))
+    if tables1.kind != tables2.kind:
+        raise ValueError("tables1 is of kind %r, tables2 of %r" % (tables1.kind, tables2.kind))
+    if tables1.device != tables2.device:
+        raise ValueError("tables1 is on %s, tables2 on %s: both tables of a pair decode are on one device" % (tables1.device, tables2.device))
+    if method not in L.METHODS:
+        raise ValueError("method %r (one of %s)" % (method, ", ".join(L.METHODS)))
+    n, Cc, dev = tables1.n, tables1.C, tables1.device
+    if n == 0:
+        return []
+    lib = L.load()
+    opt = M.pair_options(tables1.kind, beam_width, method, padding, alignment, diagonal_envelope, diagonal_width)
+    d1, d2 = np.diff(tables1.off_h), np.diff(tables2.off_h)
+    caps = np.empty(2 * n, dtype=np.int64)
+    caps[0::2], caps[1::2] = d1, d2
+    s1o, so = M.offsets(caps), M.offsets(d1 + d2)
+    r1, r2 = int(tables1.off_h[-1]), int(tables2.off_h[-1])
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        host = torch.empty(3 * n + 2, dtype=torch.int64, pin_memory=True)
+        host.numpy()[:2 * n + 1] = s1o
+        host.numpy()[2 * n + 1:] = so
+        d_off = host.to(dev, non_blocking=True)
+        d_s1o, d_so = d_off[:2 * n + 1], d_off[2 * n + 1:]
+        seq1d = torch.empty(int(s1o[-1]), dtype=torch.uint8, device=dev)
+        seq = torch.empty(int(so[-1]), dtype=torch.uint8, device=dev)
+        l12 = torch.zeros((2, n), dtype=torch.int32, device=dev)
+        lens, st = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        ident = torch.zeros(n, dtype=torch.float64, device=dev)
+        env = torch.zeros((r1, 2), dtype=torch.int32, device=dev) if envelope else None
+        wsb = lib.po_pair_decode_workspace_bytes(n, r1, r2, int(d1.max()), int(d2.max()), Cc, C.byref(opt))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if stats is not None else None
+
+        def mark(k):
+            if marks:
+                marks[k].record(stream)
+        mark(0)
+        L.check(lib.po_pair_decode_batch(tables1.y.data_ptr(), tables1.off.data_ptr(), tables2.y.data_ptr(), tables2.off.data_ptr(),
+                                         n, Cc, C.byref(opt), seq1d.data_ptr(), d_s1o.data_ptr(), l12[0].data_ptr(), l12[1].data_ptr(),
+                                         ident.data_ptr(), env.data_ptr() if envelope else None, seq.data_ptr(), d_so.data_ptr(),
+                                         lens.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb, stream.cuda_stream), "po_pair_decode_batch")
+        mark(1)
+        len1d = l12.t().contiguous().view(-1)     # read 1 of pair i at 2i, read 2 at 2i + 1: seq1d's order
+        text1d = _Text(lib, "pair_1d", seq1d, d_s1o, len1d, None, 2 * n, stream, copy=False)
+        text = _Text(lib, "pair", seq, d_so, lens, st, n, stream, copy=False)
+        mark(2)
+        text1d.copy()
+        text.copy()
+        l12_h, lens_h, st_h, ident_h = _to_host(l12), _to_host(lens), _to_host(st), _to_host(ident)
+        env_h = _to_host(env) if envelope else None
+        mark(3)
+        stream.synchronize()
+    b1, o1 = text1d.arrays()
+    b, o = text.arrays()
+    if stats is not None:
+        stats.update(decode_ms=marks[0].elapsed_time(marks[1]), pack_ms=marks[1].elapsed_time(marks[2]), copy_ms=marks[2].elapsed_time(marks[3]))
+        stats.update(text_bytes=int(o1[-1] + o[-1]), copied_bytes=int(text1d.copied + text.copied), capacity_bytes=int(s1o[-1] + so[-1]))
+    l12n = l12_h.numpy()
+    out = []
+    M.pair_records(out, b1, o1, b, o, l12n[0], l12n[1], lens_h.numpy(), st_h.numpy(), ident_h.numpy(),
+                   env_h.numpy() if envelope else None, tables1.off_h)(0, n)
+    return out
