@@ -193,6 +193,37 @@ int po_pack_strings(const char* seq, const int64_t* seq_off, const int32_t* seq_
 int po_pack_strings_h(const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h, int n,
                       char* packed_h, int64_t* packed_off_h);
 
+/* ---- CTC loss and gradient on tensors where they lie (po_ctc.hip) ------------------------------------------
+ * Item i: logits x [T_i][C] at items[i] (po_ingest_strided's table and dtypes; f64 with normalize = 0 only), rows
+ * row_off[i] .. row_off[i+1]; labels int32 [L_i] at labels + label_off[i], values 0 .. C-2 (the alphabet's order; blank is
+ * canonical column C-1).  perm_h (host, or NULL): canonical column c is source column perm_h[c], a permutation.
+ * lp = log_softmax(x) per frame in float64 (normalize = 0: x holds log-probabilities, widened as they are).
+ *   loss[i]    = -log P(l_i | lp) over 2L+1 states; PO_MODEL_CTC: label states do not loop and every blank may be skipped;
+ *                PO_MODEL_MERGE: standard CTC.  First frame in state 0 or 1, last frame in one of the last two states.
+ *   grad[t][c] = softmax(x[t])[c] - sum_{s: label(s) = c} exp(alpha_t(s) + beta_t(s) - log Z)   (normalize = 0: -occupancy),
+ *                written through grad_items (a second item table, grad_dtype f32 / f16 / bf16, column perm_h[c]).
+ *                grad_items NULL: loss only, no backward pass.
+ *   status[i]  (or NULL): 0; PO_E_ENVELOPE: no path (L > T; merge: L + adjacent equal labels > T): loss +inf, gradient rows
+ *                zero; PO_E_ARG: a label outside [0, C-2] or offsets that decrease: loss NaN; PO_E_UNSUPPORTED / PO_E_CAP: an
+ *                item whose label is longer than PO_CTC_MAX_LABEL / than max_states admits: loss NaN.  T = 0 with L = 0: 0.
+ * The caller passes total_rows = row_off[n], total_states = sum T_i * (2 L_i + 1) (read with a gradient only) and
+ * max_states = max 2 L_i + 1.  Enqueue-only on `stream`: the entry reads no device memory and does not synchronise.
+ * Before any launch: PO_E_UNSUPPORTED for PO_MODEL_FLIPFLOP, f64 with normalize, max_states > 2 * PO_CTC_MAX_LABEL + 1 (the
+ * lattice rows are kept in LDS); PO_E_ARG for C outside 2..8, negative sizes, an unknown dtype, a perm that is no
+ * permutation, null pointers with n > 0, ws_bytes < po_ctc_loss_workspace_bytes(...).  n == 0: PO_OK. */
+#define PO_CTC_MAX_LABEL 1200
+size_t po_ctc_loss_workspace_bytes(int n, int64_t total_rows, int64_t total_states, int C, int with_grad);
+int po_ctc_loss(const po_ingest_item* items, const int64_t* row_off, int n, int C, int dtype, int normalize, const int* perm_h,
+                const int32_t* labels, const int64_t* label_off, int model, int64_t total_rows, int64_t total_states,
+                int max_states, float* loss, int32_t* status, const po_ingest_item* grad_items, int grad_dtype, void* ws,
+                size_t ws_bytes, void* stream);
+/* host twin: the source as po_ingest_strided_h takes it; grad_h (or NULL): row_off_h[n] dense rows of C values of grad_dtype,
+ * in the source's column order */
+int po_ctc_loss_h(const void* src_h, int64_t src_elems, const int64_t* item_off_h, const int64_t* row_stride_h,
+                  const int64_t* col_stride_h, const int64_t* row_off_h, int n, int C, int dtype, int normalize,
+                  const int* perm_h, const int32_t* labels_h, const int64_t* label_off_h, int model, float* loss_h,
+                  int32_t* status_h, void* grad_h, int grad_dtype);
+
 /* ---- transducer.argmax_decode / viterbi_decode ------------------------------------------
  * replaces transducer.py:27-33 (argmax), :72-73 (poreover), :83-89 (bonito), :35-59 +
  * :94-103 (flip-flop Viterbi) and pair_decode.get_sequence_mapping (pair_decode.py:114-142).

@@ -31,7 +31,7 @@ import torch
 from . import _lib as L
 from . import _marshal as M
 
-__all__ = ["Tables", "viterbi", "beam_search", "pair_decode"]
+__all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss"]
 
 LAYOUTS = ("NTC", "TNC")
 KIND_COLUMNS = {"poreover": 5, "bonito": 5, "flipflop": 8}
@@ -39,6 +39,8 @@ KIND_PERM = {"poreover": None, "bonito": [1, 2, 3, 4, 0], "flipflop": None}     
 RC_PERM = {5: [3, 2, 1, 0, 4], 8: [3, 2, 1, 0, 7, 6, 5, 4]}                      # transducer.reverse_complement
 _DTYPES = {torch.float32: L.DTYPES["float32"], torch.float16: L.DTYPES["float16"], torch.bfloat16: L.DTYPES["bfloat16"],
            torch.float64: L.DTYPES["float64"]}
+_F64_LOGITS = ("float64 logits are not normalised here (the reference normalises in the array's own precision): "
+               "pass log-probabilities with normalized=True, or float32 logits")
 
 
 def _perm(kind, reverse_complement):
@@ -90,6 +92,20 @@ def _check_device(x, what):
         raise ValueError("%s is on %s: tensors on the GPU are taken here, host arrays by poreover_amd.batch" % (what, x.device))
 
 
+def _lengths(lengths, n, T):
+    """the frames of each item of a padded batch as int64 (None: T each); a device tensor costs one synchronising .cpu()"""
+    if lengths is None:
+        return np.full(n, T, dtype=np.int64)
+    if isinstance(lengths, torch.Tensor):
+        lengths = lengths.cpu().numpy()
+    lens = np.asarray(lengths)
+    if lens.ndim != 1 or len(lens) != n:
+        raise ValueError("lengths must hold one length per item: %d items, lengths of shape %s" % (n, lens.shape))
+    if len(lens) and (not np.issubdtype(lens.dtype, np.integer) or lens.min() < 0 or lens.max() > T):
+        raise ValueError("lengths must be integers in [0, T = %d]" % T)
+    return lens.astype(np.int64)
+
+
 def _check_kind(kind):
     if kind not in KIND_COLUMNS:
         raise ValueError("kind %r (one of %s)" % (kind, ", ".join(KIND_COLUMNS)))
@@ -123,17 +139,7 @@ class Tables:
             raise ValueError("layout %r (one of %s)" % (layout, ", ".join(LAYOUTS)))
         _check_tensor(x, "x", 3, KIND_COLUMNS[kind])
         n, T = (x.shape[0], x.shape[1]) if layout == "NTC" else (x.shape[1], x.shape[0])
-        if lengths is None:
-            lens = np.full(n, T, dtype=np.int64)
-        else:
-            if isinstance(lengths, torch.Tensor):
-                lengths = lengths.cpu().numpy()
-            lens = np.asarray(lengths)
-            if lens.ndim != 1 or len(lens) != n:
-                raise ValueError("lengths must hold one length per item: %d items, lengths of shape %s" % (n, lens.shape))
-            if len(lens) and (not np.issubdtype(lens.dtype, np.integer) or lens.min() < 0 or lens.max() > T):
-                raise ValueError("lengths must be integers in [0, T = %d]" % T)
-            lens = lens.astype(np.int64)
+        lens = _lengths(lengths, n, T)
         _check_device(x, "x")
         return cls._ingest(_items(x, layout), lens, x.dtype, x.device, kind, normalized, reverse_complement)
 
@@ -168,8 +174,7 @@ class Tables:
     def _ingest(cls, items, lens, dtype, device, kind, normalized, reverse_complement, route=None):
         """route: None = by the items' strides; L.INGEST_TILED / L.INGEST_PER_FRAME force a kernel (the tests compare them)"""
         if dtype == torch.float64 and not normalized:
-            raise TypeError("float64 logits are not normalised here (the reference normalises in the array's own precision): "
-                            "pass log-probabilities with normalized=True, or float32 logits")
+            raise TypeError(_F64_LOGITS)
         n, Cc = len(lens), KIND_COLUMNS[kind]
         off_h = M.offsets(lens)
         rows = int(off_h[-1])
@@ -387,3 +392,154 @@ def pair_decode(tables1, tables2, beam_width=5, method="row_col", padding=5, ali
     M.pair_records(out, b1, o1, b, o, l12n[0], l12n[1], lens_h.numpy(), st_h.numpy(), ident_h.numpy(),
                    env_h.numpy() if envelope else None, tables1.off_h)(0, n)
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------- training
+REDUCTIONS = ("none", "mean", "sum")
+_SYMBOLS = {"A": 0, "C": 1, "G": 2, "T": 3}
+
+
+def _labels(labels, label_lengths, n):
+    """(int32 symbols back to back, int64 lengths (n,)) of a list of str over ACGT, a list of int sequences, or a concatenated
+    1-D int array / tensor with label_lengths; symbols are 0..3, checked here, the item named"""
+    if isinstance(labels, torch.Tensor):
+        labels = labels.cpu().numpy()
+    if label_lengths is not None:
+        if isinstance(label_lengths, torch.Tensor):
+            label_lengths = label_lengths.cpu().numpy()
+        ll = np.asarray(label_lengths)
+        flat = np.asarray(labels)
+        if ll.ndim != 1 or len(ll) != n or (len(ll) and (not np.issubdtype(ll.dtype, np.integer) or ll.min() < 0)):
+            raise ValueError("label_lengths must hold one length >= 0 per item: %d items, label_lengths of shape %s" % (n, ll.shape))
+        if flat.ndim != 1 or (flat.size and not np.issubdtype(flat.dtype, np.integer)):
+            raise ValueError("labels with label_lengths must be a 1-D integer array, the items' labels back to back")
+        ll = ll.astype(np.int64)
+        if int(ll.sum()) != flat.size:
+            raise ValueError("label_lengths add up to %d, labels holds %d symbols" % (int(ll.sum()), flat.size))
+        parts = np.split(flat.astype(np.int64), np.cumsum(ll)[:-1]) if n else []
+    else:
+        if isinstance(labels, np.ndarray) and labels.ndim == 1 and labels.dtype != object and n != 0:
+            raise ValueError("a concatenated labels array needs label_lengths")
+        labels = list(labels)
+        if len(labels) != n:
+            raise ValueError("labels must hold one label per item: %d items, %d labels" % (n, len(labels)))
+        parts = []
+        for i, lab in enumerate(labels):
+            if isinstance(lab, str):
+                bad = sorted(set(lab) - set(_SYMBOLS))
+                if bad:
+                    raise ValueError("labels[%d] holds %r: a label is a string over ACGT" % (i, bad[0]))
+                parts.append(np.array([_SYMBOLS[ch] for ch in lab], dtype=np.int64))
+            else:
+                if isinstance(lab, torch.Tensor):
+                    lab = lab.cpu().numpy()
+                a = np.asarray(lab)
+                if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+                    raise ValueError("labels[%d] must be a str over ACGT or a 1-D sequence of ints in 0..3" % i)
+                parts.append(a.astype(np.int64))
+    for i, a in enumerate(parts):
+        if a.size and (a.min() < 0 or a.max() > 3):
+            raise ValueError("labels[%d] holds %d: symbols are 0..3 (A, C, G, T)" % (i, int(a[(a < 0) | (a > 3)][0])))
+    lens = np.array([a.size for a in parts], dtype=np.int64)
+    flat = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, np.int32)
+    return flat, lens
+
+
+def _ctc_engine(x, layout, perm, model, normalized, lens, lab, lab_lens, with_grad):
+    """perm: the canonical columns' places in x (None: as they are); model: "ctc" or "ctc_merge_repeats".  One po_ctc_loss call on the current stream of x's device: (per-item loss (N,) float32, the gradient with respect to x in
+    x's shape — float32 for float64 x, x's dtype otherwise, padded frames zero — or None).  Enqueue-only."""
+    n, Cc = len(lens), x.shape[2]
+    dev = x.device
+    T = x.shape[1] if layout == "NTC" else x.shape[0]
+    off_h, loff_h = M.offsets(lens), M.offsets(lab_lens)
+    rows = int(off_h[-1])
+    states = int((lens * (2 * lab_lens + 1)).sum())
+    max_states = int(2 * lab_lens.max() + 1)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        g = None
+        if with_grad:
+            gdtype = torch.float32 if x.dtype == torch.float64 else x.dtype
+            g = (torch.zeros if lens.min() < T else torch.empty)(x.shape, dtype=gdtype, device=dev)
+        nlab = max((len(lab) + 1) // 2, 1)
+        host = torch.empty(8 * n + 2 + nlab, dtype=torch.int64, pin_memory=True)   # both item tables, both offset tables, the labels
+        h = host.numpy()
+        h[:3 * n] = _items(x, layout).reshape(-1)
+        h[3 * n:6 * n] = _items(g, layout).reshape(-1) if with_grad else 0
+        h[6 * n:7 * n + 1] = off_h
+        h[7 * n + 1:8 * n + 2] = loff_h
+        h[8 * n + 2:].view(np.int32)[:len(lab)] = lab
+        d = host.to(dev, non_blocking=True)
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        wsb = lib.po_ctc_loss_workspace_bytes(n, rows, states, Cc, 1 if with_grad else 0)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        L.check(lib.po_ctc_loss(d.data_ptr(), d[6 * n:].data_ptr(), n, Cc, _DTYPES[x.dtype], 0 if normalized else 1,
+                                M.perm_array(perm, Cc), d[8 * n + 2:].data_ptr(), d[7 * n + 1:].data_ptr(),
+                                L.MODELS[model], rows, states, max_states, loss.data_ptr(), None,
+                                d[3 * n:].data_ptr() if with_grad else None, _DTYPES[g.dtype] if with_grad else 0,
+                                ws.data_ptr(), wsb, stream.cuda_stream), "po_ctc_loss")
+    return loss, g
+
+
+class _CtcLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, layout, kind, normalized, lens, lab, lab_lens):
+        loss, g = _ctc_engine(x, layout, KIND_PERM[kind], L.MODEL_OF_KIND[kind], normalized, lens, lab, lab_lens, True)
+        ctx.save_for_backward(g)
+        ctx.layout, ctx.dtype = layout, x.dtype
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        g, = ctx.saved_tensors
+        w = grad_loss.to(torch.float32)
+        w = w[:, None, None] if ctx.layout == "NTC" else w[None, :, None]
+        return (g * w).to(ctx.dtype), None, None, None, None, None, None
+
+
+def ctc_loss(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreover", normalized=False, reduction="mean",
+             zero_infinity=False):
+    """The CTC loss of a padded batch of logits against labels, for the decoder of `kind`, differentiable with respect to x.
+
+    x, lengths, layout, kind and normalized are Tables.from_logits': a device tensor (N, T, 5) or (T, N, 5) of float32, float16
+    or bfloat16 logits (normalized=True: log-probabilities, float64 too) with any strides, read where it lies.  kind "poreover"
+    is the reference's default lattice, `ctc` (a label state does not loop, the blank between two labels may always be
+    skipped: what torch.nn.functional.ctc_loss does not offer); "bonito" is standard CTC with merged repeats on blank-first
+    columns.  "flipflop" has no CTC loss.  labels: a list of str over ACGT, a list of int sequences (0..3), or one 1-D int
+    array / CPU tensor with label_lengths; device tensors of labels or lengths are accepted and cost a synchronising .cpu().
+
+    Returns a float32 tensor on x's device: (N,) for reduction "none"; "sum" is the sum over items; "mean" is the MEAN OVER
+    ITEMS, as the reference's train_ctc_model takes it — not torch's division of each loss by its target length.  An item that
+    no path can produce (more symbols than frames; with merged repeats also one frame per adjacent equal pair) has loss +inf —
+    0 with zero_infinity=True — and a gradient of zeros either way.
+
+    When x requires grad, the forward makes loss and gradient in one engine call (po_ctc_loss) and keeps the gradient in x's
+    dtype and shape, padded frames zero; the backward is that tensor times the incoming per-item gradient (once
+    differentiable: no double backward).  Otherwise the loss-only form runs.  Everything is enqueued on
+    torch.cuda.current_stream(x.device), workspace and outputs come from torch's allocator, and nothing synchronises: the loss
+    stays on the device.  Labels of up to 1200 symbols."""
+    _check_kind(kind)
+    if kind == "flipflop":
+        raise ValueError("kind 'flipflop' has no CTC loss: poreover (ctc) or bonito (ctc_merge_repeats)")
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r (one of %s)" % (layout, ", ".join(LAYOUTS)))
+    if reduction not in REDUCTIONS:
+        raise ValueError("reduction %r (one of %s)" % (reduction, ", ".join(REDUCTIONS)))
+    _check_tensor(x, "x", 3, KIND_COLUMNS[kind])
+    if x.dtype == torch.float64 and not normalized:
+        raise TypeError(_F64_LOGITS)
+    n, T = (x.shape[0], x.shape[1]) if layout == "NTC" else (x.shape[1], x.shape[0])
+    lens = _lengths(lengths, n, T)
+    lab, lab_lens = _labels(labels, label_lengths, n)
+    _check_device(x, "x")
+    if n == 0:
+        loss = torch.zeros(0, dtype=torch.float32, device=x.device) + 0 * x.sum().to(torch.float32)
+    elif x.requires_grad and torch.is_grad_enabled():
+        loss = _CtcLoss.apply(x, layout, kind, normalized, lens, lab, lab_lens)
+    else:
+        loss, _ = _ctc_engine(x, layout, KIND_PERM[kind], L.MODEL_OF_KIND[kind], normalized, lens, lab, lab_lens, False)
+    if zero_infinity:
+        loss = torch.where(torch.isinf(loss), torch.zeros_like(loss), loss)
+    return loss if reduction == "none" else (loss.mean() if reduction == "mean" else loss.sum())
