@@ -133,6 +133,26 @@ long long po_debug_deferred_pairs(int reset);
  * score table instead of the skewed-wavefront kernel.  Process-wide; results are identical. */
 int po_set_align_route(int legacy);
 
+/* test hooks of the lattice's routing.  po_qual_batch_route is po_qual_batch (below: its arguments, refusals
+ * and results) with the choice of lattice kernel as a last argument:
+ *   PO_QUAL_ROUTE_GENERAL  qual_kernel by its four launch classes: what po_qual_batch launches
+ *   PO_QUAL_ROUTE_AUTO     what po_fastq_tables and po_pair_qual pass by default.  Today the same as GENERAL: neither
+ *                          instantiation of qual_reg_kernel is on the automatic route
+ *   PO_QUAL_ROUTE_REG      the reads whose ring holds at most 64 indices (a band of 1 to 31, or no band and at most 63
+ *                          labels) on qual_reg_kernel, the rest as before: for the tests and scripts/bench_tensors_fastq.py
+ * The workspace is po_qual_workspace_bytes' on every route, and so are the bits of odds, logp and status.
+ * po_set_qual_route: the route that po_fastq_tables and po_pair_qual pass from now on, process-wide (any other value: PO_E_ARG).
+ * po_debug_qual_reg_reads: the reads that were launched on qual_reg_kernel since the last reset (reset != 0 clears the count);
+ * counted on the host at the launch, no synchronise. */
+#define PO_QUAL_ROUTE_GENERAL 0
+#define PO_QUAL_ROUTE_AUTO 1
+#define PO_QUAL_ROUTE_REG 2
+int po_set_qual_route(int route);
+long long po_debug_qual_reg_reads(int reset);
+int po_qual_batch_route(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
+                        const int64_t* label_off, const int32_t* guide, int band_size, double* odds, double* logp,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream, int route);
+
 /* ---- trace ingest ------------------------------------------------------------------------------
  * replaces decode.logit_to_log_likelihood (decode.py:34-39), the uint8 trace scaling of
  * model_from_trace (decode.py:89-93,99-103), the Bonito column order (decode.py:79) and
@@ -913,6 +933,55 @@ int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const double* y2
                    const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h,
                    int band_size, const int32_t* unbanded_h, char* qual1d_h, char* qual_h, int32_t* qual_status_h,
                    double* odds1d_h, double* odds_cons_h, int32_t* guide_h);
+
+/* ---- the quality stages on tables that are on the device already --------------------------------
+ * For a caller whose float64 tables and decoded strings are device buffers (poreover_amd.tensors): nothing is uploaded but
+ * the stages' small plan tables, and every output is a device buffer of the caller's, written on `stream`.  Both entries
+ * run the stage bodies of their host-buffer twins (the same launchers, the same kernels, the same bits).
+ *   - They are NOT enqueue-only: like po_qual_batch they read the offset tables and the per-read lengths (po_pair_qual:
+ *     the statuses too) back to the host, where the lattices' and the aligner's plans are made, and they return after
+ *     a last synchronise of `stream`.
+ *   - The stages' intermediate buffers (frame maps, guides, consumed counts, the aligner's rows, labels, lattice rows) are
+ *     allocated with hipMalloc for the length of the call and freed when it returns: not from the caller's allocator, the
+ *     one departure from the rule of the other device-pointer entries.  (A workspace-query form is not offered yet.)
+ *   - PO_MODEL_FLIPFLOP (po_fastq_tables: PO_KIND_FLIPFLOP too) is PO_E_UNSUPPORTED.  Every argument error that can be
+ *     told without the device is answered before anything is read back, and every one before the first allocation,
+ *     with the entry's name in the text.
+ *
+ * po_fastq_tables: steps (1) to (6) of po_basecall_fastq_batch_h's quality stages on the table y / y_off (C must be 5;
+ * y_off from 0) and the strings seq at seq_off (from 0; a read's room must hold a base per frame and its string, PO_E_CAP
+ * naming the read) with their lengths seq_len and the decode's status.
+ *   - model, kind:   PO_MODEL_CTC with PO_KIND_POREOVER or PO_MODEL_MERGE with PO_KIND_BONITO (any other combination:
+ *                    PO_E_ARG); kind selects the Viterbi call that makes the frame map
+ *   - scored_is_viterbi: 1: seq / seq_len / status are po_viterbi_batch's of `kind` WITH its frame map, passed as `map`
+ *                    (int32 per frame at y_off): no second Viterbi call, no alignment.  0: the strings are something else (a
+ *                    beam search's); map is not read; a second Viterbi call with its map, then the mode, gather, align and
+ *                    consumed stages, as po_basecall_fastq_batch_h runs them behind its beam search
+ *   - band_size:     po_qual_batch's; <= 0: no band, no guide
+ *   - unbanded_h (or NULL): HOST int32[n]; with a band, a non-zero entry scores that read without one while the others
+ *                    keep theirs (the retry of a lost lattice).  A flagged read has L = 0 in the banded po_qual_batch call
+ *                    and is scored by a second call without a band
+ *   - qual:          the FASTQ characters 33 + Q, seq_len[i] of them at seq_off[i]; other bytes are left as they are
+ *   - qual_status:   int32[n], po_qual_batch's status per read (a flagged read: the unbanded call's); PO_E_ENVELOPE is
+ *                    reported, not retried; a read with a non-zero status gets '!' throughout
+ *   - odds (or NULL): the log-odds, five float64 per base, DENSE: read i's rows start at the sum of max(seq_len, 0) of the
+ *                    unflagged reads before it; the flagged reads' rows follow behind all of those, in read order
+ *   - guide (or NULL): the guide, int32 per frame at y_off[i]; untouched for band_size <= 0 */
+int po_fastq_tables(const double* y, const int64_t* y_off, int n, int C, int model, int kind, const char* seq,
+                    const int64_t* seq_off, const int32_t* seq_len, const int32_t* status, const int32_t* map,
+                    int scored_is_viterbi, int band_size, const int32_t* unbanded_h, char* qual, int32_t* qual_status,
+                    double* odds, int32_t* guide, void* stream);
+
+/* po_pair_qual: po_pair_qual_h with every _h buffer a device buffer, except unbanded_h, which stays on the host.  The four
+ * items per pair, the layouts of qual1d, qual, qual_status[4 n], odds1d, odds_cons and guide, the refusals (after the
+ * tables have been read back) and the bits are po_pair_qual_h's.  qual1d (seq1d_off[2 n] bytes) and qual (seq_off[n] bytes)
+ * are overwritten WHOLE, with zeros outside the strings (as po_pair_qual_h's host buffers are).  The odds come with one small
+ * copy per item. */
+int po_pair_qual(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int model,
+                 const char* seq1d, const int64_t* seq1d_off, const int32_t* len1, const int32_t* len2, const char* seq,
+                 const int64_t* seq_off, const int32_t* seq_len, const int32_t* status, int band_size,
+                 const int32_t* unbanded_h, char* qual1d, char* qual, int32_t* qual_status, double* odds1d, double* odds_cons,
+                 int32_t* guide, void* stream);
 
 /* ---- `pair-basecall` over one or several devices of a node ----------------------------------
  * A po_pair_basecaller holds a model, the pair decoder's options and a list of devices, as a po_basecaller does for

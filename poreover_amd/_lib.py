@@ -22,6 +22,7 @@ KINDS = {"poreover": 0, "bonito": 1, "flipflop": 2}
 MODEL_OF_KIND = {"poreover": "ctc", "bonito": "ctc_merge_repeats", "flipflop": "ctc_flipflop"}   # the tree model that decodes a basecaller kind
 DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2, "float64": 3}   # PO_DTYPE_* of po_ingest_strided
 INGEST_TILED, INGEST_PER_FRAME = 0x100, 0x200
+QUAL_ROUTE_GENERAL, QUAL_ROUTE_AUTO, QUAL_ROUTE_REG = 0, 1, 2          # PO_QUAL_ROUTE_* of po_qual_batch_route
 K_VITERBI, K_BEAM1D, K_BEAM2D, K_ALIGN, K_ENVELOPE, K_BEAM2D_MAIN = range(6)
 _CODE_NAMES = {E_CAP: "PO_E_CAP (buffer too small)", E_ARG: "PO_E_ARG (bad argument)",
                E_ENVELOPE: "PO_E_ENVELOPE (envelope undefined for the reference)",
@@ -97,6 +98,8 @@ PROTOTYPES = {
     "po_reg_pool_release": (C.c_int, []),
     "po_debug_deferred_pairs": (C.c_longlong, [C.c_int]),
     "po_set_align_route": (C.c_int, [C.c_int]),
+    "po_set_qual_route": (C.c_int, [C.c_int]),
+    "po_debug_qual_reg_reads": (C.c_longlong, [C.c_int]),
     "po_ingest_batch": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dp, _vp]),
     "po_ingest_batch_h": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _dp]),
     "po_ingest_strided": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int64, _dp, _vp]),
@@ -247,6 +250,10 @@ PROTOTYPES = {
                                                  C.POINTER(C.c_float)]),
     "po_pair_qual_h": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _cp, _i64p, _i32p, _i32p,
                                  C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p]),
+    "po_pair_qual": (C.c_int, [_dp, _i64p, _dp, _i64p, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _cp, _i64p, _i32p, _i32p,
+                               C.c_int, _i32p, _cp, _cp, _i32p, _dp, _dp, _i32p, _vp]),
+    "po_fastq_tables": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _i64p, _i32p, _i32p, _i32p, C.c_int, C.c_int,
+                                  _i32p, _cp, _i32p, _dp, _i32p, _vp]),
     "po_fastq_pair_phred_h": (C.c_int, [_dp, _dp, _cp, _i64p, C.c_int, C.c_char_p, _i32p, _i32p, _cp]),
     "po_pair_basecaller_create": (C.c_void_p, [C.POINTER(C.c_int), C.c_int, C.POINTER(CallLayer), C.c_int, _vp, C.c_int64,
                                                C.POINTER(PairBasecallerOptions)]),
@@ -320,6 +327,8 @@ PROTOTYPES = {
     "po_qual_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "po_qual_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, C.c_int, _dp, _dp, _i32p,
                                 _vp, C.c_size_t, _vp]),
+    "po_qual_batch_route": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, C.c_int, _dp, _dp, _i32p,
+                                      _vp, C.c_size_t, _vp, C.c_int]),
     "po_qual_batch_h": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _cp, _i64p, _i32p, C.c_int, _dp, _dp,
                                   _i32p]),
     "po_event_create": (C.c_void_p, []),
@@ -538,6 +547,17 @@ def deferred_pairs(reset=False):
 def set_align_route(legacy=False):
     """test / tuning hook (po_set_align_route): the banded aligner on its row-at-a-time kernel (True) or the skewed wavefront"""
     check(load(False).po_set_align_route(1 if legacy else 0), "po_set_align_route")
+
+
+def set_qual_route(route):
+    """test hook (po_set_qual_route): the route that the quality entries on resident tables pass to the lattice from now on,
+    QUAL_ROUTE_AUTO (the default), QUAL_ROUTE_GENERAL or QUAL_ROUTE_REG (rings of at most 64 indices on qual_reg_kernel)"""
+    check(load(False).po_set_qual_route(int(route)), "po_set_qual_route")
+
+
+def qual_reg_reads(reset=False):
+    """test hook (po_debug_qual_reg_reads): the reads launched on qual_reg_kernel since the last reset"""
+    return int(load(False).po_debug_qual_reg_reads(1 if reset else 0))
 
 
 def check(rc, what):

@@ -130,24 +130,39 @@ namespace {
 
 typedef PoBasecallFastq FastqOut;
 
+// the decode's strings as the quality stages read them: a PoSeqOut of this call, or buffers the caller holds (po_fastq_tables)
+struct FqStrings {
+    const char* seq; const int64_t* off; const int32_t* len; const int32_t* status;   // device
+    size_t cap;                                                                       // bytes of seq: off[n]
+};
+FqStrings fq_strings(const PoSeqOut& out) { return {out.seq.as<char>(), out.off.as<int64_t>(), out.len.as<int32_t>(), out.status.as<int32_t>(), out.cap}; }
+
 // The quality stages, enqueued behind the decoder on its stream: the table dy, the strings of `out` and
 // (Viterbi) the frame map stay where they are; lengths, statuses, modes and offsets are the only words that cross.
+// po_basecall_body runs them behind its decoder, po_fastq_tables on tables and strings of the caller's.
 struct FastqStages {
-    PoDev map, vseq, vlen, vst, mode, consumed, guide, labels, label_off, odds, logp, qst, qual, wsv, wsq;
+    PoDev map, vseq, vlen, vst, mode, consumed, guide, labels, label_off, label_off_u, odds, logp, qst, qual, wsv, wsq;
     PoFqAligner al;   // the pairs that need an alignment (po_fastq_stages.h)
-    std::vector<int64_t> label_off_h;
+    std::vector<int64_t> label_off_h, label_off_u_h;   // the dense label layout of the banded call, of the one without a band
+    int64_t total_b = 0, total_u = 0;                  // labels of the first call (all of them without flags), of the second
     int32_t* called_len = nullptr;   // device: the Viterbi call's lengths
+    const int32_t* mapp = nullptr;   // device: the frame map of the Viterbi call: `map`, or the caller's
     // The Viterbi call with its frame map is the decode itself only for Viterbi of PO_KIND_POREOVER.  For PO_KIND_BONITO the
     // map follows the reference's get_sequence_mapping, whose count can differ from the string's; po_viterbi_batch reports
     // that as PO_E_ARG in the read's status (such a read gets the diagonal, as in quality.call_guides), and the decode's
     // own status has to stay what po_basecall_batch_h gives: the map then comes from a second Viterbi call, as for the beam.
+    // (po_fastq_tables' caller may pass the map-making call's strings, status and map: no second call for either kind.)
     bool second = false;
+    bool align = false;   // the scored strings are not the Viterbi call's: the pairs that differ go to the aligner
+    int qual_route = PO_QUAL_ROUTE_GENERAL;   // the lattice's kernels: po_qual_batch's (po_fastq_tables: po_qual_entry_route())
 
-    // before the decoder: the buffers whose size is known from the signals
-    int prepare(int n, int64_t rows, int kind, int beam_width, size_t cap) {
+    // before the decoder: the buffers whose size is known from the signals.  caller_map: the frame map, where the caller has it
+    int prepare(int n, int64_t rows, int kind, bool second_, bool align_, size_t cap, const int32_t* caller_map = nullptr) {
         al.reset();
-        second = beam_width > 0 || kind != PO_KIND_POREOVER;
-        PO_HIPCHK(map.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        second = second_;
+        align = align_;
+        if (!caller_map) PO_HIPCHK(map.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        mapp = caller_map ? caller_map : map.as<int32_t>();
         PO_HIPCHK(mode.up(nullptr, sizeof(int32_t) * n));
         PO_HIPCHK(guide.up(nullptr, sizeof(int32_t) * (size_t)rows));
         PO_HIPCHK(qst.up(nullptr, sizeof(int32_t) * n));
@@ -159,17 +174,17 @@ struct FastqStages {
             PO_HIPCHK(vst.up(nullptr, sizeof(int32_t) * n));
             PO_HIPCHK(wsv.up(nullptr, po_viterbi_workspace_bytes(n, rows, NOUT, kind)));
         }
-        if (beam_width > 0) PO_HIPCHK(consumed.up(nullptr, sizeof(int32_t) * (size_t)rows));
+        if (align) PO_HIPCHK(consumed.up(nullptr, sizeof(int32_t) * (size_t)rows));
         return PO_OK;
     }
 
     // steps 1 to 3: the Viterbi call with its map, the pairs that need an alignment, the guide
-    int guides(const char* me, const FastqOut& fq, const double* dy, const int64_t* dsoff, int n, int64_t rows, const char* alphabet,
-               int kind, int beam_width, const PoSeqOut& out, hipStream_t stream) {
+    int guides(const char* me, int band_size, const double* dy, const int64_t* dsoff, int n, int64_t rows, const char* alphabet,
+               int kind, const FqStrings& out, hipStream_t stream) {
         int rc;
-        const char* called = out.seq.as<char>();
-        const int32_t* called_st = out.status.as<int32_t>();
-        called_len = out.len.as<int32_t>();
+        const char* called = out.seq;
+        const int32_t* called_st = out.status;
+        called_len = const_cast<int32_t*>(out.len);
         if (second) {
             rc = po_viterbi_batch(dy, dsoff, n, NOUT, alphabet, kind, nullptr, vseq, out.off, vlen, map, vst, wsv,
                                   po_viterbi_workspace_bytes(n, rows, NOUT, kind), stream);
@@ -180,10 +195,10 @@ struct FastqStages {
         }
         po_launch_fastq_mode(out.seq, out.len, called, called_len, called_st, out.off, n, mode, stream);
         PO_HIPCHK(hipGetLastError());
-        if (beam_width > 0) {
+        if (align) {
             std::vector<int32_t> h(3 * (size_t)n);   // mode | scored lengths | called lengths
             PO_HIPCHK(hipMemcpyAsync(h.data(), mode.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
-            PO_HIPCHK(hipMemcpyAsync(h.data() + n, out.len.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+            PO_HIPCHK(hipMemcpyAsync(h.data() + n, out.len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             PO_HIPCHK(hipMemcpyAsync(h.data() + 2 * n, vlen.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
             PO_HIPCHK(hipStreamSynchronize(stream));
             for (int i = 0; i < n; ++i)
@@ -200,36 +215,64 @@ struct FastqStages {
                 PO_HIPCHK(hipGetLastError());
             }
         }
-        if (fq.band_size > 0) {
-            po_launch_fastq_guide(map, beam_width > 0 ? consumed.as<int32_t>() : nullptr, dsoff, n, rows, called_len, out.len, mode,
+        if (band_size > 0) {
+            po_launch_fastq_guide(mapp, align ? consumed.as<int32_t>() : nullptr, dsoff, n, rows, called_len, out.len, mode,
                                   guide, stream);
             PO_HIPCHK(hipGetLastError());
         }
         return PO_OK;
     }
 
-    // steps 4 to 6: dense labels, the lattice on the resident table, Phred characters at the strings' offsets
-    int lattice(const FastqOut& fq, const double* dy, const int64_t* dsoff, int n, int64_t rows, int64_t max_rows,
-                const char* alphabet, int kind, const PoSeqOut& out, hipStream_t stream) {
+    // steps 4 to 6: dense labels, the lattice on the resident table, Phred characters at the strings' offsets in `qual_out`.
+    // unbanded_h (or NULL): with a band, a flagged read is scored in a second po_qual_batch call without one and has L = 0
+    // in the first, as the pair stages do it (po_pair_fastq_plan.h): the second call's labels and odds lie behind the
+    // first's, and the read's status is the second call's.  Without flags this is one call, as it always was.
+    int lattice(int band_size, const int32_t* unbanded_h, const double* dy, const int64_t* dsoff, int n, int64_t rows, int64_t max_rows,
+                const char* alphabet, int kind, const FqStrings& out, char* qual_out, hipStream_t stream) {
         std::vector<int32_t> len((size_t)n);
-        PO_HIPCHK(hipMemcpyAsync(len.data(), out.len.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+        PO_HIPCHK(hipMemcpyAsync(len.data(), out.len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
         PO_HIPCHK(hipStreamSynchronize(stream));
+        bool split = false;
+        for (int i = 0; unbanded_h && band_size > 0 && i < n; ++i) split = split || unbanded_h[i] != 0;
         label_off_h.assign((size_t)n + 1, 0);
-        for (int i = 0; i < n; ++i) label_off_h[(size_t)i + 1] = label_off_h[i] + std::max(len[i], 0);
-        const int64_t total = label_off_h[n];
+        label_off_u_h.assign((size_t)n + 1, 0);
+        for (int i = 0; i < n; ++i) {
+            const bool u = split && unbanded_h[i] != 0;
+            label_off_h[(size_t)i + 1] = label_off_h[i] + (u ? 0 : std::max(len[i], 0));
+            label_off_u_h[(size_t)i + 1] = label_off_u_h[i] + (u ? std::max(len[i], 0) : 0);
+        }
+        total_b = label_off_h[n];
+        total_u = label_off_u_h[n];
+        const int64_t total = total_b + total_u;
         const int model = kind == PO_KIND_BONITO ? PO_MODEL_MERGE : PO_MODEL_CTC;   // the tree model of the decoder's kind
-        const size_t wqb = po_qual_workspace_bytes(n, rows, max_rows, total, fq.band_size, model);
+        size_t wqb = po_qual_workspace_bytes(n, rows, max_rows, total_b, band_size, model);
+        if (split) wqb = std::max(wqb, po_qual_workspace_bytes(n, rows, max_rows, total_u, 0, model));
         PO_HIPCHK(label_off.up(label_off_h.data(), sizeof(int64_t) * label_off_h.size()));
+        if (split) {   // (the statuses of the call without a band: a second half, before anything is written to the first)
+            PO_HIPCHK(label_off_u.up(label_off_u_h.data(), sizeof(int64_t) * label_off_u_h.size()));
+            PO_HIPCHK(qst.up(nullptr, sizeof(int32_t) * 2 * (size_t)n));
+        }
         PO_HIPCHK(labels.up(nullptr, (size_t)total));
         PO_HIPCHK(odds.up(nullptr, sizeof(double) * 5 * (size_t)total));
         PO_HIPCHK(wsq.up(nullptr, wqb));
-        po_launch_fastq_gather(out.seq, out.seq, out.off, nullptr, 1, label_off, n, total, labels, stream);
-        PO_HIPCHK(hipGetLastError());
-        const int rc = po_qual_batch(dy, dsoff, n, NOUT, alphabet, model, labels, label_off, fq.band_size > 0 ? guide.as<int32_t>() : nullptr,
-                                     fq.band_size, odds, logp, qst, wsq, wqb, stream);
-        if (rc != PO_OK) return rc;
-        po_launch_fastq_phred(odds, labels, label_off, qst, out.off, n, total, alphabet, qual, stream);
-        PO_HIPCHK(hipGetLastError());
+        for (int u = 0; u < (split ? 2 : 1); ++u) {
+            const int64_t tot = u ? total_u : total_b, at = u ? total_b : 0;
+            const int64_t* lo = u ? label_off_u.as<int64_t>() : label_off.as<int64_t>();
+            const int band = u ? 0 : band_size;
+            char* lab = labels.as<char>() + at;
+            double* od = odds.as<double>() + at * 5;
+            int32_t* q = qst.as<int32_t>() + (u ? n : 0);
+            po_launch_fastq_gather(out.seq, out.seq, out.off, nullptr, 1, lo, n, tot, lab, stream);
+            PO_HIPCHK(hipGetLastError());
+            const int rc = po_qual_batch_route(dy, dsoff, n, NOUT, alphabet, model, lab, lo, band > 0 ? guide.as<int32_t>() : nullptr, band,
+                                               od, logp, q, wsq, wqb, stream, qual_route);
+            if (rc != PO_OK) return rc;
+            po_launch_fastq_phred(od, lab, lo, q, out.off, n, tot, alphabet, qual_out, stream);
+            PO_HIPCHK(hipGetLastError());
+        }
+        for (int i = 0; split && i < n; ++i)   // (the retry's few reads: a word each)
+            if (unbanded_h[i] != 0)
+                PO_HIPCHK(hipMemcpyAsync(qst.as<int32_t>() + i, qst.as<int32_t>() + n + i, sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
         return PO_OK;
     }
 
@@ -316,7 +359,7 @@ int po_basecall_body(PoBasecallResident* st, hipStream_t stream, bool signal_res
     PO_HIPCHK(dws2.up(nullptr, wsb2));
     FastqStages& fs = st->fs;
     if (fq) {
-        rc = fs.prepare(n_reads, rows, kind, beam_width, out.cap);
+        rc = fs.prepare(n_reads, rows, kind, beam_width > 0 || kind != PO_KIND_POREOVER, beam_width > 0, out.cap);
         if (rc != PO_OK) return rc;
     }
 
@@ -338,11 +381,11 @@ int po_basecall_body(PoBasecallResident* st, hipStream_t stream, bool signal_res
     PO_HIPCHK(decode.mark(stream));
     if (fq) {   // the quality stages, on the table, the strings and (Viterbi) the frame map the decoder left on the device
         PO_HIPCHK(guides.mark(stream));
-        rc = fs.guides(name, *fq, dy, dsoff, n_reads, rows, alphabet, kind, beam_width, out, stream);
+        rc = fs.guides(name, fq->band_size, dy, dsoff, n_reads, rows, alphabet, kind, fq_strings(out), stream);
         if (rc != PO_OK) return rc;
         PO_HIPCHK(guides.mark(stream));
         PO_HIPCHK(lattice.mark(stream));
-        rc = fs.lattice(*fq, dy, dsoff, n_reads, rows, plan.max_rows, alphabet, kind, out, stream);
+        rc = fs.lattice(fq->band_size, nullptr, dy, dsoff, n_reads, rows, plan.max_rows, alphabet, kind, fq_strings(out), fs.qual, stream);
         if (rc != PO_OK) return rc;
         PO_HIPCHK(lattice.mark(stream));
     }
@@ -397,4 +440,67 @@ extern "C" int po_basecall_fastq_batch_h(const float* signal_h, const int64_t* s
     return basecall_impl("po_basecall_fastq_batch_h", signal_h, sig_off_h, n_reads, window, overlap, layers_h, n_layers, weights_h,
                          n_weights, alphabet, kind, beam_width, model, max_windows_per_pass, seq_h, seq_off_h, seq_len_h, status_h,
                          logits_h, stage_ms_h, &fq);
+}
+
+// The quality stages alone, on tables and strings that somebody else left on the device: what
+// po_basecall_fastq_batch_h runs behind its decoder, through the same FastqStages.
+extern "C" int po_fastq_tables(const double* y, const int64_t* y_off, int n, int C, int model, int kind, const char* seq,
+                               const int64_t* seq_off, const int32_t* seq_len, const int32_t* status, const int32_t* map,
+                               int scored_is_viterbi, int band_size, const int32_t* unbanded_h, char* qual, int32_t* qual_status,
+                               double* odds, int32_t* guide, void* stream_) {
+    const char* name = "po_fastq_tables";
+    const std::string me = std::string(name) + ": ";
+    hipStream_t stream = (hipStream_t)stream_;
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (n < 0) return po_fail(PO_E_ARG, me + "n " + std::to_string(n));
+    if (scored_is_viterbi != 0 && scored_is_viterbi != 1)
+        return po_fail(PO_E_ARG, me + "scored_is_viterbi " + std::to_string(scored_is_viterbi) + " (0 or 1)");
+    const struct { const void* p; const char* name; } ptrs[] = {
+        {y, "y"}, {y_off, "y_off"}, {seq, "seq"}, {seq_off, "seq_off"}, {seq_len, "seq_len"}, {status, "status"},
+        {scored_is_viterbi ? (const void*)map : (const void*)name, "map"}, {qual, "qual"}, {qual_status, "qual_status"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
+    if (model == PO_MODEL_FLIPFLOP || kind == PO_KIND_FLIPFLOP)
+        return po_fail(PO_E_UNSUPPORTED, me + "the flip-flop model has no quality lattice");
+    if (C != NOUT) return po_fail(PO_E_ARG, me + "C " + std::to_string(C) + " (5: A, C, G, T and the blank)");
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, me + "model " + std::to_string(model));
+    if (kind != PO_KIND_POREOVER && kind != PO_KIND_BONITO) return po_fail(PO_E_ARG, me + "kind " + std::to_string(kind));
+    if ((kind == PO_KIND_BONITO) != (model == PO_MODEL_MERGE))
+        return po_fail(PO_E_ARG, me + "model " + std::to_string(model) + " is not the tree model of kind " + std::to_string(kind));
+    if (n == 0) return PO_OK;
+    std::vector<int64_t> h(2 * ((size_t)n + 1));   // the tables' row offsets | the strings'
+    PO_HIPCHK(po_read_tables(y_off, seq_off, n, stream, h.data()));
+    const int64_t *yo = h.data(), *so = h.data() + n + 1;
+    if (yo[0] != 0 || so[0] != 0) return po_fail(PO_E_ARG, me + (yo[0] != 0 ? "y_off" : "seq_off") + "[0] must be 0");
+    int64_t max_rows = 0;
+    for (int i = 0; i < n; ++i) {
+        if (yo[i + 1] < yo[i] || so[i + 1] < so[i])
+            return po_fail(PO_E_ARG, me + (yo[i + 1] < yo[i] ? "y_off" : "seq_off") + " decreases at read " + std::to_string(i));
+        if (so[i + 1] - so[i] < yo[i + 1] - yo[i])   // (the Viterbi call of the guides is written at the strings' offsets)
+            return po_fail(PO_E_CAP, me + "read " + std::to_string(i) + " has room for " + std::to_string(so[i + 1] - so[i]) +
+                           " characters and " + std::to_string(yo[i + 1] - yo[i]) + " frames");
+        max_rows = std::max(max_rows, yo[i + 1] - yo[i]);
+    }
+    const int64_t rows = yo[n];
+    std::vector<int32_t> len_h((size_t)n);
+    PO_HIPCHK(hipMemcpyAsync(len_h.data(), seq_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost, stream));
+    PO_HIPCHK(hipStreamSynchronize(stream));
+    for (int i = 0; i < n; ++i)
+        if (len_h[i] > so[i + 1] - so[i])
+            return po_fail(PO_E_CAP, me + "read " + std::to_string(i) + " has " + std::to_string(len_h[i]) + " characters in room for " +
+                           std::to_string(so[i + 1] - so[i]));
+    const FqStrings out = {seq, seq_off, seq_len, status, (size_t)so[n]};
+
+    FastqStages fs;
+    fs.qual_route = po_qual_entry_route();
+    int rc = fs.prepare(n, rows, kind, !scored_is_viterbi, !scored_is_viterbi, out.cap, scored_is_viterbi ? map : nullptr);
+    if (rc == PO_OK) rc = fs.guides(name, band_size, y, y_off, n, rows, "ACGT", kind, out, stream);
+    if (rc == PO_OK) rc = fs.lattice(band_size, unbanded_h, y, y_off, n, rows, max_rows, "ACGT", kind, out, qual, stream);
+    if (rc != PO_OK) return rc;
+    PO_HIPCHK(po_out(qual_status, fs.qst.p, sizeof(int32_t) * n, true, stream));
+    PO_HIPCHK(po_out(odds, fs.odds.p, sizeof(double) * 5 * (size_t)(fs.total_b + fs.total_u), true, stream));
+    if (band_size > 0) PO_HIPCHK(po_out(guide, fs.guide.p, sizeof(int32_t) * (size_t)rows, true, stream));
+    PO_HIPCHK(hipStreamSynchronize(stream));   // (the stages' buffers are this call's: they go when it returns)
+    return PO_OK;
 }

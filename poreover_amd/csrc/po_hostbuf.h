@@ -74,6 +74,19 @@ struct PoDev {
     template <class T> operator T*() const { return (T*)p; }   // an argument of a launch: no cast at the call site
 };
 
+// ---- a result on its way out.  A *_h twin's goes to the host with a blocking copy; an entry whose outputs are the caller's
+// device buffers (po_fastq_tables, po_pair_qual) gets it on the call's stream.  src_d: device memory; src_h: host memory
+// that may go out of scope when the function returns (the device form waits for the copy).
+inline hipError_t po_out(void* dst, const void* src_d, size_t bytes, bool dev, hipStream_t s) {
+    if (!dst || !bytes) return hipSuccess;
+    return dev ? hipMemcpyAsync(dst, src_d, bytes, hipMemcpyDeviceToDevice, s) : hipMemcpy(dst, src_d, bytes, hipMemcpyDeviceToHost);
+}
+inline hipError_t po_out_h(void* dst, const void* src_h, size_t bytes, hipStream_t s) {
+    if (!dst || !bytes) return hipSuccess;
+    hipError_t e = hipMemcpyAsync(dst, src_h, bytes, hipMemcpyHostToDevice, s);
+    return e == hipSuccess ? hipStreamSynchronize(s) : e;
+}
+
 // one ragged input: the items' rows (`width` bytes each) from row r.base of src_h on, and the rebased table
 struct PoRows {
     PoDev data, off;

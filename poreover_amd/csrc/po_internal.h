@@ -168,6 +168,10 @@ int po_launch_fastq_pair_phred(const double* odds1, const int64_t* pos1, const i
                                const int64_t* seq_off, const int64_t* dense_off, int n, int64_t total, const char* alphabet,
                                char* qual, hipStream_t stream);
 
+// po_qual.hip: what the entries on resident tables pass to po_qual_batch_route (include/poreover_hip.h): PO_QUAL_ROUTE_AUTO
+// unless po_set_qual_route forced the other
+int po_qual_entry_route();
+
 // po_eval.hip (enqueue only; the rules are po_eval_rules.h's).  Pair i of po_launch_edit_distance is a[a_off[i] ..] of
 // a_len[i] symbols (a_len NULL: a_off[i + 1] - a_off[i]) against b[b_off[i] .. b_off[i + 1])
 int po_launch_eval_path(const float* probs, int n, int T, uint8_t* pred, int32_t* pred_len, hipStream_t stream);

@@ -117,6 +117,7 @@ struct PairFastqStages {
     size_t s1b = 0, cap = 0, wvb = 0;
     bool banded = false;
     int kind = PO_KIND_POREOVER;
+    int qual_route = PO_QUAL_ROUTE_GENERAL;   // the lattices' kernels: po_qual_batch's (po_pair_qual: po_qual_entry_route())
 
     // before the decoder: the buffers whose size is known from the tables
     int prepare(const PairQualIn& in, const PairFastqOut& fq) {
@@ -255,8 +256,9 @@ struct PairFastqStages {
                 int32_t* q = qst[k].as<int32_t>() + (u ? n : 0);
                 po_launch_fastq_gather(scored(in, k), scored(in, k), scored_off(in, k), nullptr, 1, lo, n, tot, lab, stream);
                 PO_HIPCHK(hipGetLastError());
-                const int rc = po_qual_batch(in.y[s], in.y_off[s], n, NOUT, "ACGT", in.model, lab, lo, u ? nullptr : guide[k].as<int32_t>(),
-                                             u ? 0 : fq.band_size, od, logp, q, wsq, wqb, stream);
+                const int rc = po_qual_batch_route(in.y[s], in.y_off[s], n, NOUT, "ACGT", in.model, lab, lo,
+                                                   u ? nullptr : guide[k].as<int32_t>(), u ? 0 : fq.band_size, od, logp, q, wsq, wqb, stream,
+                                                   qual_route);
                 if (rc != PO_OK) return rc;
                 if (k < 2) {
                     po_launch_fastq_phred(od, lab, lo, q, off1d[s], n, tot, "ACGT", qual1d, stream);
@@ -270,19 +272,27 @@ struct PairFastqStages {
         return PO_OK;
     }
 
-    // after the synchronise: the characters, the statuses and (where asked for) the odds and the guides
-    int down(const PairQualIn& in, const PairFastqOut& fq) {
+    // after the synchronise: the characters, the statuses and (where asked for) the odds and the guides.  dev: fq's
+    // pointers are device buffers of the caller's (po_pair_qual), filled on `stream`; otherwise host buffers
+    int down(const PairQualIn& in, const PairFastqOut& fq, bool dev = false, hipStream_t stream = nullptr) {
         const int n = in.n;
-        PO_HIPCHK(qual1d.down(fq.qual1d_h, s1b));
-        PO_HIPCHK(qual.down(fq.qual_h, cap));
-        std::vector<int32_t> st(2 * (size_t)n);
+        PO_HIPCHK(po_out(fq.qual1d_h, qual1d.p, s1b, dev, stream));
+        PO_HIPCHK(po_out(fq.qual_h, qual.p, cap, dev, stream));
+        std::vector<int32_t> st(2 * (size_t)n), qs_dev;
         std::vector<double> dense;
+        if (dev) qs_dev.resize(PO_PQ_ITEMS * (size_t)n);
+        int32_t* qs = dev ? qs_dev.data() : fq.qual_status_h;
         for (int k = 0; k < PO_PQ_ITEMS; ++k) {
             const int s = po_pq_side(k);
             PO_HIPCHK(qst[k].down(st.data(), sizeof(int32_t) * st.size()));
-            for (int i = 0; i < n; ++i) fq.qual_status_h[PO_PQ_ITEMS * (size_t)i + k] = po_pair_fastq_status(plan, k, i, st.data());
+            for (int i = 0; i < n; ++i) qs[PO_PQ_ITEMS * (size_t)i + k] = po_pair_fastq_status(plan, k, i, st.data());
             double* dst = k < 2 ? fq.odds1d_h : fq.odds_cons_h ? fq.odds_cons_h + (size_t)(k - 2) * 5 * cap : nullptr;
-            if (dst && plan.total(k) > 0) {   // dense on the device, at the strings' offsets in the caller's tables
+            if (dst && plan.total(k) > 0 && dev) {   // (an optional output: one small copy per item, device to device)
+                for (int i = 0; i < n; ++i) {
+                    const int64_t L = plan.len[k][i], at = k < 2 ? plan.off1d[s][i] : in.seq_off_h[i];
+                    if (L > 0) PO_HIPCHK(po_out(dst + at * 5, odds[k].as<double>() + plan.pos[k][i] * 5, sizeof(double) * 5 * (size_t)L, true, stream));
+                }
+            } else if (dst && plan.total(k) > 0) {   // dense on the device, at the strings' offsets in the caller's tables
                 dense.resize((size_t)plan.total(k) * 5);
                 PO_HIPCHK(odds[k].down(dense.data(), sizeof(double) * dense.size()));
                 for (int i = 0; i < n; ++i) {
@@ -291,8 +301,10 @@ struct PairFastqStages {
                 }
             }
             if (fq.guide_h && banded)
-                PO_HIPCHK(guide[k].down(fq.guide_h + po_pair_fastq_guide_base(k, in.rows[0], in.rows[1]), sizeof(int32_t) * (size_t)in.rows[s]));
+                PO_HIPCHK(po_out(fq.guide_h + po_pair_fastq_guide_base(k, in.rows[0], in.rows[1]), guide[k].p,
+                                 sizeof(int32_t) * (size_t)in.rows[s], dev, stream));
         }
+        if (dev) PO_HIPCHK(po_out_h(fq.qual_status_h, qs_dev.data(), sizeof(int32_t) * qs_dev.size(), stream));
         return PO_OK;
     }
 };
@@ -557,6 +569,63 @@ extern "C" int po_pair_basecall_fastq_batch_h(const float* signal_h, const int64
                               seq1d_off_h, len1_h, len2_h, identity_h, seq_h, seq_off_h, seq_len_h, status_h, logits_h, stage_ms_h, &fq);
 }
 
+namespace {
+
+// the refusals that po_pair_qual_h and po_pair_qual share, on host copies of the tables: every table from 0 and
+// non-decreasing, a decoded pair's strings within their room
+int pair_qual_check(const std::string& me, int n, const int64_t* y1_off_h, const int64_t* y2_off_h, const int64_t* seq1d_off_h,
+                    const int64_t* seq_off_h, const int32_t* len1_h, const int32_t* len2_h, const int32_t* seq_len_h,
+                    const int32_t* status_h) {
+    const struct { const int64_t* off; int count; const char* name; } tables[] = {
+        {y1_off_h, n, "y1_off"}, {y2_off_h, n, "y2_off"}, {seq1d_off_h, 2 * n, "seq1d_off"}, {seq_off_h, n, "seq_off"}};
+    for (const auto& tb : tables) {
+        if (tb.off[0] != 0) return po_fail(PO_E_ARG, me + tb.name + "[0] is " + std::to_string(tb.off[0]) + " (must be 0)");
+        for (int i = 0; i < tb.count; ++i)
+            if (tb.off[i + 1] < tb.off[i]) return po_fail(PO_E_ARG, me + tb.name + " decreases at item " + std::to_string(i));
+    }
+    for (int i = 0; i < n; ++i) {
+        if (status_h[i] != 0) continue;   // (what a pair that is not decoded holds is not read)
+        const int64_t room[3] = {seq1d_off_h[2 * (size_t)i + 1] - seq1d_off_h[2 * (size_t)i],
+                                 seq1d_off_h[2 * (size_t)i + 2] - seq1d_off_h[2 * (size_t)i + 1], seq_off_h[i + 1] - seq_off_h[i]};
+        const int32_t len[3] = {len1_h[i], len2_h[i], seq_len_h[i]};
+        for (int k = 0; k < 3; ++k)
+            if (len[k] < 0 || len[k] > room[k])
+                return po_fail(PO_E_CAP, me + "pair " + std::to_string(i) + ": " + (k == 0 ? "seq1" : k == 1 ? "seq2" : "the consensus") +
+                               " has " + std::to_string(len[k]) + " characters in room for " + std::to_string(room[k]));
+    }
+    return PO_OK;
+}
+
+// the stages on tables and strings that are on the device (in.y, in.seq1d, in.seq, in.seq_off), the rest of `in` filled
+// here from the host copies of the tables; dev: fq's outputs are device buffers
+int pair_qual_body(const char* name, PairQualIn& in, const PairFastqOut& fq, const int64_t* y1_off_h, const int64_t* y2_off_h,
+                   const int64_t* seq1d_off_h, const int64_t* seq_off_h, const int32_t* len1_h, const int32_t* len2_h,
+                   const int32_t* seq_len_h, const int32_t* status_h, bool dev, hipStream_t stream) {
+    const int n = in.n;
+    const int64_t* yo_h[2] = {y1_off_h, y2_off_h};
+    for (int s = 0; s < 2; ++s) {
+        in.rows[s] = yo_h[s][n];
+        in.max_rows[s] = 0;
+        for (int i = 0; i < n; ++i) in.max_rows[s] = std::max(in.max_rows[s], yo_h[s][i + 1] - yo_h[s][i]);
+    }
+    in.seq1d_off_h = seq1d_off_h;
+    in.seq_off_h = seq_off_h;
+    PairFastqStages fs;
+    if (dev) fs.qual_route = po_qual_entry_route();
+    int rc = fs.prepare(in, fq);
+    if (rc == PO_OK) rc = fs.viterbi(in, stream);
+    if (rc == PO_OK) rc = fs.guides(name, in, fq, status_h, len1_h, len2_h, seq_len_h, stream);
+    if (rc == PO_OK) rc = fs.lattice(in, fq, stream);
+    if (rc != PO_OK) return rc;
+    PO_HIPCHK(hipStreamSynchronize(stream));
+    rc = fs.down(in, fq, dev, stream);
+    if (rc != PO_OK) return rc;
+    if (dev) PO_HIPCHK(hipStreamSynchronize(stream));   // (the stages' buffers are this call's: they go when it returns)
+    return PO_OK;
+}
+
+}  // namespace
+
 extern "C" int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const double* y2_h, const int64_t* y2_off_h, int n, int model,
                               const char* seq1d_h, const int64_t* seq1d_off_h, const int32_t* len1_h, const int32_t* len2_h,
                               const char* seq_h, const int64_t* seq_off_h, const int32_t* seq_len_h, const int32_t* status_h,
@@ -576,35 +645,16 @@ extern "C" int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const
     if (null_quality_pointer(me, fq) != PO_OK) return PO_E_ARG;
     if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, me + "the flip-flop model has no quality lattice");
     if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, me + "model " + std::to_string(model));
-    const struct { const int64_t* off; int count; const char* name; } tables[] = {
-        {y1_off_h, n, "y1_off"}, {y2_off_h, n, "y2_off"}, {seq1d_off_h, 2 * n, "seq1d_off"}, {seq_off_h, n, "seq_off"}};
-    for (const auto& tb : tables) {
-        if (tb.off[0] != 0) return po_fail(PO_E_ARG, me + tb.name + "[0] is " + std::to_string(tb.off[0]) + " (must be 0)");
-        for (int i = 0; i < tb.count; ++i)
-            if (tb.off[i + 1] < tb.off[i]) return po_fail(PO_E_ARG, me + tb.name + " decreases at item " + std::to_string(i));
-    }
-    for (int i = 0; i < n; ++i) {
-        if (status_h[i] != 0) continue;   // (what a pair that is not decoded holds is not read)
-        const int64_t room[3] = {seq1d_off_h[2 * (size_t)i + 1] - seq1d_off_h[2 * (size_t)i],
-                                 seq1d_off_h[2 * (size_t)i + 2] - seq1d_off_h[2 * (size_t)i + 1], seq_off_h[i + 1] - seq_off_h[i]};
-        const int32_t len[3] = {len1_h[i], len2_h[i], seq_len_h[i]};
-        for (int k = 0; k < 3; ++k)
-            if (len[k] < 0 || len[k] > room[k])
-                return po_fail(PO_E_CAP, me + "pair " + std::to_string(i) + ": " + (k == 0 ? "seq1" : k == 1 ? "seq2" : "the consensus") +
-                               " has " + std::to_string(len[k]) + " characters in room for " + std::to_string(room[k]));
-    }
+    int rc = pair_qual_check(me, n, y1_off_h, y2_off_h, seq1d_off_h, seq_off_h, len1_h, len2_h, seq_len_h, status_h);
+    if (rc != PO_OK) return rc;
     if (n == 0) return PO_OK;
 
-    hipStream_t stream = nullptr;
     PoDev y[2], yo[2], s1, sq, so;
     PairQualIn in;
     const double* y_h[2] = {y1_h, y2_h};
     const int64_t* yo_h[2] = {y1_off_h, y2_off_h};
     for (int s = 0; s < 2; ++s) {
-        in.rows[s] = yo_h[s][n];
-        in.max_rows[s] = 0;
-        for (int i = 0; i < n; ++i) in.max_rows[s] = std::max(in.max_rows[s], yo_h[s][i + 1] - yo_h[s][i]);
-        PO_HIPCHK(y[s].up(y_h[s], sizeof(double) * NOUT * (size_t)in.rows[s]));
+        PO_HIPCHK(y[s].up(y_h[s], sizeof(double) * NOUT * (size_t)yo_h[s][n]));
         PO_HIPCHK(yo[s].up(yo_h[s], sizeof(int64_t) * ((size_t)n + 1)));
         in.y[s] = y[s]; in.y_off[s] = yo[s];
     }
@@ -612,14 +662,49 @@ extern "C" int po_pair_qual_h(const double* y1_h, const int64_t* y1_off_h, const
     PO_HIPCHK(sq.up(seq_h, (size_t)seq_off_h[n]));
     PO_HIPCHK(so.up(seq_off_h, sizeof(int64_t) * ((size_t)n + 1)));
     in.n = n; in.model = model;
-    in.seq1d = s1; in.seq1d_off_h = seq1d_off_h;
-    in.seq = sq; in.seq_off = so; in.seq_off_h = seq_off_h;
-    PairFastqStages fs;
-    int rc = fs.prepare(in, fq);
-    if (rc == PO_OK) rc = fs.viterbi(in, stream);
-    if (rc == PO_OK) rc = fs.guides(name, in, fq, status_h, len1_h, len2_h, seq_len_h, stream);
-    if (rc == PO_OK) rc = fs.lattice(in, fq, stream);
-    if (rc != PO_OK) return rc;
+    in.seq1d = s1; in.seq = sq; in.seq_off = so;
+    return pair_qual_body(name, in, fq, y1_off_h, y2_off_h, seq1d_off_h, seq_off_h, len1_h, len2_h, seq_len_h, status_h, false, nullptr);
+}
+
+// po_pair_qual_h on buffers that are on the device already: the same stages, nothing uploaded but the
+// plan's small tables.  The offset tables, lengths and statuses are read back: the plan is made on the host.
+extern "C" int po_pair_qual(const double* y1, const int64_t* y1_off, const double* y2, const int64_t* y2_off, int n, int model,
+                            const char* seq1d, const int64_t* seq1d_off, const int32_t* len1, const int32_t* len2, const char* seq,
+                            const int64_t* seq_off, const int32_t* seq_len, const int32_t* status, int band_size,
+                            const int32_t* unbanded_h, char* qual1d, char* qual, int32_t* qual_status, double* odds1d,
+                            double* odds_cons, int32_t* guide, void* stream_) {
+    const char* name = "po_pair_qual";
+    const std::string me = std::string(name) + ": ";
+    hipStream_t stream = (hipStream_t)stream_;
+    po_set_error("");
+    // ---- every argument error, before the first allocation
+    if (n < 0) return po_fail(PO_E_ARG, me + "n " + std::to_string(n));
+    const struct { const void* p; const char* name; } ptrs[] = {
+        {y1, "y1"}, {y1_off, "y1_off"}, {y2, "y2"}, {y2_off, "y2_off"}, {seq1d, "seq1d"}, {seq1d_off, "seq1d_off"},
+        {len1, "len1"}, {len2, "len2"}, {seq, "seq"}, {seq_off, "seq_off"}, {seq_len, "seq_len"}, {status, "status"},
+        {qual1d, "qual1d"}, {qual, "qual"}, {qual_status, "qual_status"}};
+    for (const auto& a : ptrs)
+        if (!a.p) return po_fail(PO_E_ARG, me + "null argument " + a.name);
+    if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, me + "the flip-flop model has no quality lattice");
+    if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, me + "model " + std::to_string(model));
+    if (n == 0) return PO_OK;
+    const size_t N = (size_t)n;
+    std::vector<int64_t> off(5 * N + 4);   // y1_off | y2_off | seq_off | seq1d_off
+    std::vector<int32_t> w(4 * N);         // len1 | len2 | seq_len | status
+    int64_t *y1o = off.data(), *y2o = y1o + N + 1, *so = y2o + N + 1, *s1o = so + N + 1;
+    PO_HIPCHK(hipMemcpyAsync(y1o, y1_off, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, stream));
+    PO_HIPCHK(hipMemcpyAsync(y2o, y2_off, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, stream));
+    PO_HIPCHK(hipMemcpyAsync(so, seq_off, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost, stream));
+    PO_HIPCHK(hipMemcpyAsync(s1o, seq1d_off, sizeof(int64_t) * (2 * N + 1), hipMemcpyDeviceToHost, stream));
+    const int32_t* words[4] = {len1, len2, seq_len, status};
+    for (int k = 0; k < 4; ++k) PO_HIPCHK(hipMemcpyAsync(w.data() + k * N, words[k], sizeof(int32_t) * N, hipMemcpyDeviceToHost, stream));
     PO_HIPCHK(hipStreamSynchronize(stream));
-    return fs.down(in, fq);
+    const int rc = pair_qual_check(me, n, y1o, y2o, s1o, so, w.data(), w.data() + N, w.data() + 2 * N, w.data() + 3 * N);
+    if (rc != PO_OK) return rc;
+    const PairFastqOut fq = {band_size, unbanded_h, qual1d, qual, qual_status, odds1d, odds_cons, guide};
+    PairQualIn in;
+    in.y[0] = y1; in.y_off[0] = y1_off; in.y[1] = y2; in.y_off[1] = y2_off;
+    in.n = n; in.model = model;
+    in.seq1d = seq1d; in.seq = seq; in.seq_off = seq_off;
+    return pair_qual_body(name, in, fq, y1o, y2o, s1o, so, w.data(), w.data() + N, w.data() + 2 * N, w.data() + 3 * N, true, stream);
 }

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -373,6 +374,298 @@ __global__ __launch_bounds__(64) void qual_kernel(QArgs a) {
     }
 }
 
+// ---- qual_reg_kernel: qual_kernel's lattice for a ring of at most 64 indices, the state in registers.
+// Lane = ring index.  The row of pass 1, prev / cur of pass 2, the five accumulators and the merge model's four runs are
+// registers of the lane; the upper and the lower neighbour's values come from a lane read (__shfl) whose index is formed
+// mod W.  No LDS, no barrier.  The stored rows keep qual_kernel's layout.  Every cell's operands enter the same q_lae calls
+// in the same order as in qual_kernel; where qual_kernel branches around a term, the term is computed and selected away
+// (q_lae(x, -inf) is x, bit for bit), so odds, logp and status are qual_kernel's bits.  The guide value is requested two
+// steps ahead, the y row, the label codes around the lane's state and the stored row one step ahead, all of them
+// unconditionally (clamped addresses): no load waits under a branch inside a frame loop.
+template <bool MERGE>
+__global__ __launch_bounds__(64) void qual_reg_kernel(QArgs a) {
+    const int lane = threadIdx.x;
+    const QDesc d = a.desc[a.first + blockIdx.x];
+    const int i = d.read;
+    const int A = a.A, C = A + 1, B = a.band;
+    const int W = d.wr;   // <= 64
+    const bool full = d.full != 0;
+    const int64_t r0 = a.y_off[i];
+    const int T = (int)(a.y_off[i + 1] - r0);
+    const double* y = a.y + r0 * C;
+    const char* lab = a.labels + a.label_off[i];
+    const int L = (int)(a.label_off[i + 1] - a.label_off[i]);
+    const int32_t* g = a.guide ? a.guide + r0 : nullptr;
+    double* odds = a.odds + a.label_off[i] * 5;
+    const double NINF = q_ninf();
+
+    // ---- arguments: label characters, guide (qual_kernel's) ----
+    int bad = 0;
+    for (int j = lane; j < L; j += 64) bad |= (q_code(a.alphabet, A, lab[j]) < 0);
+    if (g)
+        for (int t = lane; t < T; t += 64) {
+            const int c = g[t], p = t > 0 ? g[t - 1] : 0;
+            bad |= (c < 0) | (c > L) | (c < p);
+        }
+    bad = __ballot(bad) != 0ull;
+    for (int64_t j = lane; j < (int64_t)L * 5; j += 64) odds[j] = 0.0;
+    if (bad || L == 0 || T <= 0) {
+        if (lane == 0) {
+            double bs = 0.0;
+            if (!bad && L == 0)
+                for (int t = 0; t < T; ++t) bs = bs + y[(int64_t)t * C + A];
+            const bool ok = !bad && L == 0;
+            a.status[i] = bad ? PO_E_ARG : (ok ? PO_OK : PO_E_ENVELOPE);
+            a.logp[i] = ok ? bs : NINF;
+        }
+        return;
+    }
+
+    const bool act = lane < W;
+    const int ridx = act ? lane : 0;
+    const int ru = ridx + 1 == W ? 0 : ridx + 1, rl = ridx == 0 ? W - 1 : ridx - 1;
+    // the band centre of row u = 0 .. T (rows outside are clamped: a prefetch for a step that does not come)
+    auto centre = [&](int u) -> int {
+        int t = u > 0 ? u - 1 : 0;
+        t = t < T ? t : T - 1;
+        return g ? g[t] : (int)(((int64_t)(t + 1) * L) / T);
+    };
+    auto row_at = [&](int u, int c) -> QRow {
+        QRow r;
+        r.base = full ? 0 : c - B - 1;
+        int bm = r.base % W;
+        r.bm = bm < 0 ? bm + W : bm;
+        r.lo = B >= 1 ? max(0, c - B) : 0;
+        r.hi = B >= 1 ? min(L, c + B) : L;
+        if (u == 0) r.lo = r.hi = 0;
+        return r;
+    };
+    auto k_of = [&](int rx, const QRow& r) -> int { int x = rx - r.bm; x += (x < 0) ? W : 0; return r.base + x; };
+    auto adm = [&](int k, const QRow& r) -> bool { return k >= r.lo && k <= r.hi; };
+    // s[k-2] | s[k-1] << 4 | s[k] << 8 (15: there is none), qual_kernel's pack_of without its cache: three byte loads
+    auto pack_at = [&](int k) -> int {
+        int v = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int q = k - 2 + j;
+            const bool in = q >= 0 && q < L;
+            const int c = q_code(a.alphabet, A, lab[in ? q : 0]) & 3;
+            v |= (in ? c : 15) << (4 * j);
+        }
+        return v;
+    };
+    auto load_y = [&](int t, double (&ye)[4], double& yb) {
+        t = t < 0 ? 0 : (t < T ? t : T - 1);
+        const double* yr = y + (int64_t)t * C;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) ye[b] = b < A ? yr[b] : NINF;
+        yb = yr[A];
+    };
+    auto ysel = [&](const double (&ye)[4], int c) -> double { return c == 0 ? ye[0] : (c == 1 ? ye[1] : (c == 2 ? ye[2] : ye[3])); };
+
+    constexpr int nb = MERGE ? 2 : 1, nbx = nb - 1;
+    double* beta = a.beta + d.beta_off;          // row u: beta[(u * nb + which) * W + ridx]
+
+    // ---- pass 1: backward ----
+    double pB, pX = NINF;   // row u + 1 at this lane's ring index
+    {
+        QRow rn = row_at(T, centre(T));
+        {
+            const int k = k_of(ridx, rn);
+            pB = (k == L && adm(k, rn)) ? 0.0 : NINF;
+            if (MERGE) pX = pB;
+            if (act) {
+                beta[((int64_t)T * nb) * W + ridx] = pB;
+                if (MERGE) beta[((int64_t)T * nb + 1) * W + ridx] = pB;
+            }
+        }
+        QRow r = row_at(T - 1, centre(T - 1));
+        int cm = centre(T - 2);            // the centre of row u - 1, a step before its row is made
+        int pk = pack_at(k_of(ridx, r));
+        double ye[4], yb;
+        load_y(T - 1, ye, yb);
+        for (int u = T - 1; u >= 0; --u) {
+            const QRow rm = row_at(u - 1 > 0 ? u - 1 : 0, cm);   // (u == 0: not used)
+            const int cmm = centre(u - 2 > 0 ? u - 2 : 0);
+            const int pkm = pack_at(k_of(ridx, rm));
+            double yem[4], ybm;
+            load_y(u - 1, yem, ybm);
+            const int k = k_of(ridx, r);
+            const bool in = adm(k, r);
+            const int c0 = (pk >> 8) & 15, c1 = (pk >> 4) & 15;   // s[k], s[k-1]
+            const bool same = k_of(ridx, rn) == k, right = k_of(ru, rn) == k + 1 && k < L;
+            const double upB = __shfl(pB, ru);
+            double vB = NINF, vX = NINF;
+            if (!MERGE) {
+                const double stay = same ? pB + yb : NINF;
+                const double emit = right ? upB + ysel(ye, c0) : NINF;
+                const double v = q_lae(stay, emit);
+                vB = in ? v : NINF;
+            } else {
+                const double upX = __shfl(pX, ru);
+                const double toB = same ? pB + yb : NINF;
+                const double nxt = right ? upX + ysel(ye, c0) : NINF;
+                const double v = q_lae(toB, nxt);
+                vB = (in && (k > 0 || u == 0)) ? v : NINF;
+                const double rep = same ? pX + ysel(ye, c1) : NINF;
+                const bool dif = k < L && c0 != c1;
+                const double x = q_lae(q_lae(toB, rep), dif ? nxt : NINF);
+                vX = (in && k > 0) ? x : NINF;
+            }
+            if (act) {
+                beta[((int64_t)u * nb) * W + ridx] = vB;
+                if (MERGE) beta[((int64_t)u * nb + 1) * W + ridx] = vX;
+            }
+            pB = vB;
+            pX = vX;
+            rn = r;
+            r = rm;
+            cm = cmm;
+            pk = pkm;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) ye[b] = yem[b];
+            yb = ybm;
+        }
+    }
+    __syncthreads();   // the stored rows are read back by other lanes than wrote them: once, between the passes
+    // F = beta(0, 0), if row 0 holds state 0 (pB is row 0 now)
+    const QRow rz = row_at(0, centre(0));
+    double F = NINF;
+    {
+        const int x = -rz.base;   // state 0's offset in the window
+        int rx = rz.bm + (x >= 0 && x < W ? x : 0);
+        rx -= rx >= W ? W : 0;
+        const double f = __shfl(pB, rx);
+        if (x >= 0 && x < W) F = f;
+    }
+    if (!(F > NINF)) {
+        if (lane == 0) { a.status[i] = PO_E_ENVELOPE; a.logp[i] = NINF; }
+        return;
+    }
+    if (lane == 0) { a.status[i] = PO_OK; a.logp[i] = F; }
+
+    // ---- pass 2: forward, joins ----
+    double acc[5], run[4];
+    auto flush = [&](int p) {   // position p's accumulators leave this lane
+        if (!act || p < 0 || p >= L) return;
+        const int own = q_code(a.alphabet, A, lab[p]) & 3;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) odds[(int64_t)p * 5 + b] = (b == own) ? 0.0 : (b < A ? acc[b] - F : NINF);
+        odds[(int64_t)p * 5 + 4] = acc[4] - F;
+    };
+    QRow rp = rz;
+    double aB = k_of(ridx, rp) == 0 ? 0.0 : NINF, aX = NINF;   // row t at this lane's ring index
+#pragma unroll
+    for (int b = 0; b < 5; ++b) acc[b] = NINF;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) run[b] = NINF;
+    QRow rn = row_at(1, centre(1));
+    int cnn = centre(2);                 // the centre of row t + 2, a step before its row is made
+    int pk = pack_at(k_of(ridx, rn));
+    double ye[4], yb;
+    load_y(0, ye, yb);
+    double pf_own = beta[((int64_t)1 * nb) * W + ridx];          // row t + 1 at this ring index, and its upper neighbour's
+    double pf_nb = beta[((int64_t)1 * nb + nbx) * W + ru];      // (merge: label state)
+    for (int t = 0; t < T; ++t) {
+        const int un = t + 2 < T ? t + 2 : T;                     // (the last step: row T again, not used)
+        const QRow rnn = row_at(un, cnn);
+        const int cnnn = centre(t + 3);
+        const int pkn = pack_at(k_of(ridx, rnn));
+        double yen[4], ybn;
+        load_y(t + 1, yen, ybn);
+        const double nx_own = beta[((int64_t)un * nb) * W + ridx];
+        const double nx_nb = beta[((int64_t)un * nb + nbx) * W + ru];
+        const int kn = k_of(ridx, rn), ko = k_of(ridx, rp);
+        const bool same = ko == kn, left = k_of(rl, rp) == kn - 1, right = k_of(ru, rn) == kn + 1;
+        if (!same) {
+            flush(ko - 1);
+#pragma unroll
+            for (int b = 0; b < 5; ++b) acc[b] = NINF;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) run[b] = NINF;
+        }
+        const int p = kn - 1;
+        const bool here = adm(kn, rn);
+        const bool pos = p >= 0 && p < L;
+        const int pq = pos ? pk : 0xfff;
+        const int c0 = (pq >> 8) & 15, c2 = pq & 15;
+        const int cn = c0 == 15 ? -1 : c0;         // s[p+1]
+        const int cq = c2 == 15 ? -1 : c2;         // s[p-1]
+        const int cs = pos ? ((pq >> 4) & 15) : 0;   // s[p] = the base that enters state kn
+        const double b_own = pf_own, b_nb = pf_nb;
+        const double lB = __shfl(aB, rl);
+        double nB = NINF, nX = NINF;
+        if (!MERGE) {
+            const double a_same = same ? aB : NINF;
+            const double a_left = left ? lB : NINF;
+            const bool add = pos && a_left > NINF;
+            const double gsub = a_left + b_own;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const double v = q_lae(acc[b], gsub + ye[b]);
+                acc[b] = (add && b < A) ? v : acc[b];
+            }
+            const double dv = q_lae(acc[4], a_left + ysel(ye, cn) + b_nb);
+            acc[4] = (add && cn >= 0 && right) ? dv : acc[4];
+            const double v = q_lae(a_same + yb, pos ? a_left + ysel(ye, cs) : NINF);
+            nB = here ? v : NINF;
+        } else {
+            const double lX = __shfl(aX, rl);
+            const double aB_same = same ? aB : NINF, aX_same = same ? aX : NINF;
+            const double aB_left = left ? lB : NINF, aX_left = left ? lX : NINF;
+            const double bXr = right ? b_nb : NINF;
+            const double Pb = yb + b_own;
+            const double Qn = cn >= 0 ? ysel(ye, cn) + bXr : NINF;
+            const double PQ = q_lae(Pb, Qn);
+            const double e0 = aB_left, e1 = q_lae(aB_left, aX_left);
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const double r = run[b];
+                const double v = q_lae(acc[b], r + (b == cn ? Pb : PQ));
+                acc[b] = (pos && b < A && r > NINF) ? v : acc[b];
+                const double w = q_lae(r, b == cq ? e0 : e1) + ye[b];
+                run[b] = (pos && b < A) ? (here ? w : NINF) : r;
+            }
+            const double dv = q_lae(acc[4], (cq == cn ? e0 : e1) + ysel(ye, cn) + bXr);
+            acc[4] = (pos && cn >= 0) ? dv : acc[4];
+            // the blank state of position 0 exists in row 0 only (the tree's root)
+            const double vb = q_lae(aB_same, aX_same) + yb;
+            nB = (here && kn > 0) ? vb : NINF;
+            const double vx = q_lae(q_lae(aX_same, aB_left), (cq >= 0 && cq != cs) ? aX_left : NINF) + ysel(ye, cs);
+            nX = (here && pos) ? vx : NINF;
+        }
+        aB = nB;
+        aX = nX;
+        rp = rn;
+        rn = rnn;
+        cnn = cnnn;
+        pk = pkn;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) ye[b] = yen[b];
+        yb = ybn;
+        pf_own = nx_own;
+        pf_nb = nx_nb;
+    }
+    // row T: the substitution run and the deletion of the last position end with the read
+    {
+        const int k = k_of(ridx, rp);
+        const int p = k - 1;
+        const bool left = k_of(rl, rp) == p;
+        const double lB = __shfl(aB, rl);
+        const double lX = MERGE ? __shfl(aX, rl) : NINF;
+        if (p == L - 1) {
+            if (!MERGE) {
+                acc[4] = left ? lB : NINF;
+            } else {
+                acc[4] = left ? q_lae(lB, lX) : NINF;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) acc[b] = q_lae(acc[b], run[b]);
+            }
+        }
+        flush(p);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------------------ host
 namespace {
 
@@ -402,9 +695,34 @@ size_t po_qual_workspace_bytes(int n, int64_t total_rows, int64_t max_rows, int6
     return al256((size_t)beta + 8) + al256((size_t)st + 8) + al256(sizeof(QDesc) * (size_t)n) + 256;
 }
 
+// which route the entries on resident tables (po_fastq_tables, po_pair_qual) pass: process-wide like po_set_align_route.
+// PO_QUAL_ROUTE_AUTO is the default; PO_QUAL_ROUTE_REG is for the tests and the bench
+static std::atomic<int> g_qual_route{PO_QUAL_ROUTE_AUTO};
+static std::atomic<long long> g_qual_reg_reads{0};
+int po_set_qual_route(int route) {
+    if (route != PO_QUAL_ROUTE_GENERAL && route != PO_QUAL_ROUTE_AUTO && route != PO_QUAL_ROUTE_REG)
+        return po_fail(PO_E_ARG, "po_set_qual_route: route " + std::to_string(route));
+    g_qual_route.store(route);
+    return PO_OK;
+}
+int po_qual_entry_route() { return g_qual_route.load(); }
+long long po_debug_qual_reg_reads(int reset) {
+    return reset ? g_qual_reg_reads.exchange(0) : g_qual_reg_reads.load();
+}
+
 int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
                   const int64_t* label_off, const int32_t* guide, int band_size, double* odds, double* logp,
                   int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+    return po_qual_batch_route(y, y_off, n, C, alphabet, model, labels, label_off, guide, band_size, odds, logp, status, ws, ws_bytes,
+                               stream, PO_QUAL_ROUTE_GENERAL);
+}
+
+// po_qual_batch with the choice of kernel.  PO_QUAL_ROUTE_GENERAL launches what po_qual_batch always launched, and so does
+// PO_QUAL_ROUTE_AUTO: no instantiation of qual_reg_kernel is on the automatic route (both read spilled scalar
+// registers back inside their frame loops).  PO_QUAL_ROUTE_REG sends the reads whose ring holds at most 64 indices to it
+int po_qual_batch_route(const double* y, const int64_t* y_off, int n, int C, const char* alphabet, int model, const char* labels,
+                        const int64_t* label_off, const int32_t* guide, int band_size, double* odds, double* logp,
+                        int32_t* status, void* ws, size_t ws_bytes, void* stream, int route) {
     po_set_error("");
     if (model == PO_MODEL_FLIPFLOP) return po_fail(PO_E_UNSUPPORTED, "po_qual_batch: the flip-flop model has no quality lattice");
     if (model != PO_MODEL_CTC && model != PO_MODEL_MERGE) return po_fail(PO_E_ARG, "po_qual_batch: unknown model");
@@ -428,7 +746,8 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
     const int per = q_per_state(model), nb = q_nb(model);
     // launch classes: state in LDS of at most 4, 16, 48 KiB, state in the workspace — a read's dynamic LDS is its class's
     // largest, so one wide read does not take the occupancy of the narrow ones launched with it
-    constexpr int NCLS = 4;
+    // (and, on PO_QUAL_ROUTE_REG, a fifth behind them: a ring of at most 64 indices, state in registers, no LDS)
+    constexpr int NCLS = 4, REG = NCLS;
     const int64_t cls_cap[NCLS - 1] = {512, 2048, QL_LDS_MAX};
     int64_t nbeta = 0, nst = 0, lds[NCLS] = {0, 0, 0, 0};
     std::vector<int> cls((size_t)n);
@@ -443,7 +762,10 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
         nbeta += (T + 1) * w * nb;
         d.read = i;
         d.pad = 0;
-        if (w * per <= QL_LDS_MAX) {
+        if (route == PO_QUAL_ROUTE_REG && w <= 64) {
+            d.st_off = -1;
+            cls[i] = REG;
+        } else if (w * per <= QL_LDS_MAX) {
             d.st_off = -1;
             int c = 0;
             while (w * per > cls_cap[c]) ++c;
@@ -457,8 +779,8 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
     }
     std::vector<QDesc> sorted;
     sorted.reserve((size_t)n);
-    int first[NCLS + 1] = {0, 0, 0, 0, 0};
-    for (int c = 0; c < NCLS; ++c) {
+    int first[NCLS + 2] = {0, 0, 0, 0, 0, 0};
+    for (int c = 0; c <= NCLS; ++c) {
         for (int i = 0; i < n; ++i)
             if (cls[i] == c) sorted.push_back(desc[i]);
         first[c + 1] = (int)sorted.size();
@@ -474,6 +796,12 @@ int po_qual_batch(const double* y, const int64_t* y_off, int n, int C, const cha
         if (first[c + 1] == first[c]) continue;
         a.first = first[c];
         hipLaunchKernelGGL(qual_kernel, dim3(first[c + 1] - first[c]), dim3(64), (size_t)lds[c] * 8, s, a);
+    }
+    if (first[REG + 1] > first[REG]) {
+        g_qual_reg_reads += first[REG + 1] - first[REG];
+        a.first = first[REG];
+        if (a.merge) hipLaunchKernelGGL(qual_reg_kernel<true>, dim3(first[REG + 1] - first[REG]), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL(qual_reg_kernel<false>, dim3(first[REG + 1] - first[REG]), dim3(64), 0, s, a);
     }
     PO_HIPCHK(hipGetLastError());
     return PO_OK;

@@ -17,6 +17,15 @@ offset tables back where include/poreover_hip.h says so.  The size of the packed
 the copy takes the share of the buffer that the previous call's text needed, with a margin, and the rare call whose text is
 longer fetches the rest with a second copy and synchronise.)
 
+qualities=True (viterbi, beam_search, pair_decode) runs the quality stages behind the decode, after its one
+synchronise, on the same stream and on the decode's string buffers and Tables.y where they lie: nothing is uploaded again.  The
+quality entries (po_fastq_tables, po_pair_qual) are not enqueue-only: they read the offset tables and the per-read lengths back
+and synchronise the stream before they return; the characters then come down as the strings do (po_pack_strings, one more
+synchronise).  Their intermediate buffers — frame maps, guides, consumed counts, the aligner's rows, labels, lattice rows —
+are allocated with hipMalloc for the length of the call, outside torch's allocator; the outputs are torch tensors.  A read or
+item whose banded lattice is lost costs one more such call, in which the lattice runs on that item alone; the stages in front
+of the lattice (the second Viterbi call, modes and guides of a beam search's or a pair's retry) still run over the whole batch.
+
 The first workspace query of a process that selects the register-state pair kernel makes that kernel's multi-GB slice pool with
 hipMalloc, outside torch's allocator: _lib.reg_pool_prewarm / _lib.reg_pool_release (po_reg_pool_prewarm / po_reg_pool_release)
 are the handles.
@@ -30,6 +39,7 @@ import torch
 
 from . import _lib as L
 from . import _marshal as M
+from . import quality as Q
 
 __all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss"]
 
@@ -263,7 +273,8 @@ def _to_host(t):
     return h
 
 
-def _decode_1d(tables, entry, return_map=False, beam_width=0):
+def _decode_1d(tables, entry, return_map=False, beam_width=0, keep=None):
+    """keep: a dict that receives the decode's device buffers (seq, lens, st, mp): what the quality stages read"""
     lib = L.load()
     n, Cc, dev = tables.n, tables.C, tables.device
     rows = int(tables.off_h[-1])
@@ -272,12 +283,13 @@ def _decode_1d(tables, entry, return_map=False, beam_width=0):
         stream = torch.cuda.current_stream(dev)
         seq = torch.empty(max(rows, 1), dtype=torch.uint8, device=dev)
         lens, st = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
-        mp = torch.zeros(max(rows, 1), dtype=torch.int32, device=dev) if return_map else None
+        with_map = return_map or (keep is not None and entry == "viterbi")   # (the quality stages read the map on the device)
+        mp = torch.zeros(max(rows, 1), dtype=torch.int32, device=dev) if with_map else None
         if entry == "viterbi":
             wsb = lib.po_viterbi_workspace_bytes(n, rows, Cc, L.KINDS[tables.kind])
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             L.check(lib.po_viterbi_batch(tables.y.data_ptr(), tables.off.data_ptr(), n, Cc, b"ACGT", L.KINDS[tables.kind], None,
-                                         seq.data_ptr(), tables.off.data_ptr(), lens.data_ptr(), mp.data_ptr() if return_map else None,
+                                         seq.data_ptr(), tables.off.data_ptr(), lens.data_ptr(), mp.data_ptr() if with_map else None,
                                          st.data_ptr(), ws.data_ptr(), wsb, stream.cuda_stream), "po_viterbi_batch")
         else:
             wsb = lib.po_beam1d_workspace_bytes(n, rows, int(np.diff(tables.off_h).max()), Cc, int(beam_width), model)
@@ -290,42 +302,133 @@ def _decode_1d(tables, entry, return_map=False, beam_width=0):
         lens_h, st_h = _to_host(lens), _to_host(st)
         mp_h = _to_host(mp) if return_map else None
         stream.synchronize()
+    if keep is not None:
+        keep.update(seq=seq, lens=lens, st=st, mp=mp)
     return text, lens_h.numpy(), st_h.numpy(), (mp_h.numpy() if return_map else None)
 
 
-def viterbi(tables, return_map=False):
-    """batch.viterbi_batch on resident tables: the sequences, and with return_map (sequences, maps, status)"""
+def _check_qualities(who, tables, qual_band):
+    """the argument checks of qualities=True, none of which needs a device; the device check last.  Returns the band."""
+    Q.refuse_flipflop(tables.kind, "%s(qualities=True)" % who)
+    band = Q.check_band("tensors." + who, qual_band)
+    _check_device(tables.y, "tables")
+    return band
+
+
+def _qual_1d(tables, keep, lens_h, scored_is_viterbi, band, details):
+    """Per-base qualities of a 1-D decode whose strings are still on the device (po_fastq_tables), on the
+    decode's stream: (the chr(33 + Q) strings, int32 status).  A read whose banded lattice is lost is scored once more
+    without a band (quality.retry_unbanded): the retry call flags it in unbanded_h and sees the other reads with length 0, so
+    its lattice scores that read alone (the second Viterbi call and the guide stages of a beam search's retry still run over
+    all reads).  details (a dict or None) receives odds (per read float64 (L, 5), after the retry), guides (the first
+    call's int32 guides; None without a band) and retried."""
+    lib = L.load()
+    n, dev = tables.n, tables.device
+    rows = int(tables.off_h[-1])
+    model, kind = L.MODELS[L.MODEL_OF_KIND[tables.kind]], L.KINDS[tables.kind]
+    ln = np.maximum(lens_h[:n], 0).astype(np.int64)
+    guides = {}
+
+    def run(keys, band_):
+        first = len(keys) == n and band_ == band
+        flags = None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            lens_d, lk = keep["lens"], ln
+            if not first:   # the retry: the flagged reads without a band, nothing of the others
+                flags = np.zeros(n, dtype=np.int32)
+                flags[list(keys)] = 1
+                lens_d = torch.where(torch.from_numpy(flags).to(dev) != 0, keep["lens"], torch.zeros_like(keep["lens"]))
+                lk = np.where(flags != 0, ln, 0)
+            qual = torch.empty(max(rows, 1), dtype=torch.uint8, device=dev)
+            qst = torch.zeros(n, dtype=torch.int32, device=dev)
+            odds = torch.empty((max(int(lk.sum()), 1), 5), dtype=torch.float64, device=dev) if details is not None else None
+            gd = torch.zeros(max(rows, 1), dtype=torch.int32, device=dev) if details is not None and first and band > 0 else None
+            L.check(lib.po_fastq_tables(tables.y.data_ptr(), tables.off.data_ptr(), n, tables.C, model, kind, keep["seq"].data_ptr(),
+                                        tables.off.data_ptr(), lens_d.data_ptr(), keep["st"].data_ptr(),
+                                        keep["mp"].data_ptr() if scored_is_viterbi else None, 1 if scored_is_viterbi else 0,
+                                        max(int(band), 0), M.ptr(flags), qual.data_ptr(), qst.data_ptr(),
+                                        odds.data_ptr() if odds is not None else None, gd.data_ptr() if gd is not None else None,
+                                        stream.cuda_stream), "po_fastq_tables")
+            text = _Text(lib, "qual_1d", qual[:rows], tables.off, lens_d, None, n, stream)
+            qst_h = _to_host(qst)
+            odds_h = _to_host(odds) if odds is not None else None
+            gd_h = _to_host(gd) if gd is not None else None
+            stream.synchronize()
+        buf, off = text.arrays()
+        strs = M.strings(buf, off, lk)
+        if gd_h is not None:
+            o = tables.off_h
+            guides.update({i: gd_h.numpy()[o[i]:o[i + 1]].copy() for i in range(n)})
+        at = M.offsets(lk)   # (dense: without flags every read in order; in the retry the flagged reads alone)
+        return {k: ((strs[k], odds_h.numpy()[at[k]:at[k + 1]].copy() if odds_h is not None else None), int(qst_h.numpy()[k]))
+                for k in keys}
+
+    got, retried = Q.retry_unbanded(run, range(n), band)
+    status = np.array([got[i][1] for i in range(n)], dtype=np.int32)
+    Q.warn_unscored_reads(dict(enumerate(status)))
+    if details is not None:
+        details.update(odds=[got[i][0][1] for i in range(n)], guides=[guides[i] for i in range(n)] if guides else None,
+                       retried=retried)
+    return [got[i][0][0] for i in range(n)], status
+
+
+def viterbi(tables, return_map=False, qualities=False, qual_band=Q.DEFAULT_BAND, qual_details=None):
+    """batch.viterbi_batch on resident tables: the sequences, and with return_map (sequences, maps, status).
+    qualities=True adds per-base qualities: (sequences, quals, qual_status), with return_map (sequences, maps,
+    status, quals, qual_status) — quals the FASTQ strings chr(33 + Q), qual_status int32 per read, 0 where the read is scored
+    (any other read has Q 0 throughout and a line in the log).  The decode is its own frame map's Viterbi call, so the
+    quality stages run without a second one.  qual_band: quality.DEFAULT_BAND; <= 0: no band.  qual_details is a diagnostic hook
+    (the tests' and the bench script's): a dict that receives odds, guides and retried (_qual_1d), at the cost of copying them."""
     _check_tables(tables)
+    band = _check_qualities("viterbi", tables, qual_band) if qualities else None
     if tables.n == 0:
-        return ([], [], np.zeros(0, np.int32)) if return_map else []
-    text, lens, st, mp = _decode_1d(tables, "viterbi", return_map)
-    M.raise_on_status(st, tables.n, "viterbi decode of read", allowed=(L.E_ARG,) if return_map else ())
+        out = ([], [], np.zeros(0, np.int32)) if return_map else ([],)
+        if qualities:
+            out += ([], np.zeros(0, np.int32))
+        return out if return_map or qualities else []
+    keep = {} if qualities else None
+    text, lens, st, mp = _decode_1d(tables, "viterbi", return_map, keep=keep)
+    M.raise_on_status(st, tables.n, "viterbi decode of read", allowed=(L.E_ARG,) if return_map or qualities else ())
     buf, off = text.arrays()
     seqs = M.strings(buf, off, lens)
+    tail = _qual_1d(tables, keep, lens, True, band, qual_details) if qualities else ()
     if not return_map:
-        return seqs
+        return (seqs,) + tuple(tail) if qualities else seqs
     o = tables.off_h
-    return seqs, [mp[o[i]:o[i] + lens[i]].astype(np.int64) for i in range(tables.n)], st[:tables.n].copy()
+    return (seqs, [mp[o[i]:o[i] + lens[i]].astype(np.int64) for i in range(tables.n)], st[:tables.n].copy()) + tuple(tail)
 
 
-def beam_search(tables, beam_width=25):
-    """batch.beam_search_batch on resident tables (the tree model is the kind's)"""
+def beam_search(tables, beam_width=25, qualities=False, qual_band=Q.DEFAULT_BAND, qual_details=None):
+    """batch.beam_search_batch on resident tables (the tree model is the kind's).  qualities=True: (sequences, quals,
+    qual_status) as for viterbi; the guides come from a second, cheap Viterbi call with its frame map, aligned to the beam
+    search's strings where they differ (quality.call_guides' rule, on the device).  qual_details: viterbi's diagnostic hook."""
     _check_tables(tables)
+    band = _check_qualities("beam_search", tables, qual_band) if qualities else None
     if tables.n == 0:
-        return []
-    text, lens, st, _ = _decode_1d(tables, "beam", beam_width=beam_width)
+        return ([], [], np.zeros(0, np.int32)) if qualities else []
+    keep = {} if qualities else None
+    text, lens, st, _ = _decode_1d(tables, "beam", beam_width=beam_width, keep=keep)
     M.raise_on_status(st, tables.n, "beam search of read")
     buf, off = text.arrays()
-    return M.strings(buf, off, lens)
+    seqs = M.strings(buf, off, lens)
+    if not qualities:
+        return seqs
+    return (seqs,) + tuple(_qual_1d(tables, keep, lens, False, band, qual_details))
 
 
 def pair_decode(tables1, tables2, beam_width=5, method="row_col", padding=5, alignment="banded", diagonal_envelope=False,
-                diagonal_width=50, envelope=False, stats=None):
+                diagonal_width=50, envelope=False, stats=None, qualities=False, qual_band=Q.DEFAULT_BAND, odds=False):
     """batch.pair_decode_batch (single="viterbi") on resident tables: its records, the envelope (None unless envelope=True: it is
     as large as the tables' rows, and is neither written nor copied otherwise).  Both tables are of one n, kind and device.
     stats: a dict that receives the bytes of text (text_bytes), of text copied (copied_bytes) and of the text buffers
     (capacity_bytes), and the device milliseconds of the engine call, the compaction and the copies (decode_ms, pack_ms, copy_ms:
-    events on the stream, read after the synchronise)."""
+    events on the stream, read after the synchronise).
+    qualities=True: every record of a decoded pair also gets qual1, qual2 (None where the record has no 1-D call), qual and
+    qual_status (four ints) — quality.pair_fields' fields, what pair_basecall_signals(qualities=True) returns and
+    pair_basecall.write_pair_fastq writes — from po_pair_qual on the decode's device buffers; an item whose
+    banded lattice is lost is scored once more without a band (quality.pair_retry).  odds=True, a diagnostic option as in
+    pair_basecall_signals, adds odds1, odds2, odds_cons1, odds_cons2, float64 (L, 5), each copied down item by item."""
     _check_tables(tables1, "tables1")
     _check_tables(tables2, "tables2")
     if tables1.n != tables2.n:
@@ -337,6 +440,9 @@ def pair_decode(tables1, tables2, beam_width=5, method="row_col", padding=5, ali
     if method not in L.METHODS:
         raise ValueError("method %r (one of %s)" % (method, ", ".join(L.METHODS)))
     n, Cc, dev = tables1.n, tables1.C, tables1.device
+    if odds and not qualities:
+        raise ValueError("pair_decode: odds is an option of qualities=True")
+    band = _check_qualities("pair_decode", tables1, qual_band) if qualities else None
     if n == 0:
         return []
     lib = L.load()
@@ -391,7 +497,65 @@ def pair_decode(tables1, tables2, beam_width=5, method="row_col", padding=5, ali
     out = []
     M.pair_records(out, b1, o1, b, o, l12n[0], l12n[1], lens_h.numpy(), st_h.numpy(), ident_h.numpy(),
                    env_h.numpy() if envelope else None, tables1.off_h)(0, n)
+    if qualities:
+        dec = dict(seq1d=seq1d, s1o=d_s1o, l12=l12, len1d=len1d, seq=seq, so=d_so, lens=lens, st=st, s1o_h=s1o, so_h=so)
+        for r, f in zip(out, _qual_pairs(tables1, tables2, out, dec, band, odds)):
+            if f is not None:
+                r.update(f)
     return out
+
+
+def _qual_pairs(tables1, tables2, records, dec, band, odds):
+    """quality.pair_fields' dicts for the records of a pair decode whose strings are still on the device (po_pair_qual), on
+    the decode's stream.  The retry call (quality.pair_retry) flags the lost items in unbanded_h and sees every other pair
+    as not decoded, so that nothing of theirs is scored twice."""
+    lib = L.load()
+    n, dev = tables1.n, tables1.device
+    model = L.MODELS[L.MODEL_OF_KIND[tables1.kind]]
+    s1o, so = dec["s1o_h"], dec["so_h"]
+
+    def run(which, flags):
+        recs = records
+        ub, st_d = None, dec["st"]
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            if flags is not None:
+                ub = np.zeros((n, 4), dtype=np.int32)
+                ub[which] = np.asarray(flags, dtype=np.int32).reshape(-1, 4)
+                take = np.zeros(n, dtype=bool)
+                take[which] = True
+                st_d = torch.where(torch.from_numpy(take).to(dev), dec["st"], torch.ones_like(dec["st"]))
+                recs = [r if t else {"status": 1} for r, t in zip(records, take)]
+            qual1d = torch.empty(max(int(s1o[-1]), 1), dtype=torch.uint8, device=dev)
+            qual = torch.empty(max(int(so[-1]), 1), dtype=torch.uint8, device=dev)
+            qst = torch.zeros(4 * n, dtype=torch.int32, device=dev)
+            od1 = torch.zeros((max(int(s1o[-1]), 1), 5), dtype=torch.float64, device=dev) if odds else None
+            odc = torch.zeros((2, max(int(so[-1]), 1), 5), dtype=torch.float64, device=dev) if odds else None
+            L.check(lib.po_pair_qual(tables1.y.data_ptr(), tables1.off.data_ptr(), tables2.y.data_ptr(), tables2.off.data_ptr(), n, model,
+                                     dec["seq1d"].data_ptr(), dec["s1o"].data_ptr(), dec["l12"][0].data_ptr(), dec["l12"][1].data_ptr(),
+                                     dec["seq"].data_ptr(), dec["so"].data_ptr(), dec["lens"].data_ptr(), st_d.data_ptr(),
+                                     max(int(band), 0), M.ptr(ub), qual1d.data_ptr(), qual.data_ptr(), qst.data_ptr(),
+                                     od1.data_ptr() if odds else None, odc.data_ptr() if odds else None, None, stream.cuda_stream),
+                    "po_pair_qual")
+            text1d = _Text(lib, "pair_qual_1d", qual1d[:int(s1o[-1])], dec["s1o"], dec["len1d"], None, 2 * n, stream)
+            text = _Text(lib, "pair_qual", qual[:int(so[-1])], dec["so"], dec["lens"], st_d, n, stream)
+            qst_h = _to_host(qst)
+            od1_h, odc_h = (_to_host(od1), _to_host(odc)) if odds else (None, None)
+            stream.synchronize()
+        b1, o1 = text1d.arrays()
+        b, o = text.arrays()
+        fields = Q.pair_fields(recs, o1, o, b1, b, qst_h.numpy())   # (the packed characters at the packed offsets)
+        if odds:   # (the odds lie at the strings' own offsets)
+            a1, ac = od1_h.numpy(), odc_h.numpy()
+            for i, (r, f) in enumerate(zip(recs, fields)):
+                if f is not None:
+                    b1_, b2_, b_ = int(s1o[2 * i]), int(s1o[2 * i + 1]), int(so[i])
+                    l1, l2, ln = len(r["seq1"]), len(r["seq2"]), len(r["consensus"])
+                    f["odds1"], f["odds2"] = a1[b1_:b1_ + l1].copy(), a1[b2_:b2_ + l2].copy()
+                    f["odds_cons1"], f["odds_cons2"] = ac[0, b_:b_ + ln].copy(), ac[1, b_:b_ + ln].copy()
+        return [records[i] for i in which], [fields[i] for i in which]
+
+    return Q.pair_retry(run, n, band, "tensors.pair_decode", check_strings=False)[1]
 
 
 # --------------------------------------------------------------------------------------------------------------- training
