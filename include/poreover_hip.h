@@ -244,6 +244,44 @@ int po_ctc_loss_h(const void* src_h, int64_t src_elems, const int64_t* item_off_
                   const int* perm_h, const int32_t* labels_h, const int64_t* label_off_h, int model, float* loss_h,
                   int32_t* status_h, void* grad_h, int grad_dtype);
 
+/* ---- CTC forced alignment on tensors where they lie (po_falign.hip) ----------------------------------------
+ * Where in time a known sequence sits: the best path of po_ctc_loss's lattice.  Items, dtypes, normalize, perm_h, labels and
+ * model are po_ctc_loss's (f64 with normalize = 0 only; blank is canonical column C-1); lp = log_softmax(x) per frame in
+ * float64.  States 0 .. 2L (even: blank, odd 2k+1: symbol k); V_0(s) = lp[0][col(s)] for s < 2, -inf otherwise;
+ * V_t(s) = max over the admitted predecessors {s, s-1, s-2} of V_{t-1} + lp[t][col(s)], float64, one addition per frame in
+ * frame order.  TIES GO TO THE LARGER PREDECESSOR STATE (stay before step before skip), and to state 2L over 2L-1 at the end:
+ * the outputs are a function of the input alone and a numpy restatement gives the same bits.
+ *   score[i]   = max(V_{T-1}(2L), V_{T-1}(2L-1)), float64
+ *   states     (or NULL) int32, row i at states + i * states_stride: the best path's state in frames t < T_i, -1 in frames
+ *              T_i <= t < states_stride (written here: the caller may pass uninitialised memory)
+ *   starts, stops (or NULL) int32 [total labels] at label_off[i]: the first frame of symbol k's label state and one past its
+ *              last (PO_MODEL_CTC: stops = starts + 1)
+ *   status[i]  (or NULL): 0; PO_E_ENVELOPE: no path of finite score (L > T; merge: L + adjacent equal labels > T; or the best
+ *              score is -inf): score -inf, path outputs -1; PO_E_ARG: a label outside [0, C-2] or offsets that decrease: score
+ *              NaN, path outputs -1; PO_E_UNSUPPORTED / PO_E_CAP: a label longer than PO_CTC_MAX_LABEL / than max_states
+ *              admits, an item with more frames than states_stride, or bit rows that do not fit total_words: score NaN, path
+ *              outputs -1.  T = 0 with L = 0: score 0, status 0.  The entry is not told how many values starts and stops hold:
+ *              label_off is the caller's word for that, and an item whose label_off entries decrease or span more than
+ *              PO_CTC_MAX_LABEL symbols has its states row set to -1 and its starts / stops left untouched.
+ * The caller passes total_rows = row_off[n], total_words = sum T_i * ceil((2 L_i + 1) / 64) (the trace-back keeps two bits
+ * per cell, 16 bytes per 64 states of a frame) and max_states = max 2 L_i + 1.  Enqueue-only on `stream`: the entry reads no
+ * device memory and does not synchronise.
+ * Before any launch: PO_E_UNSUPPORTED for PO_MODEL_FLIPFLOP, f64 with normalize, max_states > 2 * PO_CTC_MAX_LABEL + 1 (the
+ * lattice rows are kept in LDS); PO_E_ARG for C outside 2..8, negative sizes, an unknown dtype, a perm that is no
+ * permutation, null pointers with n > 0, states with a states_stride that cannot hold the longest item (it has
+ * ceil(total_rows / n) frames at least), ws_bytes < po_forced_align_workspace_bytes(...).  n == 0: PO_OK. */
+size_t po_forced_align_workspace_bytes(int n, int64_t total_rows, int64_t total_words, int C);
+int po_forced_align(const po_ingest_item* items, const int64_t* row_off, int n, int C, int dtype, int normalize,
+                    const int* perm_h, const int32_t* labels, const int64_t* label_off, int model, int64_t total_rows,
+                    int64_t total_words, int max_states, double* score, int32_t* states, int64_t states_stride, int32_t* starts,
+                    int32_t* stops, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+/* host twin: the source as po_ctc_loss_h takes it; states_h (or NULL): n rows of states_stride, which must hold the longest
+ * item (PO_E_ARG naming both otherwise); starts_h / stops_h (or NULL): label_off_h[n] - label_off_h[0] values */
+int po_forced_align_h(const void* src_h, int64_t src_elems, const int64_t* item_off_h, const int64_t* row_stride_h,
+                      const int64_t* col_stride_h, const int64_t* row_off_h, int n, int C, int dtype, int normalize,
+                      const int* perm_h, const int32_t* labels_h, const int64_t* label_off_h, int model, double* score_h,
+                      int32_t* states_h, int64_t states_stride, int32_t* starts_h, int32_t* stops_h, int32_t* status_h);
+
 /* ---- transducer.argmax_decode / viterbi_decode ------------------------------------------
  * replaces transducer.py:27-33 (argmax), :72-73 (poreover), :83-89 (bonito), :35-59 +
  * :94-103 (flip-flop Viterbi) and pair_decode.get_sequence_mapping (pair_decode.py:114-142).

@@ -113,6 +113,11 @@ PROTOTYPES = {
                               C.c_int64, C.c_int, _vp, _i32p, _vp, C.c_int, _vp, C.c_size_t, _vp]),
     "po_ctc_loss_h": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                                 _i32p, _i64p, C.c_int, _vp, _i32p, _vp, C.c_int]),
+    "po_forced_align_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int64, C.c_int]),
+    "po_forced_align": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _i32p, _i64p, C.c_int,
+                                  C.c_int64, C.c_int64, C.c_int, _dp, _i32p, C.c_int64, _i32p, _i32p, _i32p, _vp, C.c_size_t, _vp]),
+    "po_forced_align_h": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(C.c_int), _i32p, _i64p, C.c_int, _dp, _i32p, C.c_int64, _i32p, _i32p, _i32p]),
     "po_viterbi_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "po_viterbi_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _vp, _cp, _i64p, _i32p,
                                    _i32p, _i32p, _vp, C.c_size_t, _vp]),

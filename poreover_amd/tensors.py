@@ -41,7 +41,7 @@ from . import _lib as L
 from . import _marshal as M
 from . import quality as Q
 
-__all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss"]
+__all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss", "forced_align", "Alignment"]
 
 LAYOUTS = ("NTC", "TNC")
 KIND_COLUMNS = {"poreover": 5, "bonito": 5, "flipflop": 8}
@@ -707,3 +707,99 @@ def ctc_loss(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreove
     if zero_infinity:
         loss = torch.where(torch.isinf(loss), torch.zeros_like(loss), loss)
     return loss if reduction == "none" else (loss.mean() if reduction == "mean" else loss.sum())
+
+
+# -------------------------------------------------------------------------------------------------------- forced alignment
+class Alignment:
+    """Where in time each item's label sits (forced_align's return), as device tensors:
+
+        scores         (N,) float64: the best path's log-probability (-inf: no path; NaN: the item was refused)
+        states         (N, T) int32, batch-major whatever x's layout: the path's lattice state per frame — even 2k: the blank
+                       in front of symbol k, odd 2k + 1: symbol k — and -1 in padded frames and in items without a path
+        starts, stops  (total symbols,) int32: the first frame of each symbol's label state and one past its last, the items
+                       back to back; item i's are starts[label_offsets[i]:label_offsets[i + 1]]
+        label_offsets  (N + 1,) int64 numpy array on the host
+        status         (N,) int32: 0, or the engine's PO_E_* code of that item (_lib.E_ENVELOPE: no path of finite score)
+    """
+    __slots__ = ("scores", "states", "starts", "stops", "label_offsets", "status")
+
+    def __init__(self, scores, states, starts, stops, label_offsets, status):
+        self.scores, self.states, self.starts, self.stops = scores, states, starts, stops
+        self.label_offsets, self.status = label_offsets, status
+
+    def spans(self, i):
+        """item i's (L_i, 2) int32 numpy array of (start, stop) frames.  Copies to the host: this SYNCHRONISES."""
+        a, b = int(self.label_offsets[i]), int(self.label_offsets[i + 1])
+        return torch.stack((self.starts[a:b], self.stops[a:b]), dim=1).cpu().numpy()
+
+
+def _align_engine(x, layout, perm, model, normalized, lens, lab, lab_lens, with_path=True):
+    """perm and model as _ctc_engine takes them.  One po_forced_align call on the current stream of x's device: an Alignment.
+    with_path=False: the scores alone (states, starts, stops None; no decision is stored, no trace-back runs).  Enqueue-only."""
+    n, Cc = len(lens), x.shape[2]
+    dev = x.device
+    T = x.shape[1] if layout == "NTC" else x.shape[0]
+    off_h, loff_h = M.offsets(lens), M.offsets(lab_lens).astype(np.int64)
+    rows = int(off_h[-1])
+    words = int((lens * ((2 * lab_lens + 1 + 63) // 64)).sum())     # a frame's decisions: 16 bytes per 64 states
+    max_states = int(2 * lab_lens.max() + 1)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        nlab = max((len(lab) + 1) // 2, 1)
+        host = torch.empty(5 * n + 2 + nlab, dtype=torch.int64, pin_memory=True)   # the item table, both offset tables, the labels
+        h = host.numpy()
+        h[:3 * n] = _items(x, layout).reshape(-1)
+        h[3 * n:4 * n + 1] = off_h
+        h[4 * n + 1:5 * n + 2] = loff_h
+        h[5 * n + 2:].view(np.int32)[:len(lab)] = lab
+        d = host.to(dev, non_blocking=True)
+        scores = torch.empty(n, dtype=torch.float64, device=dev)
+        states = torch.empty((n, T), dtype=torch.int32, device=dev) if with_path else None
+        starts = torch.empty(len(lab), dtype=torch.int32, device=dev) if with_path else None
+        stops = torch.empty(len(lab), dtype=torch.int32, device=dev) if with_path else None
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        wsb = lib.po_forced_align_workspace_bytes(n, rows, words, Cc)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        L.check(lib.po_forced_align(d.data_ptr(), d[3 * n:].data_ptr(), n, Cc, _DTYPES[x.dtype], 0 if normalized else 1,
+                                    M.perm_array(perm, Cc), d[5 * n + 2:].data_ptr(), d[4 * n + 1:].data_ptr(),
+                                    L.MODELS[model], rows, words, max_states, scores.data_ptr(),
+                                    states.data_ptr() if with_path and T else None, T,
+                                    starts.data_ptr() if with_path and len(lab) else None,
+                                    stops.data_ptr() if with_path and len(lab) else None, status.data_ptr(),
+                                    ws.data_ptr(), wsb, stream.cuda_stream), "po_forced_align")
+    return Alignment(scores, states, starts, stops, loff_h, status)
+
+
+def forced_align(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreover", normalized=False):
+    """The best path of each item's label through the CTC lattice of `kind`: which frame emitted which symbol.
+
+    x, lengths, labels, label_lengths, layout, kind and normalized are ctc_loss's, with its checks: a device tensor (N, T, 5)
+    or (T, N, 5) of float32, float16 or bfloat16 logits (normalized=True: log-probabilities, float64 too) with any strides,
+    read where it lies.  kind "poreover" is the `ctc` lattice (a label state lasts one frame, the blank between two labels
+    may always be skipped), "bonito" standard CTC with merged repeats on blank-first columns; "flipflop" has no aligner here.
+
+    Returns an Alignment of device tensors.  The maximisation runs in float64 on the float64 log-softmax of x, and among
+    paths of equal score the one that stays in the larger state longest is taken (ties go to stay, then step, then skip), so
+    the result is a function of x alone.  An item that no path can produce (ctc_loss: +inf) has score -inf, status
+    PO_E_ENVELOPE and -1 everywhere.  Not differentiable: x is detached.
+
+    Everything is enqueued on torch.cuda.current_stream(x.device) in one engine call (po_forced_align), workspace and outputs
+    come from torch's allocator, and nothing synchronises.  Labels of up to 1200 symbols."""
+    _check_kind(kind)
+    if kind == "flipflop":
+        raise ValueError("kind 'flipflop' has no forced alignment: poreover (ctc) or bonito (ctc_merge_repeats)")
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r (one of %s)" % (layout, ", ".join(LAYOUTS)))
+    _check_tensor(x, "x", 3, KIND_COLUMNS[kind])
+    if x.dtype == torch.float64 and not normalized:
+        raise TypeError(_F64_LOGITS)
+    n, T = (x.shape[0], x.shape[1]) if layout == "NTC" else (x.shape[1], x.shape[0])
+    lens = _lengths(lengths, n, T)
+    lab, lab_lens = _labels(labels, label_lengths, n)
+    _check_device(x, "x")
+    if n == 0:
+        e32 = torch.empty(0, dtype=torch.int32, device=x.device)
+        return Alignment(torch.empty(0, dtype=torch.float64, device=x.device), torch.empty((0, T), dtype=torch.int32, device=x.device),
+                         e32, e32.clone(), np.zeros(1, np.int64), e32.clone())
+    return _align_engine(x.detach(), layout, KIND_PERM[kind], L.MODEL_OF_KIND[kind], normalized, lens, lab, lab_lens)
