@@ -282,6 +282,39 @@ int po_forced_align_h(const void* src_h, int64_t src_elems, const int64_t* item_
                       const int* perm_h, const int32_t* labels_h, const int64_t* label_off_h, int model, double* score_h,
                       int32_t* states_h, int64_t states_stride, int32_t* starts_h, int32_t* stops_h, int32_t* status_h);
 
+/* ---- read accuracy against truth on tensors where they lie (po_acc.hip) ------------------------------------
+ * po_logits_path: the argmax path of every item as uint8 codes 0..3.  Items, row_off and dtypes are po_ingest_strided's (f64
+ * too: nothing is normalised), C must be 5, perm_h (host, or NULL) as po_ctc_loss takes it: canonical column c (A, C, G, T,
+ * blank) is source column perm_h[c].  Per frame the class of the first maximum of the 5 raw values in canonical order: a later
+ * value replaces the best only when it is strictly greater, or when it is NaN and the best is not.  PO_KIND_POREOVER: every
+ * frame whose class is no blank emits it, repeats kept; PO_KIND_BONITO: a frame emits when its class is no blank and differs
+ * from the previous frame's class.  Item i's codes go to pred + i * pred_stride, their count to pred_len[i]; what lies past
+ * the count is left alone.  An item with more frames than pred_stride writes no code and pred_len[i] = -1.
+ * Enqueue-only on `stream`.  Before any HIP call: PO_E_UNSUPPORTED for PO_KIND_FLIPFLOP; PO_E_ARG for an unknown kind, negative
+ * n, C != 5, an unknown dtype, a perm that is no permutation, a negative pred_stride, null pointers with n > 0; the host twin
+ * (the source as po_ingest_strided_h takes it) knows the lengths and also refuses a pred_stride that cannot hold the longest
+ * item, naming both.  n == 0: PO_OK.
+ *
+ * po_edit_stats: global unit-cost alignment of hypothesis a against truth b, pair i = a[a_off[i] ..) of a_len[i] bytes
+ * against b[b_off[i] ..) of b_len[i] bytes (a_len / b_len device int32, or NULL for off[i+1] - off[i]; bytes are compared for
+ * equality).  dist[i] = the edit distance d; matches[i] = the most matches m over all alignments of distance d.  With the
+ * lengths la, lb: mismatches = la + lb - 2m - d, insertions (bytes of a that b lacks) = d - lb + m, deletions = d - la + m,
+ * alignment length = m + d, identity = m / (m + d).  status[i]: 0; PO_E_CAP with dist = matches = -1 where the shorter
+ * string has more than PO_EDIT_MAX_SHORT = 4095 bytes or the longer more than PO_EDIT_STATS_MAX_LONG; PO_E_ARG with -1, -1
+ * for a negative length.  The rest of the batch is answered; the same pair gives the same bits at every batch position.
+ * Enqueue-only on `stream`.  PO_E_ARG before any HIP call: negative n, null pointers with n > 0; the host twin also refuses
+ * tables that decrease and a length outside its offsets' room (its tables' first entry need not be 0).  n == 0: PO_OK. */
+#define PO_EDIT_STATS_MAX_LONG 262142
+int po_logits_path(const po_ingest_item* items, const int64_t* row_off, int n, int C, int dtype, const int* perm_h, int kind,
+                   uint8_t* pred, int64_t pred_stride, int32_t* pred_len, void* stream);
+int po_logits_path_h(const void* src_h, int64_t src_elems, const int64_t* item_off_h, const int64_t* row_stride_h,
+                     const int64_t* col_stride_h, const int64_t* row_off_h, int n, int C, int dtype, const int* perm_h, int kind,
+                     uint8_t* pred_h, int64_t pred_stride, int32_t* pred_len_h);
+int po_edit_stats(const uint8_t* a, const int64_t* a_off, const int32_t* a_len, const uint8_t* b, const int64_t* b_off,
+                  const int32_t* b_len, int n, int32_t* dist, int32_t* matches, int32_t* status, void* stream);
+int po_edit_stats_h(const uint8_t* a_h, const int64_t* a_off_h, const int32_t* a_len_h, const uint8_t* b_h, const int64_t* b_off_h,
+                    const int32_t* b_len_h, int n, int32_t* dist_h, int32_t* matches_h, int32_t* status_h);
+
 /* ---- transducer.argmax_decode / viterbi_decode ------------------------------------------
  * replaces transducer.py:27-33 (argmax), :72-73 (poreover), :83-89 (bonito), :35-59 +
  * :94-103 (flip-flop Viterbi) and pair_decode.get_sequence_mapping (pair_decode.py:114-142).

@@ -78,6 +78,7 @@ PAIR_BASECALL_STAGES = CALL_STAGES + ("stitch_tables", "pair_decode")
 PAIR_BASECALL_FASTQ_STAGES = PAIR_BASECALL_STAGES + ("guides", "lattice_phred")
 TRAIN_STAGES = ("forward", "ctc", "back_recur", "gemm", "adam")
 EVAL_STAGES = ("forward", "ctc", "path_edit")
+EDIT_STATS_MAX_LONG = 262142   # po_edit_stats: the longer string of a pair (PO_EDIT_STATS_MAX_LONG; beyond it: E_CAP, distance and matches -1)
 EDIT_MAX_SHORT = 4095    # po_edit_distance_batch_h / po_train_eval: the shorter string of a pair (beyond it: E_CAP, distance -1)
 
 _vp, _i64p, _i32p, _dp, _cp = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p
@@ -118,6 +119,11 @@ PROTOTYPES = {
                                   C.c_int64, C.c_int64, C.c_int, _dp, _i32p, C.c_int64, _i32p, _i32p, _i32p, _vp, C.c_size_t, _vp]),
     "po_forced_align_h": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     C.POINTER(C.c_int), _i32p, _i64p, C.c_int, _dp, _i32p, C.c_int64, _i32p, _i32p, _i32p]),
+    "po_logits_path": (C.c_int, [_vp, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, _cp, C.c_int64, _i32p, _vp]),
+    "po_logits_path_h": (C.c_int, [_vp, C.c_int64, _i64p, _i64p, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                   _cp, C.c_int64, _i32p]),
+    "po_edit_stats": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _i32p, _i32p, _i32p, _vp]),
+    "po_edit_stats_h": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _i32p, _i32p, _i32p]),
     "po_viterbi_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "po_viterbi_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _vp, _cp, _i64p, _i32p,
                                    _i32p, _i32p, _vp, C.c_size_t, _vp]),

@@ -41,7 +41,8 @@ from . import _lib as L
 from . import _marshal as M
 from . import quality as Q
 
-__all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss", "forced_align", "Alignment"]
+__all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss", "forced_align", "Alignment", "argmax_path", "edit_stats",
+           "accuracy", "EditStats"]
 
 LAYOUTS = ("NTC", "TNC")
 KIND_COLUMNS = {"poreover": 5, "bonito": 5, "flipflop": 8}
@@ -803,3 +804,226 @@ def forced_align(x, lengths, labels, label_lengths=None, layout="NTC", kind="por
         return Alignment(torch.empty(0, dtype=torch.float64, device=x.device), torch.empty((0, T), dtype=torch.int32, device=x.device),
                          e32, e32.clone(), np.zeros(1, np.int64), e32.clone())
     return _align_engine(x.detach(), layout, KIND_PERM[kind], L.MODEL_OF_KIND[kind], normalized, lens, lab, lab_lens)
+
+
+# ---------------------------------------------------------------------------------------------------------------- accuracy
+class EditStats:
+    """How each hypothesis aligns to its truth (edit_stats' and accuracy's return), as device int32 (N,) tensors:
+
+        distance      the unit-cost edit distance d of the global alignment
+        matches       the most matches m over all alignments of that distance
+        hyp_lengths   the hypotheses' lengths la (accuracy: the argmax paths')
+        ref_lengths   the truths' lengths lb
+        status        0, or the engine's PO_E_* code of that pair (_lib.E_CAP: the shorter string has more than 4095 symbols
+                      or the longer more than _lib.EDIT_STATS_MAX_LONG; distance and matches are -1 there)
+
+    Everything else follows from these and is torch arithmetic on the device, nothing synchronises: mismatches, insertions
+    (hypothesis bases the truth lacks, accuracy.alignment_summary's naming), deletions, alignment_lengths = m + d;
+    identity() = m / (m + d), what the reference's `benchmark` and accuracy.alignment_summary report, and error_rate() =
+    d / lb, train.validation_error's quantity."""
+    __slots__ = ("distance", "matches", "hyp_lengths", "ref_lengths", "status")
+
+    def __init__(self, distance, matches, hyp_lengths, ref_lengths, status):
+        self.distance, self.matches, self.hyp_lengths, self.ref_lengths, self.status = distance, matches, hyp_lengths, ref_lengths, status
+
+    @property
+    def mismatches(self):
+        return self.hyp_lengths + self.ref_lengths - 2 * self.matches - self.distance
+
+    @property
+    def insertions(self):
+        return self.distance - self.ref_lengths + self.matches
+
+    @property
+    def deletions(self):
+        return self.distance - self.hyp_lengths + self.matches
+
+    @property
+    def alignment_lengths(self):
+        return self.matches + self.distance
+
+    def _answered(self, v):
+        return torch.where(self.status != 0, torch.full_like(v, float("nan")), v)
+
+    def identity(self):
+        """float64 (N,): matches / alignment length; 0.0 where both strings are empty; NaN where status != 0"""
+        al = self.alignment_lengths.to(torch.float64)
+        v = self.matches.to(torch.float64) / al.clamp(min=1.0)
+        return self._answered(torch.where(al > 0, v, torch.zeros_like(v)))
+
+    def error_rate(self):
+        """float64 (N,): distance / truth length (an empty truth divides by zero as torch does); NaN where status != 0"""
+        return self._answered(self.distance.to(torch.float64) / self.ref_lengths.to(torch.float64))
+
+
+def _empty_stats(dev):
+    return EditStats(*(torch.empty(0, dtype=torch.int32, device=dev) for _ in range(5)))
+
+
+def _bytes_words(nbytes):
+    return (int(nbytes) + 7) // 8
+
+
+def _path_launch(lib, d_items, d_off, n, x, kind, codes, plen, stream):
+    L.check(lib.po_logits_path(d_items.data_ptr(), d_off.data_ptr(), n, x.shape[2], _DTYPES[x.dtype], M.perm_array(KIND_PERM[kind], x.shape[2]),
+                               L.KINDS[kind], codes.data_ptr() if codes.numel() else None, codes.shape[1], plen.data_ptr(),
+                               stream.cuda_stream), "po_logits_path")
+
+
+def _check_path_args(who, x, lengths, layout, kind):
+    """ctc_loss's checks of x, lengths, layout and kind, in its order (float64 logits are taken: nothing is normalised);
+    returns (n, T, lens).  The device check is the caller's last."""
+    _check_kind(kind)
+    if kind == "flipflop":
+        raise ValueError("kind 'flipflop' has no %s: poreover (ctc) or bonito (ctc_merge_repeats)" % who)
+    if layout not in LAYOUTS:
+        raise ValueError("layout %r (one of %s)" % (layout, ", ".join(LAYOUTS)))
+    _check_tensor(x, "x", 3, KIND_COLUMNS[kind])
+    n, T = (x.shape[0], x.shape[1]) if layout == "NTC" else (x.shape[1], x.shape[0])
+    return n, T, _lengths(lengths, n, T)
+
+
+def argmax_path(x, lengths=None, layout="NTC", kind="poreover"):
+    """The argmax path of every item of a padded batch, on the device: (codes (N, T) uint8, lengths (N,) int32), item i's
+    bases 0..3 (A, C, G, T) in codes[i, :lengths[i]]; what lies past a length is unspecified.
+
+    x, lengths, layout and kind are ctc_loss's: a device tensor (N, T, 5) or (T, N, 5) of float32, float16, bfloat16 or float64
+    with any strides, read where it lies.  Per frame the class of the first maximum of the five raw values (nothing is
+    normalised, so logits, log-probabilities and probabilities give the same path; a NaN counts as the largest value).  kind
+    "poreover": every non-blank frame emits its class, repeats kept (train.validation_error's path, blank last); "bonito":
+    blank-first columns, and a frame emits when its class is no blank and differs from the previous frame's (the groupby
+    collapse).  Where no two of a frame's values tie this is tensors.viterbi's string.
+
+    One engine call (po_logits_path) on torch.cuda.current_stream(x.device), outputs from torch's allocator, and nothing
+    synchronises (device tensors of lengths cost a synchronising .cpu(), as everywhere here)."""
+    n, T, lens = _check_path_args("argmax path", x, lengths, layout, kind)
+    _check_device(x, "x")
+    dev = x.device
+    codes = torch.empty((n, T), dtype=torch.uint8, device=dev)
+    plen = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return codes, plen
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        host = torch.empty(4 * n + 1, dtype=torch.int64, pin_memory=True)   # the item table and the offsets: one small copy
+        h = host.numpy()
+        h[:3 * n] = _items(x.detach(), layout).reshape(-1)
+        h[3 * n:] = M.offsets(lens)
+        d = host.to(dev, non_blocking=True)
+        _path_launch(lib, d, d[3 * n:], n, x, kind, codes, plen, stream)
+    return codes, plen
+
+
+def _stats_launch(lib, n, a, a_off, a_len, b, b_off, stream):
+    dev = b.device
+    dist, matches, status = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(3))
+    L.check(lib.po_edit_stats(a.data_ptr(), a_off.data_ptr(), a_len.data_ptr() if a_len is not None else None, b.data_ptr(),
+                              b_off.data_ptr(), None, n, dist.data_ptr(), matches.data_ptr(), status.data_ptr(), stream.cuda_stream),
+            "po_edit_stats")
+    return dist, matches, status
+
+
+def _is_path_pair(hyp):
+    return isinstance(hyp, tuple) and len(hyp) == 2 and isinstance(hyp[0], torch.Tensor)
+
+
+def edit_stats(hyp, ref):
+    """Global unit-cost alignment of each hypothesis against its truth: an EditStats of device tensors.
+
+    hyp and ref: each a list of str over ACGT or of int sequences (0..3), one per pair — the strings of tensors.viterbi,
+    beam_search or pair_decode against their truths — uploaded in one pinned copy.  hyp may instead be argmax_path's
+    (codes, lengths) pair, used where it lies on its device.  Of all alignments of minimum edit distance the one with the most
+    matches is taken, so matches can exceed accuracy.alignment_summary's (whose trace-back prefers the diagonal: "AB" against
+    "BA" has two edits and one match here, none there); the distance is the same.
+
+    One engine call (po_edit_stats) on the current stream of the hypotheses' device (lists: the current device), outputs from
+    torch's allocator, and nothing synchronises.  A pair whose shorter string has more than 4095 symbols has status
+    _lib.E_CAP."""
+    pair = _is_path_pair(hyp)
+    if pair:
+        codes, plen = hyp
+        if not isinstance(plen, torch.Tensor) or codes.dtype != torch.uint8 or plen.dtype != torch.int32:
+            raise TypeError("hyp as a pair is argmax_path's (codes uint8, lengths int32) tensors")
+        if codes.dim() != 2 or plen.dim() != 1 or plen.shape[0] != codes.shape[0] or (codes.shape[1] > 1 and codes.stride(1) != 1):
+            raise ValueError("hyp as a pair is (codes (N, T) with adjacent columns, lengths (N,)): shapes %s and %s" % (tuple(codes.shape), tuple(plen.shape)))
+        if codes.device != plen.device:
+            raise ValueError("codes is on %s, lengths on %s" % (codes.device, plen.device))
+        n = codes.shape[0]
+        a_flat, a_lens = None, None
+    else:
+        if isinstance(hyp, (str, bytes)) or isinstance(ref, (str, bytes)):
+            raise TypeError("hyp and ref are lists of sequences, one per pair")
+        hyp = list(hyp)
+        n = len(hyp)
+        a_flat, a_lens = _labels(hyp, None, n)
+    if isinstance(ref, (str, bytes)):
+        raise TypeError("hyp and ref are lists of sequences, one per pair")
+    ref = list(ref)
+    if len(ref) != n:
+        raise ValueError("hyp holds %d sequences, ref %d" % (n, len(ref)))
+    b_flat, b_lens = _labels(ref, None, n)
+    if pair:
+        _check_device(codes, "hyp")
+        dev = codes.device
+    else:
+        if not torch.cuda.is_available():
+            raise ValueError("edit_stats runs on the GPU and none is available")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if n == 0:
+        return _empty_stats(dev)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        na, nb = (0 if pair else _bytes_words(len(a_flat))), _bytes_words(len(b_flat))
+        host = torch.empty(2 * n + 2 + max(na, 1) + max(nb, 1), dtype=torch.int64, pin_memory=True)   # both offset tables, both texts
+        h = host.numpy()
+        h[:n + 1] = np.arange(n + 1, dtype=np.int64) * codes.stride(0) if pair else M.offsets(a_lens)
+        h[n + 1:2 * n + 2] = M.offsets(b_lens)
+        at_a, at_b = 2 * n + 2, 2 * n + 2 + max(na, 1)
+        if not pair:
+            h[at_a:at_b].view(np.uint8)[:len(a_flat)] = a_flat
+        h[at_b:].view(np.uint8)[:len(b_flat)] = b_flat
+        d = host.to(dev, non_blocking=True)
+        lens32 = (d[1:2 * n + 2] - d[:2 * n + 1]).to(torch.int32)      # (entry n is the step between the tables: unused)
+        a = codes if pair else d[at_a:]
+        if pair and codes.numel() == 0:
+            a = d[at_a:]
+        dist, matches, status = _stats_launch(lib, n, a, d, plen if pair else None, d[at_b:], d[n + 1:], stream)
+    return EditStats(dist, matches, plen if pair else lens32[:n], lens32[n + 1:], status)
+
+
+def accuracy(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreover"):
+    """How accurate the argmax calls of a padded batch are against the truth: an EditStats of device tensors, from which
+    identity() (matches / alignment length, the figure a basecaller trainer prints) and error_rate() follow.
+
+    x, lengths, labels, label_lengths, layout and kind are ctc_loss's, with its checks; float64 is taken too, since nothing is
+    normalised.  The hypothesis of item i is argmax_path's, the truth its label; the alignment is edit_stats'.
+
+    One pinned upload (item table, offsets, labels), then two engine calls (po_logits_path, po_edit_stats) on
+    torch.cuda.current_stream(x.device); the paths, the outputs and nothing else come from torch's allocator, and nothing
+    synchronises: the result stays on the device.  Not differentiable."""
+    n, T, lens = _check_path_args("accuracy", x, lengths, layout, kind)
+    lab, lab_lens = _labels(labels, label_lengths, n)
+    _check_device(x, "x")
+    dev = x.device
+    if n == 0:
+        return _empty_stats(dev)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        nb = max(_bytes_words(len(lab)), 1)
+        host = torch.empty(6 * n + 3 + nb, dtype=torch.int64, pin_memory=True)   # the item table, three offset tables, the labels
+        h = host.numpy()
+        h[:3 * n] = _items(x.detach(), layout).reshape(-1)
+        h[3 * n:4 * n + 1] = M.offsets(lens)
+        h[4 * n + 1:5 * n + 2] = np.arange(n + 1, dtype=np.int64) * T
+        h[5 * n + 2:6 * n + 3] = M.offsets(lab_lens)
+        h[6 * n + 3:].view(np.uint8)[:len(lab)] = lab
+        d = host.to(dev, non_blocking=True)
+        codes = torch.empty((n, max(T, 1)), dtype=torch.uint8, device=dev)
+        plen = torch.empty(n, dtype=torch.int32, device=dev)
+        _path_launch(lib, d, d[3 * n:], n, x, kind, codes, plen, stream)
+        ref_lens = (d[5 * n + 3:6 * n + 3] - d[5 * n + 2:6 * n + 2]).to(torch.int32)
+        dist, matches, status = _stats_launch(lib, n, codes, d[4 * n + 1:], plen, d[6 * n + 3:], d[5 * n + 2:], stream)
+    return EditStats(dist, matches, plen, ref_lens, status)
