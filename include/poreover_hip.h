@@ -315,6 +315,38 @@ int po_edit_stats(const uint8_t* a, const int64_t* a_off, const int32_t* a_len, 
 int po_edit_stats_h(const uint8_t* a_h, const int64_t* a_off_h, const int32_t* a_len_h, const uint8_t* b_h, const int64_t* b_off_h,
                     const int32_t* b_len_h, int n, int32_t* dist_h, int32_t* matches_h, int32_t* status_h);
 
+/* ---- where the edits sit: ops, confusion (po_aln.hip) -------------------------------------------------------
+ * po_edit_align: po_edit_stats' alignment with its columns.  Pairs, lengths, dist, matches and the caps are po_edit_stats'.
+ * The ops of pair i go to ops + i * ops_stride, one byte a column, front to back: 0 '=' (equal bytes), 1 'X' (unequal), 2 'I'
+ * (a byte of a that b lacks), 3 'D' (a byte of b that a lacks); ops_len[i] = m + d of them, exactly m of them 0; bytes at and
+ * past ops_len[i] are left untouched.  With D the key table of §23.1 (rows a, columns b) the walk goes from (la, lb) to (0, 0)
+ * and takes at (i, j) the first move that holds: the diagonal if D[i][j] == D[i-1][j-1] + (a[i-1] != b[j-1] ? 4096 : -1), else
+ * I if D[i][j] == D[i-1][j] + 4096, else D.  So the ops are a function of the two strings alone, whichever string the kernel
+ * puts on its lanes; a gap in a homopolymer goes to its left end.
+ * trace: device words the kernels use between them; pair i's room is trace_off[i+1] - trace_off[i] words from trace +
+ * trace_off[i] (trace_off: device int64[n + 1], non-decreasing), and po_edit_align_trace_words(la, lb) words hold a pair of la
+ * against lb bytes.  That function (host, no HIP call) is non-decreasing in both arguments (lengths past the caps count as the
+ * caps), so a bound on the lengths bounds the room.
+ * confusion (or NULL): n tables of 5 x 5 int32, confusion[i * 25 + r * 5 + h] = the columns of pair i whose b byte is r and
+ * whose a byte is h, 4 standing for a gap: '=' counts [c][c], 'X' [b][a], 'I' [4][a], 'D' [b][4]; [4][4] is 0.  A column that
+ * consumes a byte above 3 is counted in no cell.
+ * status[i]: 0; PO_E_CAP with dist = matches = ops_len = -1 at po_edit_stats' caps; PO_E_CAP with dist and matches answered
+ * and ops_len = -1 where the pair's room is below po_edit_align_trace_words(la, lb) or m + d > ops_stride: nothing is written
+ * to that pair's trace, ops or confusion; PO_E_ARG with -1 everywhere for a negative length.  The rest of the batch is
+ * answered; the same pair gives the same bits at every batch position.
+ * Enqueue-only on `stream`: no allocation, no host read of device memory, no synchronisation.  PO_E_ARG before any HIP call:
+ * negative n, negative ops_stride, null pointers with n > 0 (confusion may be NULL).  n == 0: PO_OK.  The host twin sizes and
+ * owns the trace; ops_h and confusion_h go up as they are, so untouched bytes come back as they were; it also refuses tables
+ * that decrease and a length outside its offsets' room. */
+#define PO_EDIT_ALIGN_CELLS 25
+size_t po_edit_align_trace_words(int64_t la_max, int64_t lb_max);
+int po_edit_align(const uint8_t* a, const int64_t* a_off, const int32_t* a_len, const uint8_t* b, const int64_t* b_off,
+                  const int32_t* b_len, int n, uint32_t* trace, const int64_t* trace_off, uint8_t* ops, int64_t ops_stride,
+                  int32_t* ops_len, int32_t* dist, int32_t* matches, int32_t* confusion, int32_t* status, void* stream);
+int po_edit_align_h(const uint8_t* a_h, const int64_t* a_off_h, const int32_t* a_len_h, const uint8_t* b_h, const int64_t* b_off_h,
+                    const int32_t* b_len_h, int n, uint8_t* ops_h, int64_t ops_stride, int32_t* ops_len_h, int32_t* dist_h,
+                    int32_t* matches_h, int32_t* confusion_h, int32_t* status_h);
+
 /* ---- transducer.argmax_decode / viterbi_decode ------------------------------------------
  * replaces transducer.py:27-33 (argmax), :72-73 (poreover), :83-89 (bonito), :35-59 +
  * :94-103 (flip-flop Viterbi) and pair_decode.get_sequence_mapping (pair_decode.py:114-142).

@@ -124,6 +124,10 @@ PROTOTYPES = {
                                    _cp, C.c_int64, _i32p]),
     "po_edit_stats": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _i32p, _i32p, _i32p, _vp]),
     "po_edit_stats_h": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _i32p, _i32p, _i32p]),
+    "po_edit_align_trace_words": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "po_edit_align": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _vp, _i64p, _cp, C.c_int64, _i32p, _i32p, _i32p, _i32p,
+                                _i32p, _vp]),
+    "po_edit_align_h": (C.c_int, [_cp, _i64p, _i32p, _cp, _i64p, _i32p, C.c_int, _cp, C.c_int64, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "po_viterbi_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int, C.c_int]),
     "po_viterbi_batch": (C.c_int, [_dp, _i64p, C.c_int, C.c_int, C.c_char_p, C.c_int, _vp, _cp, _i64p, _i32p,
                                    _i32p, _i32p, _vp, C.c_size_t, _vp]),

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libporeover_hip.so")
-SOURCES = ["po_capi.hip", "po_ctc.hip", "po_falign.hip", "po_viterbi.hip", "po_beam1d.hip", "po_beam2d.hip", "po_beam2d_grid.hip", "po_beam2d_route.hip", "po_beam2d_reg.hip", "po_pair.hip", "po_lattice.hip", "po_prefix.hip", "po_ingest.hip", "po_ingest_strided.hip", "po_gamma.hip", "po_stream.hip", "po_call.hip", "po_train.hip", "po_train_group.hip", "po_map.hip", "po_label.hip", "po_qual.hip", "po_basecall.hip", "po_fastq.hip", "po_pair_basecall.hip", "po_eval.hip", "po_acc.hip", "po_prep.hip", "po_basecall_stream.hip", "po_skip.hip", "po_pair_basecall_stream.hip"]
+SOURCES = ["po_capi.hip", "po_ctc.hip", "po_falign.hip", "po_viterbi.hip", "po_beam1d.hip", "po_beam2d.hip", "po_beam2d_grid.hip", "po_beam2d_route.hip", "po_beam2d_reg.hip", "po_pair.hip", "po_lattice.hip", "po_prefix.hip", "po_ingest.hip", "po_ingest_strided.hip", "po_gamma.hip", "po_stream.hip", "po_call.hip", "po_train.hip", "po_train_group.hip", "po_map.hip", "po_label.hip", "po_qual.hip", "po_basecall.hip", "po_fastq.hip", "po_pair_basecall.hip", "po_eval.hip", "po_acc.hip", "po_aln.hip", "po_prep.hip", "po_basecall_stream.hip", "po_skip.hip", "po_pair_basecall_stream.hip"]
 HEADERS = ["po_device.h", os.path.join("..", "..", "include", "poreover_hip.h")]
 # The pair beam search is four sources: po_beam2d.hip (beam2d_kernel), po_beam2d_grid.hip (beam2d_grid_kernel), po_beam2d_reg.hip
 # (beam2d_reg_kernel) and po_beam2d_route.hip (the host layer that chooses among them, with the pre-pass and walk kernels).

@@ -42,7 +42,7 @@ from . import _marshal as M
 from . import quality as Q
 
 __all__ = ["Tables", "viterbi", "beam_search", "pair_decode", "ctc_loss", "forced_align", "Alignment", "argmax_path", "edit_stats",
-           "accuracy", "EditStats"]
+           "accuracy", "EditStats", "edit_alignment", "accuracy_alignment", "EditAlignment"]
 
 LAYOUTS = ("NTC", "TNC")
 KIND_COLUMNS = {"poreover": 5, "bonito": 5, "flipflop": 8}
@@ -928,18 +928,9 @@ def _is_path_pair(hyp):
     return isinstance(hyp, tuple) and len(hyp) == 2 and isinstance(hyp[0], torch.Tensor)
 
 
-def edit_stats(hyp, ref):
-    """Global unit-cost alignment of each hypothesis against its truth: an EditStats of device tensors.
-
-    hyp and ref: each a list of str over ACGT or of int sequences (0..3), one per pair — the strings of tensors.viterbi,
-    beam_search or pair_decode against their truths — uploaded in one pinned copy.  hyp may instead be argmax_path's
-    (codes, lengths) pair, used where it lies on its device.  Of all alignments of minimum edit distance the one with the most
-    matches is taken, so matches can exceed accuracy.alignment_summary's (whose trace-back prefers the diagonal: "AB" against
-    "BA" has two edits and one match here, none there); the distance is the same.
-
-    One engine call (po_edit_stats) on the current stream of the hypotheses' device (lists: the current device), outputs from
-    torch's allocator, and nothing synchronises.  A pair whose shorter string has more than 4095 symbols has status
-    _lib.E_CAP."""
+def _pair_args(hyp, ref):
+    """edit_stats' checks of its two arguments, the device apart: (n, path or None, a_flat, a_lens, b_flat, b_lens); path is
+    argmax_path's (codes, lengths) where hyp is that pair"""
     pair = _is_path_pair(hyp)
     if pair:
         codes, plen = hyp
@@ -963,34 +954,66 @@ def edit_stats(hyp, ref):
     if len(ref) != n:
         raise ValueError("hyp holds %d sequences, ref %d" % (n, len(ref)))
     b_flat, b_lens = _labels(ref, None, n)
-    if pair:
-        _check_device(codes, "hyp")
-        dev = codes.device
-    else:
-        if not torch.cuda.is_available():
-            raise ValueError("edit_stats runs on the GPU and none is available")
-        dev = torch.device("cuda", torch.cuda.current_device())
+    return n, (hyp if pair else None), a_flat, a_lens, b_flat, b_lens
+
+
+def _pair_device(who, path):
+    """the last check: the hypotheses' device, or the current one for lists"""
+    if path is not None:
+        _check_device(path[0], "hyp")
+        return path[0].device
+    if not torch.cuda.is_available():
+        raise ValueError("%s runs on the GPU and none is available" % who)
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _pair_upload(n, path, a_flat, a_lens, b_flat, b_lens, dev, table=None):
+    """One pinned copy: both offset tables, `table` (int64, or None) and both texts.  Returns (a, a_off, a_len, b, b_off,
+    hyp_lengths, ref_lengths, table on the device) as po_edit_stats takes them."""
+    pair = path is not None
+    codes, plen = path if pair else (None, None)
+    nt = 0 if table is None else len(table)
+    na, nb = (0 if pair else _bytes_words(len(a_flat))), _bytes_words(len(b_flat))
+    host = torch.empty(2 * n + 2 + nt + max(na, 1) + max(nb, 1), dtype=torch.int64, pin_memory=True)   # both offset tables, both texts
+    h = host.numpy()
+    h[:n + 1] = np.arange(n + 1, dtype=np.int64) * codes.stride(0) if pair else M.offsets(a_lens)
+    h[n + 1:2 * n + 2] = M.offsets(b_lens)
+    if nt:
+        h[2 * n + 2:2 * n + 2 + nt] = table
+    at_a, at_b = 2 * n + 2 + nt, 2 * n + 2 + nt + max(na, 1)
+    if not pair:
+        h[at_a:at_b].view(np.uint8)[:len(a_flat)] = a_flat
+    h[at_b:].view(np.uint8)[:len(b_flat)] = b_flat
+    d = host.to(dev, non_blocking=True)
+    lens32 = (d[1:2 * n + 2] - d[:2 * n + 1]).to(torch.int32)      # (entry n is the step between the tables: unused)
+    a = codes if pair else d[at_a:]
+    if pair and codes.numel() == 0:
+        a = d[at_a:]
+    return a, d, (plen if pair else None), d[at_b:], d[n + 1:], (plen if pair else lens32[:n]), lens32[n + 1:], d[2 * n + 2:]
+
+
+def edit_stats(hyp, ref):
+    """Global unit-cost alignment of each hypothesis against its truth: an EditStats of device tensors.
+
+    hyp and ref: each a list of str over ACGT or of int sequences (0..3), one per pair — the strings of tensors.viterbi,
+    beam_search or pair_decode against their truths — uploaded in one pinned copy.  hyp may instead be argmax_path's
+    (codes, lengths) pair, used where it lies on its device.  Of all alignments of minimum edit distance the one with the most
+    matches is taken, so matches can exceed accuracy.alignment_summary's (whose trace-back prefers the diagonal: "AB" against
+    "BA" has two edits and one match here, none there); the distance is the same.
+
+    One engine call (po_edit_stats) on the current stream of the hypotheses' device (lists: the current device), outputs from
+    torch's allocator, and nothing synchronises.  A pair whose shorter string has more than 4095 symbols has status
+    _lib.E_CAP."""
+    n, path, a_flat, a_lens, b_flat, b_lens = _pair_args(hyp, ref)
+    dev = _pair_device("edit_stats", path)
     if n == 0:
         return _empty_stats(dev)
     lib = L.load()
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev)
-        na, nb = (0 if pair else _bytes_words(len(a_flat))), _bytes_words(len(b_flat))
-        host = torch.empty(2 * n + 2 + max(na, 1) + max(nb, 1), dtype=torch.int64, pin_memory=True)   # both offset tables, both texts
-        h = host.numpy()
-        h[:n + 1] = np.arange(n + 1, dtype=np.int64) * codes.stride(0) if pair else M.offsets(a_lens)
-        h[n + 1:2 * n + 2] = M.offsets(b_lens)
-        at_a, at_b = 2 * n + 2, 2 * n + 2 + max(na, 1)
-        if not pair:
-            h[at_a:at_b].view(np.uint8)[:len(a_flat)] = a_flat
-        h[at_b:].view(np.uint8)[:len(b_flat)] = b_flat
-        d = host.to(dev, non_blocking=True)
-        lens32 = (d[1:2 * n + 2] - d[:2 * n + 1]).to(torch.int32)      # (entry n is the step between the tables: unused)
-        a = codes if pair else d[at_a:]
-        if pair and codes.numel() == 0:
-            a = d[at_a:]
-        dist, matches, status = _stats_launch(lib, n, a, d, plen if pair else None, d[at_b:], d[n + 1:], stream)
-    return EditStats(dist, matches, plen if pair else lens32[:n], lens32[n + 1:], status)
+        a, a_off, a_len, b, b_off, hyp_lens, ref_lens, _ = _pair_upload(n, path, a_flat, a_lens, b_flat, b_lens, dev)
+        dist, matches, status = _stats_launch(lib, n, a, a_off, a_len, b, b_off, stream)
+    return EditStats(dist, matches, hyp_lens, ref_lens, status)
 
 
 def accuracy(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreover"):
@@ -1027,3 +1050,166 @@ def accuracy(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreove
         ref_lens = (d[5 * n + 3:6 * n + 3] - d[5 * n + 2:6 * n + 2]).to(torch.int32)
         dist, matches, status = _stats_launch(lib, n, codes, d[4 * n + 1:], plen, d[6 * n + 3:], d[5 * n + 2:], stream)
     return EditStats(dist, matches, plen, ref_lens, status)
+
+
+# --------------------------------------------------------------------------------------------------------------- alignment
+OPS = "=XID"     # the codes of EditAlignment.ops: 0 equal, 1 unequal, 2 a hypothesis symbol the truth lacks, 3 a truth symbol the hypothesis lacks
+
+
+class EditAlignment:
+    """Where the edits sit (edit_alignment's and accuracy_alignment's return), as device tensors:
+
+        stats         the EditStats of the same alignment
+        ops           (N, W) uint8: item i's columns front to back in ops[i, :ops_lengths[i]], codes 0 '=', 1 'X', 2 'I' (a
+                      hypothesis symbol the truth lacks), 3 'D' (a truth symbol the hypothesis lacks); what lies past a length
+                      is unspecified
+        ops_lengths   (N,) int32: matches + distance, or -1 where status != 0
+        confusion     (N, 5, 5) int32 or None: confusion[i, r, h] counts the columns with truth symbol r and hypothesis symbol
+                      h, 4 standing for a gap; all zero where status != 0
+
+    Of all alignments of minimum distance with the most matches the one taken is fixed by the walk back from the end: the
+    diagonal first, then I, then D, so a gap in a homopolymer sits at its left end and the ops depend on the two strings alone.
+    status is _lib.E_CAP beyond edit_stats' caps (everything -1)."""
+    __slots__ = ("stats", "ops", "ops_lengths", "confusion")
+
+    def __init__(self, stats, ops, ops_lengths, confusion):
+        self.stats, self.ops, self.ops_lengths, self.confusion = stats, ops, ops_lengths, confusion
+
+    def _index(self, gap):
+        cols = torch.arange(self.ops.shape[1], device=self.ops.device, dtype=torch.int32)
+        takes = (cols[None, :] < self.ops_lengths[:, None]) & (self.ops != gap)
+        idx = torch.cumsum(takes, dim=1, dtype=torch.int32) - 1
+        return torch.where(takes, idx, torch.full_like(idx, -1))
+
+    def hyp_index(self):
+        """(N, W) int32: the index of the hypothesis symbol each column consumes; -1 at a D and past the length"""
+        return self._index(3)
+
+    def ref_index(self):
+        """(N, W) int32: the index of the truth symbol each column consumes; -1 at an I and past the length"""
+        return self._index(2)
+
+    def confusion_total(self):
+        """(5, 5) int64: the confusion tables of the items with status == 0, added up"""
+        if self.confusion is None:
+            raise ValueError("the alignment was made with confusion=False")
+        keep = (self.stats.status == 0).to(torch.int64)
+        return (self.confusion.to(torch.int64) * keep[:, None, None]).sum(dim=0)
+
+    def cigar(self, i):
+        """item i's ops as a run-length string ("12=1X3I"; "" for an empty alignment, None where status != 0).  Copies the
+        item to the host: this synchronises."""
+        n = int(self.ops_lengths[i])
+        if n < 0:
+            return None
+        o = self.ops[i, :n].cpu().numpy()
+        if n == 0:
+            return ""
+        cut = np.flatnonzero(np.diff(o)) + 1
+        starts = np.concatenate([[0], cut])
+        runs = np.diff(np.concatenate([starts, [n]]))
+        return "".join("%d%s" % (r, OPS[o[st]]) for st, r in zip(starts, runs))
+
+
+def trace_words(la, lb):
+    """po_edit_align_trace_words without the library: the 32-bit words of the trace of la against lb symbols (lengths past
+    the caps count as the caps)"""
+    s, l = min(int(la), int(lb)), max(int(la), int(lb))
+    if s < 0:
+        return 0
+    s, l = min(s, L.EDIT_MAX_SHORT), min(l, L.EDIT_STATS_MAX_LONG)
+    k = 1
+    while k < (s + 64) // 64:
+        k *= 2
+    rows = 16 // k if k < 16 else 1
+    return -(-l // rows) * (64 if k < 16 else 4 * k)
+
+
+def _trace_table(who, la, lb, max_trace_bytes):
+    """(trace_off int64 (n + 1), W) from host-known bounds of the pairs' lengths; refuses a trace past max_trace_bytes"""
+    off = np.zeros(len(lb) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([trace_words(x, y) for x, y in zip(la, lb)], dtype=np.int64) if len(lb) else 0
+    if 4 * int(off[-1]) > int(max_trace_bytes):
+        raise ValueError("%s: the trace of this batch takes %d bytes, max_trace_bytes is %d: align smaller batches (or raise it)"
+                         % (who, 4 * int(off[-1]), int(max_trace_bytes)))
+    return off, (int(max(x + y for x, y in zip(la, lb))) if len(lb) else 0)
+
+
+def _empty_alignment(dev, W, confusion):
+    return EditAlignment(_empty_stats(dev), torch.empty((0, W), dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                         torch.empty((0, 5, 5), dtype=torch.int32, device=dev) if confusion else None)
+
+
+def _align_launch(lib, n, a, a_off, a_len, b, b_off, trace_off, words, W, confusion, stream):
+    dev = b.device
+    dist, matches, status, ops_len = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    trace = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    flat = torch.empty(max(n * W, 1), dtype=torch.uint8, device=dev)
+    conf = torch.zeros((n, 5, 5), dtype=torch.int32, device=dev) if confusion else None
+    L.check(lib.po_edit_align(a.data_ptr(), a_off.data_ptr(), a_len.data_ptr() if a_len is not None else None, b.data_ptr(),
+                              b_off.data_ptr(), None, n, trace.data_ptr(), trace_off.data_ptr(), flat.data_ptr(), W, ops_len.data_ptr(),
+                              dist.data_ptr(), matches.data_ptr(), conf.data_ptr() if confusion else None, status.data_ptr(),
+                              stream.cuda_stream), "po_edit_align")
+    return dist, matches, status, flat[:n * W].view(n, W), ops_len, conf
+
+
+def edit_alignment(hyp, ref, confusion=True, max_trace_bytes=1 << 30):
+    """edit_stats with the alignment's columns: an EditAlignment of device tensors.
+
+    hyp and ref are edit_stats': lists of str over ACGT or of int sequences, or argmax_path's (codes, lengths) pair as hyp,
+    used where it lies.  The engine keeps two bits per cell of each pair's table between its kernels, in a buffer sized from
+    what the host knows (the lists' lengths; for a pair codes.shape[1] bounds every hypothesis): 4095 against 4095 symbols take
+    4 MB.  A batch whose trace would pass max_trace_bytes raises ValueError before anything is loaded or allocated.
+    W = the largest la + lb of those bounds.
+
+    One pinned upload, one engine call (po_edit_align) on the current stream of the hypotheses' device (lists: the current
+    device); trace, ops and outputs come from torch's allocator and nothing synchronises."""
+    n, path, a_flat, a_lens, b_flat, b_lens = _pair_args(hyp, ref)
+    la = [path[0].shape[1]] * n if path is not None else [int(v) for v in a_lens]
+    toff, W = _trace_table("edit_alignment", la, [int(v) for v in b_lens], max_trace_bytes)
+    dev = _pair_device("edit_alignment", path)
+    if n == 0:
+        return _empty_alignment(dev, W, confusion)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        a, a_off, a_len, b, b_off, hyp_lens, ref_lens, d_toff = _pair_upload(n, path, a_flat, a_lens, b_flat, b_lens, dev, toff)
+        dist, matches, status, ops, ops_len, conf = _align_launch(lib, n, a, a_off, a_len, b, b_off, d_toff, int(toff[-1]), W, confusion, stream)
+    return EditAlignment(EditStats(dist, matches, hyp_lens, ref_lens, status), ops, ops_len, conf)
+
+
+def accuracy_alignment(x, lengths, labels, label_lengths=None, layout="NTC", kind="poreover", confusion=True, max_trace_bytes=1 << 30):
+    """accuracy with the alignment's columns: an EditAlignment of device tensors, its .stats what accuracy returns.
+
+    x, lengths, labels, label_lengths, layout and kind are accuracy's, with its checks in its order.  The hypothesis of item i is
+    argmax_path's, at most T symbols, which sizes the trace (max_trace_bytes as in edit_alignment) and W = T + the longest label.
+
+    One pinned upload, two engine calls (po_logits_path, po_edit_align) on torch.cuda.current_stream(x.device); nothing
+    synchronises.  Not differentiable."""
+    n, T, lens = _check_path_args("accuracy_alignment", x, lengths, layout, kind)
+    lab, lab_lens = _labels(labels, label_lengths, n)
+    toff, W = _trace_table("accuracy_alignment", [T] * n, [int(v) for v in lab_lens], max_trace_bytes)
+    _check_device(x, "x")
+    dev = x.device
+    if n == 0:
+        return _empty_alignment(dev, W, confusion)
+    lib = L.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev)
+        nb = max(_bytes_words(len(lab)), 1)
+        host = torch.empty(7 * n + 4 + nb, dtype=torch.int64, pin_memory=True)   # the item table, four offset tables, the labels
+        h = host.numpy()
+        h[:3 * n] = _items(x.detach(), layout).reshape(-1)
+        h[3 * n:4 * n + 1] = M.offsets(lens)
+        h[4 * n + 1:5 * n + 2] = np.arange(n + 1, dtype=np.int64) * max(T, 1)
+        h[5 * n + 2:6 * n + 3] = M.offsets(lab_lens)
+        h[6 * n + 3:7 * n + 4] = toff
+        h[7 * n + 4:].view(np.uint8)[:len(lab)] = lab
+        d = host.to(dev, non_blocking=True)
+        codes = torch.empty((n, max(T, 1)), dtype=torch.uint8, device=dev)
+        plen = torch.empty(n, dtype=torch.int32, device=dev)
+        _path_launch(lib, d, d[3 * n:], n, x, kind, codes, plen, stream)
+        ref_lens = (d[5 * n + 3:6 * n + 3] - d[5 * n + 2:6 * n + 2]).to(torch.int32)
+        dist, matches, status, ops, ops_len, conf = _align_launch(lib, n, codes, d[4 * n + 1:], plen, d[7 * n + 4:], d[5 * n + 2:], d[6 * n + 3:],
+                                                                  int(toff[-1]), W, confusion, stream)
+    return EditAlignment(EditStats(dist, matches, plen, ref_lens, status), ops, ops_len, conf)
